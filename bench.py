@@ -16,6 +16,8 @@ steps (barrier + synchronize on both sides).  `roofline` is measured live: an ex
 timed region brackets every launch of the dominant kernel (the fp32-MFMA Winograd conv) with hipEvents on
 its launch stream (tg_prof_*), achieved = sum of algorithmic FLOPs / sum of kernel time.  `cpu_baseline` times
 the CPU oracle (oracle/terragan_oracle.py, "port") on the host cores, rank 0 at N=1 only.
+`--dump-outputs DIR` writes what the last timed step computed (step_outputs) as DIR/<name>.npy right after the timed
+region; the inputs and initial weights are seeded, so two builds run with the same arguments compare output for output.
 
 Roofline fields (every one can be recomputed from profiles/*_conv_launches.csv + *_kernel_stats.csv):
   achieved          EXECUTED MFMA TFLOP/s of the dominant kernel = algorithmic FLOPs / 2.25 / kernel time (Winograd
@@ -95,10 +97,44 @@ def cpu_baseline(size=TILE, batch=BATCH, seconds_budget=45.0):
                       f"({el:.1f} s); b1_value = {n1} steps at batch 1 (BASELINE configs[0], {el1:.1f} s)"}
 
 
+DUMP_ARRAY_BYTES = 16 << 20     # --dump-outputs: larger arrays are written as a fixed-seed sample of this size
+DUMP_SEED = 1234
+
+
+def step_outputs(out, G, D):
+    """What the timed path hands its caller after one step, as named host arrays: train_step's return dict (generator
+    output + loss scalars) and the state the step updated in place (G's and D's floating-point state_dict entries, each
+    flattened in logical order and concatenated in state_dict order).  An array larger than DUMP_ARRAY_BYTES becomes a
+    sample at DUMP_SEED-drawn positions, the same positions for the same size, so runs with the same arguments compare
+    element for element.  Three arrays of at most 16 MB plus six scalars stay under 64 MB in all."""
+    arrays = {k: v.detach() for k, v in out.items()}
+    for name, m in (("G_state", G), ("D_state", D)):
+        arrays[name] = torch.cat([t.detach().reshape(-1).float() for t in m.state_dict().values() if t.is_floating_point()])
+    res = {}
+    for name, t in arrays.items():
+        t = t.reshape(-1) if t.dtype == torch.float64 else t.float().reshape(-1)
+        n = DUMP_ARRAY_BYTES // t.element_size()
+        if t.numel() > n:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(t.numel(), (n,), generator=g).sort().values
+            res[name] = t[idx.to(t.device)].cpu().numpy()
+        else:
+            res[name] = t.reshape(arrays[name].shape).cpu().numpy()
+    assert sum(a.nbytes for a in res.values()) <= 64 << 20
+    return res
+
+
+def dump_outputs(arrays, dirpath):
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (default: BASELINE config 2)")
     ap.add_argument("--size", type=int, default=TILE)
@@ -110,7 +146,11 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="capture the train step in a hipGraph and replay it (tg_hip.graph; single GPU; pays off at small batches)")
     ap.add_argument("--prof-dump", default=None, help="write the per-launch table of the instrumented pass to this CSV")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0; see step_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     # before the first HIP call (torch.cuda.is_available() initialises the runtime): the host driver only supports dmabuf IPC
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -174,12 +214,14 @@ def main():
         gstep = GraphedTrainStep(G, D, crit, oG, oD, warmup=2)
 
     def run(k):
+        out = None
         for i in range(k):
             real, mask = batches[i % nb]
             if gstep is not None:
-                gstep(real, mask)
+                out = gstep(real, mask)
             else:
-                train_step(G, D, crit, oG, oD, real, mask, grad_sync=sync)
+                out = train_step(G, D, crit, oG, oD, real, mask, grad_sync=sync)
+        return out
 
     run(max(args.warmup, 3) if gstep is not None else args.warmup)      # the capture (3rd call) stays outside the timed region
     torch.cuda.synchronize()
@@ -187,7 +229,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(args.steps)
+    last = run(args.steps)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -197,6 +239,10 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        # copied before anything else runs: a graph replay overwrites `last`, the probe steps below update the weights
+        dump_outputs(step_outputs(last, G, D), args.dump_outputs)
+    del last
 
     if gstep is not None:
         gstep.flush()

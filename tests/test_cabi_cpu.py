@@ -113,6 +113,32 @@ def test_bench_input_recipe_matches_oracle_copy():
         assert torch.equal(a, a2) and torch.equal(m, m2)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: train_step's return dict and the updated G / D state as float .npy files, 64 MB at most,
+    large arrays as a fixed-seed sample (the same positions on every run)."""
+    import bench
+    from mvp_gan.src.models import Discriminator, PConvUNet
+    torch.manual_seed(0)
+    G, D = PConvUNet(), Discriminator()
+    out = {"gen": torch.randn(4, 1, 1280, 1024), "g_total": torch.tensor([0.5]), "d_loss": torch.tensor([0.25])}
+    a = bench.step_outputs(out, G, D)
+    b = bench.step_outputs(out, G, D)
+    assert sorted(a) == ["D_state", "G_state", "d_loss", "g_total", "gen"]
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+    assert a["g_total"].tolist() == [0.5]
+    n_g = sum(t.numel() for t in G.state_dict().values() if t.is_floating_point())
+    assert a["G_state"].size == bench.DUMP_ARRAY_BYTES // 4 < n_g                       # sampled
+    assert a["gen"].size == bench.DUMP_ARRAY_BYTES // 4 < out["gen"].numel()
+    assert np.isin(a["gen"], out["gen"].numpy()).all()
+    d_state = torch.cat([t.reshape(-1).float() for t in D.state_dict().values() if t.is_floating_point()])
+    assert np.array_equal(a["D_state"], d_state.numpy())                               # small enough: whole
+    bench.dump_outputs(a, str(tmp_path / "dump"))
+    for k in a:
+        assert np.array_equal(np.load(tmp_path / "dump" / (k + ".npy")), a[k])
+
+
 def test_vgg_trunk_weights_resolution(tmp_path, monkeypatch):
     """losses.py:31-34: the reference loads torchvision's ImageNet VGG16.  Offline that cannot work: the mirror must (i) RAISE
     unless the caller opts in to the stand-in trunk, (ii) load a local vgg16-format state-dict through

@@ -276,7 +276,7 @@ W16_WGRAD_CASES = [   # B, H, W, Cin, Cout, k, stride, pad
 
 
 @pytest.mark.parametrize("case", W16_WGRAD_CASES)
-def test_wino16_wgrad(dev, case):
+def test_wino16_wgrad(dev, case, tmp_path):
     import csv
     from tg_hip import lib as L, ops as O
     B, H, W, Cin, Cout, k, s_, pad = case
@@ -295,7 +295,7 @@ def test_wino16_wgrad(dev, case):
     dw, db = O.conv_wgrad(x.to(dev), dy.to(dev), w, k, s_, pad)
     torch.cuda.synchronize()
     lib.tg_prof_enable(0)
-    path = "/tmp/_w16g_%d.csv" % sum(case)
+    path = str(tmp_path / "launches.csv")
     assert lib.tg_prof_dump(path.encode()) == 0
     tags = [r["cfg"] for r in csv.DictReader(open(path))]
     for kind in (0, 1, 2, 3):
