@@ -136,6 +136,14 @@ int tg_conv_wgrad_bnin(const TgConv* g, const float* x, const TgBnAct* bn, const
 int tg_conv_dgrad_p(const TgConv* g, const float* dy, const float* w, const float* wprep, const float* in_mask,
                     const float* x_act, int act, float slope, float* dx, int accumulate, float* ws,
                     size_t ws_bytes, tg_stream_t stream);
+/* ReLU gates in one bit per element, for backward passes that need only act'(x) of a ReLU output (the frozen VGG trunk under
+ * activation checkpointing): a [rows][C] fp32 tensor -> bits [rows][C/32] uint32, bit c % 32 of word c / 32 = (a > 0) -- the
+ * predicate of the fused fp32 gate (-0.0 and NaN give 0).  C % 32 == 0; pointers 16-byte aligned. */
+int tg_relu_gate_pack(const float* a, int64_t rows, int C, uint32_t* bits, tg_stream_t stream);
+/* tg_conv_dgrad_p gated by such bits (gate_bits [B][H][W][Cin/32], Cin % 32 == 0) in place of x_act / act / slope: the same
+ * result bit for bit as the fp32 ReLU gate.  accumulate must be 0. */
+int tg_conv_dgrad_gbits(const TgConv* g, const float* dy, const float* w, const float* wprep, const float* in_mask,
+                        const uint32_t* gate_bits, float* dx, int accumulate, float* ws, size_t ws_bytes, tg_stream_t stream);
 
 /* Leave `cus` of the 256 CUs free in the launches that otherwise occupy every CU with one long-running workgroup (the
  * Winograd kernels): data-parallel runs set this so that RCCL's kernels on the communication stream can be scheduled

@@ -1632,9 +1632,11 @@ extern "C" size_t tg_conv_dgrad_ws_bytes(const TgConv* g) {
     return (wt + (want < cap ? want : cap)) * sizeof(float);
 }
 
+// gate_bits (tg_conv_dgrad_gbits): handed to the stride-1 3x3 Winograd launches, which set *gate_bits_done where their kernel read
+// them; every other route runs ungated and the caller applies the bits.  It steers the route like `gate` (no space-to-depth path).
 static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, float* wprep, int prep, const float* in_mask, float* dx,
                            int accumulate, const float* gate, int gate_act, float gate_slope, float* ws, size_t ws_bytes,
-                           tg_stream_t stream);
+                           tg_stream_t stream, const uint32_t* gate_bits = nullptr, int* gate_bits_done = nullptr);
 extern "C" int tg_conv_dgrad(const TgConv* g, const float* dy, const float* w, const float* in_mask, float* dx,
                              int accumulate, float* ws, size_t ws_bytes, tg_stream_t stream) {
     return conv_dgrad_impl(g, dy, w, nullptr, 0, in_mask, dx, accumulate, nullptr, 0, 0.f, ws, ws_bytes, stream);
@@ -1654,6 +1656,24 @@ extern "C" int tg_conv_dgrad_p(const TgConv* g, const float* dy, const float* w,
     const bool usable = wprep != nullptr && !(x_act != nullptr && g && s2d_ok(g));
     return conv_dgrad_impl(g, dy, w, usable ? const_cast<float*>(wprep) : nullptr, usable ? 1 : 0, in_mask, dx, accumulate, x_act,
                            act, slope, ws, ws_bytes, stream);
+}
+// tg_conv_dgrad_p with a ReLU gate of one bit per element (tg_relu_gate_pack of the activation) in place of the fp32 gate: the
+// same result bit for bit.  The pipelined Winograd kernels read the bits in their epilogue; every other launch is followed by
+// gate_bits_apply, the same final multiply as a pass of its own.
+extern "C" int tg_conv_dgrad_gbits(const TgConv* g, const float* dy, const float* w, const float* wprep, const float* in_mask,
+                                   const uint32_t* gate_bits, float* dx, int accumulate, float* ws, size_t ws_bytes, tg_stream_t stream) {
+    int rc = check_conv(g, "tg_conv_dgrad_gbits");
+    if (rc) return rc;
+    TG_REQUIRE(dy && w && gate_bits && dx && ws, "tg_conv_dgrad_gbits: null pointer");
+    TG_REQUIRE(!accumulate, "tg_conv_dgrad_gbits: a gated dgrad does not accumulate");
+    TG_REQUIRE(g->Cin % 32 == 0, "tg_conv_dgrad_gbits: needs Cin %% 32 == 0 (one gate word per 32 channels), got %d", g->Cin);
+    TG_REQUIRE((reinterpret_cast<uintptr_t>(gate_bits) & 15) == 0, "tg_conv_dgrad_gbits: pointers must be 16-byte aligned");
+    const bool usable = wprep != nullptr && !s2d_ok(g);     // (as tg_conv_dgrad_p's gated form: no space-to-depth path)
+    int done = 0;
+    rc = conv_dgrad_impl(g, dy, w, usable ? const_cast<float*>(wprep) : nullptr, usable ? 1 : 0, in_mask, dx, 0, nullptr, TG_ACT_NONE, 0.f,
+                         ws, ws_bytes, stream, gate_bits, &done);
+    if (rc || done) return rc;
+    return gate_bits_apply_launch(dx, gate_bits, (int64_t)g->B * g->H * g->W, g->Cin, (hipStream_t)stream);
 }
 extern "C" int tg_conv_wprep(const TgConv* g, int mode, const float* w, float* wprep, tg_stream_t stream) {
     TG_REQUIRE(g && w && wprep, "tg_conv_wprep: null pointer");
@@ -1691,14 +1711,14 @@ extern "C" int tg_conv_wprep_run(const void* items_dev, int n, tg_stream_t strea
 }
 static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, float* wprep, int prep, const float* in_mask, float* dx,
                            int accumulate, const float* gate, int gate_act, float gate_slope, float* ws, size_t ws_bytes,
-                           tg_stream_t stream) {
+                           tg_stream_t stream, const uint32_t* gate_bits, int* gate_bits_done) {
     int rc = check_conv(g, "tg_conv_dgrad");
     if (rc) return rc;
     TG_REQUIRE(w && (prep < 0 || (dy && dx && ws)), "tg_conv_dgrad: null pointer");
     TG_REQUIRE(aligned16(dy) && aligned16(w) && aligned16(dx) && aligned16(ws) && aligned16(wprep),
                "tg_conv_dgrad: pointers must be 16-byte aligned");
     TG_REQUIRE(prep == 0 || wprep != nullptr, "tg_conv_dgrad: prepared weights expected");
-    if (s2d_ok(g) && gate == nullptr && (prep < 0 || ws_bytes >= tg_conv_dgrad_ws_bytes(g))) {
+    if (s2d_ok(g) && gate == nullptr && gate_bits == nullptr && (prep < 0 || ws_bytes >= tg_conv_dgrad_ws_bytes(g))) {
         // dx2 = 3x3 stride-1 dgrad over the space-to-depth layout, then depth-to-space (+ mask, + accumulate)
         hipStream_t s2 = (hipStream_t)stream;
         const TgConv g2 = s2d_geom(g);
@@ -1729,7 +1749,8 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
         TG_CHECK_LAUNCH("d2s_kernel");
         return TG_OK;
     }
-    TG_REQUIRE(!(s2d_ok(g) && gate == nullptr && prep > 0), "tg_conv_dgrad: workspace too small for the prepared 5x5 stride-2 path");
+    TG_REQUIRE(!(s2d_ok(g) && gate == nullptr && gate_bits == nullptr && prep > 0),
+               "tg_conv_dgrad: workspace too small for the prepared 5x5 stride-2 path");
     const int taps = g->k * g->k;
     // head of the workspace = transposed / transformed weights unless the caller prepared them
     const size_t wt_floats = prep ? 0 : dgrad_wt_floats(g);
@@ -1755,7 +1776,12 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
         p.wino_u = wt;
         p.wino_ready = prep;
         p.wino4 = g->precision == TG_PREC_F32_WINO4;
-        if (wino44_ok(p)) return launch_wino44(p, s);
+        p.gate_bits = gate_bits;
+        if (wino44_ok(p)) {
+            rc = launch_wino44(p, s);
+            if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
+            return rc;
+        }
         size_t avail = ws2_floats;
         if (wino44_prepared_unusable(p)) {         // see conv_fwd_impl: F(4x4) image prepared, F(2x2) launch -> transform per call
             const size_t uf = dgrad_wt_floats(g);
@@ -1767,7 +1793,9 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
             avail -= uf;
         }
         TG_REQUIRE(p.bf16 ? wino16_ok(p) : wino_ok(p), "tg_conv_dgrad: internal: Winograd geometry predicate mismatch");
-        return p.bf16 ? launch_wino16(p, avail, s) : launch_wino(p, avail, s);
+        rc = p.bf16 ? launch_wino16(p, avail, s) : launch_wino(p, avail, s);
+        if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
+        return rc;
     }
     if (wino22_dgrad_geom_ok(g)) {
         // 4x4 stride 2: the four parity classes as Winograd F(2x2,2x2) problems in one launch (wino22.inc)

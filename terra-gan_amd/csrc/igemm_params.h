@@ -49,11 +49,19 @@ struct IGemmParams {
     unsigned char* pool_code;
     int pool_only;
     BnIn in_bn;             // (the 64 -> 1 channel LDS-patch kernel only: `final`, smallconv.hip)
+    // optional [dst pixels][N/32] words, bit c % 32 of word c / 32 = (ReLU output > 0) (tg_relu_gate_pack): a ReLU gate in one
+    // bit per element, exclusive with `gate`.  Read natively by the GBITS instantiations of the pipelined Winograd kernels (which
+    // set gate_bits_done); every other launch runs ungated and tg_conv_dgrad_gbits applies the bits afterwards (gate_bits_apply).
+    const uint32_t* gate_bits;
+    int gate_bits_done;
 };
 __device__ __forceinline__ float gate_factor(const IGemmParams& p, size_t idx) {
     const float gv = p.gate[idx];
     return gv > 0.f ? 1.f : (p.gate_act == TG_ACT_LEAKY ? p.gate_slope : 0.f);
 }
+
+// dx[row][c] *= bit c of the row's words: the multiply of gate_factor (ReLU) as a pass of its own (pointwise.hip)
+int gate_bits_apply_launch(float* dx, const uint32_t* bits, int64_t rows, int C, hipStream_t s);
 
 // Up to 4 independent problems in ONE launch (the parity classes of a stride-2 dgrad)
 struct IGemmMulti {

@@ -1609,6 +1609,52 @@ extern "C" int tg_maxpool2_bwd_code(const float* dout, const unsigned char* code
     TG_CHECK_LAUNCH("maxpool2_bwd_code_kernel");
     return TG_OK;
 }
+// ReLU gates in one bit per element (tg_relu_gate_pack).  With C % 32 == 0 the words of a row [C/32] are the rows' slice of a
+// FLAT bit array over the [rows][C] tensor: word w holds elements 32 w .. 32 w + 31.  A thread takes one 16-byte quad per trip
+// (coalesced: a wave reads 1 KB), forms its nibble with the predicate of gate_factor (a > 0: -0, NaN -> 0), and the eight lanes
+// of a word merge their nibbles by three xor-shuffles (groups of 8 lanes are active or inactive as a whole: n4 % 8 == 0).
+__global__ __launch_bounds__(256) void relu_gate_pack_kernel(const float* __restrict__ a, int64_t n4, uint32_t* __restrict__ bits) {
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < n4; idx += (int64_t)gridDim.x * 256) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(a + 4 * idx);
+        uint32_t w = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w |= (v[e] > 0.f ? 1u : 0u) << e;
+        w <<= 4 * (idx & 7);
+        w |= __shfl_xor(w, 1, 64);
+        w |= __shfl_xor(w, 2, 64);
+        w |= __shfl_xor(w, 4, 64);
+        if ((idx & 7) == 0) bits[idx >> 3] = w;
+    }
+}
+extern "C" int tg_relu_gate_pack(const float* a, int64_t rows, int C, uint32_t* bits, tg_stream_t stream) {
+    TG_REQUIRE(a && bits, "tg_relu_gate_pack: null pointer");
+    TG_REQUIRE(rows > 0 && C > 0 && (C % 32) == 0, "tg_relu_gate_pack: needs rows > 0 and C %% 32 == 0 (rows %lld, C %d)",
+               (long long)rows, C);
+    TG_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(bits)) & 15) == 0,
+               "tg_relu_gate_pack: pointers must be 16-byte aligned");
+    const int64_t n4 = rows * (C / 4);
+    hipLaunchKernelGGL(relu_gate_pack_kernel, dim3(ew_grid(n4, 256)), dim3(256), 0, S(stream), a, n4, bits);
+    TG_CHECK_LAUNCH("relu_gate_pack_kernel");
+    return TG_OK;
+}
+// dx *= (bit of the element ? 1 : 0): the gate multiply of a bit-gated dgrad whose conv launch ran ungated (tg_conv_dgrad_gbits);
+// the same single multiply the fused epilogues apply last, so the result is the same bit for bit
+__global__ __launch_bounds__(256) void gate_bits_apply_kernel(float* __restrict__ dx, const uint32_t* __restrict__ bits, int64_t n4) {
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < n4; idx += (int64_t)gridDim.x * 256) {
+        const uint32_t w = bits[idx >> 3] >> (4 * (idx & 7));
+        f32x4 o = *reinterpret_cast<const f32x4*>(dx + 4 * idx);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] *= (w >> e) & 1u ? 1.f : 0.f;
+        *reinterpret_cast<f32x4*>(dx + 4 * idx) = o;
+    }
+}
+int gate_bits_apply_launch(float* dx, const uint32_t* bits, int64_t rows, int C, hipStream_t s) {
+    TG_REQUIRE(dx && bits && rows > 0 && (C % 32) == 0, "gate_bits_apply: bad arguments");
+    const int64_t n4 = rows * (C / 4);
+    hipLaunchKernelGGL(gate_bits_apply_kernel, dim3(ew_grid(n4, 256)), dim3(256), 0, s, dx, bits, n4);
+    TG_CHECK_LAUNCH("gate_bits_apply_kernel");
+    return TG_OK;
+}
 extern "C" int tg_maxpool2_bwd(const float* dout, const float* x, int B, int H, int W, int C, int relu_gate, float* dx,
                                tg_stream_t stream) {
     TG_REQUIRE(dout && x && dx && B > 0 && H > 1 && W > 1 && C > 0, "tg_maxpool2_bwd: bad arguments");

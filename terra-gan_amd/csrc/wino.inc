@@ -602,7 +602,9 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_kernel(const IGemmParams p,
 // POOL: the 2x2 max-pool of the activated output goes out with it (p.pool_dst, VGG trunk conv1_2 / conv2_2): a 2x2 output tile IS a
 // pooling window -- its two columns are the two halves j of the epilogue (same lane), its two rows sit in the waves xh = 0 / 1, so the
 // xh = 1 wave hands its row maxima over through the exchange slot it has just consumed (no extra barrier) and the xh = 0 wave stores.
-template <bool GATED, bool STEAL, bool POOL = false>
+// GBITS (with GATED): the ReLU gate comes as p.gate_bits -- one dword per pixel and 32-channel group, shared by the 8 lanes of a
+// row of tile_rows4i, each of which takes its nibble (channels e_nb0 + 4 (lane & 7) .. + 3; e_nb0 is a multiple of 32 here).
+template <bool GATED, bool STEAL, bool POOL = false, bool GBITS = false>
 __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmParams p, const WinoGeom q, const float* __restrict__ U) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Vs = smem;                            // [2][16][64][8]
@@ -815,8 +817,19 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
             // lane offset of this half inside dst / gate ([pixel][N] floats), marker beyond the right edge
             const uint32_t e_voff = ci.ox0 + 2 * (lane >> 3) + j < p.OW
                                         ? ((e_lane_px + j * p.ds) * (uint32_t)p.N + 4 * (lane & 7)) * 4u : 0x80000000u;
-            f32x4 gq[GATED ? 4 : 1];
-            if constexpr (GATED) {
+            f32x4 gq[GATED && !GBITS ? 4 : 1];
+            uint32_t gw[GBITS ? 4 : 1];
+            if constexpr (GBITS) {
+                const int nw32 = p.N >> 5;
+                const auto brsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(p.gate_bits), 0, (int)((size_t)p.B * p.DH * p.DW * nw32 * 4), 0x00020000);
+                const uint32_t b_voff = ci.ox0 + 2 * (lane >> 3) + j < p.OW ? (e_lane_px + j * p.ds) * (uint32_t)nw32 * 4u : 0x80000000u;
+#pragma unroll
+                for (int t4 = 0; t4 < 4; ++t4) {
+                    const int row = min(e_row0 + 2 * t4, p.OH - 1);
+                    gw[t4] = __builtin_amdgcn_raw_buffer_load_b32(brsrc, b_voff, ((e_pix0 + row * e_pitch) * nw32 + (e_nb0 >> 5)) * 4, 0)
+                             >> (4 * (lane & 7));
+                }
+            } else if constexpr (GATED) {
                 const auto grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gate), 0, (int)((size_t)p.B * p.DH * p.DW * p.N * 4), 0x00020000);
 #pragma unroll
                 for (int t4 = 0; t4 < 4; ++t4) {
@@ -838,7 +851,10 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
                     f32x4 o = (v4 + bq) * rsq[j][t4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = o[e] > 0.f ? o[e] : o[e] * act_neg + 0.f;     // none / ReLU / leaky (act_neg = 1 / 0 / slope); + 0: ReLU gives +0
-                    if constexpr (GATED) {
+                    if constexpr (GBITS) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] *= (gw[t4] >> e) & 1u ? 1.f : 0.f;
+                    } else if constexpr (GATED) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] *= gq[t4][e] > 0.f ? 1.f : gate_neg;
                     }
@@ -985,12 +1001,13 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
     const bool pipe = fast && !no_pipe && nchunks - (p.splits - 1) * q.chunks_per_split >= 2 && q.chunks_per_split >= 2 &&
                       (size_t)p.B * p.DH * p.DW * p.N * 4 < ((size_t)1 << 31);
     typedef void (*WinoKern)(const IGemmParams, const WinoGeom, const float*);
-    static const WinoKern kerns[14] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
+    static const WinoKern kerns[16] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
                                        wino_kernel<true, true, false>, wino_pipe_kernel<false, false>, wino_pipe_kernel<true, false>,
                                        wino_kernel<false, false, true>, wino_kernel<false, true, true>, wino_kernel<true, false, true>,
                                        wino_kernel<true, true, true>, wino_pipe_kernel<false, true>, wino_pipe_kernel<true, true>,
-                                       wino_pipe_kernel<false, false, true>, wino_pipe_kernel<false, true, true>};
-    static LdsOptIn opts[14];
+                                       wino_pipe_kernel<false, false, true>, wino_pipe_kernel<false, true, true>,
+                                       wino_pipe_kernel<true, false, false, true>, wino_pipe_kernel<true, true, false, true>};
+    static LdsOptIn opts[16];
     q.qctr = wino_queue_block(s, p.splits, q.total_work);
     // the fused 2x2 max-pool: whole pooling windows inside the output, one split, the plain dst grid
     static const bool no_pool = getenv("TG_NO_FUSED_POOL") != nullptr;
@@ -999,7 +1016,11 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
     if (pool) p.pool_done = 1;
     TG_REQUIRE(pool || !(p.pool_code || p.pool_only), "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
     TG_REQUIRE(!p.pool_code || p.act == TG_ACT_RELU, "tg_conv_fwd_pool_code: needs a ReLU output");
-    const int ki = pool ? (q.qctr ? 13 : 12) : (q.qctr ? 6 : 0) + (pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0));
+    // bit gates (p.gate_bits): read by the pipelined kernel in one split; any other launch runs ungated and the caller applies them
+    const bool gbits = p.gate_bits != nullptr && pipe && p.splits == 1;
+    if (gbits) p.gate_bits_done = 1;
+    const int ki = gbits ? (q.qctr ? 15 : 14)
+                 : pool ? (q.qctr ? 13 : 12) : (q.qctr ? 6 : 0) + (pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0));
     if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds, "wino")) return rc;
     {
         const double flops = 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale;      // ALGORITHMIC flops of the convolution (direct form)

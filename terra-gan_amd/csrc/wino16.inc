@@ -330,7 +330,8 @@ __global__ __launch_bounds__(WINO_THREADS) void wino16_kernel(const IGemmParams 
 // transform lives in the image buffers of the step just consumed plus the patch area (output halves one after the other).
 // With 16-channel steps a 64-channel layer has FOUR steps per item: the prologue was a quarter of its time.
 // POOL: the 2x2 max-pool of the activated output is written with it, exactly as in wino_pipe_kernel<.., POOL> (wino.inc)
-template <bool GATED, bool POOL = false>
+// GBITS (with GATED): the ReLU gate as p.gate_bits, exactly as in wino_pipe_kernel<.., GBITS> (wino.inc)
+template <bool GATED, bool POOL = false, bool GBITS = false>
 __global__ __launch_bounds__(WINO_THREADS) void wino16_pipe_kernel(const IGemmParams p, const WinoGeom q, const __bf16* __restrict__ U) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __bf16* Vh = reinterpret_cast<__bf16*>(smem);              // [2][16][64][16]
@@ -524,8 +525,19 @@ __global__ __launch_bounds__(WINO_THREADS) void wino16_pipe_kernel(const IGemmPa
             }
             const uint32_t e_voff = ci.ox0 + 2 * (lane >> 3) + j < p.OW
                                         ? ((e_lane_px + j * p.ds) * (uint32_t)p.N + 4 * (lane & 7)) * 4u : 0x80000000u;
-            f32x4 gq[GATED ? 4 : 1];
-            if constexpr (GATED) {
+            f32x4 gq[GATED && !GBITS ? 4 : 1];
+            uint32_t gw[GBITS ? 4 : 1];
+            if constexpr (GBITS) {
+                const int nw32 = p.N >> 5;
+                const auto brsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(p.gate_bits), 0, (int)((size_t)p.B * p.DH * p.DW * nw32 * 4), 0x00020000);
+                const uint32_t b_voff = ci.ox0 + 2 * (lane >> 3) + j < p.OW ? (e_lane_px + j * p.ds) * (uint32_t)nw32 * 4u : 0x80000000u;
+#pragma unroll
+                for (int t4 = 0; t4 < 4; ++t4) {
+                    const int row = min(e_row0 + 2 * t4, p.OH - 1);
+                    gw[t4] = __builtin_amdgcn_raw_buffer_load_b32(brsrc, b_voff, ((e_pix0 + row * e_pitch) * nw32 + (e_nb0 >> 5)) * 4, 0)
+                             >> (4 * (lane & 7));
+                }
+            } else if constexpr (GATED) {
                 const auto grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gate), 0, (int)((size_t)p.B * p.DH * p.DW * p.N * 4), 0x00020000);
 #pragma unroll
                 for (int t4 = 0; t4 < 4; ++t4) {
@@ -547,7 +559,10 @@ __global__ __launch_bounds__(WINO_THREADS) void wino16_pipe_kernel(const IGemmPa
                     f32x4 o = (v4 + bq) * rsq[j][t4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f) + act_neg * fminf(o[e], 0.f);     // none / ReLU / leaky
-                    if constexpr (GATED) {
+                    if constexpr (GBITS) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] *= (gw[t4] >> e) & 1u ? 1.f : 0.f;
+                    } else if constexpr (GATED) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] *= gq[t4][e] > 0.f ? 1.f : gate_neg;
                     }
@@ -680,17 +695,20 @@ static int launch_wino16(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) 
     const bool pipe = fast && !no_pipe && nchunks - (p.splits - 1) * q.chunks_per_split >= 2 && q.chunks_per_split >= 2 &&
                       (size_t)p.B * p.DH * p.DW * p.N * 4 < ((size_t)1 << 31);       // (the epilogue's descriptors on dst / gate)
     typedef void (*W16Kern)(const IGemmParams, const WinoGeom, const __bf16*);
-    static const W16Kern kerns[7] = {wino16_kernel<false, false>, wino16_kernel<false, true>, wino16_kernel<true, false>,
+    static const W16Kern kerns[8] = {wino16_kernel<false, false>, wino16_kernel<false, true>, wino16_kernel<true, false>,
                                      wino16_kernel<true, true>, wino16_pipe_kernel<false>, wino16_pipe_kernel<true>,
-                                     wino16_pipe_kernel<false, true>};
-    static LdsOptIn opts[7];
+                                     wino16_pipe_kernel<false, true>, wino16_pipe_kernel<true, false, true>};
+    static LdsOptIn opts[8];
     static const bool no_pool = getenv("TG_NO_FUSED_POOL") != nullptr;
     const bool pool = p.pool_dst && !no_pool && pipe && !gated && p.splits == 1 && !(p.OH & 1) && !(p.OW & 1) && p.ds == 1 && p.dy0 == 0 &&
                       p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && !p.accumulate;
     if (pool) p.pool_done = 1;
     TG_REQUIRE(pool || !(p.pool_code || p.pool_only), "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
     TG_REQUIRE(!p.pool_code || p.act == TG_ACT_RELU, "tg_conv_fwd_pool_code: needs a ReLU output");
-    const int ki = pool ? 6 : pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0);
+    // bit gates: the pipelined kernel in one split reads them, any other launch runs ungated (see launch_wino)
+    const bool gbits = p.gate_bits != nullptr && pipe && p.splits == 1;
+    if (gbits) p.gate_bits_done = 1;
+    const int ki = gbits ? 7 : pool ? 6 : pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0);
     const size_t lds_bytes = pipe ? W16_PIPE_LDS_BYTES : W16_LDS_BYTES;
     if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds_bytes, "wino16")) return rc;
     {

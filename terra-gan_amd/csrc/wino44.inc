@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void wino44_weights_kernel(const float* __rest
     wino44_weights_body(w, U, N, K, ww);
 }
 
-template <bool GATED>
+// GBITS (with GATED): the ReLU gate as p.gate_bits, one dword per pixel and 32-channel group (e_nb0 = n0 + 32 nh, n0 a multiple
+// of 64), each lane of a row of tile_rows4i taking its nibble -- as in wino_pipe_kernel<.., GBITS> (wino.inc)
+template <bool GATED, bool GBITS = false>
 __global__ __launch_bounds__(WINO_THREADS) void wino44_kernel(const IGemmParams p, const Wino44Geom q, const float* __restrict__ U) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Vs = smem;                          // [2][36][2][32][4]
@@ -338,8 +340,19 @@ __global__ __launch_bounds__(WINO_THREADS) void wino44_kernel(const IGemmParams 
             const int di = px >> 1, dj = px & 1;
             const uint32_t e_voff = e_lane_ox + dj < p.OW ? e_lane : 0x80000000u;
             const int e_row0 = e_oy0 + 2 * ah + di;                              // + 4 * t4
-            f32x4 gq[GATED ? 4 : 1];
-            if constexpr (GATED) {       // the gate quads of this pixel position ahead of its stores (vmcnt counts stores too)
+            f32x4 gq[GATED && !GBITS ? 4 : 1];
+            uint32_t gw[GBITS ? 4 : 1];
+            if constexpr (GBITS) {       // the gate words of this pixel position ahead of its stores
+                const int nw32 = p.N >> 5;
+                const auto brsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(p.gate_bits), 0, (int)((size_t)p.B * p.DH * p.DW * nw32 * 4), 0x00020000);
+                const uint32_t b_voff = e_lane_ox + dj < p.OW ? (uint32_t)(4 * (lane >> 3) * p.ds * nw32) * 4u : 0x80000000u;
+#pragma unroll
+                for (int t4 = 0; t4 < 4; ++t4) {
+                    const int row = min(e_row0 + 4 * t4, p.OH - 1);
+                    gw[t4] = __builtin_amdgcn_raw_buffer_load_b32(brsrc, b_voff, ((e_pix0 + row * e_pitch + dj * p.ds) * nw32 + (e_nb0 >> 5)) * 4, 0)
+                             >> (4 * (lane & 7));
+                }
+            } else if constexpr (GATED) {       // the gate quads of this pixel position ahead of its stores (vmcnt counts stores too)
                 const auto grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.gate), 0, (int)((size_t)p.B * p.DH * p.DW * p.N * 4), 0x00020000);
 #pragma unroll
                 for (int t4 = 0; t4 < 4; ++t4) {
@@ -358,7 +371,10 @@ __global__ __launch_bounds__(WINO_THREADS) void wino44_kernel(const IGemmParams 
                 f32x4 o = v4 + bq;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = fmaxf(o[e], 0.f) + act_neg * fminf(o[e], 0.f);         // none / ReLU / leaky
-                if constexpr (GATED) {
+                if constexpr (GBITS) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] *= (gw[t4] >> e) & 1u ? 1.f : 0.f;
+                } else if constexpr (GATED) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] *= gq[t4][e] > 0.f ? 1.f : gate_neg;
                 }
@@ -428,16 +444,19 @@ static int launch_wino44(IGemmParams& p, hipStream_t s) {
     if (p.wino_ready < 0) return TG_OK;
     const size_t lds = (size_t)W4_LDS_FLOATS * sizeof(float);
     const bool gated = p.gate != nullptr;
+    const bool gbits = p.gate_bits != nullptr;      // (one split always: the bits are read here)
+    if (gbits) p.gate_bits_done = 1;
+    const int ki = gbits ? 2 : gated ? 1 : 0;
     typedef void (*Kern)(const IGemmParams, const Wino44Geom, const float*);
-    static const Kern kerns[2] = {wino44_kernel<false>, wino44_kernel<true>};
-    static LdsOptIn opts[2];
-    if (int rc = lds_opt_in(opts[gated], reinterpret_cast<const void*>(kerns[gated]), lds, "wino44")) return rc;
+    static const Kern kerns[3] = {wino44_kernel<false>, wino44_kernel<true>, wino44_kernel<true, true>};
+    static LdsOptIn opts[3];
+    if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds, "wino44")) return rc;
     {
         const double flops = 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale;
         const double bytes = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.N * p.Ktot + (double)p.M * p.N);
         ProfScope ps(s, 0, flops, bytes, p.M, p.N, p.Ktot, p.C, 1, 4044);
         const int grid = q.total_work < wino_cus() ? q.total_work : wino_cus();
-        hipLaunchKernelGGL(kerns[gated], dim3(grid), dim3(WINO_THREADS), lds, s, p, q, (const float*)p.wino_u);
+        hipLaunchKernelGGL(kerns[ki], dim3(grid), dim3(WINO_THREADS), lds, s, p, q, (const float*)p.wino_u);
     }
     TG_CHECK_LAUNCH("wino44_kernel");
     return TG_OK;

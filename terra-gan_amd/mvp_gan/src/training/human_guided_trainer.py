@@ -31,9 +31,10 @@ def human_guided_step(generator, criterion, optimizer, images, masks, human_mask
     GP = generator._tensors()
     img, mask = as_bhw(images, "human_guided_step"), as_bhw(masks, "human_guided_step")
     B, H, W = img.shape
-    gen, gctx = E.generator_forward(GP, O.mul(img, mask), mask, generator.training)
+    ckpt = getattr(generator, "activation_checkpointing", False)
+    gen, gctx = E.generator_forward(GP, O.mul(img, mask), mask, generator.training, checkpoint=ckpt)
     wb, wh = criterion.base_loss_weight, criterion.human_feedback_weight
-    total, _parts, dgen = criterion_forward(criterion, gen, img, mask, want_grad=True, scale=wb)
+    total, _parts, dgen = criterion_forward(criterion, gen, img, mask, want_grad=True, scale=wb, checkpoint=ckpt)
     if human_masks is not None:
         h = (as_bhw(human_masks, "human_guided_step") > 0).float()          # losses.py:168
         out5, _ = O.pixel_losses(gen, img, h, wh, 0.0, wh * max(criterion.boundary_weight, 0.0), l1_weight=h, dpred=dgen,

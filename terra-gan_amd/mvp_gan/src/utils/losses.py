@@ -128,10 +128,13 @@ class _PixelLossFn(torch.autograd.Function):
         return dp.reshape(ctx.shape), None, None, None, None, None, None, None
 
 
-def criterion_forward(crit, pred, target, mask, want_grad, gscale=None, l1_weight=None, w_l1=1.0, scale=1.0, both=None):
+def criterion_forward(crit, pred, target, mask, want_grad, gscale=None, l1_weight=None, w_l1=1.0, scale=1.0, both=None,
+                      checkpoint=False):
     """Fused value(+gradient) of InpaintingLoss on [B][H][W] tensors.
     Returns (total 1-elem tensor, parts dict of 1-elem tensors, dpred or None).  `scale` multiplies
-    the whole loss (HumanGuidedLoss's base_loss_weight)."""
+    the whole loss (HumanGuidedLoss's base_loss_weight).  checkpoint (activation checkpointing, with want_grad): the VGG trunk
+    keeps only bit-packed ReLU gates of the prediction half and its pool codes for the backward (vgg_forward(keep="gates")),
+    not its fp32 activations -- the same values bit for bit."""
     w_p, w_tv, w_b = crit.perceptual_weight, crit.tv_weight, crit.boundary_weight
     out5, dp = O.pixel_losses(pred, target, mask, w_l1 * scale, max(w_tv, 0.0) * scale, max(w_b, 0.0) * scale,
                               l1_weight=l1_weight, gscale=gscale, want_grad=want_grad, eps=crit.boundary_loss.epsilon)
@@ -144,7 +147,7 @@ def criterion_forward(crit, pred, target, mask, want_grad, gscale=None, l1_weigh
             both = torch.empty((2 * B,) + tuple(pred.shape[1:]), dtype=pred.dtype, device=pred.device)
             both[:B].copy_(pred)        # device-to-device memcpy (plumbing)
             both[B:].copy_(target)
-        feats, vctx = E.vgg_forward(V, both, keep=want_grad)
+        feats, vctx = E.vgg_forward(V, both, keep=("gates" if checkpoint else True) if want_grad else False, nb=B)
         fp, ft = feats[:B], feats[B:]
         # (the features are ReLU outputs: the L1 gradient comes out already gated by features[15])
         perc, dfeat = O.l1_mean(fp, ft, w_p * scale, gscale=gscale, want_grad=want_grad, relu_gate=True)

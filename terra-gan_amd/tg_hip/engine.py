@@ -472,10 +472,18 @@ def discriminator_replay_running_stats(P, ctx, order=(0,)):
 # --------------------------------------------------------------------------------------------------
 # frozen VGG16 trunk (features[:16]) on a 1-channel image repeated x3 (losses.py:79-90)
 # --------------------------------------------------------------------------------------------------
-def vgg_forward(V, img, keep=True, wino4=None):
+def vgg_forward(V, img, keep=True, wino4=None, nb=None):
     """V: {'0.weight','0.bias',...,'0.folded'}; img [B][H][W].  Returns (features, ctx).
     wino4 (forward kernels): None = F(2x2,3x3) unless TG_VGG_WINO4_FWD=1 (see the note at the top of this file); True / False
-    force F(4x4,3x3) on (wherever the geometry allows) / off."""
+    force F(4x4,3x3) on (wherever the geometry allows) / off.
+    keep: what the context holds for vgg_backward.  True: every conv's ReLU output (fp32, all B images).  False: nothing
+    (no backward).  "gates" (activation checkpointing): the trunk is frozen, so its backward needs only the weights, the ReLU gate
+    of each conv output that the next conv's dgrad is gated by -- kept as relu_gate_pack bits of the first `nb` images (None: all),
+    1/32 of the fp32 bytes over nb of B images -- and the pool codes; no full-resolution fp32 activation is retained, the trunk's
+    output (features[15]) included, so vgg_backward then needs gated=True.  Where the pool-code path does not take a pooled conv
+    (odd sizes, TG_NO_POOL_CODE=1, F(4x4) forward) its pool keeps today's input tensor (all B images, fp32)."""
+    gates = keep == "gates"
+    assert keep in (True, False) or gates, keep
     h = img.reshape(*img.shape, 1)
     steps = []
     pooled = code = None
@@ -484,7 +492,7 @@ def vgg_forward(V, img, keep=True, wino4=None):
             # (the conv below has written the pooled tensor with its own output where the sizes are even)
             o = pooled if pooled is not None else O.maxpool2_fwd(h)
             if keep:
-                steps.append(NS(kind="M", x=h, code=code))
+                steps.append(NS(kind="M", x=h if (code is None or not gates) else None, code=code))
             pooled = code = None
         else:
             w = V["0.folded"] if item == 0 else V[f"{item}.weight"]
@@ -500,7 +508,11 @@ def vgg_forward(V, img, keep=True, wino4=None):
                 o = O.conv_fwd(h, w, V[f"{item}.bias"], 3, 1, 1, act=O.ACT_RELU, pool=pool, wino4=w4)
                 if pool:
                     o, pooled = o
-            if keep:
+            if gates:
+                # the input of the next conv (no pool between): its dgrad is gated by this output's ReLU
+                feeds = i + 1 < len(VGG_TRUNK) and VGG_TRUNK[i + 1] != "M"
+                steps.append(NS(kind="C", w=w, x_shape=tuple(h.shape), a=None, bits=O.relu_gate_pack(o, nb) if feeds else None))
+            elif keep:
                 steps.append(NS(kind="C", w=w, x_shape=tuple(h.shape), a=o))
         h = o
     return h, NS(steps=steps)
@@ -525,11 +537,18 @@ def vgg_backward(ctx, dfeat, nb=None, wino4=None, gated=False):
             gated = True
         else:
             a = None if st.a is None else (st.a if nb is None else st.a[:nb])      # (None: a pooled conv under the pool-code path)
+            if not gated and a is None:
+                raise ValueError("vgg_backward: this context keeps no activation of the trunk's output: pass gated=True")
             dy = da if gated else O.act_bwd(da, a, O.ACT_RELU)
             shp = st.x_shape if nb is None else (nb,) + tuple(st.x_shape[1:])
             below = steps[i - 1] if i > 0 else None
             O.tag(f"vgg{VGG_TRUNK[i]}.dgrad")
-            if below is not None and below.kind == "C":      # input of this conv = ReLU output of the conv below
+            if below is not None and below.kind == "C" and getattr(below, "bits", None) is not None:    # keep="gates"
+                assert below.bits.shape[0] == shp[0], "vgg_backward: the gate bits were packed for another number of images"
+                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, gate_bits=below.bits,
+                                  wino4=_vgg_wino4(st.w, shp[0], shp[1], shp[2], shp[3], w4, VGG_WINO4))
+                gated = True
+            elif below is not None and below.kind == "C":    # input of this conv = ReLU output of the conv below
                 ga = below.a if nb is None else below.a[:nb]
                 da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, gate=ga, gate_act=O.ACT_RELU,
                                   wino4=_vgg_wino4(st.w, shp[0], shp[1], shp[2], shp[3], w4, VGG_WINO4))

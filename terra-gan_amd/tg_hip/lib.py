@@ -64,6 +64,8 @@ SIGNATURES = {
     "tg_conv_fwd_bnin": (I, [CP, P, C.POINTER(TgBnAct), P, P, I, F, P, P, SZ, P]),
     "tg_conv_wgrad_bnin": (I, [CP, P, C.POINTER(TgBnAct), P, P, P, P, SZ, P]),
     "tg_conv_dgrad_p": (I, [CP, P, P, P, P, P, I, F, P, I, P, SZ, P]),
+    "tg_relu_gate_pack": (I, [P, I64, I, P, P]),
+    "tg_conv_dgrad_gbits": (I, [CP, P, P, P, P, P, P, I, P, SZ, P]),
     "tg_conv_wgrad_ws_bytes": (SZ, [CP]),
     "tg_conv_wgrad": (I, [CP, P, P, P, P, P, P, SZ, P]),
     "tg_fold_cin": (I, [P, I, I, I, P, P]),

@@ -292,9 +292,23 @@ def maxpool2_bwd_code(dout, code):
     return dx
 
 
-def conv_dgrad(dy, w, x_shape, k, stride, pad, in_mask=None, out=None, gate=None, gate_act=ACT_RELU, gate_slope=0.0, wino4=False):
+def relu_gate_pack(a, nb=None):
+    """ReLU gates of the first `nb` images of an NHWC activation [B][H][W][C] (C % 32 == 0) in one bit per element:
+    uint32 [nb][H][W][C/32], bit c % 32 of word c / 32 = (a > 0) -- the predicate of conv_dgrad's fp32 gate (tg_relu_gate_pack)."""
+    _chk(a, "a")
+    B, H, W, Cc = a.shape
+    nb = B if nb is None else nb
+    assert 0 < nb <= B, (nb, B)
+    bits = torch.empty((nb, H, W, Cc // 32), dtype=torch.uint32, device=a.device)
+    L.check(_lib().tg_relu_gate_pack(_p(a), nb * H * W, Cc, C.c_void_p(bits.data_ptr()), _stream()), "tg_relu_gate_pack")
+    return bits
+
+
+def conv_dgrad(dy, w, x_shape, k, stride, pad, in_mask=None, out=None, gate=None, gate_act=ACT_RELU, gate_slope=0.0, wino4=False,
+               gate_bits=None):
     """dx for an input of shape x_shape=[B,H,W,Cin]; accumulates into `out` when given.  `gate` = output of the
-    activation that produced x: its backward is fused into the epilogue (dx *= act'(gate))."""
+    activation that produced x: its backward is fused into the epilogue (dx *= act'(gate)).  `gate_bits` = relu_gate_pack of a
+    ReLU output in place of `gate` (exclusive with it): the same dx bit for bit (tg_conv_dgrad_gbits)."""
     _chk(dy, "dy"); _chk(in_mask, "in_mask"); _chk(out, "out"); _chk(gate, "gate")
     wv = weight_view(w)
     B, H, W, Cin = x_shape
@@ -303,6 +317,14 @@ def conv_dgrad(dy, w, x_shape, k, stride, pad, in_mask=None, out=None, gate=None
     dx = out if out is not None else empty(B, H, W, Cin, like=dy)
     lib = _lib()
     ws = workspace(lib.tg_conv_dgrad_ws_bytes(C.byref(g)))
+    if gate_bits is not None:
+        assert gate is None and out is None, "conv_dgrad: gate_bits is exclusive with gate and does not accumulate"
+        assert gate_bits.dtype == torch.uint32 and gate_bits.is_contiguous() and tuple(gate_bits.shape) == (B, H, W, Cin // 32), \
+            (gate_bits.dtype, tuple(gate_bits.shape), tuple(x_shape))
+        L.check(lib.tg_conv_dgrad_gbits(C.byref(g), _p(dy), _p(wv), _p(_prepared(w, wv, g, WPREP_DGRAD)), _p(in_mask),
+                                        C.c_void_p(gate_bits.data_ptr()), _p(dx), 0, _p(ws), ws.numel() * 4, _stream()),
+                "tg_conv_dgrad_gbits")
+        return dx
     if gate is not None:
         assert out is None and tuple(gate.shape) == tuple(x_shape)
     L.check(lib.tg_conv_dgrad_p(C.byref(g), _p(dy), _p(wv), _p(_prepared(w, wv, g, WPREP_DGRAD)), _p(in_mask), _p(gate),
