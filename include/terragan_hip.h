@@ -402,6 +402,35 @@ int tg_quality_metrics(const float* pred, const float* target, const float* mask
 int tg_u8_to_tiles(const uint8_t* img_u8, const uint8_t* mask_u8, int64_t n, float* img_f32, float* mask_f32,
                    tg_stream_t stream);
 
+/* ---- whole-raster inpainting (mvp_gan/src/inpaint_raster.py; no reference counterpart: the reference quantises each source
+ * grid to a uint8 512^2 PNG and never reassembles the tiles, utils/data_extraction.py:60-115, main_pipeline.py:497-530) ----
+ * A float32 DSM [H][W] in metres is cut into overlapping windows of wh x ww.  Per axis the window starts are min(i*s, N-w),
+ * i = 0..n-1, with s = w - overlap and n = ceil((N - w) / s) + 1; window index = iy * nx + ix.  A pixel is KNOWN when
+ * mask != 0 (mask may be NULL), it is finite, and (use_nodata) it differs from nodata. */
+typedef struct TgRasterPlan {
+    int32_t H, W;           /* raster */
+    int32_t wh, ww;         /* window sides, 1 <= wh <= H, 1 <= ww <= W */
+    int32_t overlap;        /* 0 <= overlap < min(wh, ww) */
+    int32_t ny, nx;         /* window grid; must equal the formula above */
+} TgRasterPlan;
+
+/* Per window: lo / hi = min / max over its known pixels (0 / 0 when it has none; a -0 extreme is stored as +0),
+ * counts[2*win] = known pixels, counts[2*win+1] = holes.  lo, hi: [ny*nx]; counts: [ny*nx][2].  Deterministic. */
+int tg_raster_window_stats(const float* dem, const float* mask, const TgRasterPlan* plan, int use_nodata, float nodata,
+                           float* lo, float* hi, int32_t* counts, tg_stream_t stream);
+/* Network input of the windows win_idx[0..n) (device int32, 1 <= n <= 65535): x[j] = known ? (z - lo) / (hi - lo) : 0 (IEEE
+ * fp32; 0 when hi == lo), m[j] = known; x, m: [n][wh][ww]. */
+int tg_raster_gather(const float* dem, const float* mask, const TgRasterPlan* plan, int use_nodata, float nodata,
+                     const float* lo, const float* hi, const int32_t* win_idx, int n, float* x, float* m, tg_stream_t stream);
+/* Composite raster out [H][W]: known pixels are copied bit for bit; a hole gets sum_j w_j * (lo_j + o_j * (hi_j - lo_j)) /
+ * sum_j w_j over the covering windows j with run_of_window[j] = k >= 0 (their generator output o_j = wout[k], wout:
+ * [n_run][wh][ww]), summed window row ascending, then column.  w = r_y * r_x, r(t) = min(1, (t+0.5)/overlap,
+ * (w-t-0.5)/overlap) (1 when overlap == 0) with the ramp of a side on the raster border replaced by 1.  A hole no running
+ * window covers is NaN and counted in *unfilled (device int32, zeroed by the call).  No float atomics: bitwise deterministic. */
+int tg_raster_blend(const float* dem, const float* mask, const TgRasterPlan* plan, int use_nodata, float nodata,
+                    const float* lo, const float* hi, const int32_t* run_of_window, const float* wout, int n_run, float* out,
+                    int32_t* unfilled, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

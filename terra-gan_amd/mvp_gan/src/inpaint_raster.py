@@ -1,0 +1,225 @@
+"""Inpaint a whole DSM raster: overlapping windows, per-window min-max over the known pixels, generator in eval mode,
+results blended back in metres on the GPU (csrc/raster.hip).
+
+The reference cannot do this: it min-max scales each source grid to a uint8 512^2 PNG, losing the absolute heights
+(utils/data_extraction.py:60-115), and never reassembles the tiles (main_pipeline.py:497-530).
+
+Semantics:
+  - known pixel: mask != 0 (if a mask is given; 1 = keep, 0 = hole), finite, and != nodata (if given);
+  - window plan per axis: w = min(window, N), s = w - overlap, starts 0, s, 2s, ... with the last clamped to N - w;
+  - per window lo / hi = min / max over its known pixels; network input x = (z - lo) / (hi - lo) at known pixels, 0 at
+    holes (0 everywhere when hi == lo); output in metres lo + out * (hi - lo);
+  - only windows with >= 1 known pixel and >= 1 hole run through the generator;
+  - a hole gets sum_j w_j * metres_j / sum_j w_j over the running windows covering it (window row, then column), with
+    w = r_y * r_x, r(t) = min(1, (t+0.5)/overlap, (w-t-0.5)/overlap) and the ramp of a raster-border side replaced by 1;
+  - known pixels are returned bit for bit; a hole no running window covers is NaN and counted in info["unfilled"].
+
+CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --checkpoint ck.pth --out out.asc
+"""
+import argparse
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+MIN_SIDE = 40          # smallest window side the generator is tested at (fixture g72x40b3)
+
+Plan = namedtuple("Plan", "H W wh ww overlap ys xs")
+
+
+def _axis_starts(N, w, overlap):
+    s = w - overlap
+    n = -(-(N - w) // s) + 1
+    return [min(i * s, N - w) for i in range(n)]
+
+
+def plan_windows(H, W, window=512, overlap=64):
+    """Host-only window plan: Plan(H, W, wh, ww, overlap, ys, xs), window (iy, ix) covering
+    rows ys[iy] .. ys[iy] + wh and columns xs[ix] .. xs[ix] + ww."""
+    H, W, window, overlap = int(H), int(W), int(window), int(overlap)
+    if H < 1 or W < 1:
+        raise ValueError(f"plan_windows: empty raster {H}x{W}")
+    wh, ww = min(window, H), min(window, W)
+    if min(wh, ww) < MIN_SIDE:
+        raise ValueError(f"plan_windows: window {wh}x{ww} (raster {H}x{W}, window {window}) has a side below {MIN_SIDE} px")
+    if not 0 <= overlap < min(wh, ww):
+        raise ValueError(f"plan_windows: overlap {overlap} must be in [0, {min(wh, ww)}) for window {wh}x{ww}")
+    return Plan(H, W, wh, ww, overlap, _axis_starts(H, wh, overlap), _axis_starts(W, ww, overlap))
+
+
+def window_ramp(w, overlap, first=False, last=False):
+    """1-D blend weight r(t), t = 0..w-1 (float64); `first` / `last`: that side of the window lies on the raster border."""
+    t = np.arange(w, dtype=np.float64)
+    r = np.ones(w, dtype=np.float64)
+    if overlap > 0:
+        if not first:
+            r = np.minimum(r, (t + 0.5) / overlap)
+        if not last:
+            r = np.minimum(r, (w - t - 0.5) / overlap)
+    return r
+
+
+# ---- ESRI ASCII grid ------------------------------------------------------------------------------------------------
+_ASC_KEYS = ("ncols", "nrows", "xllcorner", "xllcenter", "yllcorner", "yllcenter", "cellsize", "nodata_value")
+
+
+def read_asc(path):
+    """-> (float32 array [nrows][ncols], header): header is a list of (key, value string) in file order, kept verbatim
+    so that write_asc reproduces it."""
+    header = []
+    with open(path) as f:
+        lines = f.readlines()
+    i = 0
+    while i < len(lines):
+        tok = lines[i].split()
+        if len(tok) == 2 and tok[0].lower() in _ASC_KEYS:
+            header.append((tok[0], tok[1]))
+            i += 1
+        else:
+            break
+    keys = {k.lower() for k, _ in header}
+    if not {"ncols", "nrows", "cellsize"} <= keys or not (keys & {"xllcorner", "xllcenter"}) or \
+            not (keys & {"yllcorner", "yllcenter"}):
+        raise ValueError(f"{path}: not an ESRI ASCII grid (header {header})")
+    nrows, ncols = int(asc_value(header, "nrows")), int(asc_value(header, "ncols"))
+    vals = np.array(" ".join(lines[i:]).split(), dtype=np.float32)
+    if vals.size != nrows * ncols:
+        raise ValueError(f"{path}: {vals.size} values for a {nrows}x{ncols} grid")
+    return vals.reshape(nrows, ncols), header
+
+
+def asc_value(header, key, default=None):
+    for k, v in header:
+        if k.lower() == key.lower():
+            return v
+    return default
+
+
+def asc_nodata(header):
+    v = asc_value(header, "NODATA_value")
+    return None if v is None else float(v)
+
+
+def write_asc(path, arr, header):
+    """Write [nrows][ncols] values under `header` (as read_asc returns it).  float32 values are written with 9
+    significant digits (they read back bit for bit); NaN is written as the header's NODATA_value when it has one."""
+    arr = np.asarray(arr, dtype=np.float32)
+    nrows, ncols = int(asc_value(header, "nrows")), int(asc_value(header, "ncols"))
+    if arr.shape != (nrows, ncols):
+        raise ValueError(f"write_asc: array {arr.shape} does not match the header's {nrows}x{ncols}")
+    nd = asc_value(header, "NODATA_value")
+    with open(path, "w") as f:
+        for k, v in header:
+            f.write(f"{k} {v}\n")
+        for row in arr:
+            txt = ["%.9g" % v for v in row.tolist()]
+            if nd is not None:
+                txt = [nd if t == "nan" else t for t in txt]
+            f.write(" ".join(txt) + "\n")
+
+
+# ---- GPU path -------------------------------------------------------------------------------------------------------
+def _load_generator(generator_or_checkpoint, device):
+    from .models.generator import PConvUNet
+    if isinstance(generator_or_checkpoint, PConvUNet):
+        return generator_or_checkpoint
+    generator = PConvUNet().to(device)                          # as evaluate() loads it
+    ckpt = torch.load(generator_or_checkpoint, map_location=device)
+    generator.load_state_dict(ckpt["generator_state_dict"] if isinstance(ckpt, dict) and "generator_state_dict" in ckpt else ckpt)
+    return generator
+
+
+def _to_device_f32(a, device, what, binary=False):
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError(f"inpaint_raster: {what} is on {a.device}; pass a numpy array or a HIP tensor")
+        if binary and a.dtype != torch.float32:
+            a = a != 0
+        return a.to(device=device, dtype=torch.float32).contiguous()
+    a = np.asarray(a)
+    if binary:
+        a = a != 0
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+@torch.no_grad()
+def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16):
+    """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
+    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled)."""
+    from tg_hip import engine as E
+    from tg_hip import ops as O
+    if not torch.cuda.is_available():
+        raise RuntimeError("inpaint_raster: no HIP device visible; this build has no CPU path")
+    if batch < 1:
+        raise ValueError(f"inpaint_raster: batch {batch} < 1")
+    device = torch.device("cuda", torch.cuda.current_device())
+    z = _to_device_f32(dem, device, "dem")
+    if z.dim() != 2:
+        raise ValueError(f"inpaint_raster: dem must be [H, W], got {tuple(z.shape)}")
+    m = None if mask is None else _to_device_f32(mask, device, "mask", binary=True)
+    if m is not None and m.shape != z.shape:
+        raise ValueError(f"inpaint_raster: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
+    pl = plan_windows(*z.shape, window=window, overlap=overlap)
+    cp = O.raster_plan(pl.H, pl.W, pl.wh, pl.ww, pl.overlap, len(pl.ys), len(pl.xs))
+    nwin = len(pl.ys) * len(pl.xs)
+    if nodata is not None and math.isnan(nodata):
+        nodata = None                                           # NaN is never a value: non-finite pixels are holes already
+
+    lo, hi, counts = O.raster_window_stats(z, m, cp, nodata)
+    c = counts.cpu().numpy()                                    # the one host sync before the result
+    run = np.flatnonzero((c[:, 0] > 0) & (c[:, 1] > 0)).astype(np.int32)
+    run_of = np.full(nwin, -1, dtype=np.int32)
+    run_of[run] = np.arange(run.size, dtype=np.int32)
+    run_of_d = torch.from_numpy(run_of).to(device)
+
+    wout = torch.empty(run.size, pl.wh, pl.ww, dtype=torch.float32, device=device)
+    if run.size:
+        P = _load_generator(generator_or_checkpoint, device)._tensors()
+        run_d = torch.from_numpy(run).to(device)
+        nb = min(batch, run.size)
+        xb = torch.empty(nb, pl.wh, pl.ww, dtype=torch.float32, device=device)
+        mb = torch.empty_like(xb)
+        for b0 in range(0, run.size, nb):
+            b1 = min(b0 + nb, run.size)
+            x, mk = O.raster_gather(z, m, cp, lo, hi, run_d[b0:b1], nodata, x=xb[:b1 - b0], m=mb[:b1 - b0])
+            E.generator_forward(P, x, mk, training=False, out=wout[b0:b1])
+    out, unfilled = O.raster_blend(z, m, cp, lo, hi, run_of_d, wout, nodata)
+    return out, {"windows": nwin, "run": int(run.size), "unfilled": int(unfilled.item())}
+
+
+# ---- CLI ------------------------------------------------------------------------------------------------------------
+def _read_mask(path, shape):
+    if path.lower().endswith(".asc"):
+        mk, _ = read_asc(path)
+    else:
+        from PIL import Image
+        mk = np.asarray(Image.open(path).convert("L"))
+    if mk.shape != shape:
+        raise ValueError(f"mask {path} is {mk.shape[0]}x{mk.shape[1]}, the raster {shape[0]}x{shape[1]} (no resizing)")
+    return mk != 0
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Inpaint the holes of an ESRI ASCII grid DSM with a TERRA-GAN generator.")
+    ap.add_argument("--dem", required=True, help="input .asc raster (NODATA_value cells are holes)")
+    ap.add_argument("--mask", help="optional mask (.png or .asc) of the raster's size: nonzero = keep, 0 = hole")
+    ap.add_argument("--checkpoint", required=True, help="generator checkpoint (.pth), loaded as evaluate() does")
+    ap.add_argument("--out", required=True, help="output .asc raster")
+    ap.add_argument("--window", type=int, default=512)
+    ap.add_argument("--overlap", type=int, default=64)
+    ap.add_argument("--batch", type=int, default=16)
+    a = ap.parse_args(argv)
+    dem, header = read_asc(a.dem)
+    mask = _read_mask(a.mask, dem.shape) if a.mask else None
+    out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=asc_nodata(header), window=a.window, overlap=a.overlap,
+                               batch=a.batch)
+    if info["unfilled"] and asc_value(header, "NODATA_value") is None:
+        header = header + [("NODATA_value", "-9999")]
+    write_asc(a.out, out.cpu().numpy(), header)
+    print(f"{a.out}: {info['windows']} windows, {info['run']} run, {info['unfilled']} holes left unfilled")
+    return info
+
+
+if __name__ == "__main__":
+    main()

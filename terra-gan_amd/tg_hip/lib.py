@@ -32,12 +32,17 @@ class TgBnAct(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("mean", "rstd", "gamma", "beta")] + [("act", C.c_int32), ("slope", C.c_float)]
 
 
+class TgRasterPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("H", "W", "wh", "ww", "overlap", "ny", "nx")]
+
+
 class TgError(RuntimeError):
     pass
 
 
 P, I, I64, F, SZ, D = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t, C.c_double
 CP = C.POINTER(TgConv)
+RP = C.POINTER(TgRasterPlan)
 
 # name -> (restype, argtypes); mirrors include/terragan_hip.h line by line
 SIGNATURES = {
@@ -113,6 +118,9 @@ SIGNATURES = {
     "tg_quality_metrics_ws_bytes": (SZ, [I64, I, I]),
     "tg_quality_metrics": (I, [P, P, P, I64, I, I, P, P, SZ, P]),
     "tg_u8_to_tiles": (I, [P, P, I64, P, P, P]),
+    "tg_raster_window_stats": (I, [P, P, RP, I, F, P, P, P, P]),
+    "tg_raster_gather": (I, [P, P, RP, I, F, P, P, P, I, P, P, P]),
+    "tg_raster_blend": (I, [P, P, RP, I, F, P, P, P, P, I, P, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

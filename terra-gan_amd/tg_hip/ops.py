@@ -773,6 +773,73 @@ def u8_to_tiles(img_u8=None, mask_u8=None):
     return img, msk
 
 
+def raster_plan(H, W, wh, ww, overlap, ny, nx):
+    return L.TgRasterPlan(H, W, wh, ww, overlap, ny, nx)
+
+
+def _raster_in(dem, mask, plan):
+    _chk(dem, "dem"); _chk(mask, "mask")
+    if tuple(dem.shape) != (plan.H, plan.W) or (mask is not None and tuple(mask.shape) != (plan.H, plan.W)):
+        raise L.TgError(f"raster: dem {tuple(dem.shape)} / mask {None if mask is None else tuple(mask.shape)} "
+                        f"differ from the plan's {plan.H}x{plan.W}")
+
+
+def _i32(t, n, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == n):
+        raise L.TgError(f"{name}: expected a contiguous int32 HIP tensor of {n} elements")
+
+
+def raster_window_stats(dem, mask, plan, nodata=None):
+    """-> (lo [nwin], hi [nwin], counts int32 [nwin][2] = known, holes) over the windows of `plan` (tg_raster_window_stats)."""
+    _raster_in(dem, mask, plan)
+    nwin = plan.ny * plan.nx
+    lo, hi = empty(nwin, like=dem), empty(nwin, like=dem)
+    counts = torch.empty(nwin, 2, dtype=torch.int32, device=dem.device)
+    L.check(_lib().tg_raster_window_stats(_p(dem), _p(mask), C.byref(plan), int(nodata is not None),
+                                          0.0 if nodata is None else float(nodata), _p(lo), _p(hi), _p(counts), _stream()),
+            "tg_raster_window_stats")
+    return lo, hi, counts
+
+
+def raster_gather(dem, mask, plan, lo, hi, win_idx, nodata=None, x=None, m=None):
+    """Normalised network input and mask [n][wh][ww] of the windows win_idx (int32 HIP tensor) (tg_raster_gather)."""
+    _raster_in(dem, mask, plan)
+    n, nwin = win_idx.numel(), plan.ny * plan.nx
+    _i32(win_idx, n, "win_idx")
+    _chk(lo, "lo"); _chk(hi, "hi")
+    assert lo.numel() == nwin and hi.numel() == nwin, (lo.shape, hi.shape, nwin)
+    shape = (n, plan.wh, plan.ww)
+    x = empty(*shape, like=dem) if x is None else x
+    m = empty(*shape, like=dem) if m is None else m
+    for t, nm in ((x, "x"), (m, "m")):
+        _chk(t, nm)
+        if tuple(t.shape) != shape:
+            raise L.TgError(f"raster_gather: {nm} {tuple(t.shape)} != {shape}")
+    L.check(_lib().tg_raster_gather(_p(dem), _p(mask), C.byref(plan), int(nodata is not None),
+                                    0.0 if nodata is None else float(nodata), _p(lo), _p(hi), _p(win_idx), n, _p(x), _p(m),
+                                    _stream()), "tg_raster_gather")
+    return x, m
+
+
+def raster_blend(dem, mask, plan, lo, hi, run_of_window, wout, nodata=None):
+    """-> (raster [H][W], unfilled int32 [1] device counter) (tg_raster_blend).  run_of_window: int32 [nwin], the row of
+    wout [n_run][wh][ww] holding that window's generator output, -1 where it did not run."""
+    _raster_in(dem, mask, plan)
+    nwin = plan.ny * plan.nx
+    _i32(run_of_window, nwin, "run_of_window")
+    _chk(lo, "lo"); _chk(hi, "hi"); _chk(wout, "wout")
+    assert lo.numel() == nwin and hi.numel() == nwin, (lo.shape, hi.shape, nwin)
+    if wout.dim() != 3 or tuple(wout.shape[1:]) != (plan.wh, plan.ww):
+        raise L.TgError(f"raster_blend: wout {tuple(wout.shape)} is not [n_run][{plan.wh}][{plan.ww}]")
+    out = empty(plan.H, plan.W, like=dem)
+    unfilled = torch.empty(1, dtype=torch.int32, device=dem.device)
+    L.check(_lib().tg_raster_blend(_p(dem), _p(mask), C.byref(plan), int(nodata is not None),
+                                   0.0 if nodata is None else float(nodata), _p(lo), _p(hi), _p(run_of_window),
+                                   _p(wout) if wout.numel() else None, wout.shape[0], _p(out), _p(unfilled), _stream()),
+            "tg_raster_blend")
+    return out, unfilled
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()

@@ -1,0 +1,170 @@
+"""CPU checks of whole-raster inpainting (mvp_gan/src/inpaint_raster.py): the window plan, the blend ramp, ESRI ASCII
+grid I/O, the host-side validation of the tg_raster_* entry points, and the numpy oracle the GPU tests compare with."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import raster_oracle as RO
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize("H,W,window,overlap", [(1500, 2100, 512, 64), (8192, 8192, 512, 64), (512, 512, 512, 64),
+                                                (513, 1000, 512, 0), (300, 72, 128, 16), (40, 41, 512, 39),
+                                                (1000, 900, 100, 99)])
+def test_plan_covers_flush_no_duplicates(H, W, window, overlap):
+    from mvp_gan.src.inpaint_raster import plan_windows
+    p = plan_windows(H, W, window, overlap)
+    assert (p.wh, p.ww) == (min(window, H), min(window, W))
+    for N, w, starts in ((H, p.wh, p.ys), (W, p.ww, p.xs)):
+        s = w - overlap
+        assert starts[0] == 0 and starts[-1] == N - w                     # first and last window flush with the edges
+        assert len(set(starts)) == len(starts) and starts == sorted(starts)
+        assert all(b - a == s for a, b in zip(starts[:-2], starts[1:-1]))  # stride s, only the last one clamped
+        assert len(starts) == 1 or 0 < starts[-1] - starts[-2] <= s
+        cov = np.zeros(N, int)
+        for a in starts:
+            cov[a:a + w] += 1
+        assert cov.min() >= 1                                               # full coverage
+        if len(starts) > 1 and overlap:
+            assert all(cov[a:a + overlap].min() >= 2 for a in starts[1:])   # neighbours overlap by >= overlap
+
+
+def test_plan_clamps_and_rejects():
+    from mvp_gan.src.inpaint_raster import plan_windows
+    p = plan_windows(300, 100, 512, 64)                                     # raster smaller than the window: clamped
+    assert (p.wh, p.ww, p.ys, p.xs) == (300, 100, [0], [0])
+    p = plan_windows(72, 1000, 512, 64)                                     # non-square windows
+    assert (p.wh, p.ww) == (72, 512) and p.ys == [0] and p.xs == [0, 448, 488]
+    with pytest.raises(ValueError, match="overlap"):
+        plan_windows(1000, 1000, 512, 512)
+    with pytest.raises(ValueError, match="overlap"):
+        plan_windows(60, 1000, 512, 64)                                     # overlap >= the clamped side
+    with pytest.raises(ValueError, match="overlap"):
+        plan_windows(1000, 1000, 512, -1)
+    with pytest.raises(ValueError, match="below 40"):
+        plan_windows(39, 1000, 512, 8)
+    with pytest.raises(ValueError, match="below 40"):
+        plan_windows(1000, 1000, 32, 8)
+
+
+@pytest.mark.parametrize("w,ov", [(512, 64), (512, 0), (100, 99), (41, 1), (40, 39)])
+def test_ramp_positive_and_border_rule(w, ov):
+    from mvp_gan.src.inpaint_raster import window_ramp
+    for first in (False, True):
+        for last in (False, True):
+            r = window_ramp(w, ov, first, last)
+            assert r.shape == (w,) and (r > 0).all() and (r <= 1).all()
+            np.testing.assert_array_equal(r, RO.ramp(w, ov, first, last))
+    r = window_ramp(w, ov)
+    np.testing.assert_array_equal(r, r[::-1])                               # symmetric inside the raster
+    if ov:
+        assert r[0] == 0.5 / ov and (w < 2 * ov or r[w // 2] == 1.0)
+        assert window_ramp(w, ov, first=True)[0] == 1.0 and window_ramp(w, ov, first=True)[-1] == r[-1]
+        assert window_ramp(w, ov, last=True)[-1] == 1.0 and window_ramp(w, ov, last=True)[0] == r[0]
+    assert (window_ramp(w, ov, True, True) == 1).all()
+
+
+@pytest.mark.parametrize("nodata", [None, "-9999"])
+def test_asc_round_trip(tmp_path, nodata):
+    from mvp_gan.src.inpaint_raster import asc_nodata, read_asc, write_asc
+    rng = np.random.default_rng(0)
+    z = (rng.normal(0, 1, (7, 11)) * 300 + 1234.5).astype(np.float32)
+    z[3, 4] = np.float32(1e-30)
+    lines = ["ncols 11", "nrows 7", "xllcenter 523000.5", "yllcenter 181000.25", "cellsize 0.5"]
+    if nodata:
+        lines.append(f"NODATA_value {nodata}")
+        z[0, 0] = -9999
+    body = "\n".join(" ".join("%.9g" % v for v in row) for row in z)
+    (tmp_path / "a.asc").write_text("\n".join(lines) + "\n" + body + "\n")
+    a, hdr = read_asc(tmp_path / "a.asc")
+    assert a.dtype == np.float32 and a.shape == (7, 11)
+    np.testing.assert_array_equal(a.view(np.int32), z.view(np.int32))
+    assert hdr == [tuple(line.split()) for line in lines]
+    assert asc_nodata(hdr) == (None if nodata is None else -9999.0)
+    write_asc(tmp_path / "b.asc", a, hdr)
+    b, hdr2 = read_asc(tmp_path / "b.asc")
+    assert hdr2 == hdr
+    np.testing.assert_array_equal(b.view(np.int32), a.view(np.int32))
+    a2 = a.copy()
+    a2[1, 1] = np.nan
+    write_asc(tmp_path / "c.asc", a2, hdr)                                  # NaN -> NODATA_value when the header has one
+    c, _ = read_asc(tmp_path / "c.asc")
+    assert c[1, 1] == -9999 if nodata else np.isnan(c[1, 1])
+    with pytest.raises(ValueError):
+        write_asc(tmp_path / "d.asc", a[:, :5], hdr)
+
+
+def test_asc_corner_header_five_lines(tmp_path):
+    from mvp_gan.src.inpaint_raster import read_asc, write_asc
+    (tmp_path / "a.asc").write_text("NCOLS 3\nNROWS 2\nXLLCORNER 10\nYLLCORNER 20\nCELLSIZE 1\n1 2 3\n4 5 6.5\n")
+    a, hdr = read_asc(tmp_path / "a.asc")
+    np.testing.assert_array_equal(a, np.array([[1, 2, 3], [4, 5, 6.5]], np.float32))
+    write_asc(tmp_path / "b.asc", a, hdr)
+    assert (tmp_path / "b.asc").read_text() == "NCOLS 3\nNROWS 2\nXLLCORNER 10\nYLLCORNER 20\nCELLSIZE 1\n1 2 3\n4 5 6.5\n"
+    (tmp_path / "bad.asc").write_text("ncols 3\nnrows 2\nxllcorner 0\nyllcorner 0\ncellsize 1\n1 2 3\n4 5\n")
+    with pytest.raises(ValueError, match="values"):
+        read_asc(tmp_path / "bad.asc")
+
+
+def test_raster_argument_validation_without_gpu():
+    """The tg_raster_* entry points validate the plan and pointers on the host, before any launch."""
+    import __graft_entry__ as ge
+    ge.build()
+    from tg_hip import lib as L
+    lib = L.load()
+    fake = C.c_void_p(0x1000)          # never dereferenced: every call below fails validation first
+    good = L.TgRasterPlan(1500, 2100, 512, 512, 64, 4, 5)
+    rc = lib.tg_raster_window_stats(None, None, C.byref(good), 0, 0.0, fake, fake, fake, None)
+    assert rc == -1 and b"null pointer" in lib.tg_last_error()
+    rc = lib.tg_raster_window_stats(fake, None, None, 0, 0.0, fake, fake, fake, None)
+    assert rc == -1 and b"null plan" in lib.tg_last_error()
+    bad = L.TgRasterPlan(1500, 2100, 512, 512, 64, 4, 4)
+    rc = lib.tg_raster_window_stats(fake, None, C.byref(bad), 0, 0.0, fake, fake, fake, None)
+    assert rc == -1 and b"inconsistent" in lib.tg_last_error()
+    for p, msg in ((L.TgRasterPlan(1500, 2100, 512, 512, 512, 1, 1), b"overlap"),
+                   (L.TgRasterPlan(1500, 2100, 512, 512, -1, 4, 5), b"overlap"),
+                   (L.TgRasterPlan(500, 2100, 512, 512, 64, 1, 5), b"does not fit"),
+                   (L.TgRasterPlan(0, 2100, 512, 512, 64, 1, 5), b"raster size")):
+        rc = lib.tg_raster_gather(fake, None, C.byref(p), 0, 0.0, fake, fake, fake, 1, fake, fake, None)
+        assert rc == -1 and msg in lib.tg_last_error(), lib.tg_last_error()
+    rc = lib.tg_raster_gather(fake, None, C.byref(good), 0, 0.0, fake, fake, fake, 0, fake, fake, None)
+    assert rc == -1 and b"window count" in lib.tg_last_error()
+    rc = lib.tg_raster_gather(fake, None, C.byref(good), 0, 0.0, fake, fake, None, 3, fake, fake, None)
+    assert rc == -1 and b"null pointer" in lib.tg_last_error()
+    rc = lib.tg_raster_blend(fake, None, C.byref(good), 0, 0.0, fake, fake, fake, fake, 21, fake, fake, None)
+    assert rc == -1 and b"n_run" in lib.tg_last_error()
+    rc = lib.tg_raster_blend(fake, None, C.byref(good), 0, 0.0, fake, fake, fake, None, 3, fake, fake, None)
+    assert rc == -1 and b"null pointer" in lib.tg_last_error()
+    rc = lib.tg_raster_blend(fake, None, C.byref(good), 0, 0.0, fake, fake, fake, fake, 3, fake, None, None)
+    assert rc == -1 and b"null pointer" in lib.tg_last_error()
+
+
+def test_oracle_blend_single_window_and_unfilled():
+    """The float64 blend oracle: one window covering the raster -> weight 1, holes = lo + out * (hi - lo); holes of a
+    window that did not run stay NaN and are counted."""
+    from mvp_gan.src.inpaint_raster import plan_windows
+    z = RO.terrain(64, 80, 1)
+    mask = ~RO.disc_holes(64, 80, 0.3, 2, 3, 9)
+    p = plan_windows(64, 80, 512, 16)
+    lo, hi, cnt = RO.stats(z, p, mask)
+    assert cnt.tolist() == [[mask.sum(), (~mask).sum()]] and lo[0] == z[mask].min() and hi[0] == z[mask].max()
+    out = np.random.default_rng(3).random((1, 64, 80)).astype(np.float32)
+    r, unfilled = RO.blend(z, p, lo, hi, np.array([0]), out, mask)
+    assert unfilled == 0
+    np.testing.assert_array_equal(r[mask], z[mask].astype(np.float64))
+    np.testing.assert_allclose(r[~mask], float(lo[0]) + out[0][~mask].astype(np.float64) * (float(hi[0]) - float(lo[0])), rtol=1e-15)
+    r, unfilled = RO.blend(z, p, lo, hi, np.array([-1]), out, mask)
+    assert unfilled == (~mask).sum() and np.isnan(r[~mask]).all()
+
+
+def test_cli_help_runs_without_gpu():
+    r = subprocess.run([sys.executable, "-m", "mvp_gan.src.inpaint_raster", "--help"], cwd=os.path.join(ROOT, "terra-gan_amd"),
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    for flag in ("--dem", "--mask", "--checkpoint", "--out", "--window", "--overlap", "--batch"):
+        assert flag in r.stdout
