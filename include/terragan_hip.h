@@ -431,6 +431,27 @@ int tg_raster_blend(const float* dem, const float* mask, const TgRasterPlan* pla
                     const float* lo, const float* hi, const int32_t* run_of_window, const float* wout, int n_run, float* out,
                     int32_t* unfilled, tg_stream_t stream);
 
+/* ---- training windows from a whole raster (mvp_gan/src/utils/raster_dataset.py; no reference counterpart: the reference
+ * trains on uint8 PNG tiles min-max scaled over all pixels, utils/data_extraction.py:96-100) ----
+ * Hole masks: window i (0 <= i < n) is the union of the primitives prims[offsets[i] .. offsets[i+1]) (at most 32 are read;
+ * offsets [n+1] nondecreasing, in range of prims), each 8 int32, in the window's pixel coordinates (row, column):
+ *   TG_HOLE_RECT    {0, cy, cx, a, b, u, v, 0}: with dy = i - cy, dx = j - cx, p = dx u + dy v, q = dy u - dx v,
+ *                   L2 = u^2 + v^2, a hole when p^2 <= a^2 L2 and q^2 <= b^2 L2
+ *   TG_HOLE_ELLIPSE {1, cy, cx, a, b, u, v, 0}: a hole when p^2 b^2 + q^2 a^2 <= a^2 b^2 L2
+ *   TG_HOLE_STROKE  {2, y0, x0, y1, x1, r, 0, 0}: a hole when the point-to-segment distance is <= r (exact integer test)
+ * Ranges for exactness (int64 throughout): coordinates in [-side, 2 side], 0 <= a, b, r <= 2 side, |u|, |v| <= 16.  A direction
+ * (0, 0), an ellipse with a = 0 or b = 0 (its inequality would be a line or the whole plane) or an unknown kind covers nothing.  mask: [n][side][side], 1 = keep, 0 = hole.  Bit-exact. */
+enum { TG_HOLE_RECT = 0, TG_HOLE_ELLIPSE = 1, TG_HOLE_STROKE = 2 };
+int tg_hole_masks(const int32_t* prims, const int32_t* offsets, int n, int side, float* mask, tg_stream_t stream);
+/* Windows cut from dem [H][W] (float32): draws int32 [n][3] = (y0, x0, op).  Output pixel (i, j) reads
+ * dem[y0 + a][x0 + b] with (a, b) = op & 4 ? (j, i) : (i, j), then a = side-1-a if op & 2, b = side-1-b if op & 1.
+ * lo / hi [n]: min / max of the window over the pixels with mask != 0 (norm_known) or over all pixels; a -0 extreme is stored
+ * as +0; +inf / -inf when no pixel counts.  x [n][side][side] = (z - lo) / (hi - lo) at EVERY pixel, holes included (IEEE
+ * fp32; with norm_known hole values may leave [0, 1]); 0 when hi == lo or no pixel counts.  A draw whose window leaves the
+ * raster or whose op is outside [0, 7] gets NaN in its x, lo and hi.  Order-independent integer atomics: deterministic. */
+int tg_raster_sample(const float* dem, int64_t H, int64_t W, const int32_t* draws, int n, int side, const float* mask,
+                     int norm_known, float* x, float* lo, float* hi, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

@@ -42,6 +42,7 @@ from .models._common import as_bhw, require_hip
 from .models.discriminator import Discriminator
 from .models.generator import PConvUNet
 from .utils.dataset import InpaintingDataset, resize_to_tensor
+from .utils.raster_dataset import RasterWindowLoader
 from .utils.shard_dataset import ShardLoader, is_shard
 from .evaluation.metrics import calculate_boundary_quality
 from .utils.losses import HumanGuidedLoss, InpaintingLoss, criterion_forward  # noqa: F401
@@ -252,7 +253,13 @@ def train(img_dir: Path, mask_dir: Path, generator: Optional[PConvUNet] = None,
     from tg_hip.dist import ShardSampler, broadcast_state, rank_world
     rank, world = rank_world(getattr(grad_sync, "group", None)) if grad_sync is not None else (0, 1)
     bs = tcfg.get("batch_size", 2)
-    if is_shard(str(img_dir)):
+    if isinstance(img_dir, RasterWindowLoader):
+        # windows sampled on the device from a float32 raster (utils/raster_dataset.py): the loader's own batch size applies,
+        # data-parallel ranks draw from their own streams
+        train_loader, sampler = img_dir, None
+        if grad_sync is not None:
+            train_loader.rank, train_loader.world = rank, world
+    elif is_shard(str(img_dir)):
         # pre-decoded uint8 shard (utils/shard_dataset.py): `img_dir` is the shard directory, `mask_dir` is ignored;
         # /255 and the mask binarisation run on the device, bit-identical to the PNG path below
         train_loader = ShardLoader(str(img_dir), bs, shuffle=True, device=device)
@@ -263,7 +270,9 @@ def train(img_dir: Path, mask_dir: Path, generator: Optional[PConvUNet] = None,
         sampler = ShardSampler(len(train_set), rank, world, shuffle=True, seed=int(tcfg.get("seed", 0))) if world > 1 else None
         train_loader = DataLoader(train_set, batch_size=bs, shuffle=sampler is None, sampler=sampler, num_workers=0)
     val_loader = None
-    if val_img_dir is not None and is_shard(str(val_img_dir)):
+    if isinstance(val_img_dir, RasterWindowLoader):
+        val_loader = val_img_dir
+    elif val_img_dir is not None and is_shard(str(val_img_dir)):
         val_loader = ShardLoader(str(val_img_dir), bs, shuffle=False, device=device)
     elif val_img_dir is not None and val_mask_dir is not None:
         val_loader = DataLoader(InpaintingDataset(val_img_dir, val_mask_dir, transform=transform),
@@ -297,6 +306,8 @@ def train(img_dir: Path, mask_dir: Path, generator: Optional[PConvUNet] = None,
         epoch_start = time.time()
         if sampler is not None:
             sampler.set_epoch(epoch)
+        if isinstance(train_loader, RasterWindowLoader):
+            train_loader.set_epoch(epoch)
         for batch_idx, data in enumerate(train_loader):
             real = data["image"].to(device, non_blocking=True)
             masks = data["mask"].to(device, non_blocking=True)

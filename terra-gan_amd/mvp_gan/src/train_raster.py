@@ -1,0 +1,85 @@
+"""Fine-tune the inpainting GAN on one DSM raster in metres.
+
+Train and validation windows come from RasterWindowLoader (utils/raster_dataset.py) on the geographic split of the raster
+(train and val blocks never share a pixel); holes are synthetic.  The checkpoint written to --out has the reference's keys
+(train.py's dictionary) and loads unchanged into `inpaint_raster --checkpoint`.
+
+CLI: python -m mvp_gan.src.train_raster --dem in.asc [--mask keep.png|keep.asc] [--nodata v] [--init ck.pth] --out ft.pth
+         [--window 256 --batch 16 --steps 500 --epochs 4 --seed 0 --norm known|window]
+"""
+import argparse
+import logging
+
+import torch
+
+from .inpaint_raster import _read_mask, asc_nodata, read_asc
+from .models.discriminator import Discriminator
+from .models.generator import PConvUNet
+from .train import _default_config, train
+from .utils.raster_dataset import RasterWindowLoader
+
+
+def _load_init(path, generator, discriminator, optimizer_G, optimizer_D, device):
+    """Generator weights (a train() checkpoint or a bare state dict), plus the discriminator and optimiser states when the
+    checkpoint has them.  -> the names of what was loaded."""
+    ck = torch.load(path, map_location=device, weights_only=False)
+    if not (isinstance(ck, dict) and "generator_state_dict" in ck):
+        generator.load_state_dict(ck)
+        return ["generator"]
+    generator.load_state_dict(ck["generator_state_dict"])
+    loaded = ["generator"]
+    for key, obj in (("discriminator_state_dict", discriminator), ("optimizer_G_state_dict", optimizer_G),
+                     ("optimizer_D_state_dict", optimizer_D)):
+        if key in ck:
+            obj.load_state_dict(ck[key])
+            loaded.append(key.replace("_state_dict", ""))
+    return loaded
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Fine-tune a TERRA-GAN generator on windows of one ESRI ASCII grid DSM.")
+    ap.add_argument("--dem", required=True, help="input .asc raster in metres (NODATA_value cells are never sampled)")
+    ap.add_argument("--mask", help="optional mask (.png or .asc) of the raster's size: nonzero = usable, 0 = never sampled")
+    ap.add_argument("--nodata", type=float, help="nodata value (default: the .asc header's NODATA_value)")
+    ap.add_argument("--init", help="checkpoint to start from: generator, plus discriminator / optimiser states if present")
+    ap.add_argument("--out", required=True, help="output checkpoint (.pth), reference format")
+    ap.add_argument("--window", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=500, help="train steps per epoch")
+    ap.add_argument("--val-steps", type=int, help="validation batches per epoch (default: max(1, steps // 10))")
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--block", type=int, help="side of the train / val / test blocks (default: 4 x window)")
+    ap.add_argument("--lr", type=float, default=2e-4)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--norm", choices=("known", "window"), default="known")
+    a = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(message)s")
+    if not torch.cuda.is_available():
+        raise RuntimeError("train_raster: no HIP device visible; this build has no CPU path")
+    device = torch.device("cuda", torch.cuda.current_device())
+
+    dem, header = read_asc(a.dem)
+    mask = _read_mask(a.mask, dem.shape) if a.mask else None
+    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
+    common = dict(nodata=nodata, window=a.window, batch_size=a.batch, block=a.block, norm=a.norm, seed=a.seed, device=device)
+    tr = RasterWindowLoader(dem, mask, split="train", steps_per_epoch=a.steps, **common)
+    va = RasterWindowLoader(dem, mask, split="val", steps_per_epoch=a.val_steps or max(1, a.steps // 10), augment=False,
+                            **common)
+
+    torch.manual_seed(a.seed)
+    G, D = PConvUNet().to(device), Discriminator().to(device)
+    oG = torch.optim.Adam(G.parameters(), lr=a.lr)
+    oD = torch.optim.Adam(D.parameters(), lr=a.lr)
+    loaded = _load_init(a.init, G, D, oG, oD, device) if a.init else []
+    cfg = _default_config()
+    cfg["training"].update(batch_size=a.batch, learning_rate=a.lr, epochs=a.epochs, seed=a.seed)
+    res = train(tr, None, generator=G, discriminator=D, optimizer_G=oG, optimizer_D=oD, checkpoint_path=a.out, config=cfg,
+                val_img_dir=va)
+    print(f"{a.out}: {a.epochs} epochs x {a.steps} steps of {a.batch} windows {a.window}^2 "
+          f"(admissible train {tr.info['admissible_fraction']:.3f}, val {va.info['admissible_fraction']:.3f}), "
+          f"init {'+'.join(loaded) or 'random'}, best val g_loss {res['best_val_loss']:.5f}")
+    return res
+
+
+if __name__ == "__main__":
+    main()

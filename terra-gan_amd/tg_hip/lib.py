@@ -121,6 +121,8 @@ SIGNATURES = {
     "tg_raster_window_stats": (I, [P, P, RP, I, F, P, P, P, P]),
     "tg_raster_gather": (I, [P, P, RP, I, F, P, P, P, I, P, P, P]),
     "tg_raster_blend": (I, [P, P, RP, I, F, P, P, P, P, I, P, P, P]),
+    "tg_hole_masks": (I, [P, P, I, I, P, P]),
+    "tg_raster_sample": (I, [P, I64, I64, P, I, I, P, I, P, P, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -840,6 +840,57 @@ def raster_blend(dem, mask, plan, lo, hi, run_of_window, wout, nodata=None):
     return out, unfilled
 
 
+HOLE_RECT, HOLE_ELLIPSE, HOLE_STROKE = 0, 1, 2     # primitive kinds of tg_hole_masks (terragan_hip.h)
+
+
+def _i32_rows(t, cols, name):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == cols):
+        raise L.TgError(f"{name}: expected a contiguous int32 HIP tensor [n][{cols}], got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def hole_masks(prims, offsets, side, out=None):
+    """Hole masks [n][side][side] (1 = keep, 0 = hole) from int32 primitives prims [P][8] and offsets [n+1] (tg_hole_masks).
+    offsets must be nondecreasing from 0 to P with at most 32 primitives per window: the caller's contract, not checked
+    here (that would need a host sync)."""
+    _i32_rows(prims, 8, "prims")
+    if not (offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.dim() == 1
+            and offsets.numel() >= 2):
+        raise L.TgError("offsets: expected a contiguous int32 HIP tensor [n+1], n >= 1")
+    n = offsets.numel() - 1
+    shape = (n, side, side)
+    out = torch.empty(shape, dtype=torch.float32, device=offsets.device) if out is None else out
+    _chk(out, "out")
+    if tuple(out.shape) != shape:
+        raise L.TgError(f"hole_masks: out {tuple(out.shape)} != {shape}")
+    # an empty primitive list has no storage; any non-null pointer does, since no window then reads a primitive
+    L.check(_lib().tg_hole_masks(_p(prims) if prims.numel() else _p(offsets), _p(offsets), n, int(side), _p(out), _stream()),
+            "tg_hole_masks")
+    return out
+
+
+def raster_sample(dem, draws, mask, norm_known=True, x=None, lo=None, hi=None):
+    """Windows of dem [H][W] at draws int32 [n][3] = (y0, x0, op), normalised by the min / max over mask != 0 (norm_known)
+    or over all pixels (tg_raster_sample).  mask: [n][side][side].  -> (x [n][side][side], lo [n], hi [n])."""
+    _chk(dem, "dem"); _chk(mask, "mask")
+    _i32_rows(draws, 3, "draws")
+    if dem.dim() != 2:
+        raise L.TgError(f"raster_sample: dem must be [H][W], got {tuple(dem.shape)}")
+    n = draws.shape[0]
+    if mask.dim() != 3 or mask.shape[0] != n or mask.shape[1] != mask.shape[2]:
+        raise L.TgError(f"raster_sample: mask {tuple(mask.shape)} is not [{n}][side][side]")
+    side = mask.shape[1]
+    x = empty(n, side, side, like=dem) if x is None else x
+    lo = empty(n, like=dem) if lo is None else lo
+    hi = empty(n, like=dem) if hi is None else hi
+    for t, nm, shp in ((x, "x", (n, side, side)), (lo, "lo", (n,)), (hi, "hi", (n,))):
+        _chk(t, nm)
+        if tuple(t.shape) != shp:
+            raise L.TgError(f"raster_sample: {nm} {tuple(t.shape)} != {shp}")
+    L.check(_lib().tg_raster_sample(_p(dem), dem.shape[0], dem.shape[1], _p(draws), n, side, _p(mask), int(bool(norm_known)),
+                                    _p(x), _p(lo), _p(hi), _stream()), "tg_raster_sample")
+    return x, lo, hi
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()
