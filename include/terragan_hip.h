@@ -58,7 +58,9 @@ const char* tg_last_error(void);
  * Replaces PConv2d.forward's input*mask -> input_conv -> output*mask_ratio (pconv.py:27-30,43)
  * when in_mask/ratio are given, and nn.Conv2d (+LeakyReLU/ReLU) otherwise
  * (generator.py:29,56; discriminator.py:11,15,22; losses.py:32 VGG trunk).
- * in_mask [B][H][W], bias [Cout], ratio [B][Ho][Wo] may be NULL. */
+ * in_mask [B][H][W], bias [Cout], ratio [B][Ho][Wo] may be NULL.
+ * ws >= tg_conv_fwd_ws_bytes: weight-transform room + split-K room of 64 output slabs (at most 64 Mi floats).  The split-K
+ * planners use no more than that, so the result is the same bit for bit for any larger workspace. */
 size_t tg_conv_fwd_ws_bytes(const TgConv* g);
 int tg_conv_fwd(const TgConv* g, const float* x, const float* in_mask, const float* w,
                 const float* bias, const float* ratio, int act, float slope, float* y,
@@ -66,7 +68,8 @@ int tg_conv_fwd(const TgConv* g, const float* x, const float* in_mask, const flo
 
 /* dx (+)= conv_transpose(dy, w) (.) in_mask   -- autograd of the conv above w.r.t. x.
  * dy must already carry the ratio factor.  accumulate!=0 adds into dx (skip connections).
- * ws >= tg_conv_dgrad_ws_bytes (holds the [Cin][kh][kw][Cout] transposed weights + split-K). */
+ * ws >= tg_conv_dgrad_ws_bytes (holds the [Cin][kh][kw][Cout] transposed weights + split-K room of 64 slabs of dx, at most
+ * 64 Mi floats; as for the forward, a larger workspace gives the same bits). */
 size_t tg_conv_dgrad_ws_bytes(const TgConv* g);
 int tg_conv_dgrad(const TgConv* g, const float* dy, const float* w, const float* in_mask,
                   float* dx, int accumulate, float* ws, size_t ws_bytes, tg_stream_t stream);
@@ -157,7 +160,8 @@ int tg_set_cu_reserve(int cus);
 int tg_set_work_stealing(int mode);
 
 /* dw[Cout][k][k][Cin] = sum_pixels dy (x) (x (.) in_mask);  db[Cout] = sum_pixels dy (db may be NULL).
- * Deterministic: split-K partial slabs in ws, reduced in a fixed order. */
+ * Deterministic: split-K partial slabs in ws, reduced in a fixed order.  The query sizes the slabs, bias partials and column
+ * sum from the launch's own parameters; a smaller ws is rejected (TG_ERR_ARG) before any launch. */
 size_t tg_conv_wgrad_ws_bytes(const TgConv* g);
 int tg_conv_wgrad(const TgConv* g, const float* x, const float* in_mask, const float* dy,
                   float* dw, float* db, float* ws, size_t ws_bytes, tg_stream_t stream);

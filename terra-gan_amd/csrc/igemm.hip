@@ -1352,14 +1352,21 @@ static TgConv s2d_geom(const TgConv* g) {
 static size_t s2d_x_floats(const TgConv* g) { return align_up((size_t)g->B * g->H * g->W * g->Cin, 64); }
 static size_t s2d_w_floats(const TgConv* g) { return align_up((size_t)g->Cout * 36 * g->Cin, 64); }
 
+// Split-K room of a conv whose result has `out` elements: 64 slabs, the most any planner takes (plan_splits and
+// try_igemm_multi 64, try_pgemm 32, the Winograd launchers 16), capped at 64 Mi floats.  The fwd / dgrad queries promise it and
+// the planners plan against min(what they were handed, this): a workspace larger than the query asks for leaves the split
+// counts, and so the result's bits, unchanged.
+static size_t splitk_room_floats(size_t out) {
+    const size_t cap = (size_t)64 << 20;
+    return out * 64 < cap ? out * 64 : cap;
+}
+static size_t min_floats(size_t a, size_t b) { return a < b ? a : b; }
+
 // ---- forward ----------------------------------------------------------------------------------
 extern "C" size_t tg_conv_fwd_ws_bytes(const TgConv* g) {
     if (!g) return 0;
-    // room for up to 8 slabs of the output (plan_splits shrinks to what fits)
-    size_t out = (size_t)g->B * g->Ho * g->Wo * g->Cout;
-    size_t cap = (size_t)64 << 20;  // floats
-    size_t want = out * 16;
-    size_t base = ((want < cap ? want : cap) + conv_wino_floats(g)) * sizeof(float);
+    const size_t out = (size_t)g->B * g->Ho * g->Wo * g->Cout;
+    size_t base = (splitk_room_floats(out) + conv_wino_floats(g)) * sizeof(float);
     if (s2d_ok(g)) {
         const TgConv g2 = s2d_geom(g);
         base = (s2d_x_floats(g) + s2d_w_floats(g)) * sizeof(float) + tg_conv_fwd_ws_bytes(&g2);
@@ -1480,6 +1487,7 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
     p.T = (p.C % 4) ? cdiv(p.Ktot, 32) : p.TH * p.TW * p.nchunks;
     size_t ws_floats = ws ? ws_bytes / sizeof(float) : 0;
     const size_t uf = conv_wino_floats(g);
+    const size_t room = splitk_room_floats((size_t)p.M * p.N);
     if (wino22_fwd_geom_ok(g) && (prep || (ws_floats >= uf && aligned16(ws)))) {
         // 4x4 stride 2: Winograd F(2x2,2x2) over the shifted space-to-depth view, gathered on the fly (wino22.inc)
         p.w_raw = w;
@@ -1489,7 +1497,7 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
             p.ws = ws + uf;
             ws_floats -= uf;
         }
-        return launch_wino22(g, p, 0, ws_floats, (hipStream_t)stream);
+        return launch_wino22(g, p, 0, min_floats(ws_floats, room), (hipStream_t)stream);
     }
     if (wino_fwd_geom_ok(g) && (prep || (ws_floats >= uf && aligned16(ws)))) {
         // transformed weights: prepared by the caller, or at the head of the workspace
@@ -1522,6 +1530,7 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
             TG_REQUIRE(smallconv_bnin_fwd_ok(p), "tg_conv_fwd_bnin: geometry not supported (ask tg_conv_bnin_supported first)");
         }
     }
+    ws_floats = min_floats(ws_floats, room);
     plan_splits(p, ws_floats);
     rc = launch_igemm(p, (hipStream_t)stream, ws_floats);
     if (ex) ex->pool_fused = p.pool_done;
@@ -1621,15 +1630,11 @@ static size_t dgrad_wt_floats(const TgConv* g) {
 }
 extern "C" size_t tg_conv_dgrad_ws_bytes(const TgConv* g) {
     if (!g) return 0;
-    size_t wt = dgrad_wt_floats(g);
-    size_t out = (size_t)g->B * g->H * g->W * g->Cin;
-    size_t cap = (size_t)64 << 20;
-    size_t want = out * 16;
     if (s2d_ok(g)) {
         const TgConv g2 = s2d_geom(g);
         return (s2d_x_floats(g) + s2d_w_floats(g)) * sizeof(float) + tg_conv_dgrad_ws_bytes(&g2);
     }
-    return (wt + (want < cap ? want : cap)) * sizeof(float);
+    return (dgrad_wt_floats(g) + splitk_room_floats((size_t)g->B * g->H * g->W * g->Cin)) * sizeof(float);
 }
 
 // gate_bits (tg_conv_dgrad_gbits): handed to the stride-1 3x3 Winograd launches, which set *gate_bits_done where their kernel read
@@ -1759,7 +1764,9 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
     hipStream_t s = (hipStream_t)stream;
     float* wt = prep ? wprep : ws;
     float* ws2 = ws ? ws + wt_floats : nullptr;
-    const size_t ws2_floats = ws ? ws_bytes / sizeof(float) - wt_floats : 0;
+    const size_t ws2_avail = ws ? ws_bytes / sizeof(float) - wt_floats : 0;
+    const size_t room = splitk_room_floats((size_t)g->B * g->H * g->W * g->Cin);
+    const size_t ws2_floats = min_floats(ws2_avail, room);     // what the split-K planners may use (see splitk_room_floats)
     if (wino_dgrad_geom_ok(g)) {
         // stride-1 3x3: the Winograd kernel reads W[co][tap][ci] through strides (n = ci, k = co); no transposed copy
         IGemmParams p = {};
@@ -1782,7 +1789,7 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
             if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
             return rc;
         }
-        size_t avail = ws2_floats;
+        size_t avail = ws2_avail;
         if (wino44_prepared_unusable(p)) {         // see conv_fwd_impl: F(4x4) image prepared, F(2x2) launch -> transform per call
             const size_t uf = dgrad_wt_floats(g);
             TG_REQUIRE(ws && aligned16(ws) && avail >= uf, "tg_conv_dgrad: workspace too small to re-prepare the weights (%zu < %zu floats)",
@@ -1793,6 +1800,7 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
             avail -= uf;
         }
         TG_REQUIRE(p.bf16 ? wino16_ok(p) : wino_ok(p), "tg_conv_dgrad: internal: Winograd geometry predicate mismatch");
+        avail = min_floats(avail, room);
         rc = p.bf16 ? launch_wino16(p, avail, s) : launch_wino(p, avail, s);
         if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
         return rc;
@@ -2393,11 +2401,21 @@ static void wgrad_plan(const TgConv* g, int* splits, int* steps_per_split, int* 
 int tg_colsum_launch(const float* x, int64_t rows, int C, float* out, float* ws, hipStream_t s);  // pointwise.hip
 size_t tg_colsum_ws_floats(int64_t rows, int C);
 
+// The WgradParams of a call, geometry and split plan: tg_conv_wgrad_ws_bytes sizes the workspace from the same parameters the
+// launch runs with (the small-channel routes and their partial-slab counts depend on B, Ho, Wo, stride and pad).
+static WgradParams wgrad_params(const TgConv* g) {
+    WgradParams p = {};
+    p.B = g->B; p.H = g->H; p.W = g->W; p.C = g->Cin; p.Ho = g->Ho; p.Wo = g->Wo; p.Cout = g->Cout;
+    p.k = g->k; p.stride = g->stride; p.pad = g->pad;
+    p.Mpix = g->B * g->Ho * g->Wo; p.Ktot = g->k * g->k * g->Cin;
+    wgrad_plan(g, &p.splits, &p.steps_per_split, &p.T);
+    return p;
+}
+
 extern "C" size_t tg_conv_wgrad_ws_bytes(const TgConv* g) {
     if (!g) return 0;
-    int splits, sps, T;
-    wgrad_plan(g, &splits, &sps, &T);
-    size_t slabs = align_up((size_t)splits * g->Cout * g->k * g->k * g->Cin, 64);
+    const WgradParams sp = wgrad_params(g);
+    size_t slabs = align_up((size_t)sp.splits * g->Cout * g->k * g->k * g->Cin, 64);
     {
         size_t wf = align_up(wino_wgrad_ws_floats(g), 64);
         if (wf > slabs) slabs = wf;
@@ -2413,8 +2431,6 @@ extern "C" size_t tg_conv_wgrad_ws_bytes(const TgConv* g) {
         wf = s2d_x_floats(g) + s2d_w_floats(g) + align_up(wino16_wgrad_ws_floats(&g2), 64);
         if (wino16_wgrad_ok(&g2, nullptr) && wf > slabs) slabs = wf;
     }
-    WgradParams sp = {};
-    sp.C = g->Cin; sp.Cout = g->Cout; sp.k = g->k; sp.Mpix = g->B * g->Ho * g->Wo;
     if (smallconv_wgrad_applies(sp)) {
         size_t alt = align_up(smallconv_wgrad_ws_floats(sp), 64);
         if (alt > slabs) slabs = alt;
@@ -2444,12 +2460,17 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
     TG_REQUIRE(ws_bytes >= tg_conv_wgrad_ws_bytes(g), "tg_conv_wgrad: workspace too small (%zu < %zu)", ws_bytes,
                tg_conv_wgrad_ws_bytes(g));
     hipStream_t s = (hipStream_t)stream;
-    WgradParams p = {};
+    const size_t ws_floats = ws_bytes / sizeof(float);
+    const int64_t mpix = (int64_t)g->B * g->Ho * g->Wo;
+    // the bias column-sum runs at ws + off: its partials must fit behind what the weight-gradient launch used
+    auto colsum = [&](size_t off) -> int {
+        TG_REQUIRE(off + tg_colsum_ws_floats(mpix, g->Cout) <= ws_floats,
+                   "tg_conv_wgrad: workspace too small for the bias column sum (%zu < %zu floats)", ws_floats,
+                   off + tg_colsum_ws_floats(mpix, g->Cout));
+        return tg_colsum_launch(dy, mpix, g->Cout, db, ws + off, s);
+    };
+    WgradParams p = wgrad_params(g);
     p.x = x; p.amask = in_mask; p.dy = dy;
-    p.B = g->B; p.H = g->H; p.W = g->W; p.C = g->Cin; p.Ho = g->Ho; p.Wo = g->Wo; p.Cout = g->Cout;
-    p.k = g->k; p.stride = g->stride; p.pad = g->pad;
-    p.Mpix = g->B * g->Ho * g->Wo; p.Ktot = g->k * g->k * g->Cin;
-    wgrad_plan(g, &p.splits, &p.steps_per_split, &p.T);
     if (in_bn) {
         p.in_bn = *in_bn;
         TG_REQUIRE(smallconv_wgrad_applies(p) && smallconv_bnin_wgrad_ok(p), "tg_conv_wgrad_bnin: geometry not supported");
@@ -2459,12 +2480,11 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
         {
             const double by = 4.0 * ((double)p.B * p.H * p.W * p.C + (double)p.Mpix * p.Cout + (double)p.Cout * p.Ktot);
             ProfScope ps(s, 2, 2.0 * p.Mpix * (double)p.Cout * p.Ktot, by, p.Cout, p.Ktot, p.Mpix, p.C, 1, 2001);
-            rc = smallconv_wgrad_launch(p, dw, ws, s, db, &db_done);
+            rc = smallconv_wgrad_launch(p, dw, ws, ws_floats, s, db, &db_done);
         }
         if (rc) return rc;
         if (db && !db_done) {
-            size_t used = align_up(smallconv_wgrad_ws_floats(p), 64);
-            rc = tg_colsum_launch(dy, (int64_t)p.Mpix, g->Cout, db, ws + used, s);
+            rc = colsum(align_up(smallconv_wgrad_ws_floats(p), 64));
             if (rc) return rc;
         }
         return TG_OK;
@@ -2492,8 +2512,7 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
                                g->Cin, 0);
             TG_CHECK_LAUNCH("w5x5_s2d_kernel");
             if (db) {
-                float* ws2 = wsr + align_up(w16 ? wino16_wgrad_ws_floats(&g2) : wino_wgrad_ws_floats(&g2), 64);
-                rc = tg_colsum_launch(dy, (int64_t)p.Mpix, g->Cout, db, ws2, s);
+                rc = colsum((size_t)(wsr - ws) + align_up(w16 ? wino16_wgrad_ws_floats(&g2) : wino_wgrad_ws_floats(&g2), 64));
                 if (rc) return rc;
             }
             return TG_OK;
@@ -2503,8 +2522,7 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
         rc = launch_wino16_wgrad(g, p, dw, ws, s);
         if (rc) return rc;
         if (db) {
-            float* ws2 = ws + align_up(wino16_wgrad_ws_floats(g), 64);
-            rc = tg_colsum_launch(dy, (int64_t)p.Mpix, g->Cout, db, ws2, s);
+            rc = colsum(align_up(wino16_wgrad_ws_floats(g), 64));
             if (rc) return rc;
         }
         return TG_OK;
@@ -2513,8 +2531,7 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
         rc = launch_wino_wgrad(g, p, dw, ws, s);
         if (rc) return rc;
         if (db) {
-            float* ws2 = ws + align_up(wino_wgrad_ws_floats(g), 64);
-            rc = tg_colsum_launch(dy, (int64_t)p.Mpix, g->Cout, db, ws2, s);
+            rc = colsum(align_up(wino_wgrad_ws_floats(g), 64));
             if (rc) return rc;
         }
         return TG_OK;
@@ -2523,8 +2540,7 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
         rc = launch_wino22_wgrad(g, p, dw, ws, s);
         if (rc) return rc;
         if (db) {
-            float* ws2 = ws + align_up(wino22_wgrad_ws_floats(g), 64);
-            rc = tg_colsum_launch(dy, (int64_t)p.Mpix, g->Cout, db, ws2, s);
+            rc = colsum(align_up(wino22_wgrad_ws_floats(g), 64));
             if (rc) return rc;
         }
         return TG_OK;
@@ -2545,8 +2561,7 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
         TG_CHECK_LAUNCH("slab_reduce_kernel");
     }
     if (db) {
-        float* ws2 = ws + align_up((size_t)p.splits * n, 64);
-        rc = tg_colsum_launch(dy, (int64_t)p.Mpix, g->Cout, db, ws2, s);
+        rc = colsum(align_up((size_t)p.splits * n, 64));
         if (rc) return rc;
     }
     return TG_OK;

@@ -1125,17 +1125,32 @@ bool smallconv_wgrad_applies(const WgradParams& p) {
     if (to1w_wgrad_ok(p)) return true;
     return false;
 }
+// Number of partial slabs smallconv_wgrad_launch writes: the grid of the kernel it picks for p.  The launch and the workspace size
+// both come from here, so that they cannot disagree (p needs the full geometry: B, Ho, Wo, stride and pad steer the route).
+static int smallconv_wgrad_blocks(const WgradParams& p) {
+    if (p.C == 1) return c1_wgrad_blocks(p);
+    if (to1w_wgrad_ok(p)) return p.B * cdiv(p.Ho, 4);
+    if (to1_wgrad_lds_ok(p)) {
+        const int ntiles = cdiv(p.Wo, T1_TW) * cdiv(p.Ho, T1_TH) * p.B;
+        return ntiles < 768 ? ntiles : 768;         // three workgroups per CU (five would fit: 71 us against 65, more partials to reduce)
+    }
+    const int quads = p.Mpix / 4;
+    const int qpb = cdiv(quads, to1_wgrad_blocks(p));
+    return qpb > 0 ? cdiv(quads, qpb) : 1;
+}
+// [nb][Cout][k][k][C] weight partials, then (C == 1) the [nb][Cout] bias partials
 size_t smallconv_wgrad_ws_floats(const WgradParams& p) {
-    if (to1w_wgrad_ok(p)) return (size_t)p.B * cdiv(p.Ho, 4) * p.k * p.k * p.C + 64;
-    const int blocks = p.C == 1 ? c1_wgrad_blocks(p) : (to1_wgrad_lds_ok(p) ? 768 : to1_wgrad_blocks(p));
-    return (size_t)blocks * p.Cout * p.k * p.k * p.C + (p.C == 1 ? (size_t)blocks * p.Cout : 0) + 64;     // (+ bias partials)
+    const size_t blocks = (size_t)smallconv_wgrad_blocks(p);
+    return blocks * p.Cout * p.k * p.k * p.C + (p.C == 1 ? blocks * p.Cout : 0) + 64;
 }
 // db != nullptr: the launch may produce the bias gradient as well (*db_done = 1: the caller skips its column-sum pass)
-int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, hipStream_t s, float* db, int* db_done) {
+int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, size_t ws_floats, hipStream_t s, float* db, int* db_done) {
     if (db_done) *db_done = 0;
     float* pdb = nullptr;
     TG_REQUIRE(!p.in_bn.mean || smallconv_bnin_wgrad_ok(p), "smallconv: BatchNorm-on-load is not available for this geometry");
-    int nb;
+    TG_REQUIRE(ws && ws_floats >= smallconv_wgrad_ws_floats(p), "tg_conv_wgrad: workspace too small for the partial slabs (%zu < %zu floats)",
+               ws_floats, smallconv_wgrad_ws_floats(p));
+    const int nb = smallconv_wgrad_blocks(p);
     if (p.C == 1) {
         C1Geom q;
         q.tiles_x = cdiv(p.Wo, C1_T);
@@ -1143,7 +1158,6 @@ int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, hipStream
         q.sy_min = q.sx_min = -p.pad;
         q.PH = q.PW = (C1_T - 1) * p.stride + p.k;
         const int ntiles = q.tiles_x * q.tiles_y * p.B;
-        nb = c1_wgrad_blocks(p);
         dim3 grid(nb, p.Cout / 64);
         if (!getenv("TG_C1WGRAD")) {                 // default: the MFMA kernel
             const int ntt = (p.k * p.k + 31) / 32;
@@ -1162,22 +1176,17 @@ int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, hipStream
         TG_CHECK_LAUNCH("c1wgrad_kernel");
         }
     } else if (to1w_wgrad_ok(p)) {
-        nb = p.B * cdiv(p.Ho, 4);
         if (p.k == 4) hipLaunchKernelGGL((to1wgradw_kernel<4>), dim3(p.B, p.C / 256, cdiv(p.Ho, 4)), dim3(256), 0, s, p, ws);
         else hipLaunchKernelGGL((to1wgradw_kernel<3>), dim3(p.B, p.C / 256, cdiv(p.Ho, 4)), dim3(256), 0, s, p, ws);
         TG_CHECK_LAUNCH("to1wgradw_kernel");
     } else if (to1_wgrad_lds_ok(p)) {
         const int tiles_x = cdiv(p.Wo, T1_TW), tiles_y = cdiv(p.Ho, T1_TH), ntiles = tiles_x * tiles_y * p.B;
-        nb = ntiles < 768 ? ntiles : 768;           // three workgroups per CU (five would fit: 71 us against 65, more partials to reduce)
         const size_t lds = ((size_t)T1_PH * T1_PW * 64 + T1_TH * T1_TW) * sizeof(float);
         if (p.in_bn.mean) hipLaunchKernelGGL(to1wgrad64_lds_kernel<true>, dim3(nb), dim3(256), lds, s, p, ws, tiles_x, tiles_y, ntiles);
         else hipLaunchKernelGGL(to1wgrad64_lds_kernel<false>, dim3(nb), dim3(256), lds, s, p, ws, tiles_x, tiles_y, ntiles);
         TG_CHECK_LAUNCH("to1wgrad64_lds_kernel");
     } else {
-        const int quads = p.Mpix / 4;
-        const int blocks = to1_wgrad_blocks(p);
-        const int qpb = cdiv(quads, blocks);
-        nb = cdiv(quads, qpb);
+        const int qpb = cdiv(p.Mpix / 4, to1_wgrad_blocks(p));
         if (p.k == 4) hipLaunchKernelGGL((to1wgrad64_kernel<4>), dim3(nb), dim3(256), 0, s, p, ws, qpb);
         else hipLaunchKernelGGL((to1wgrad64_kernel<3>), dim3(nb), dim3(256), 0, s, p, ws, qpb);
         TG_CHECK_LAUNCH("to1wgrad64_kernel");
