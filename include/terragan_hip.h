@@ -120,6 +120,34 @@ int tg_conv_fwd_pool_code(const TgConv* g, const float* x, const float* w, const
                           float* pool_y, unsigned char* code, float* ws, size_t ws_bytes, tg_stream_t stream);
 int tg_maxpool2_bwd_code(const float* dout, const unsigned char* code, int B, int Ho, int Wo, int C, float* dx,
                          tg_stream_t stream);
+/* Prediction-half tile maps of the frozen VGG trunk.  The trunk runs on [pred; target] stacked along the batch (2 nb images).
+ * Where the receptive field of a 16x16 output tile of a layer holds no pixel whose 32-bit pattern differs between pred[b] and
+ * target[b], the layer's output tile of image b equals that of image nb + b bit for bit (every kernel on the route computes a
+ * pixel from its input patch and the weights alone, in a fixed order).  tg_vgg_sparse_map builds, in ONE launch and from the
+ * data alone, for every conv of `plan` (a string of 'C' = 3x3 / stride-1 / pad-1 conv and 'M' = 2x2 / stride-2 max-pool, in the
+ * trunk's order; x is the trunk's 1-channel input [2 nb][H][W]):
+ *   bits   bit (b * tiles + t) of the word array: tile t (row-major over cdiv(Ho,16) x cdiv(Wo,16)) of prediction image b
+ *          may differ from the target's;
+ *   list   the set tiles as entries b * tiles + t, ascending; count = their number.  All three live on the device.
+ * tg_vgg_sparse_map_bytes is the size of `buf` (0: the map cannot be built for this geometry -- run the trunk dense);
+ * `ticket` is nb + 1 ints of device memory that are zero at the call and zero again behind the launch (the kernel's last
+ * workgroups reset them).  maps[i] (out, one per 'C') point into `buf`.  tg_conv_fwd_sparse is tg_conv_fwd_p (pool_y == code == NULL),
+ * tg_conv_fwd_pool (pool_y only) or tg_conv_fwd_pool_code (both; y unused) of the batch [pred; target]: with sp != NULL the
+ * launcher computes only the prediction tiles `sp` marks and copies the target's results into the others -- wherever its
+ * planner can honour the map (the fp32 F(2x2,3x3) pipelined kernel in one K split, static walk); any other route runs dense.
+ * The results are the same bit for bit either way. */
+typedef struct TgSparseMap {
+    const uint32_t* bits;
+    const int32_t* list;
+    const int32_t* count;
+    int32_t nb, tiles_y, tiles_x, _pad;
+} TgSparseMap;
+size_t tg_vgg_sparse_map_bytes(int nb, int H, int W, const char* plan);
+int tg_vgg_sparse_map(const float* x, int nb, int H, int W, const char* plan, void* buf, size_t buf_bytes, int* ticket,
+                      TgSparseMap* maps, tg_stream_t stream);
+int tg_conv_fwd_sparse(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias, int act,
+                       float slope, float* y, float* pool_y, unsigned char* code, const TgSparseMap* sp, float* ws,
+                       size_t ws_bytes, tg_stream_t stream);
 /* BatchNorm + activation on load: the layer's input is act(BN(x)) -- x the PRE-BatchNorm output of the layer below, statistics
  * and affine parameters in `bn` -- and that tensor is never written.  For `final` (generator.py:29,56: Conv2d(64, 1, 3, 1, 1) over
  * dec1's ReLU(BN(.)) output, pconv.py:43-48): saves dec1's BatchNorm-apply pass (one read + one write of the widest activation).

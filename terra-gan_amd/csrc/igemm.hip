@@ -1411,6 +1411,7 @@ struct FwdExtras {
     float* pool_dst = nullptr;              // 2x2 max-pool of the output, written from the output transform where the kernel can
     unsigned char* pool_code = nullptr;     // ... with the pool code, and dst itself NOT written
     const BnIn* in_bn = nullptr;            // the source is act(BN(src)), applied on load
+    const TgSparseMap* sparse = nullptr;    // prediction-half tile map of a [pred; target] batch (tg_conv_fwd_sparse)
     int pool_fused = 0;                     // out: the launcher wrote the pooled tensor
 };
 static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, const float* w, float* wprep, int prep,
@@ -1425,6 +1426,7 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
         if (!s2d_ok(g) && !wino22_fwd_geom_ok(g)) {
             FwdExtras e;
             e.pool_dst = pool_y;
+            e.sparse = ex ? ex->sparse : nullptr;
             const int rc1 = conv_fwd_impl(g, x, in_mask, w, wprep, prep, bias, ratio, act, slope, y, ws, ws_bytes, stream, nullptr, &e);
             if (rc1) return rc1;
             fused = e.pool_fused;
@@ -1525,6 +1527,7 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
         p.pool_dst = ex->pool_dst;
         p.pool_code = ex->pool_code;
         p.pool_only = ex->pool_code != nullptr;
+        p.sparse = ex->sparse;
         if (ex->in_bn) {
             p.in_bn = *ex->in_bn;
             TG_REQUIRE(smallconv_bnin_fwd_ok(p), "tg_conv_fwd_bnin: geometry not supported (ask tg_conv_bnin_supported first)");
@@ -1555,19 +1558,38 @@ extern "C" int tg_conv_pool_code_supported(const TgConv* g) {
     const long work = (long)cdiv(g->Wo, 16) * cdiv(g->Ho, 16) * g->B * (g->Cout / WINO_BN);
     return nchunks < 16 || work >= 4L * WINO_PLAN_CUS ? 1 : 0;         // (launch_wino: one K split)
 }
-extern "C" int tg_conv_fwd_pool_code(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias,
-                                     float* pool_y, unsigned char* code, float* ws, size_t ws_bytes, tg_stream_t stream) {
+static int conv_fwd_pool_code(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias, float* pool_y,
+                              unsigned char* code, const TgSparseMap* sp, float* ws, size_t ws_bytes, tg_stream_t stream) {
     TG_REQUIRE(pool_y && code && aligned16(pool_y) && (reinterpret_cast<uintptr_t>(code) & 3) == 0, "tg_conv_fwd_pool_code: bad pointers");
     TG_REQUIRE(tg_conv_pool_code_supported(g), "tg_conv_fwd_pool_code: geometry not supported (ask tg_conv_pool_code_supported first)");
     FwdExtras e;
     e.pool_dst = pool_y;
     e.pool_code = code;
+    e.sparse = sp;
     // (dst is not written: the pooled buffer stands in for the pointer checks)
     const int rc = conv_fwd_impl(g, x, nullptr, w, const_cast<float*>(wprep), wprep ? 1 : 0, bias, nullptr, TG_ACT_RELU, 0.f, pool_y, ws,
                                  ws_bytes, stream, nullptr, &e);
     if (rc) return rc;
     TG_REQUIRE(e.pool_fused, "tg_conv_fwd_pool_code: internal: the launch did not take the fused path");
     return TG_OK;
+}
+extern "C" int tg_conv_fwd_pool_code(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias,
+                                     float* pool_y, unsigned char* code, float* ws, size_t ws_bytes, tg_stream_t stream) {
+    return conv_fwd_pool_code(g, x, w, wprep, bias, pool_y, code, nullptr, ws, ws_bytes, stream);
+}
+// tg_conv_fwd_p / tg_conv_fwd_pool / tg_conv_fwd_pool_code with a prediction-half tile map (terragan_hip.h): launch_wino decides
+// whether the launch can honour it; every other route is the dense call, the same bits
+extern "C" int tg_conv_fwd_sparse(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias, int act,
+                                  float slope, float* y, float* pool_y, unsigned char* code, const TgSparseMap* sp, float* ws,
+                                  size_t ws_bytes, tg_stream_t stream) {
+    if (code) {
+        TG_REQUIRE(act == TG_ACT_RELU, "tg_conv_fwd_sparse: the pool code needs a ReLU output");
+        return conv_fwd_pool_code(g, x, w, wprep, bias, pool_y, code, sp, ws, ws_bytes, stream);
+    }
+    FwdExtras e;
+    e.sparse = sp;
+    return conv_fwd_impl(g, x, nullptr, w, const_cast<float*>(wprep), wprep ? 1 : 0, bias, nullptr, act, slope, y, ws, ws_bytes, stream,
+                         pool_y, &e);
 }
 static bool bnin_geom_ok(const TgConv* g) {
     return g && g->Cout == 1 && g->Cin == 64 && g->k == 3 && g->stride == 1 && g->pad == 1 && (g->Wo % 4) == 0;

@@ -54,6 +54,8 @@ struct IGemmParams {
     // set gate_bits_done); every other launch runs ungated and tg_conv_dgrad_gbits applies the bits afterwards (gate_bits_apply).
     const uint32_t* gate_bits;
     int gate_bits_done;
+    // tg_conv_fwd_sparse: prediction-half tile map of a [pred; target] batch (host side; launch_wino decides whether it applies)
+    const TgSparseMap* sparse;
 };
 __device__ __forceinline__ float gate_factor(const IGemmParams& p, size_t idx) {
     const float gv = p.gate[idx];

@@ -372,6 +372,260 @@ extern "C" int tg_mask_pyramid(const TgMaskPyramid* pm, int B, tg_stream_t strea
     return TG_OK;
 }
 
+// ---- prediction-half tile maps of the VGG trunk (tg_vgg_sparse_map) ------------------------------------------------------------
+// Workgroup (slice, b) turns a band of rows of prediction image b into bits: the pixels whose 32-bit patterns differ between
+// x[b] and x[nb + b], one u64 word per 64 pixels of a row (a wave ballot per word), written to the buffer -- the reads of the
+// 2 x 4 MB of the bench's batch spread over the whole chip.  The last slice of image b to finish (ticket[b]) loads the image's
+// bits into LDS and carries them through the trunk's geometry -- a 3x3 conv dilates by one pixel, a 2x2 / stride-2 pool ORs each
+// window -- and behind every conv flags its 16x16 output tiles (one byte per (b, tile)).  Receptive fields are rectangles and
+// these two steps compose exactly, so a tile is flagged iff a differing pixel lies in its receptive field.  The last image to
+// finish (ticket[nb]) packs every conv's flags into the bit words and the ascending entry list, all 1024 threads at once: a
+// word per thread, its popcount, a block scan, the entries.  Each last workgroup zeroes the ticket it drew.
+constexpr int VSM_MAX_OPS = 24, VSM_MAX_CONV = 16, VSM_LDS_WORDS = 4096;       // u64 words of one bit image (64 KB of LDS for two)
+struct VggMapArgs {
+    const uint32_t* x;
+    int nb, H, W, nops, nconv;
+    char ops[VSM_MAX_OPS];
+    int tiles_y[VSM_MAX_CONV], tiles_x[VSM_MAX_CONV];
+    int32_t* count[VSM_MAX_CONV];
+    uint32_t* bits[VSM_MAX_CONV];
+    int32_t* list[VSM_MAX_CONV];
+    unsigned char* flags[VSM_MAX_CONV];        // [nb * tiles rounded up to 32]
+    uint64_t* d0;                              // [nb][H][cdiv(W, 64)] difference bits
+    int rows_per_slice;
+    int* ticket;                               // [nb + 1]
+};
+__device__ __forceinline__ uint32_t vsm_even_bits(uint64_t v) {      // bits 0, 2, .., 62 of v -> bits 0 .. 31
+    v &= 0x5555555555555555ull;
+    v = (v | (v >> 1)) & 0x3333333333333333ull;
+    v = (v | (v >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    v = (v | (v >> 4)) & 0x00ff00ff00ff00ffull;
+    v = (v | (v >> 8)) & 0x0000ffff0000ffffull;
+    v = (v | (v >> 16)) & 0x00000000ffffffffull;
+    return (uint32_t)v;
+}
+__device__ __forceinline__ uint64_t vsm_row_mask(int W, int w, int WW) {
+    return (w == WW - 1 && (W & 63)) ? (1ull << (W & 63)) - 1 : ~0ull;
+}
+// Arrival of a workgroup at a ticket: true in the last of `n` to arrive, which then sees every store the others made before.
+// Each wave waits for its own stores to reach the L2, and ONE release (agent scope: the L2 written back for the other XCDs) and
+// one acquire per workgroup follow -- a fence in every wave made the launch 4x slower.
+__device__ __forceinline__ bool vsm_last_arrival(int* ctr, int n, int* s_last) {
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        const bool last = atomicAdd(ctr, 1) == n - 1;
+        if (last) __threadfence();
+        *s_last = last;
+    }
+    __syncthreads();
+    return *s_last;
+}
+__global__ __launch_bounds__(1024) void vgg_sparse_map_kernel(const VggMapArgs a) {
+    extern __shared__ uint64_t vsm[];                 // two bit images of VSM_LDS_WORDS words at most
+    __shared__ int scan[1024];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
+    int H = a.H, W = a.W, WW = (W + 63) >> 6;
+    uint64_t* cur = vsm;
+    uint64_t* nxt = vsm + H * WW;
+    uint64_t* d0 = a.d0 + (size_t)b * H * WW;
+    {
+        // this slice's rows of the difference image: (row, word) units over the 16 waves, 8 units' loads in flight per wave
+        const uint32_t* xp = a.x + (size_t)b * H * W;
+        const uint32_t* tp = a.x + ((size_t)a.nb + b) * H * W;
+        const int ubeg = blockIdx.x * a.rows_per_slice * WW, uend = min(H, (blockIdx.x + 1) * a.rows_per_slice) * WW;
+        for (int u0 = ubeg + wave; u0 < uend; u0 += 16 * 8) {
+            uint32_t pv[8], tv[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int u = u0 + 16 * k, y = u / WW, px = (u - y * WW) * 64 + lane;
+                pv[k] = tv[k] = 0;
+                if (u < uend && px < W) { pv[k] = xp[(size_t)y * W + px]; tv[k] = tp[(size_t)y * W + px]; }
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const uint64_t m = __ballot(pv[k] != tv[k]);
+                if (lane == 0 && u0 + 16 * k < uend) d0[u0 + 16 * k] = m;
+            }
+        }
+    }
+    if (!vsm_last_arrival(a.ticket + b, (int)gridDim.x, &s_last)) return;
+    for (int u = tid; u < H * WW; u += 1024) cur[u] = d0[u];
+    if (tid == 0) __hip_atomic_store(a.ticket + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    int ci = 0;
+    for (int o = 0; o < a.nops; ++o) {
+        if (a.ops[o] == 'C') {
+            // 3x3 conv, pad 1: dilate by one pixel
+            for (int u = tid; u < H * WW; u += 1024) {
+                const int y = u / WW, w = u - y * WW;
+                uint64_t r = 0;
+                for (int dy = -1; dy <= 1; ++dy) {
+                    const int yy = y + dy;
+                    if (yy < 0 || yy >= H) continue;
+                    const uint64_t* row = cur + yy * WW;
+                    const uint64_t v = row[w];
+                    r |= v | (v << 1) | (v >> 1);
+                    if (w > 0) r |= row[w - 1] >> 63;
+                    if (w + 1 < WW) r |= row[w + 1] << 63;
+                }
+                nxt[u] = r & vsm_row_mask(W, w, WW);
+            }
+            __syncthreads();
+            uint64_t* t = cur; cur = nxt; nxt = t;
+            // its 16x16 output tiles (a 16-pixel field never straddles a word)
+            const int ty_n = a.tiles_y[ci], tx_n = a.tiles_x[ci], tiles = ty_n * tx_n;
+            for (int t2 = tid; t2 < tiles; t2 += 1024) {
+                const int ty = t2 / tx_n, tx = t2 - ty * tx_n;
+                const int w = (16 * tx) >> 6, sh = (16 * tx) & 63;
+                uint64_t any = 0;
+                for (int y = 16 * ty; y < min(16 * ty + 16, H); ++y) any |= (cur[y * WW + w] >> sh) & 0xffffull;
+                a.flags[ci][(size_t)b * tiles + t2] = any ? 1 : 0;
+            }
+            ++ci;
+        } else {
+            // 2x2 / stride-2 max-pool (floor): a pooled pixel differs iff one of its window does
+            const int H2 = H >> 1, W2 = W >> 1, WW2 = (W2 + 63) >> 6;
+            for (int u = tid; u < H2 * WW2; u += 1024) {
+                const int y = u / WW2, w = u - y * WW2;
+                const uint64_t* r0 = cur + (2 * y) * WW;
+                const uint64_t* r1 = r0 + WW;
+                const uint64_t s0 = r0[2 * w] | r1[2 * w];
+                const uint64_t s1 = 2 * w + 1 < WW ? r0[2 * w + 1] | r1[2 * w + 1] : 0;
+                const uint64_t v = (uint64_t)vsm_even_bits(s0 | (s0 >> 1)) | ((uint64_t)vsm_even_bits(s1 | (s1 >> 1)) << 32);
+                nxt[u] = v & vsm_row_mask(W2, w, WW2);
+            }
+            H = H2; W = W2; WW = WW2;
+            __syncthreads();
+            uint64_t* t = cur; cur = nxt; nxt = t;
+        }
+        __syncthreads();
+    }
+    // the last workgroup packs the flags of every image
+    if (!vsm_last_arrival(a.ticket + a.nb, a.nb, &s_last)) return;
+    for (int c = 0; c < a.nconv; ++c) {
+        const int n = a.nb * a.tiles_y[c] * a.tiles_x[c], nw = (n + 31) >> 5;
+        int carry = 0;
+        for (int w0 = 0; w0 < nw; w0 += 1024) {
+            const int w = w0 + tid;
+            uint32_t word = 0;
+            if (w < nw) {
+                const uint4* fp = reinterpret_cast<const uint4*>(a.flags[c] + 32 * (size_t)w);
+                const uint4 f0 = fp[0], f1 = fp[1];
+                const uint32_t fw[8] = {f0.x, f0.y, f0.z, f0.w, f1.x, f1.y, f1.z, f1.w};
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) word |= ((fw[i] >> (8 * j)) & 1u) << (4 * i + j);
+                if (32 * w + 32 > n) word &= (1u << (n - 32 * w)) - 1u;
+                a.bits[c][w] = word;
+            }
+            // inclusive block scan of the popcounts
+            const int pc = __popc(word);
+            scan[tid] = pc;
+            __syncthreads();
+            for (int d = 1; d < 1024; d <<= 1) {
+                const int v = tid >= d ? scan[tid - d] : 0;
+                __syncthreads();
+                scan[tid] += v;
+                __syncthreads();
+            }
+            int pos = carry + scan[tid] - pc;
+            for (uint32_t m = word; m; m &= m - 1) a.list[c][pos++] = 32 * w + __ffs(m) - 1;
+            carry += scan[1023];
+            __syncthreads();
+        }
+        if (tid == 0) *a.count[c] = carry;
+    }
+    if (tid == 0) __hip_atomic_store(a.ticket + a.nb, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// buffer layout of one call: the difference bits, then per conv  count (4 ints) | bits (rounded to 4 words) | list | flags (bytes,
+// rounded to 32 tiles)
+struct VsmLayout {
+    int nconv, nops, H, W;
+    size_t d0;
+    int tiles_y[VSM_MAX_CONV], tiles_x[VSM_MAX_CONV];
+    size_t count[VSM_MAX_CONV], bits[VSM_MAX_CONV], list[VSM_MAX_CONV], flags[VSM_MAX_CONV];
+    size_t bytes;
+};
+static bool vsm_layout(int nb, int H, int W, const char* plan, VsmLayout& L) {
+    if (nb <= 0 || H <= 0 || W <= 0 || !plan) return false;
+    if ((size_t)H * ((W + 63) / 64) > VSM_LDS_WORDS) return false;
+    L = VsmLayout{};
+    L.H = H; L.W = W;
+    L.d0 = 0;
+    size_t off = align_up((size_t)nb * H * ((W + 63) / 64) * sizeof(uint64_t), 16);
+    int h = H, w = W;
+    for (const char* c = plan; *c; ++c) {
+        if (L.nops == VSM_MAX_OPS) return false;
+        ++L.nops;
+        if (*c == 'M') {
+            h >>= 1; w >>= 1;
+            if (h <= 0 || w <= 0) return false;
+        } else if (*c == 'C') {
+            if (L.nconv == VSM_MAX_CONV) return false;
+            const int i = L.nconv++;
+            L.tiles_y[i] = cdiv(h, 16); L.tiles_x[i] = cdiv(w, 16);
+            const size_t n = (size_t)nb * L.tiles_y[i] * L.tiles_x[i];
+            if (n > ((size_t)1 << 30)) return false;
+            L.count[i] = off; off += 16;
+            L.bits[i] = off; off += align_up((n + 31) / 32, 4) * 4;
+            L.list[i] = off; off += align_up(n, 4) * 4;
+            L.flags[i] = off; off += align_up(n, 32);
+        } else {
+            return false;
+        }
+    }
+    L.bytes = off;
+    return L.nconv > 0;
+}
+extern "C" size_t tg_vgg_sparse_map_bytes(int nb, int H, int W, const char* plan) {
+    VsmLayout L;
+    return vsm_layout(nb, H, W, plan, L) ? L.bytes : 0;
+}
+extern "C" int tg_vgg_sparse_map(const float* x, int nb, int H, int W, const char* plan, void* buf, size_t buf_bytes, int* ticket,
+                                 TgSparseMap* maps, tg_stream_t stream) {
+    VsmLayout L;
+    TG_REQUIRE(x && buf && ticket && maps, "tg_vgg_sparse_map: null pointer");
+    TG_REQUIRE(vsm_layout(nb, H, W, plan, L), "tg_vgg_sparse_map: geometry not supported (tg_vgg_sparse_map_bytes is 0)");
+    TG_REQUIRE(buf_bytes >= L.bytes && (reinterpret_cast<uintptr_t>(buf) & 15) == 0, "tg_vgg_sparse_map: buffer too small or unaligned");
+    VggMapArgs a = {};
+    a.x = reinterpret_cast<const uint32_t*>(x);
+    a.nb = nb; a.H = H; a.W = W; a.nops = L.nops; a.nconv = L.nconv; a.ticket = ticket;
+    for (int i = 0; i < L.nops; ++i) a.ops[i] = plan[i];
+    char* base = static_cast<char*>(buf);
+    a.d0 = reinterpret_cast<uint64_t*>(base + L.d0);
+    // about one workgroup per CU over the whole batch, at least 8 rows each
+    const int slices = cdiv(H, 8) < cdiv(256, nb) ? cdiv(H, 8) : cdiv(256, nb);
+    a.rows_per_slice = cdiv(H, slices);
+    for (int i = 0; i < L.nconv; ++i) {
+        a.tiles_y[i] = L.tiles_y[i]; a.tiles_x[i] = L.tiles_x[i];
+        a.count[i] = reinterpret_cast<int32_t*>(base + L.count[i]);
+        a.bits[i] = reinterpret_cast<uint32_t*>(base + L.bits[i]);
+        a.list[i] = reinterpret_cast<int32_t*>(base + L.list[i]);
+        a.flags[i] = reinterpret_cast<unsigned char*>(base + L.flags[i]);
+        maps[i] = TgSparseMap{a.bits[i], a.list[i], a.count[i], nb, L.tiles_y[i], L.tiles_x[i], 0};
+    }
+    const size_t lds = 2 * (size_t)H * ((W + 63) / 64) * sizeof(uint64_t);
+    static bool opted[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !opted[dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(vgg_sparse_map_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(2 * VSM_LDS_WORDS * sizeof(uint64_t))) != hipSuccess) {
+            tg_set_error("tg_vgg_sparse_map: LDS opt-in failed");
+            return TG_ERR_LAUNCH;
+        }
+        if (dev >= 0 && dev < 64) opted[dev] = true;
+    }
+    hipLaunchKernelGGL(vgg_sparse_map_kernel, dim3(cdiv(H, a.rows_per_slice), nb), dim3(1024), lds, S(stream), a);
+    TG_CHECK_LAUNCH("vgg_sparse_map_kernel");
+    return TG_OK;
+}
+
 // =================================================================================================
 // BatchNorm
 // =================================================================================================

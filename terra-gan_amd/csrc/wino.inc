@@ -28,6 +28,11 @@ struct WinoGeom {
     int sy_min, sx_min;
     int interleave;     // work distribution, see wino_distribute
     int* qctr;          // work-stealing counter block of this launch (nullptr: static distribution), see WinoWork
+    // prediction-half tile map of a [pred; target] batch (wino_pipe_kernel<.., SPARSE>, TgSparseMap): sp_tiles = nb x tiles
+    const uint32_t* sp_bits;
+    const int* sp_list;
+    const int* sp_count;
+    int sp_tiles, sp_nb;
 };
 struct WinoWeights {
     long sn, sk, stap;      // element strides of the raw weights: output row n, contraction index k, tap (ky*3+kx)
@@ -604,7 +609,11 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_kernel(const IGemmParams p,
 // xh = 1 wave hands its row maxima over through the exchange slot it has just consumed (no extra barrier) and the xh = 0 wave stores.
 // GBITS (with GATED): the ReLU gate comes as p.gate_bits -- one dword per pixel and 32-channel group, shared by the 8 lanes of a
 // row of tile_rows4i, each of which takes its nibble (channels e_nb0 + 4 (lane & 7) .. + 3; e_nb0 is a multiple of 32 here).
-template <bool GATED, bool STEAL, bool POOL = false, bool GBITS = false>
+// SPARSE (static walk, one split, ungated): the batch is [pred; target] (2 nb images) and q.sp_* is its tile map (tg_vgg_sparse_map).
+// The items are the target half's, dense, followed by `count` list entries of the prediction half (x q.nt, N tile fastest
+// in both parts); a target item whose tile is NOT in the map repeats its stores -- the same registers -- into image b - nb,
+// whose result is that one bit for bit.  Prediction items write only mapped tiles, mirrors only the others: one writer per tile.
+template <bool GATED, bool STEAL, bool POOL = false, bool GBITS = false, bool SPARSE = false>
 __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmParams p, const WinoGeom q, const float* __restrict__ U) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Vs = smem;                            // [2][16][64][8]
@@ -615,14 +624,28 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
     const int mw = wave & 1, nw = (wave >> 1) & 1, xh = wave >> 2;
     __shared__ int wq_slot[2];
     WinoWork<STEAL> wk;
-    wk.init(q.total_work, q.interleave, q.qctr, wq_slot);
+    int total = q.total_work;
+    if constexpr (SPARSE) {
+        const int cnt = __builtin_amdgcn_readfirstlane(*q.sp_count);
+        total = (q.sp_tiles + min(max(cnt, 0), q.sp_tiles)) * q.nt;
+    }
+    wk.init(total, q.interleave, q.qctr, wq_slot);
 
     // coordinates and patch slots of an item
-    struct Item { int nt, n0, oy0, ox0, b; uint32_t poff[2]; };
+    struct Item { int nt, n0, oy0, ox0, b, mirror; uint32_t poff[2]; };
     auto decode_item = [&](int it) {
         Item r;
         r.nt = it % q.nt;
         int tile = it / q.nt;
+        r.mirror = 0;
+        if constexpr (SPARSE) {
+            if (tile < q.sp_tiles) {             // target image nb + b: mirrored into b where the map leaves the tile out
+                r.mirror = (__builtin_amdgcn_readfirstlane(q.sp_bits[tile >> 5]) >> (tile & 31)) & 1 ? 0 : 1;
+                tile += q.sp_tiles;
+            } else {
+                tile = __builtin_amdgcn_readfirstlane(q.sp_list[tile - q.sp_tiles]);
+            }
+        }
         const int tx = tile % q.tiles_x;
         tile /= q.tiles_x;
         const int ty = tile % q.tiles_y;
@@ -778,6 +801,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
         const float act_neg = p.act == TG_ACT_RELU ? 0.f : (p.act == TG_ACT_LEAKY ? p.slope : 1.f);
         const float gate_neg = p.gate_act == TG_ACT_LEAKY ? p.gate_slope : 0.f;
         const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, (int)((size_t)p.B * p.DH * p.DW * p.N * 4), 0x00020000);
+        const int e_mdelta = SPARSE ? q.sp_nb * p.DH * p.DW * p.N * 4 : 0;       // bytes from image nb + b to image b
         f32x4 bq = {0.f, 0.f, 0.f, 0.f};
         if (p.bias && e_single) bq = *reinterpret_cast<const f32x4*>(p.bias + e_nb0 + 4 * (lane & 7));
         f32x4 pmx[POOL ? 4 : 1];
@@ -875,6 +899,10 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
                     // (a store of more than 64 bits followed by a write of its data registers) only for stores WITHOUT a
                     // scalar-register offset, as the ISA manual specifies it.
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), drsrc, e_voff + (uint32_t)soff, 0, 0);
+                    if constexpr (SPARSE) {
+                        if (ci.mirror)
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), drsrc, e_voff + (uint32_t)(soff - e_mdelta), 0, 0);
+                    }
                 } else {
                     const int t = 32 * mw + rr;
                     const int oy = ci.oy0 + 2 * (t >> 3) + xh, ox = ci.ox0 + 2 * (t & 7) + j;
@@ -927,6 +955,13 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
                     const int pix = (ci.b * PH + prow) * PW + (ci.ox0 >> 1);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), prsrc, p_voff + (uint32_t)((pix * p.N + e_nb0) * 4), 0, 0);
                     if (p.pool_code) __builtin_amdgcn_raw_buffer_store_b32(code, crsrc, c_voff + (uint32_t)(pix * p.N + e_nb0), 0, 0);
+                    if constexpr (SPARSE) {
+                        if (ci.mirror) {
+                            const int mpix = pix - q.sp_nb * PH * PW;
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), prsrc, p_voff + (uint32_t)((mpix * p.N + e_nb0) * 4), 0, 0);
+                            if (p.pool_code) __builtin_amdgcn_raw_buffer_store_b32(code, crsrc, c_voff + (uint32_t)(mpix * p.N + e_nb0), 0, 0);
+                        }
+                    }
                 }
             }
         }
@@ -1001,13 +1036,14 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
     const bool pipe = fast && !no_pipe && nchunks - (p.splits - 1) * q.chunks_per_split >= 2 && q.chunks_per_split >= 2 &&
                       (size_t)p.B * p.DH * p.DW * p.N * 4 < ((size_t)1 << 31);
     typedef void (*WinoKern)(const IGemmParams, const WinoGeom, const float*);
-    static const WinoKern kerns[16] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
+    static const WinoKern kerns[18] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
                                        wino_kernel<true, true, false>, wino_pipe_kernel<false, false>, wino_pipe_kernel<true, false>,
                                        wino_kernel<false, false, true>, wino_kernel<false, true, true>, wino_kernel<true, false, true>,
                                        wino_kernel<true, true, true>, wino_pipe_kernel<false, true>, wino_pipe_kernel<true, true>,
                                        wino_pipe_kernel<false, false, true>, wino_pipe_kernel<false, true, true>,
-                                       wino_pipe_kernel<true, false, false, true>, wino_pipe_kernel<true, true, false, true>};
-    static LdsOptIn opts[16];
+                                       wino_pipe_kernel<true, false, false, true>, wino_pipe_kernel<true, true, false, true>,
+                                       wino_pipe_kernel<false, false, false, false, true>, wino_pipe_kernel<false, false, true, false, true>};
+    static LdsOptIn opts[18];
     q.qctr = wino_queue_block(s, p.splits, q.total_work);
     // the fused 2x2 max-pool: whole pooling windows inside the output, one split, the plain dst grid
     static const bool no_pool = getenv("TG_NO_FUSED_POOL") != nullptr;
@@ -1019,7 +1055,18 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
     // bit gates (p.gate_bits): read by the pipelined kernel in one split; any other launch runs ungated and the caller applies them
     const bool gbits = p.gate_bits != nullptr && pipe && p.splits == 1;
     if (gbits) p.gate_bits_done = 1;
-    const int ki = gbits ? (q.qctr ? 15 : 14)
+    // the prediction-half tile map (tg_conv_fwd_sparse) is honoured by the pipelined kernel's static walk in one split, ungated, on
+    // the plain dst grid of a [pred; target] batch whose tile grid is the map's; everything else runs dense -- the same bits
+    const TgSparseMap* sm = p.sparse;
+    const bool sparse = sm && pipe && !gated && !gbits && !q.qctr && p.splits == 1 && !p.accumulate && !p.rowscale && p.ds == 1 &&
+                        p.dy0 == 0 && p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && (pool || !p.pool_dst) && sm->nb > 0 &&
+                        p.B == 2 * sm->nb && sm->tiles_y == q.tiles_y && sm->tiles_x == q.tiles_x && sm->bits && sm->list && sm->count;
+    if (sparse) {
+        q.sp_bits = sm->bits; q.sp_list = sm->list; q.sp_count = sm->count;
+        q.sp_nb = sm->nb; q.sp_tiles = sm->nb * q.tiles_y * q.tiles_x;
+    }
+    const int ki = sparse ? (pool ? 17 : 16)
+                 : gbits ? (q.qctr ? 15 : 14)
                  : pool ? (q.qctr ? 13 : 12) : (q.qctr ? 6 : 0) + (pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0));
     if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds, "wino")) return rc;
     {

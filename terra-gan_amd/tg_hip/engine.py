@@ -56,6 +56,10 @@ VGG_TRUNK = [0, 2, "M", 5, 7, "M", 10, 12, 14]
 VGG_WINO4 = os.environ.get("TG_VGG_WINO4", "1") != "0"
 VGG_WINO4_FWD = os.environ.get("TG_VGG_WINO4_FWD", "0") == "1"
 VGG_WINO4_MINCH = int(os.environ.get("TG_VGG_WINO4_MINCH", "128"))
+# Forward of a [pred; target] batch (vgg_forward(..., nb=B)): the prediction half's 16x16 output tiles whose receptive field holds
+# no pixel where pred and target differ are not computed -- the target's identical results are stored into them
+# (O.vgg_sparse_map, tg_conv_fwd_sparse).  Bit for bit the dense results.  TG_VGG_SPARSE=0: always dense.
+VGG_SPARSE = os.environ.get("TG_VGG_SPARSE", "1") != "0"
 POOL_CODE = os.environ.get("TG_NO_POOL_CODE") is None       # pooled convs of the trunk: pooled tensor + pool code, no full-resolution output
 
 
@@ -487,6 +491,11 @@ def vgg_forward(V, img, keep=True, wino4=None, nb=None):
     h = img.reshape(*img.shape, 1)
     steps = []
     pooled = code = None
+    smaps = None
+    if VGG_SPARSE and nb is not None and 2 * nb == img.shape[0]:
+        # nb prediction images followed by their nb targets: tile maps of every conv from the data (one launch)
+        smaps = O.vgg_sparse_map(img, nb, "".join("M" if it == "M" else "C" for it in VGG_TRUNK))
+    ci = -1
     for i, item in enumerate(VGG_TRUNK):
         if item == "M":
             # (the conv below has written the pooled tensor with its own output where the sizes are even)
@@ -496,16 +505,18 @@ def vgg_forward(V, img, keep=True, wino4=None, nb=None):
             pooled = code = None
         else:
             w = V["0.folded"] if item == 0 else V[f"{item}.weight"]
+            ci += 1
+            sp = smaps.maps[ci] if smaps is not None else None
             O.tag(f"vgg{item}.fwd")
             pool = i + 1 < len(VGG_TRUNK) and VGG_TRUNK[i + 1] == "M" and h.shape[1] % 2 == 0 and h.shape[2] % 2 == 0
             w4 = _vgg_wino4(w, h.shape[0], h.shape[1], h.shape[2], w.shape[0], wino4, VGG_WINO4_FWD)
             if pool and POOL_CODE and not w4 and O.conv_pool_code_supported(tuple(h.shape), w.shape[0]):
                 # the full-resolution output of a pooled conv has two readers, the pool and the pool's backward: it is not written
                 # at all -- the pooled tensor and a byte of (arg-max position, ReLU gate) per pooled element leave the conv instead
-                pooled, code = O.conv_fwd_pool_code(h, w, V[f"{item}.bias"])
+                pooled, code = O.conv_fwd_pool_code(h, w, V[f"{item}.bias"], sparse=sp)
                 o = None
             else:
-                o = O.conv_fwd(h, w, V[f"{item}.bias"], 3, 1, 1, act=O.ACT_RELU, pool=pool, wino4=w4)
+                o = O.conv_fwd(h, w, V[f"{item}.bias"], 3, 1, 1, act=O.ACT_RELU, pool=pool, wino4=w4, sparse=sp)
                 if pool:
                     o, pooled = o
             if gates:

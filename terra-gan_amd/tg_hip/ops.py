@@ -204,10 +204,59 @@ def _prepared(w, wv, g, mode):
     return ent[2]
 
 
-def conv_fwd(x, w, bias, k, stride, pad, in_mask=None, ratio=None, act=ACT_NONE, slope=0.0, wino4=False, pool=False):
+_sparse_tickets = {}
+
+
+class SparseMaps:
+    """Prediction-half tile maps of the VGG trunk for one [pred; target] batch (tg_vgg_sparse_map): maps[i] belongs to the i-th
+    conv of the plan.  Holds the device buffer the maps point into."""
+
+    def __init__(self, buf, maps):
+        self.buf, self.maps = buf, maps
+
+
+def vgg_sparse_map(x, nb, plan):
+    """x: the trunk's 1-channel input [2 nb][H][W] (or [2 nb][H][W][1]).  plan: 'C' (3x3 / stride-1 / pad-1 conv) and 'M'
+    (2x2 / stride-2 max-pool) in the trunk's order.  Returns SparseMaps, or None where no map can be built (the trunk then
+    runs dense: the same values).  One launch, no host synchronisation."""
+    _chk(x, "x")
+    H, W = x.shape[1], x.shape[2]
+    assert x.shape[0] == 2 * nb and x.numel() == 2 * nb * H * W, (tuple(x.shape), nb)
+    lib = _lib()
+    pb = plan.encode()
+    nbytes = lib.tg_vgg_sparse_map_bytes(nb, H, W, pb)
+    if nbytes == 0:
+        return None
+    dev = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    ticket = _sparse_tickets.get(dev)
+    if ticket is None or ticket.numel() < nb + 1:
+        if torch.cuda.is_current_stream_capturing():
+            return None                 # (the zeroed tickets must outlive any capture: allocated by an eager call first)
+        ticket = _sparse_tickets[dev] = torch.zeros(max(nb + 1, 64), dtype=torch.int32, device=x.device)
+    buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    nconv = plan.count("C")
+    maps = (L.TgSparseMap * nconv)()
+    L.check(lib.tg_vgg_sparse_map(_p(x), nb, H, W, pb, _p(buf), nbytes, _p(ticket), maps, _stream()), "tg_vgg_sparse_map")
+    return SparseMaps(buf, maps)
+
+
+def conv_fwd(x, w, bias, k, stride, pad, in_mask=None, ratio=None, act=ACT_NONE, slope=0.0, wino4=False, pool=False, sparse=None):
     """pool=True: returns (y, maxpool2(y)) from one call (tg_conv_fwd_pool: the pooled tensor leaves the conv's output transform
-    where the kernel allows, the pool kernel runs on y otherwise)."""
+    where the kernel allows, the pool kernel runs on y otherwise).  sparse: a TgSparseMap of this layer (vgg_sparse_map) -- x is
+    a [pred; target] batch and only the prediction tiles it marks are computed (tg_conv_fwd_sparse); the same values."""
     _chk(x, "x"); _chk(bias, "bias"); _chk(in_mask, "in_mask"); _chk(ratio, "ratio")
+    if sparse is not None:
+        assert in_mask is None and ratio is None
+        wv = weight_view(w)
+        _chk(wv, "weight")
+        g = conv_geom(x, wv.shape[0], k, stride, pad, wino4)
+        y = empty(g.B, g.Ho, g.Wo, g.Cout, like=x)
+        yp = empty(g.B, g.Ho // 2, g.Wo // 2, g.Cout, like=x) if pool else None
+        lib = _lib()
+        ws = workspace(lib.tg_conv_fwd_ws_bytes(C.byref(g)))
+        L.check(lib.tg_conv_fwd_sparse(C.byref(g), _p(x), _p(wv), _p(_prepared(w, wv, g, WPREP_FWD)), _p(bias), act, slope, _p(y),
+                                       _p(yp), None, C.byref(sparse), _p(ws), ws.numel() * 4, _stream()), "tg_conv_fwd_sparse")
+        return (y, yp) if pool else y
     wv = weight_view(w)
     _chk(wv, "weight")
     g = conv_geom(x, wv.shape[0], k, stride, pad, wino4)
@@ -266,9 +315,9 @@ def conv_pool_code_supported(x_shape, cout):
     return bool(_lib().tg_conv_pool_code_supported(C.byref(g)))
 
 
-def conv_fwd_pool_code(x, w, bias):
+def conv_fwd_pool_code(x, w, bias, sparse=None):
     """3x3 / stride-1 / pad-1 conv -> ReLU -> 2x2 max-pool: returns (pooled, code); the full-resolution output is not written
-    (tg_conv_fwd_pool_code).  code: uint8 [B][H/2][W/2][Cout], consumed by maxpool2_bwd_code."""
+    (tg_conv_fwd_pool_code).  code: uint8 [B][H/2][W/2][Cout], consumed by maxpool2_bwd_code.  sparse: as in conv_fwd."""
     _chk(x, "x"); _chk(bias, "bias")
     wv = weight_view(w)
     _chk(wv, "weight")
@@ -277,6 +326,11 @@ def conv_fwd_pool_code(x, w, bias):
     code = torch.empty((g.B, g.Ho // 2, g.Wo // 2, g.Cout), dtype=torch.uint8, device=x.device)
     lib = _lib()
     ws = workspace(lib.tg_conv_fwd_ws_bytes(C.byref(g)))
+    if sparse is not None:
+        L.check(lib.tg_conv_fwd_sparse(C.byref(g), _p(x), _p(wv), _p(_prepared(w, wv, g, WPREP_FWD)), _p(bias), ACT_RELU, 0.0, None,
+                                       _p(yp), C.c_void_p(code.data_ptr()), C.byref(sparse), _p(ws), ws.numel() * 4, _stream()),
+                "tg_conv_fwd_sparse")
+        return yp, code
     L.check(lib.tg_conv_fwd_pool_code(C.byref(g), _p(x), _p(wv), _p(_prepared(w, wv, g, WPREP_FWD)), _p(bias), _p(yp),
                                       C.c_void_p(code.data_ptr()), _p(ws), ws.numel() * 4, _stream()), "tg_conv_fwd_pool_code")
     return yp, code
