@@ -1093,6 +1093,65 @@ static bool try_pgemm(IGemmParams* ps, int ncls, size_t ws_floats_avail, hipStre
 #include "wino44.inc"
 #include "wino16.inc"
 
+// The F(2x2,3x3) launcher of both operand types: fp32 (wino_kernel / wino_pipe_kernel, wino.inc) and bf16 (wino16_kernel /
+// wino16_pipe_kernel, wino16.inc), as wino_plan decides.  The bf16 family has no work-stealing or tile-map variants.
+static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
+    const WinoPlan pl = wino_plan(p, ws_floats_avail);
+    p.splits = pl.splits;
+    p.Ktot = 9 * p.C;
+    TgWprepItem it = {};
+    it.kind = p.bf16 ? 5 : 1; it.N = p.N; it.K = p.C; it.w = p.w_raw; it.out = p.wino_u; it.ww = pl.ww;
+    int rc = TG_OK;
+    const auto transform = [&]() -> int {
+        if (p.bf16) {
+            hipLaunchKernelGGL(wino_weights16_kernel, dim3(ew_grid((int64_t)p.N * (p.C / 2), 256)), dim3(256), 0, s, p.w_raw,
+                               reinterpret_cast<__bf16*>(p.wino_u), p.N, p.C, pl.ww);
+            TG_CHECK_LAUNCH("wino_weights16_kernel");
+        } else {
+            hipLaunchKernelGGL(wino_weights_kernel, dim3(ew_grid((int64_t)p.N * p.C, 256)), dim3(256), 0, s, p.w_raw, p.wino_u, p.N,
+                               p.C, pl.ww);
+            TG_CHECK_LAUNCH("wino_weights_kernel");
+        }
+        return TG_OK;
+    };
+    if (wino_prep(p, it, transform, &rc)) return rc;
+    if (pl.pool) p.pool_done = 1;
+    TG_REQUIRE(pl.pool || !(p.pool_code || p.pool_only), "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
+    TG_REQUIRE(!p.pool_code || p.act == TG_ACT_RELU, "tg_conv_fwd_pool_code: needs a ReLU output");
+    if (pl.gbits) p.gate_bits_done = 1;
+    WinoProf pf = {p.bf16 ? 3 : 0, p.bf16 ? 4016 : 4064, p.M, 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale, 0.0};
+    pf.bytes = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.M + (double)p.N * p.Ktot + (double)p.M * p.N +
+                      (p.amask ? (double)p.B * p.IH * p.IW : 0.0) + (pl.pool ? 0.25 * (double)p.M * p.N : 0.0)) -
+               (p.pool_only ? (4.0 - 0.25) * (double)p.M * p.N : 0.0);      // pool_only: no dst, a code byte per pooled element
+    if (p.bf16) {
+        typedef void (*W16Kern)(const IGemmParams, const WinoGeom, const __bf16*);
+        static const W16Kern kerns[8] = {wino16_kernel<false, false>, wino16_kernel<false, true>, wino16_kernel<true, false>,
+                                         wino16_kernel<true, true>, wino16_pipe_kernel<false>, wino16_pipe_kernel<true>,
+                                         wino16_pipe_kernel<false, true>, wino16_pipe_kernel<true, false, true>};
+        static LdsOptIn opts[8];
+        const int ki = pl.kernel(false);
+        return wino_launch(kerns[ki], opts[ki], pl.pipe ? W16_PIPE_LDS_BYTES : W16_LDS_BYTES, "wino16_kernel", p, pl.q, pf, true, s);
+    }
+    typedef void (*WinoKern)(const IGemmParams, const WinoGeom, const float*);
+    static const WinoKern kerns[18] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
+                                       wino_kernel<true, true, false>, wino_pipe_kernel<false, false>, wino_pipe_kernel<true, false>,
+                                       wino_pipe_kernel<false, false, true>, wino_pipe_kernel<true, false, false, true>,
+                                       wino_kernel<false, false, true>, wino_kernel<false, true, true>, wino_kernel<true, false, true>,
+                                       wino_kernel<true, true, true>, wino_pipe_kernel<false, true>, wino_pipe_kernel<true, true>,
+                                       wino_pipe_kernel<false, true, true>, wino_pipe_kernel<true, true, false, true>,
+                                       wino_pipe_kernel<false, false, false, false, true>, wino_pipe_kernel<false, false, true, false, true>};
+    static LdsOptIn opts[18];
+    WinoGeom q = pl.q;
+    q.qctr = wino_queue_block(s, p.splits, q.total_work);
+    if (pl.sparse && !q.qctr) {
+        const TgSparseMap* sm = p.sparse;
+        q.sp_bits = sm->bits; q.sp_list = sm->list; q.sp_count = sm->count;
+        q.sp_nb = sm->nb; q.sp_tiles = sm->nb * q.tiles_y * q.tiles_x;
+    }
+    const int ki = pl.kernel(q.qctr != nullptr);
+    return wino_launch(kerns[ki], opts[ki], (size_t)WINO_LDS_FLOATS * sizeof(float), "wino_kernel", p, q, pf, true, s);
+}
+
 static int pick_bn(int N) { return N >= 128 && N % 128 == 0 ? 128 : (N > 32 ? 64 : 32); }
 
 // K-split so that small-M layers (enc5-7, dec7, dec6) still fill 256 CUs.
@@ -1109,8 +1168,10 @@ static void plan_splits(IGemmParams& p, size_t ws_floats_avail) {
     p.splits = p.T > 0 ? cdiv(p.T, p.steps_per_split) : 1;
 }
 
+// (the stride-1 3x3 Winograd launches go through launch_wino_s1; only its F(2x2,3x3) launcher writes a pool in place of dst)
 static int launch_igemm(IGemmParams& p, hipStream_t s, size_t ws_floats_avail = 0) {
     if (p.M <= 0 || p.N <= 0) return TG_OK;
+    TG_REQUIRE(!p.pool_only, "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
     if (smallconv_fwd_applies(p)) {          // 1-channel side: HBM-bound dedicated kernels (smallconv.hip)
         p.splits = 1;
         p.Ktot = p.TH * p.TW * p.C;
@@ -1118,9 +1179,6 @@ static int launch_igemm(IGemmParams& p, hipStream_t s, size_t ws_floats_avail = 
         ProfScope ps(s, 2, 2.0 * p.M * (double)p.N * p.Ktot, by, p.M, p.N, p.Ktot, p.C, 1, 2000);
         return smallconv_fwd_launch(p, s);
     }
-    if (wino44_ok(p)) return launch_wino44(p, s);
-    if (wino_ok(p)) return launch_wino(p, ws_floats_avail, s);
-    if (wino16_ok(p)) return launch_wino16(p, ws_floats_avail, s);
     {
         int rc = TG_OK;
         if (try_pgemm(&p, 1, ws_floats_avail, s, &rc)) return rc;
@@ -1374,26 +1432,65 @@ extern "C" size_t tg_conv_fwd_ws_bytes(const TgConv* g) {
     return base;
 }
 
+// The IGemmParams geometry of a forward launch (conv_fwd_impl; the queries ask their questions of the same params).  The caller
+// adds pointers and epilogue.
+static IGemmParams conv_fwd_params(const TgConv* g) {
+    IGemmParams p = {};
+    p.B = g->B; p.IH = g->H; p.IW = g->W; p.C = g->Cin;
+    p.OH = g->Ho; p.OW = g->Wo; p.N = g->Cout; p.M = g->B * g->Ho * g->Wo;
+    p.DH = g->Ho; p.DW = g->Wo; p.ds = 1; p.dy0 = 0; p.dx0 = 0;
+    p.TH = g->k; p.TW = g->k; p.ss = g->stride; p.tstep = 1; p.sy0 = -g->pad; p.sx0 = -g->pad;
+    p.KW = g->k; p.kstep = 1; p.ky0 = 0; p.kx0 = 0;
+    p.Kfull = g->k * g->k * g->Cin;
+    p.bf16 = g->precision == TG_PREC_BF16;
+    p.wino4 = g->precision == TG_PREC_F32_WINO4;
+    p.Ktot = p.TH * p.TW * p.C; p.nchunks = cdiv(p.C, 32);
+    p.T = (p.C % 4) ? cdiv(p.Ktot, 32) : p.TH * p.TW * p.nchunks;
+    return p;
+}
+// ... of a stride-1 dgrad on the Winograd kernels: dx = dy correlated with the flipped taps, the weights W[co][tap][ci] read
+// through strides (n = ci, k = co; see conv_dgrad_impl)
+static IGemmParams conv_dgrad_s1_params(const TgConv* g) {
+    IGemmParams p = {};
+    p.B = g->B; p.IH = g->Ho; p.IW = g->Wo; p.C = g->Cout;
+    p.OH = g->H; p.OW = g->W; p.N = g->Cin; p.M = g->B * g->H * g->W;
+    p.DH = g->H; p.DW = g->W; p.ds = 1;
+    p.ky0 = 0; p.kx0 = 0; p.TH = g->k; p.TW = g->k; p.ss = g->stride; p.tstep = -1; p.sy0 = g->pad; p.sx0 = g->pad;
+    p.KW = g->k; p.kstep = 1; p.Kfull = g->k * g->k * g->Cout;
+    p.bf16 = g->precision == TG_PREC_BF16;
+    p.wino4 = g->precision == TG_PREC_F32_WINO4;
+    return p;
+}
+static bool wino_fwd_geom_ok(const TgConv* g) { return wino_geom_ok(conv_fwd_params(g)); }
+static bool wino_dgrad_geom_ok(const TgConv* g) { return wino_geom_ok(conv_dgrad_s1_params(g)); }
+
+// The stride-1 3x3 Winograd route of a forward or dgrad launch (p from conv_fwd_params / conv_dgrad_s1_params with the weights
+// w_raw / wino_u / wino_ready and split-K slabs p.ws of `avail` floats): F(4x4,3x3) where the precision asks for it and the
+// launch allows, else F(2x2,3x3) with fp32 or bf16 operands.  A buffer prepared in the F(4x4) layout (it follows the geometry
+// alone) that meets a launch wino44_kernel cannot take -- row scales, an input mask, an output reaching 2 GB -- is of no use to
+// wino_kernel: F(2x2,3x3) weights are transformed per call into the workspace head (`head` floats) instead.  `room`: the split-K
+// room the workspace queries promise (splitk_room_floats).
+static int launch_wino_s1(IGemmParams& p, float* ws, size_t head, size_t avail, size_t room, hipStream_t s, const char* who) {
+    if (wino44_ok(p)) {
+        TG_REQUIRE(!p.pool_only, "%s: wino44_kernel cannot write the pool in place of the output", who);
+        return launch_wino44(p, s);
+    }
+    if (wino44_prepared_unusable(p)) {
+        TG_REQUIRE(ws && aligned16(ws) && avail >= head, "%s: workspace too small to re-prepare the weights (%zu < %zu floats)", who,
+                   avail, head);
+        p.wino_u = ws;
+        p.wino_ready = 0;
+        p.ws = ws + head;
+        avail -= head;
+    }
+    return launch_wino(p, min_floats(avail, room), s);
+}
+
 // Prepared weights.  Every weight rearrangement the conv kernels need (the Winograd transform U = G g Gt of the stride-1 3x3
 // layers, the [Cin][taps][Cout] transpose of the gather dgrads, the 3x3 x 4C regrouping of the 5x5 stride-2 layers)
 // depends on the weights only, so the caller may have it computed ONCE per optimiser step (once ever for the frozen VGG
 // trunk) by tg_conv_wprep and hand it to tg_conv_fwd_p / tg_conv_dgrad_p.  `prep`: 0 = none given (prepare per call in
 // the workspace, the tg_conv_fwd / tg_conv_dgrad behaviour), 1 = `wprep` is ready, -1 = fill `wprep` and return.
-// (bf16 mode: wino16_kernel walks K in 16-channel steps)
-static int wino_kc(const TgConv* g) {
-    static const bool off16 = getenv("TG_NO_WINO16") != nullptr;
-    return g->precision == TG_PREC_BF16 ? (off16 ? 0 : 16) : 8;
-}
-static bool wino_fwd_geom_ok(const TgConv* g) {
-    static const bool off = getenv("TG_NO_WINO") != nullptr;
-    const int kc = wino_kc(g);
-    return !off && kc && g->k == 3 && g->stride == 1 && (g->Cin % kc) == 0 && (g->Cout % WINO_BN) == 0 && g->Ho >= 16 && g->Wo >= 16;
-}
-static bool wino_dgrad_geom_ok(const TgConv* g) {
-    static const bool off = getenv("TG_NO_WINO") != nullptr;
-    const int kc = wino_kc(g);
-    return !off && kc && g->k == 3 && g->stride == 1 && (g->Cout % kc) == 0 && (g->Cin % WINO_BN) == 0 && g->H >= 16 && g->W >= 16;
-}
 static size_t dgrad_wt_floats(const TgConv* g);
 extern "C" size_t tg_conv_wprep_bytes(const TgConv* g, int mode) {
     if (!g) return 0;
@@ -1474,19 +1571,9 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
                              ws ? ws_bytes - (s2d_x_floats(g) + s2d_w_floats(g)) * sizeof(float) : 0, stream);
     }
     TG_REQUIRE(!(s2d_ok(g) && prep > 0), "tg_conv_fwd: workspace too small for the prepared 5x5 stride-2 path");
-    IGemmParams p = {};
+    IGemmParams p = conv_fwd_params(g);
     p.src = x; p.amask = in_mask; p.wmat = w; p.bias = bias; p.rowscale = ratio; p.dst = y; p.ws = ws;
-    p.B = g->B; p.IH = g->H; p.IW = g->W; p.C = g->Cin;
-    p.OH = g->Ho; p.OW = g->Wo; p.N = g->Cout; p.M = g->B * g->Ho * g->Wo;
-    p.DH = g->Ho; p.DW = g->Wo; p.ds = 1; p.dy0 = 0; p.dx0 = 0;
-    p.TH = g->k; p.TW = g->k; p.ss = g->stride; p.tstep = 1; p.sy0 = -g->pad; p.sx0 = -g->pad;
-    p.KW = g->k; p.kstep = 1; p.ky0 = 0; p.kx0 = 0;
-    p.Kfull = g->k * g->k * g->Cin;
     p.act = act; p.slope = slope; p.accumulate = 0;
-    p.bf16 = g->precision == TG_PREC_BF16;
-    p.wino4 = g->precision == TG_PREC_F32_WINO4;
-    p.Ktot = p.TH * p.TW * p.C; p.nchunks = cdiv(p.C, 32);
-    p.T = (p.C % 4) ? cdiv(p.Ktot, 32) : p.TH * p.TW * p.nchunks;
     size_t ws_floats = ws ? ws_bytes / sizeof(float) : 0;
     const size_t uf = conv_wino_floats(g);
     const size_t room = splitk_room_floats((size_t)p.M * p.N);
@@ -1501,28 +1588,8 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
         }
         return launch_wino22(g, p, 0, min_floats(ws_floats, room), (hipStream_t)stream);
     }
-    if (wino_fwd_geom_ok(g) && (prep || (ws_floats >= uf && aligned16(ws)))) {
-        // transformed weights: prepared by the caller, or at the head of the workspace
-        p.w_raw = w; p.w_sn = (long)p.Kfull; p.w_sk = 1; p.w_stap = g->Cin;
-        p.wino_u = prep ? wprep : ws;
-        p.wino_ready = prep;
-        bool in_ws = !prep;
-        if (wino44_prepared_unusable(p)) {
-            // `wprep` holds the F(4x4,3x3) image (its layout follows the geometry alone) and this launch -- row scales, an input
-            // mask, or a batch whose output reaches 2 GB -- runs on wino_kernel: F(2x2,3x3) weights, transformed per call
-            TG_REQUIRE(ws_floats >= uf && aligned16(ws), "tg_conv_fwd: workspace too small to re-prepare the weights (%zu < %zu floats)",
-                       ws_floats, uf);
-            p.wino_u = ws;
-            p.wino_ready = 0;
-            in_ws = true;
-        }
-        TG_REQUIRE(p.bf16 ? wino16_ok(p) : wino_ok(p), "tg_conv_fwd: internal: Winograd geometry predicate mismatch");
-        if (in_ws) {
-            p.ws = ws + uf;
-            ws_floats -= uf;
-        }
-    }
-    if (prep < 0 && !p.wino_u) return TG_OK;              // this layer runs on the raw weights: nothing to prepare
+    const bool wino = wino_fwd_geom_ok(g) && (prep || (ws_floats >= uf && aligned16(ws)));
+    if (prep < 0 && !wino) return TG_OK;              // this layer runs on the raw weights: nothing to prepare
     if (ex) {
         p.pool_dst = ex->pool_dst;
         p.pool_code = ex->pool_code;
@@ -1533,9 +1600,21 @@ static int conv_fwd_impl(const TgConv* g, const float* x, const float* in_mask, 
             TG_REQUIRE(smallconv_bnin_fwd_ok(p), "tg_conv_fwd_bnin: geometry not supported (ask tg_conv_bnin_supported first)");
         }
     }
-    ws_floats = min_floats(ws_floats, room);
-    plan_splits(p, ws_floats);
-    rc = launch_igemm(p, (hipStream_t)stream, ws_floats);
+    if (wino) {
+        // transformed weights: prepared by the caller, or at the head of the workspace
+        p.w_raw = w; p.w_sn = (long)p.Kfull; p.w_sk = 1; p.w_stap = g->Cin;
+        p.wino_u = prep ? wprep : ws;
+        p.wino_ready = prep;
+        if (!prep) {
+            p.ws = ws + uf;
+            ws_floats -= uf;
+        }
+        rc = launch_wino_s1(p, ws, uf, ws_floats, room, (hipStream_t)stream, "tg_conv_fwd");
+    } else {
+        ws_floats = min_floats(ws_floats, room);
+        plan_splits(p, ws_floats);
+        rc = launch_igemm(p, (hipStream_t)stream, ws_floats);
+    }
     if (ex) ex->pool_fused = p.pool_done;
     return rc;
 }
@@ -1550,13 +1629,14 @@ extern "C" int tg_conv_fwd_pool(const TgConv* g, const float* x, const float* in
 // (VGG16 features[2..4], [7..9]): pooled tensor + one code byte per pooled element (IGemmParams::pool_code), the conv output
 // itself is never written.  Only where wino_pipe_kernel<.., POOL> takes the launch in one K split.
 extern "C" int tg_conv_pool_code_supported(const TgConv* g) {
-    if (!g || (g->precision != TG_PREC_F32 && g->precision != TG_PREC_BF16) || !wino_fwd_geom_ok(g) || s2d_ok(g) || (g->Ho & 1) || (g->Wo & 1)) return 0;
-    if (getenv("TG_NO_FUSED_POOL") || getenv("TG_NO_POOL_CODE") || getenv("TG_WINO_NO_PIPE") || getenv("TG_WINO_NO_FAST")) return 0;
-    if ((size_t)g->B * g->Ho * g->Wo * g->Cout * 4 >= ((size_t)1 << 31) || (size_t)g->B * g->H * g->W * g->Cin * 4 >= ((size_t)1 << 31)) return 0;
-    const int nchunks = g->Cin / wino_kc(g);            // K steps of 8 (fp32) / 16 (bf16 operands) channels
-    if (nchunks < 2) return 0;
-    const long work = (long)cdiv(g->Wo, 16) * cdiv(g->Ho, 16) * g->B * (g->Cout / WINO_BN);
-    return nchunks < 16 || work >= 4L * WINO_PLAN_CUS ? 1 : 0;         // (launch_wino: one K split)
+    if (!g || (g->precision != TG_PREC_F32 && g->precision != TG_PREC_BF16) || !wino_fwd_geom_ok(g) || s2d_ok(g) || (g->Ho & 1) ||
+        (g->Wo & 1) || getenv("TG_NO_POOL_CODE"))
+        return 0;
+    // what launch_wino will do with this call's params, planned against the split-K room tg_conv_fwd_ws_bytes promises
+    IGemmParams p = conv_fwd_params(g);
+    float pooled;                         // (a pooled tensor is requested; the plan never reads it)
+    p.pool_dst = &pooled;
+    return wino_plan(p, splitk_room_floats((size_t)p.M * p.N)).pool ? 1 : 0;
 }
 static int conv_fwd_pool_code(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias, float* pool_y,
                               unsigned char* code, const TgSparseMap* sp, float* ws, size_t ws_bytes, tg_stream_t stream) {
@@ -1595,19 +1675,14 @@ static bool bnin_geom_ok(const TgConv* g) {
     return g && g->Cout == 1 && g->Cin == 64 && g->k == 3 && g->stride == 1 && g->pad == 1 && (g->Wo % 4) == 0;
 }
 static BnIn bnin_of(const TgBnAct* bn) { return BnIn{bn->mean, bn->rstd, bn->gamma, bn->beta, bn->act, bn->slope}; }
+static WgradParams wgrad_params(const TgConv* g);
 extern "C" int tg_conv_bnin_supported(const TgConv* g, int wgrad) {
     if (!bnin_geom_ok(g)) return 0;
     if (wgrad) {
-        WgradParams p = {};
-        p.B = g->B; p.H = g->H; p.W = g->W; p.C = g->Cin; p.Ho = g->Ho; p.Wo = g->Wo; p.Cout = g->Cout;
-        p.k = g->k; p.stride = g->stride; p.pad = g->pad;
-        p.Mpix = g->B * g->Ho * g->Wo; p.Ktot = g->k * g->k * g->Cin;
+        const WgradParams p = wgrad_params(g);
         return smallconv_wgrad_applies(p) && smallconv_bnin_wgrad_ok(p) ? 1 : 0;
     }
-    IGemmParams p = {};
-    p.B = g->B; p.IH = g->H; p.IW = g->W; p.C = g->Cin; p.OH = g->Ho; p.OW = g->Wo; p.N = g->Cout; p.M = g->B * g->Ho * g->Wo;
-    p.TH = g->k; p.TW = g->k; p.ss = g->stride; p.tstep = 1; p.sy0 = -g->pad; p.sx0 = -g->pad;
-    return smallconv_bnin_fwd_ok(p) ? 1 : 0;
+    return smallconv_bnin_fwd_ok(conv_fwd_params(g)) ? 1 : 0;
 }
 extern "C" int tg_conv_fwd_bnin(const TgConv* g, const float* x, const TgBnAct* bn, const float* w, const float* bias, int act,
                                 float slope, float* y, float* ws, size_t ws_bytes, tg_stream_t stream) {
@@ -1791,39 +1866,15 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
     const size_t ws2_floats = min_floats(ws2_avail, room);     // what the split-K planners may use (see splitk_room_floats)
     if (wino_dgrad_geom_ok(g)) {
         // stride-1 3x3: the Winograd kernel reads W[co][tap][ci] through strides (n = ci, k = co); no transposed copy
-        IGemmParams p = {};
+        IGemmParams p = conv_dgrad_s1_params(g);
         p.src = dy; p.rowscale = in_mask; p.dst = dx; p.ws = ws2;
-        p.B = g->B; p.IH = g->Ho; p.IW = g->Wo; p.C = g->Cout;
-        p.OH = g->H; p.OW = g->W; p.N = g->Cin; p.M = g->B * g->H * g->W;
-        p.DH = g->H; p.DW = g->W; p.ds = 1;
-        p.ky0 = 0; p.kx0 = 0; p.TH = 3; p.TW = 3; p.ss = 1; p.tstep = -1; p.sy0 = g->pad; p.sx0 = g->pad;
-        p.KW = 3; p.kstep = 1; p.Kfull = taps * g->Cout;
         p.act = TG_ACT_NONE; p.accumulate = accumulate;
         p.gate = gate; p.gate_act = gate_act; p.gate_slope = gate_slope;
-        p.bf16 = g->precision == TG_PREC_BF16;
         p.w_raw = w; p.w_sn = 1; p.w_sk = (long)taps * g->Cin; p.w_stap = g->Cin;
         p.wino_u = wt;
         p.wino_ready = prep;
-        p.wino4 = g->precision == TG_PREC_F32_WINO4;
         p.gate_bits = gate_bits;
-        if (wino44_ok(p)) {
-            rc = launch_wino44(p, s);
-            if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
-            return rc;
-        }
-        size_t avail = ws2_avail;
-        if (wino44_prepared_unusable(p)) {         // see conv_fwd_impl: F(4x4) image prepared, F(2x2) launch -> transform per call
-            const size_t uf = dgrad_wt_floats(g);
-            TG_REQUIRE(ws && aligned16(ws) && avail >= uf, "tg_conv_dgrad: workspace too small to re-prepare the weights (%zu < %zu floats)",
-                       avail, uf);
-            p.wino_u = ws;
-            p.wino_ready = 0;
-            p.ws = ws + uf;
-            avail -= uf;
-        }
-        TG_REQUIRE(p.bf16 ? wino16_ok(p) : wino_ok(p), "tg_conv_dgrad: internal: Winograd geometry predicate mismatch");
-        avail = min_floats(avail, room);
-        rc = p.bf16 ? launch_wino16(p, avail, s) : launch_wino(p, avail, s);
+        rc = launch_wino_s1(p, ws, dgrad_wt_floats(g), ws2_avail, room, s, "tg_conv_dgrad");
         if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
         return rc;
     }

@@ -975,33 +975,59 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
     wk.done(q.qctr);
 }
 
-static bool wino_ok(const IGemmParams& p) {
-    static const bool off = getenv("TG_NO_WINO") != nullptr;
-    if (off || p.wino_u == nullptr || p.bf16) return false;
+// ---- host side: planning and the steps every Winograd launcher shares ------------------------------
+
+// F(2x2,3x3) geometry, fp32 (wino_kernel: K steps of 8 channels) or bf16 operands (wino16_kernel: 16).  The TgConv-level
+// questions (wino_fwd_geom_ok / wino_dgrad_geom_ok) ask it of the params their launches are built from.
+static int wino_kc(const IGemmParams& p) { return p.bf16 ? 16 : 8; }
+static bool wino_geom_ok(const IGemmParams& p) {
+    static const bool off = getenv("TG_NO_WINO") != nullptr, off16 = getenv("TG_NO_WINO16") != nullptr;
+    if (off || (p.bf16 && off16)) return false;
     if (p.TH != 3 || p.TW != 3 || p.ss != 1 || (p.tstep != 1 && p.tstep != -1) || (p.kstep != 1 && p.kstep != -1)) return false;
-    if ((p.C % 8) != 0 || (p.N % WINO_BN) != 0 || p.OH < 16 || p.OW < 16) return false;
-    return true;
+    return (p.C % wino_kc(p)) == 0 && (p.N % WINO_BN) == 0 && p.OH >= 16 && p.OW >= 16;
 }
 static size_t wino_u_floats(int N, int C) { return (size_t)16 * N * C; }
 
-static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
-    WinoGeom q = {};
-    q.tiles_x = cdiv(p.OW, 16);
-    q.tiles_y = cdiv(p.OH, 16);
-    q.nt = p.N / WINO_BN;
-    q.total_work = q.tiles_x * q.tiles_y * p.B * q.nt;
-    q.interleave = wino_interleave_ok(wino_u_floats(p.N, p.C) * sizeof(float));
-    const int sy_b = p.sy0 + 2 * p.tstep, sx_b = p.sx0 + 2 * p.tstep;
-    q.sy_min = p.sy0 < sy_b ? p.sy0 : sy_b;
-    q.sx_min = p.sx0 < sx_b ? p.sx0 : sx_b;
+// source offset -> weight tap of the 3x3 transform (the tap walk of p: forward, or flipped for a dgrad)
+static WinoWeights wino_weights_map(const IGemmParams& p, int sy_min, int sx_min) {
     WinoWeights ww = {};
     ww.sn = p.w_sn; ww.sk = p.w_sk; ww.stap = p.w_stap;
     ww.k_fast = p.w_sk == 1;
     for (int t = 0; t < 3; ++t) {
-        ww.kyu[p.sy0 + t * p.tstep - q.sy_min] = p.ky0 + t * p.kstep;
-        ww.kxv[p.sx0 + t * p.tstep - q.sx_min] = p.kx0 + t * p.kstep;
+        ww.kyu[p.sy0 + t * p.tstep - sy_min] = p.ky0 + t * p.kstep;
+        ww.kxv[p.sx0 + t * p.tstep - sx_min] = p.kx0 + t * p.kstep;
     }
-    const int nchunks = p.C / 8;
+    return ww;
+}
+
+// Everything an F(2x2,3x3) launch decides, from its params and its split-K room alone: no allocation, no launch, no stream.
+// launch_wino runs it; tg_conv_pool_code_supported asks it whether the pool would be fused.
+struct WinoPlan {
+    WinoGeom q;             // tile grid, work count, K chunking (qctr and the tile-map fields are the launch's)
+    WinoWeights ww;
+    int splits;
+    bool fast, pipe, gated, pool, gbits;
+    bool sparse;            // the prediction-half tile map can be honoured, by a launch without a work-stealing queue
+    // index into launch_wino's kernel tables: 0-7 the static walk, 8-15 the same with a work-stealing queue, 16-17 the tile map
+    int kernel(bool queued) const {
+        if (sparse && !queued) return pool ? 17 : 16;
+        return (queued ? 8 : 0) + (gbits ? 7 : pool ? 6 : pipe ? 4 + gated : (fast ? 2 : 0) + gated);
+    }
+};
+static WinoPlan wino_plan(const IGemmParams& p, size_t ws_floats_avail) {
+    WinoPlan pl = {};
+    WinoGeom& q = pl.q;
+    q.tiles_x = cdiv(p.OW, 16);
+    q.tiles_y = cdiv(p.OH, 16);
+    q.nt = p.N / WINO_BN;
+    q.total_work = q.tiles_x * q.tiles_y * p.B * q.nt;
+    const size_t u_bytes = wino_u_floats(p.N, p.C) * (p.bf16 ? sizeof(__bf16) : sizeof(float));
+    q.interleave = wino_interleave_ok(u_bytes);
+    const int sy_b = p.sy0 + 2 * p.tstep, sx_b = p.sx0 + 2 * p.tstep;
+    q.sy_min = p.sy0 < sy_b ? p.sy0 : sy_b;
+    q.sx_min = p.sx0 < sx_b ? p.sx0 : sx_b;
+    pl.ww = wino_weights_map(p, q.sy_min, q.sx_min);
+    const int nchunks = p.C / wino_kc(p);
     int splits = 1;
     if (nchunks >= 16) {
         int smax = nchunks / 8 < 16 ? nchunks / 8 : 16;
@@ -1009,79 +1035,63 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
         splits = choose_splits(q.total_work, smax, WINO_PLAN_CUS);
     }
     q.chunks_per_split = cdiv(nchunks, splits);
-    p.splits = cdiv(nchunks, q.chunks_per_split);
-    p.Ktot = 9 * p.C;
-
-    if (p.wino_ready < 0 && g_wprep_capture) {       // tg_conv_wprep_item: describe the preparation instead of launching it
-        TgWprepItem it = {};
-        it.kind = 1; it.N = p.N; it.K = p.C; it.w = p.w_raw; it.out = p.wino_u; it.ww = ww;
-        *g_wprep_capture = it;
-        g_wprep_captured = 1;
-        return TG_OK;
-    }
-    if (p.wino_ready <= 0) {      // 0: per-call preparation in the workspace; -1: tg_conv_wprep filling the caller's buffer
-        hipLaunchKernelGGL(wino_weights_kernel, dim3(ew_grid((int64_t)p.N * p.C, 256)), dim3(256), 0, s, p.w_raw, p.wino_u, p.N,
-                           p.C, ww);
-        TG_CHECK_LAUNCH("wino_weights_kernel");
-    }
-    if (p.wino_ready < 0) return TG_OK;          // preparation only (tg_conv_wprep)
-    const size_t lds = (size_t)WINO_LDS_FLOATS * sizeof(float);
+    pl.splits = cdiv(nchunks, q.chunks_per_split);
+    const bool one = pl.splits == 1;
     static const bool no_fast = getenv("TG_WINO_NO_FAST") != nullptr;
-    const bool fast = !no_fast && p.amask == nullptr && (size_t)p.B * p.IH * p.IW * p.C * 4 < ((size_t)1 << 31) &&
-                      wino_u_floats(p.N, p.C) * 4 < ((size_t)1 << 31);
-    const bool gated = p.gate != nullptr && p.splits == 1;
+    pl.fast = !no_fast && p.amask == nullptr && (size_t)p.B * p.IH * p.IW * p.C * 4 < ((size_t)1 << 31) && u_bytes < ((size_t)1 << 31);
+    pl.gated = p.gate != nullptr && one;
     // the cross-item pipeline needs two K steps in every split
     static const bool no_pipe = getenv("TG_WINO_NO_PIPE") != nullptr;
     // ... and its epilogue addresses dst / gate through buffer descriptors (32-bit byte offsets)
-    const bool pipe = fast && !no_pipe && nchunks - (p.splits - 1) * q.chunks_per_split >= 2 && q.chunks_per_split >= 2 &&
-                      (size_t)p.B * p.DH * p.DW * p.N * 4 < ((size_t)1 << 31);
-    typedef void (*WinoKern)(const IGemmParams, const WinoGeom, const float*);
-    static const WinoKern kerns[18] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
-                                       wino_kernel<true, true, false>, wino_pipe_kernel<false, false>, wino_pipe_kernel<true, false>,
-                                       wino_kernel<false, false, true>, wino_kernel<false, true, true>, wino_kernel<true, false, true>,
-                                       wino_kernel<true, true, true>, wino_pipe_kernel<false, true>, wino_pipe_kernel<true, true>,
-                                       wino_pipe_kernel<false, false, true>, wino_pipe_kernel<false, true, true>,
-                                       wino_pipe_kernel<true, false, false, true>, wino_pipe_kernel<true, true, false, true>,
-                                       wino_pipe_kernel<false, false, false, false, true>, wino_pipe_kernel<false, false, true, false, true>};
-    static LdsOptIn opts[18];
-    q.qctr = wino_queue_block(s, p.splits, q.total_work);
+    pl.pipe = pl.fast && !no_pipe && nchunks - (pl.splits - 1) * q.chunks_per_split >= 2 && q.chunks_per_split >= 2 &&
+              (size_t)p.B * p.DH * p.DW * p.N * 4 < ((size_t)1 << 31);
     // the fused 2x2 max-pool: whole pooling windows inside the output, one split, the plain dst grid
+    const bool plain_dst = p.ds == 1 && p.dy0 == 0 && p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && !p.accumulate;
     static const bool no_pool = getenv("TG_NO_FUSED_POOL") != nullptr;
-    const bool pool = p.pool_dst && !no_pool && pipe && !gated && p.splits == 1 && !(p.OH & 1) && !(p.OW & 1) && p.ds == 1 && p.dy0 == 0 &&
-                      p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && !p.accumulate;
-    if (pool) p.pool_done = 1;
-    TG_REQUIRE(pool || !(p.pool_code || p.pool_only), "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
-    TG_REQUIRE(!p.pool_code || p.act == TG_ACT_RELU, "tg_conv_fwd_pool_code: needs a ReLU output");
+    pl.pool = p.pool_dst && !no_pool && pl.pipe && !pl.gated && one && !(p.OH & 1) && !(p.OW & 1) && plain_dst;
     // bit gates (p.gate_bits): read by the pipelined kernel in one split; any other launch runs ungated and the caller applies them
-    const bool gbits = p.gate_bits != nullptr && pipe && p.splits == 1;
-    if (gbits) p.gate_bits_done = 1;
-    // the prediction-half tile map (tg_conv_fwd_sparse) is honoured by the pipelined kernel's static walk in one split, ungated, on
-    // the plain dst grid of a [pred; target] batch whose tile grid is the map's; everything else runs dense -- the same bits
+    pl.gbits = p.gate_bits != nullptr && pl.pipe && one;
+    // the prediction-half tile map (tg_conv_fwd_sparse; fp32 only) is honoured by the pipelined kernel's static walk in one split,
+    // ungated, on the plain dst grid of a [pred; target] batch whose tile grid is the map's; everything else runs dense -- the same bits
     const TgSparseMap* sm = p.sparse;
-    const bool sparse = sm && pipe && !gated && !gbits && !q.qctr && p.splits == 1 && !p.accumulate && !p.rowscale && p.ds == 1 &&
-                        p.dy0 == 0 && p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && (pool || !p.pool_dst) && sm->nb > 0 &&
-                        p.B == 2 * sm->nb && sm->tiles_y == q.tiles_y && sm->tiles_x == q.tiles_x && sm->bits && sm->list && sm->count;
-    if (sparse) {
-        q.sp_bits = sm->bits; q.sp_list = sm->list; q.sp_count = sm->count;
-        q.sp_nb = sm->nb; q.sp_tiles = sm->nb * q.tiles_y * q.tiles_x;
+    pl.sparse = !p.bf16 && sm && pl.pipe && !pl.gated && !pl.gbits && one && !p.rowscale && plain_dst && (pl.pool || !p.pool_dst) &&
+                sm->nb > 0 && p.B == 2 * sm->nb && sm->tiles_y == q.tiles_y && sm->tiles_x == q.tiles_x && sm->bits && sm->list && sm->count;
+    return pl;
+}
+
+// The weight-preparation step every Winograd launcher starts with.  wino_ready < 0 (tg_conv_wprep): transform into wino_u and
+// stop -- or, while tg_conv_wprep_item captures, only describe the transform (`it`; kind 0: not batchable).  wino_ready == 0:
+// transform per call.  Returns true when the call ends here, with *rc its result.
+template <class Transform>
+static bool wino_prep(const IGemmParams& p, const TgWprepItem& it, Transform transform, int* rc) {
+    *rc = TG_OK;
+    if (p.wino_ready < 0 && g_wprep_capture) {
+        if (it.kind) *g_wprep_capture = it;
+        g_wprep_captured = it.kind ? 1 : -1;
+        return true;
     }
-    const int ki = sparse ? (pool ? 17 : 16)
-                 : gbits ? (q.qctr ? 15 : 14)
-                 : pool ? (q.qctr ? 13 : 12) : (q.qctr ? 6 : 0) + (pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0));
-    if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds, "wino")) return rc;
+    if (p.wino_ready <= 0 && (*rc = transform()) != TG_OK) return true;
+    return p.wino_ready < 0;
+}
+
+// The launch every Winograd launcher ends with: LDS opt-in, the profile record (ALGORITHMIC flops of the direct form), the
+// persistent grid -- one workgroup per CU (or per work item, if fewer), each walking a contiguous range of items or pulling from
+// the launch's work-stealing queues, p.splits deep -- and the split-K epilogue of a single-class launch (`reduce`).
+struct WinoProf {
+    int kind, cfg, M;
+    double flops, bytes;
+};
+template <class Geom, class UT>
+static int wino_launch(void (*kern)(const IGemmParams, const Geom, const UT*), LdsOptIn& opt, size_t lds, const char* name,
+                       const IGemmParams& p, const Geom& q, const WinoProf& pf, bool reduce, hipStream_t s) {
+    if (int rc = lds_opt_in(opt, reinterpret_cast<const void*>(kern), lds, name)) return rc;
     {
-        const double flops = 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale;      // ALGORITHMIC flops of the convolution (direct form)
-        const double bytes = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.M + (double)p.N * p.Ktot + (double)p.M * p.N +
-                                    (p.amask ? (double)p.B * p.IH * p.IW : 0.0) + (pool ? 0.25 * (double)p.M * p.N : 0.0)) -
-                             (p.pool_only ? (4.0 - 0.25) * (double)p.M * p.N : 0.0);      // pool_only: no dst, a code byte per pooled element
-        ProfScope ps(s, 0, flops, bytes, p.M, p.N, p.Ktot, p.C, p.splits, 4064);
-        // persistent workgroups: one per CU (141 KB LDS), each walking a contiguous range of work items (or pulling from the
-        // launch's work-stealing queues: data-parallel runs)
+        ProfScope ps(s, pf.kind, pf.flops, pf.bytes, pf.M, p.N, p.Ktot, p.C, p.splits, pf.cfg);
         const int grid = q.total_work < wino_cus() ? q.total_work : wino_cus();
-        hipLaunchKernelGGL(kerns[ki], dim3(grid, 1, p.splits), dim3(WINO_THREADS), lds, s, p, q, (const float*)p.wino_u);
+        hipLaunchKernelGGL(kern, dim3(grid, 1, p.splits), dim3(WINO_THREADS), lds, s, p, q, reinterpret_cast<const UT*>(p.wino_u));
     }
-    TG_CHECK_LAUNCH("wino_kernel");
-    if (p.splits > 1) {
+    TG_CHECK_LAUNCH(name);
+    if (reduce && p.splits > 1) {
         hipLaunchKernelGGL(igemm_splitk_epilogue, dim3(ew_grid((int64_t)p.M * p.N, 256)), dim3(256), 0, s, p);
         TG_CHECK_LAUNCH("igemm_splitk_epilogue");
     }

@@ -638,96 +638,6 @@ __global__ __launch_bounds__(WINO_THREADS) void wino16_pipe_kernel(const IGemmPa
     }
 }
 
-static bool wino16_ok(const IGemmParams& p) {
-    static const bool off = getenv("TG_NO_WINO") != nullptr || getenv("TG_NO_WINO16") != nullptr;
-    if (off || p.wino_u == nullptr || !p.bf16) return false;
-    if (p.TH != 3 || p.TW != 3 || p.ss != 1 || (p.tstep != 1 && p.tstep != -1) || (p.kstep != 1 && p.kstep != -1)) return false;
-    if ((p.C % 16) != 0 || (p.N % WINO_BN) != 0 || p.OH < 16 || p.OW < 16) return false;
-    return true;
-}
-
-static int launch_wino16(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
-    WinoGeom q = {};
-    q.tiles_x = cdiv(p.OW, 16);
-    q.tiles_y = cdiv(p.OH, 16);
-    q.nt = p.N / WINO_BN;
-    q.total_work = q.tiles_x * q.tiles_y * p.B * q.nt;
-    q.interleave = wino_interleave_ok((size_t)16 * p.N * p.C * sizeof(__bf16));
-    const int sy_b = p.sy0 + 2 * p.tstep, sx_b = p.sx0 + 2 * p.tstep;
-    q.sy_min = p.sy0 < sy_b ? p.sy0 : sy_b;
-    q.sx_min = p.sx0 < sx_b ? p.sx0 : sx_b;
-    WinoWeights ww = {};
-    ww.sn = p.w_sn; ww.sk = p.w_sk; ww.stap = p.w_stap;
-    ww.k_fast = p.w_sk == 1;
-    for (int t = 0; t < 3; ++t) {
-        ww.kyu[p.sy0 + t * p.tstep - q.sy_min] = p.ky0 + t * p.kstep;
-        ww.kxv[p.sx0 + t * p.tstep - q.sx_min] = p.kx0 + t * p.kstep;
-    }
-    const int nchunks = p.C / 16;
-    int splits = 1;
-    if (nchunks >= 16) {
-        int smax = nchunks / 8 < 16 ? nchunks / 8 : 16;
-        while (smax > 1 && (size_t)smax * p.M * p.N > ws_floats_avail) --smax;
-        splits = choose_splits(q.total_work, smax, WINO_PLAN_CUS);
-    }
-    q.chunks_per_split = cdiv(nchunks, splits);
-    p.splits = cdiv(nchunks, q.chunks_per_split);
-    p.Ktot = 9 * p.C;
-    __bf16* U16 = reinterpret_cast<__bf16*>(p.wino_u);
-    if (p.wino_ready < 0 && g_wprep_capture) {       // tg_conv_wprep_item: describe the preparation instead of launching it (kind 5)
-        TgWprepItem it = {};
-        it.kind = 5; it.N = p.N; it.K = p.C; it.w = p.w_raw; it.out = p.wino_u; it.ww = ww;
-        *g_wprep_capture = it;
-        g_wprep_captured = 1;
-        return TG_OK;
-    }
-    if (p.wino_ready <= 0) {
-        hipLaunchKernelGGL(wino_weights16_kernel, dim3(ew_grid((int64_t)p.N * (p.C / 2), 256)), dim3(256), 0, s, p.w_raw, U16, p.N,
-                           p.C, ww);
-        TG_CHECK_LAUNCH("wino_weights16_kernel");
-    }
-    if (p.wino_ready < 0) return TG_OK;          // preparation only (tg_conv_wprep)
-    static const bool no_fast = getenv("TG_WINO_NO_FAST") != nullptr;
-    const bool fast = !no_fast && p.amask == nullptr && (size_t)p.B * p.IH * p.IW * p.C * 4 < ((size_t)1 << 31) &&
-                      (size_t)16 * p.N * p.C * 2 < ((size_t)1 << 31);
-    const bool gated = p.gate != nullptr && p.splits == 1;
-    static const bool no_pipe = getenv("TG_WINO_NO_PIPE") != nullptr;
-    const bool pipe = fast && !no_pipe && nchunks - (p.splits - 1) * q.chunks_per_split >= 2 && q.chunks_per_split >= 2 &&
-                      (size_t)p.B * p.DH * p.DW * p.N * 4 < ((size_t)1 << 31);       // (the epilogue's descriptors on dst / gate)
-    typedef void (*W16Kern)(const IGemmParams, const WinoGeom, const __bf16*);
-    static const W16Kern kerns[8] = {wino16_kernel<false, false>, wino16_kernel<false, true>, wino16_kernel<true, false>,
-                                     wino16_kernel<true, true>, wino16_pipe_kernel<false>, wino16_pipe_kernel<true>,
-                                     wino16_pipe_kernel<false, true>, wino16_pipe_kernel<true, false, true>};
-    static LdsOptIn opts[8];
-    static const bool no_pool = getenv("TG_NO_FUSED_POOL") != nullptr;
-    const bool pool = p.pool_dst && !no_pool && pipe && !gated && p.splits == 1 && !(p.OH & 1) && !(p.OW & 1) && p.ds == 1 && p.dy0 == 0 &&
-                      p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && !p.accumulate;
-    if (pool) p.pool_done = 1;
-    TG_REQUIRE(pool || !(p.pool_code || p.pool_only), "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
-    TG_REQUIRE(!p.pool_code || p.act == TG_ACT_RELU, "tg_conv_fwd_pool_code: needs a ReLU output");
-    // bit gates: the pipelined kernel in one split reads them, any other launch runs ungated (see launch_wino)
-    const bool gbits = p.gate_bits != nullptr && pipe && p.splits == 1;
-    if (gbits) p.gate_bits_done = 1;
-    const int ki = gbits ? 7 : pool ? 6 : pipe ? 4 + (gated ? 1 : 0) : (fast ? 2 : 0) + (gated ? 1 : 0);
-    const size_t lds_bytes = pipe ? W16_PIPE_LDS_BYTES : W16_LDS_BYTES;
-    if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds_bytes, "wino16")) return rc;
-    {
-        const double flops = 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale;      // ALGORITHMIC flops of the convolution (direct form)
-        const double bytes = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.M + (double)p.N * p.Ktot + (double)p.M * p.N +
-                                    (p.amask ? (double)p.B * p.IH * p.IW : 0.0) + (pool ? 0.25 * (double)p.M * p.N : 0.0)) -
-                             (p.pool_only ? (4.0 - 0.25) * (double)p.M * p.N : 0.0);      // pool_only: no dst, a code byte per pooled element
-        ProfScope ps(s, 3, flops, bytes, p.M, p.N, p.Ktot, p.C, p.splits, 4016);
-        const int grid = q.total_work < wino_cus() ? q.total_work : wino_cus();
-        hipLaunchKernelGGL(kerns[ki], dim3(grid, 1, p.splits), dim3(WINO_THREADS), lds_bytes, s, p, q, (const __bf16*)U16);
-    }
-    TG_CHECK_LAUNCH("wino16_kernel");
-    if (p.splits > 1) {
-        hipLaunchKernelGGL(igemm_splitk_epilogue, dim3(ew_grid((int64_t)p.M * p.N, 256)), dim3(256), 0, s, p);
-        TG_CHECK_LAUNCH("igemm_splitk_epilogue");
-    }
-    return TG_OK;
-}
-
 // =================================================================================================
 // Winograd wgrad F(3x3,2x2) with bf16 MFMA operands (bf16 mode):  dW = Gt [ sum_tiles (A dY At) (.) (Bt X B) ] G
 // =================================================================================================

@@ -438,20 +438,16 @@ static int launch_wino22(const TgConv* g, IGemmParams& p, int dgrad, size_t ws_f
     q.chunks_per_split = cdiv(nchunks, splits);
     p.splits = cdiv(nchunks, q.chunks_per_split);
     p.Ktot = 4 * p.C;
-    if (p.wino_ready < 0 && g_wprep_capture) {       // tg_conv_wprep_item: describe the preparation instead of launching it
-        TgWprepItem it = {};
-        it.kind = 3; it.N = p.N; it.K = p.C; it.w = p.w_raw; it.out = p.wino_u; it.w22 = ww;
-        *g_wprep_capture = it;
-        g_wprep_captured = 1;
-        return TG_OK;
-    }
-    if (p.wino_ready <= 0) {
+    TgWprepItem it = {};
+    it.kind = 3; it.N = p.N; it.K = p.C; it.w = p.w_raw; it.out = p.wino_u; it.w22 = ww;
+    int rc = TG_OK;
+    const auto transform = [&]() -> int {
         hipLaunchKernelGGL(wino22_weights_kernel, dim3(ew_grid((int64_t)p.N * p.C * q.ncls, 256)), dim3(256), 0, s, p.w_raw, p.wino_u, p.N,
                            p.C, ww);
         TG_CHECK_LAUNCH("wino22_weights_kernel");
-    }
-    if (p.wino_ready < 0) return TG_OK;
-    const size_t lds = (size_t)W22_LDS_FLOATS * sizeof(float);
+        return TG_OK;
+    };
+    if (wino_prep(p, it, transform, &rc)) return rc;
     static const bool no_fast = getenv("TG_WINO_NO_FAST") != nullptr;
     const size_t src_bytes = (size_t)g->B * (dgrad ? (size_t)g->Ho * g->Wo * g->Cout : (size_t)g->H * g->W * g->Cin) * 4;
     const bool fast = !no_fast && p.amask == nullptr && src_bytes < ((size_t)1 << 31) && wino22_u_floats(g) * 4 < ((size_t)1 << 31);
@@ -463,17 +459,12 @@ static int launch_wino22(const TgConv* g, IGemmParams& p, int dgrad, size_t ws_f
     static LdsOptIn opts[8];
     q.qctr = wino_queue_block(s, p.splits, q.total_work);
     const int ki = (q.qctr ? 4 : 0) + (fast ? 2 : 0) + (gated ? 1 : 0);
-    if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds, "wino22")) return rc;
-    {
-        const double mtot = (double)p.M * q.ncls;
-        const double flops = 2.0 * mtot * (double)p.N * p.Ktot;              // ALGORITHMIC flops (direct form: 16 taps)
-        const double bytes = 4.0 * ((double)g->B * (dgrad ? g->Ho * g->Wo * g->Cout : g->H * g->W * g->Cin) + 16.0 * g->Cin * g->Cout +
-                                    mtot * p.N + (p.rowscale ? mtot : 0.0));
-        ProfScope ps(s, 0, flops, bytes, (int)mtot, p.N, p.Ktot, p.C, p.splits, 4022);
-        const int grid = q.total_work < wino_cus() ? q.total_work : wino_cus();
-        hipLaunchKernelGGL(kerns[ki], dim3(grid, 1, p.splits), dim3(WINO_THREADS), lds, s, p, q, (const float*)p.wino_u);
-    }
-    TG_CHECK_LAUNCH("wino22_kernel");
+    const double mtot = (double)p.M * q.ncls;
+    const WinoProf pf = {0, 4022, (int)mtot, 2.0 * mtot * (double)p.N * p.Ktot,              // (direct form: 16 taps)
+                         4.0 * ((double)g->B * (dgrad ? g->Ho * g->Wo * g->Cout : g->H * g->W * g->Cin) + 16.0 * g->Cin * g->Cout +
+                                mtot * p.N + (p.rowscale ? mtot : 0.0))};
+    // the split-K slabs of the ncls classes are reduced by one launch of the multi-class epilogue
+    if ((rc = wino_launch(kerns[ki], opts[ki], (size_t)W22_LDS_FLOATS * sizeof(float), "wino22_kernel", p, q, pf, false, s))) return rc;
     if (p.splits > 1) {
         IGemmMulti pm = {};
         for (int c = 0; c < q.ncls; ++c) {

@@ -427,22 +427,17 @@ static int launch_wino44(IGemmParams& p, hipStream_t s) {
     const int sy_b = p.sy0 + 2 * p.tstep, sx_b = p.sx0 + 2 * p.tstep;
     q.sy_min = p.sy0 < sy_b ? p.sy0 : sy_b;
     q.sx_min = p.sx0 < sx_b ? p.sx0 : sx_b;
-    WinoWeights ww = {};
-    ww.sn = p.w_sn; ww.sk = p.w_sk; ww.stap = p.w_stap;
-    ww.k_fast = p.w_sk == 1;
-    for (int t = 0; t < 3; ++t) {
-        ww.kyu[p.sy0 + t * p.tstep - q.sy_min] = p.ky0 + t * p.kstep;
-        ww.kxv[p.sx0 + t * p.tstep - q.sx_min] = p.kx0 + t * p.kstep;
-    }
+    const WinoWeights ww = wino_weights_map(p, q.sy_min, q.sx_min);
     p.splits = 1;
     p.Ktot = 9 * p.C;
-    if (p.wino_ready < 0 && g_wprep_capture) { g_wprep_captured = -1; return TG_OK; }      // not batched: prepared once (frozen trunk)
-    if (p.wino_ready <= 0) {
+    const TgWprepItem it = {};        // (kind 0: not batched -- prepared once, for the frozen trunk)
+    int rc = TG_OK;
+    const auto transform = [&]() -> int {
         hipLaunchKernelGGL(wino44_weights_kernel, dim3(ew_grid((int64_t)p.N * p.C, 256)), dim3(256), 0, s, p.w_raw, p.wino_u, p.N, p.C, ww);
         TG_CHECK_LAUNCH("wino44_weights_kernel");
-    }
-    if (p.wino_ready < 0) return TG_OK;
-    const size_t lds = (size_t)W4_LDS_FLOATS * sizeof(float);
+        return TG_OK;
+    };
+    if (wino_prep(p, it, transform, &rc)) return rc;
     const bool gated = p.gate != nullptr;
     const bool gbits = p.gate_bits != nullptr;      // (one split always: the bits are read here)
     if (gbits) p.gate_bits_done = 1;
@@ -450,14 +445,7 @@ static int launch_wino44(IGemmParams& p, hipStream_t s) {
     typedef void (*Kern)(const IGemmParams, const Wino44Geom, const float*);
     static const Kern kerns[3] = {wino44_kernel<false>, wino44_kernel<true>, wino44_kernel<true, true>};
     static LdsOptIn opts[3];
-    if (int rc = lds_opt_in(opts[ki], reinterpret_cast<const void*>(kerns[ki]), lds, "wino44")) return rc;
-    {
-        const double flops = 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale;
-        const double bytes = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.N * p.Ktot + (double)p.M * p.N);
-        ProfScope ps(s, 0, flops, bytes, p.M, p.N, p.Ktot, p.C, 1, 4044);
-        const int grid = q.total_work < wino_cus() ? q.total_work : wino_cus();
-        hipLaunchKernelGGL(kerns[ki], dim3(grid), dim3(WINO_THREADS), lds, s, p, q, (const float*)p.wino_u);
-    }
-    TG_CHECK_LAUNCH("wino44_kernel");
-    return TG_OK;
+    const WinoProf pf = {0, 4044, p.M, 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale,
+                         4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.N * p.Ktot + (double)p.M * p.N)};
+    return wino_launch(kerns[ki], opts[ki], (size_t)W4_LDS_FLOATS * sizeof(float), "wino44_kernel", p, q, pf, false, s);
 }

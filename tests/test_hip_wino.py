@@ -634,3 +634,70 @@ def test_conv_fwd_pool_code_and_its_backward(dev, case):
     assert torch.equal(dx1, dx0), float((dx1 - dx0).abs().max())
     assert float(dx1.abs().sum()) > 0 and float((dx1 == 0).float().mean()) > 0.75
     assert not O.conv_pool_code_supported((2, 32, 32, 128), 128)          # a K-split plan: stays on the two-output form
+    assert not O.conv_pool_code_supported((2, 33, 48, 64), 64)            # odd output rows: no whole pooling windows
+
+
+# precision, B, H, W, Cin, Cout: work items (16 x 16 tiles x B x Cout / 64) around 256, 512 and 1024 on both sides of the K-split
+# rule (fp32 splits from Cin 128 on, bf16 from Cin 256 on), ragged tile edges
+POOL_QUERY_CASES = [
+    ("f32", 32, 64, 64, 128, 64),      # 512 items, Cin 128: one split (choose_splits(512, 2, 256) == 1) -- fused
+    ("f32", 16, 64, 64, 128, 64),      # 256 items: one split -- fused
+    ("f32", 2, 32, 32, 128, 128),      # 16 items: two splits -- the pool kernel
+    ("f32", 3, 80, 80, 128, 128),      # 150 items, ragged: one split -- fused
+    ("f32", 9, 64, 64, 256, 64),       # 144 items, Cin 256: three splits
+    ("f32", 19, 64, 64, 256, 64),      # 304 items: four splits
+    ("f32", 15, 128, 128, 256, 64),    # 960 items: one split
+    ("f32", 16, 128, 128, 256, 64),    # 1024 items: one split
+    ("f32", 4, 50, 46, 64, 64),        # Cin 64 never splits; ragged
+    ("bf16", 8, 64, 64, 256, 64),      # 128 items, Cin 256: two splits
+    ("bf16", 32, 64, 64, 256, 64),     # 512 items: one split -- fused
+    ("bf16", 16, 64, 64, 128, 64),     # Cin 128 never splits in bf16
+    ("bf16", 6, 48, 48, 64, 128),      # Cin 64, 108 items
+]
+
+
+@pytest.mark.parametrize("case", POOL_QUERY_CASES)
+def test_conv_pool_code_supported_is_the_fused_launch(dev, tmp_path, case):
+    """tg_conv_pool_code_supported answers 1 exactly where tg_conv_fwd_pool's launch fuses the pool (its one launch record counts
+    the pooled tensor); there conv_fwd_pool_code matches conv + ReLU + max-pool bit for bit."""
+    import csv
+    from tg_hip import lib as L
+    from tg_hip import ops as O
+    prec, B, H, W, Cin, Cout = case
+    lib = L.load()
+    g = torch.Generator().manual_seed(B * H + Cin + Cout)
+    x = torch.randn(B, H, W, Cin, generator=g).to(dev)
+    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / (3 * Cin ** 0.5)).contiguous(memory_format=torch.channels_last).to(dev)
+    b = (torch.randn(Cout, generator=g) * 0.1).to(dev)
+    try:
+        O.set_precision(prec)
+        supported = O.conv_pool_code_supported(tuple(x.shape), Cout)
+        O.conv_fwd(x, w, b, 3, 1, 1, act=O.ACT_RELU, pool=True)          # (weights prepared outside the recorded region)
+        for kind in (0, 1, 2, 3):
+            lib.tg_prof_summary(kind, None, None, None, None)
+        lib.tg_prof_enable(1)
+        y, yp = O.conv_fwd(x, w, b, 3, 1, 1, act=O.ACT_RELU, pool=True)
+        torch.cuda.synchronize()
+        lib.tg_prof_enable(0)
+        path = str(tmp_path / "launches.csv")
+        assert lib.tg_prof_dump(path.encode()) == 0
+        rows = list(csv.DictReader(open(path)))
+        for kind in (0, 1, 2, 3):
+            lib.tg_prof_summary(kind, None, None, None, None)
+        wino = ("3", "4016") if prec == "bf16" else ("0", "4064")
+        assert [(r["kind"], r["cfg"]) for r in rows] == [wino], rows
+        plain_mb = 4 * (x.numel() + y.numel() + w.numel() + y.numel() // Cout) / 1e6
+        pooled_mb = 4 * yp.numel() / 1e6
+        alg_mb = float(rows[0]["alg_mb"])
+        fused = abs(alg_mb - (plain_mb + pooled_mb)) < 1e-3 * plain_mb
+        assert fused or abs(alg_mb - plain_mb) < 1e-3 * plain_mb, (alg_mb, plain_mb, pooled_mb)
+        assert supported == fused, (case, supported, rows[0])
+        p0 = O.maxpool2_fwd(O.conv_fwd(x, w, b, 3, 1, 1, act=O.ACT_RELU))
+        assert torch.equal(yp, p0)
+        if supported:
+            assert rows[0]["splits"] == "1"
+            p1, _code = O.conv_fwd_pool_code(x, w, b)
+            assert torch.equal(p1, p0), float((p1 - p0).abs().max())
+    finally:
+        lib.tg_prof_enable(0)
+        O.set_precision("f32")
