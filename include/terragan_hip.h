@@ -484,6 +484,38 @@ int tg_hole_masks(const int32_t* prims, const int32_t* offsets, int n, int side,
 int tg_raster_sample(const float* dem, int64_t H, int64_t W, const int32_t* draws, int n, int side, const float* mask,
                      int norm_known, float* x, float* lo, float* hi, tg_stream_t stream);
 
+/* ---- above-ground objects from the DSM alone (mvp_gan/src/object_mask.py; no reference counterpart: the reference draws its
+ * masks from aerial imagery with OpenCV heuristics, utils/mask_processing/core.py) ----
+ * Progressive morphological filter, 8-connected components, area filter and buffer.  Rasters are
+ * row-major [H][W] with 1 <= H, W and H * W < 2^31.  The morphology window of p with radius r is the square (2r+1)^2 centred on
+ * p, clipped at the raster border; a radius past the raster is the whole raster.  Buffers come from the caller, no call
+ * allocates or synchronises, and every result is bitwise deterministic (min / max, fp32 subtraction, integer atomics). */
+enum { TG_MORPH_ERODE = 0, TG_MORPH_DILATE = 1 };
+enum { TG_OBJMASK_MAX_BUFFER = 64 };
+/* known [H][W] uint8 = mask != 0 (mask may be NULL), finite, and (use_nodata) != nodata; known_t [W][H] its transpose
+ * (may be NULL). */
+int tg_objmask_known(const float* dem, const float* mask, int H, int W, int use_nodata, float nodata, uint8_t* known,
+                     uint8_t* known_t, tg_stream_t stream);
+/* out [H][W] = min (op TG_MORPH_ERODE) / max (TG_MORPH_DILATE) of in over the pixels q of the window of p with known[q] != 0
+ * (known may be NULL: every pixel counts); +inf / -inf where the window has none.  radius >= 0; tmp: [H*W] floats;
+ * in, tmp and out distinct. */
+int tg_objmask_morph(const float* in, const uint8_t* known, int H, int W, int radius, int op, float* tmp, float* out,
+                     tg_stream_t stream);
+/* One filter step: s_out = dilate_r(erode_r(s_in)), the erosion reading s_in and the dilation reading the eroded values at
+ * known pixels only (known [H][W], known_t [W][H] from tg_objmask_known); s_out has a value at every pixel.  flags [H][W]
+ * uint8 is set to 1 where known and s_in - s_out > dh in fp32 (dh finite, >= 0), and left alone elsewhere.  t0, t1: [H*W]
+ * floats; s_in, t0, t1, s_out distinct. */
+int tg_objmask_pmf_step(const float* s_in, const uint8_t* known, const uint8_t* known_t, int H, int W, int radius, float dh,
+                        float* t0, float* t1, float* s_out, uint8_t* flags, tg_stream_t stream);
+/* 8-connected components of flags != 0: labels [H][W] int32 = the smallest linear index y*W + x in the pixel's component,
+ * -1 where not flagged; area [H*W] int32 = the component's pixel count at that index, 0 elsewhere. */
+int tg_objmask_components(const uint8_t* flags, int H, int W, int32_t* labels, int32_t* area, tg_stream_t stream);
+/* Components with area >= min_area are objects; objects [H][W] uint8 = 1 within the clipped square of radius buffer_px
+ * (0 .. TG_OBJMASK_MAX_BUFFER) of an object pixel; keep [H][W] float = known && !objects.  counts [4] int32 (zeroed by the
+ * call): flagged pixels, components kept, components removed, object pixels. */
+int tg_objmask_filter(const uint8_t* known, const int32_t* labels, const int32_t* area, int H, int W, int min_area,
+                      int buffer_px, uint8_t* objects, float* keep, int32_t* counts, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

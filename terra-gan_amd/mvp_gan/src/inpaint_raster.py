@@ -14,7 +14,11 @@ Semantics:
     w = r_y * r_x, r(t) = min(1, (t+0.5)/overlap, (w-t-0.5)/overlap) and the ramp of a raster-border side replaced by 1;
   - known pixels are returned bit for bit; a hole no running window covers is NaN and counted in info["unfilled"].
 
+With `objects` (an object_mask.ObjectSpec) the above-ground objects are found on the GPU first (mvp_gan/src/object_mask.py)
+and the keep mask, known and not an object, replaces `mask`: the result is bare earth.
+
 CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --checkpoint ck.pth --out out.asc
+         [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]]
 """
 import argparse
 import math
@@ -144,9 +148,12 @@ def _to_device_f32(a, device, what, binary=False):
 
 
 @torch.no_grad()
-def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16):
+def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16, objects=None,
+                   cellsize=None):
     """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
-    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled)."""
+    objects: an ObjectSpec to remove the above-ground objects first (cellsize, metres per pixel, is then required).
+    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, and with objects the object_mask info
+    under "objects")."""
     from tg_hip import engine as E
     from tg_hip import ops as O
     if not torch.cuda.is_available():
@@ -160,6 +167,10 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
     m = None if mask is None else _to_device_f32(mask, device, "mask", binary=True)
     if m is not None and m.shape != z.shape:
         raise ValueError(f"inpaint_raster: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
+    oinfo = None
+    if objects is not None:
+        from .object_mask import object_mask
+        _, m, oinfo = object_mask(z, m, nodata=nodata, cellsize=cellsize, spec=objects)
     pl = plan_windows(*z.shape, window=window, overlap=overlap)
     cp = O.raster_plan(pl.H, pl.W, pl.wh, pl.ww, pl.overlap, len(pl.ys), len(pl.xs))
     nwin = len(pl.ys) * len(pl.xs)
@@ -185,7 +196,10 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
             x, mk = O.raster_gather(z, m, cp, lo, hi, run_d[b0:b1], nodata, x=xb[:b1 - b0], m=mb[:b1 - b0])
             E.generator_forward(P, x, mk, training=False, out=wout[b0:b1])
     out, unfilled = O.raster_blend(z, m, cp, lo, hi, run_of_d, wout, nodata)
-    return out, {"windows": nwin, "run": int(run.size), "unfilled": int(unfilled.item())}
+    info = {"windows": nwin, "run": int(run.size), "unfilled": int(unfilled.item())}
+    if oinfo is not None:
+        info["objects"] = oinfo
+    return out, info
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------
@@ -209,11 +223,24 @@ def main(argv=None):
     ap.add_argument("--window", type=int, default=512)
     ap.add_argument("--overlap", type=int, default=64)
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--remove-objects", action="store_true",
+                    help="find above-ground objects in the DSM (cellsize from the header) and inpaint them to bare earth")
+    ap.add_argument("--objects-out", help="with --remove-objects: write the object map (.png or .asc, nonzero = object)")
+    from .object_mask import add_spec_args, object_mask, spec_from_args, write_mask
+    add_spec_args(ap)
     a = ap.parse_args(argv)
+    if a.objects_out and not a.remove_objects:
+        ap.error("--objects-out needs --remove-objects")
     dem, header = read_asc(a.dem)
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=asc_nodata(header), window=a.window, overlap=a.overlap,
-                               batch=a.batch)
+    nodata = asc_nodata(header)
+    if a.remove_objects:                      # what inpaint_raster(objects=...) does, keeping the object map for --objects-out
+        objects, mask, oinfo = object_mask(dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")),
+                                           spec=spec_from_args(a))
+        if a.objects_out:
+            write_mask(a.objects_out, objects.cpu().numpy(), header)
+        print(f"{oinfo['objects']} objects, {oinfo['object_pixels']} px removed")
+    out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)

@@ -5,16 +5,20 @@ Train and validation windows come from RasterWindowLoader (utils/raster_dataset.
 (train.py's dictionary) and loads unchanged into `inpaint_raster --checkpoint`.
 
 CLI: python -m mvp_gan.src.train_raster --dem in.asc [--mask keep.png|keep.asc] [--nodata v] [--init ck.pth] --out ft.pth
-         [--window 256 --batch 16 --steps 500 --epochs 4 --seed 0 --norm known|window]
+         [--window 256 --batch 16 --steps 500 --epochs 4 --seed 0 --norm known|window] [--remove-objects [spec flags]]
+
+--remove-objects finds the above-ground objects in the DSM (mvp_gan/src/object_mask.py, cellsize from the header) and never
+samples a window that touches one, so the generator learns bare earth.
 """
 import argparse
 import logging
 
 import torch
 
-from .inpaint_raster import _read_mask, asc_nodata, read_asc
+from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc
 from .models.discriminator import Discriminator
 from .models.generator import PConvUNet
+from .object_mask import add_spec_args, spec_from_args
 from .train import _default_config, train
 from .utils.raster_dataset import RasterWindowLoader
 
@@ -52,6 +56,9 @@ def main(argv=None):
     ap.add_argument("--lr", type=float, default=2e-4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--norm", choices=("known", "window"), default="known")
+    ap.add_argument("--remove-objects", action="store_true",
+                    help="never sample windows that touch an above-ground object found in the DSM")
+    add_spec_args(ap)
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not torch.cuda.is_available():
@@ -62,6 +69,8 @@ def main(argv=None):
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
     common = dict(nodata=nodata, window=a.window, batch_size=a.batch, block=a.block, norm=a.norm, seed=a.seed, device=device)
+    if a.remove_objects:
+        common.update(objects=spec_from_args(a), cellsize=float(asc_value(header, "cellsize")))
     tr = RasterWindowLoader(dem, mask, split="train", steps_per_epoch=a.steps, **common)
     va = RasterWindowLoader(dem, mask, split="val", steps_per_epoch=a.val_steps or max(1, a.steps // 10), augment=False,
                             **common)

@@ -20,6 +20,10 @@ over its known pixels only.  RasterWindowLoader feeds train() straight from the 
     whole window (norm="window").  x is written at every pixel, holes included: it is the training target; with
     norm="known" hole values may fall outside [0, 1].
 
+With `objects` (an object_mask.ObjectSpec and the raster's cellsize) the above-ground objects are found on the GPU
+(mvp_gan/src/object_mask.py) and become invalid pixels before the summed-area table is built: no target window holds a
+roof or a tree crown.
+
 Every draw is a pure function of (seed, split, epoch, rank, batch index) through numpy SeedSequence; split "val" and "test"
 ignore the epoch, so their loss is comparable across epochs.  Per batch the host draws the parameters, makes one pinned,
 double-buffered, non-blocking upload and two library calls.  The only host wait is on the upload of two batches back, before
@@ -81,7 +85,7 @@ class RasterWindowLoader:
     metres: image = the normalised window (the target), mask = 1 keep / 0 hole."""
 
     def __init__(self, dem, mask=None, *, nodata=None, window=256, batch_size=16, steps_per_epoch=None, split=None, block=None,
-                 augment=True, norm="known", holes=HoleSpec(), seed=0, rank=0, world=1, device=None):
+                 augment=True, norm="known", holes=HoleSpec(), seed=0, rank=0, world=1, device=None, objects=None, cellsize=None):
         if isinstance(window, (tuple, list)):
             if len(window) != 2 or int(window[0]) != int(window[1]):
                 raise ValueError(f"RasterWindowLoader: window {tuple(window)} must be square")
@@ -120,6 +124,13 @@ class RasterWindowLoader:
             valid &= m != 0
         if nodata is not None and not math.isnan(nodata):
             valid &= z != np.float32(nodata)
+        object_fraction = None
+        if objects is not None:
+            from ..object_mask import object_mask
+            obj, _, _ = object_mask(z, None if mask is None else m, nodata=nodata, cellsize=cellsize, spec=objects)
+            obj = obj.cpu().numpy() != 0
+            object_fraction = float(obj.mean())
+            valid &= ~obj
         sat = np.zeros((H + 1, W + 1), np.int32)                # invalid pixels above and left of (y, x)
         np.cumsum(np.cumsum(~valid, axis=0, dtype=np.int32), axis=1, dtype=np.int32, out=sat[1:, 1:])
         self._sat = sat
@@ -130,6 +141,8 @@ class RasterWindowLoader:
                              f"{H}x{W} raster")
         self.info = {"admissible_origins": n_adm, "origins": n_org, "admissible_fraction": n_adm / n_org,
                      "valid_fraction": float(valid.mean())}
+        if object_fraction is not None:
+            self.info["object_fraction"] = object_fraction
         self.steps_per_epoch = max(1, -(-n_adm // (w * w * self.batch_size))) if steps_per_epoch is None else int(steps_per_epoch)
         if self.steps_per_epoch < 1:
             raise ValueError(f"RasterWindowLoader: steps_per_epoch {steps_per_epoch} < 1")

@@ -130,6 +130,11 @@ SIGNATURES = {
     "tg_raster_blend": (I, [P, P, RP, I, F, P, P, P, P, I, P, P, P]),
     "tg_hole_masks": (I, [P, P, I, I, P, P]),
     "tg_raster_sample": (I, [P, I64, I64, P, I, I, P, I, P, P, P, P]),
+    "tg_objmask_known": (I, [P, P, I, I, I, F, P, P, P]),
+    "tg_objmask_morph": (I, [P, P, I, I, I, I, P, P, P]),
+    "tg_objmask_pmf_step": (I, [P, P, P, I, I, I, F, P, P, P, P, P]),
+    "tg_objmask_components": (I, [P, I, I, P, P, P]),
+    "tg_objmask_filter": (I, [P, P, P, I, I, I, I, P, P, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

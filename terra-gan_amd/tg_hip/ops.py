@@ -945,6 +945,103 @@ def raster_sample(dem, draws, mask, norm_known=True, x=None, lo=None, hi=None):
     return x, lo, hi
 
 
+MORPH_ERODE, MORPH_DILATE = 0, 1                  # tg_objmask_morph ops (terragan_hip.h)
+OBJMASK_MAX_BUFFER = 64
+
+
+def _hip(t, dtype, shape, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise L.TgError(f"{name}: expected a contiguous {dtype} HIP tensor {list(shape)}, got {got}")
+
+
+def _raster_hw(t, name):
+    if not isinstance(t, torch.Tensor) or t.dim() != 2:
+        raise L.TgError(f"{name}: expected a [H][W] tensor")
+    H, W = t.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise L.TgError(f"{name}: raster {H}x{W} must be non-empty with H*W < 2^31 (int32 labels)")
+    return int(H), int(W)
+
+
+def _radius(r, H, W):
+    r = int(r)
+    if r < 0:
+        raise L.TgError(f"objmask: radius {r} < 0")
+    return min(r, max(H, W))             # a window past the raster is the raster: the same result
+
+
+def objmask_known(dem, mask=None, nodata=None, transposed=True):
+    """-> (known uint8 [H][W], known_t uint8 [W][H] or None): mask != 0, finite and != nodata (tg_objmask_known)."""
+    H, W = _raster_hw(dem, "dem")
+    _hip(dem, torch.float32, (H, W), "dem")
+    if mask is not None:
+        _hip(mask, torch.float32, (H, W), "mask")
+    known = torch.empty(H, W, dtype=torch.uint8, device=dem.device)
+    known_t = torch.empty(W, H, dtype=torch.uint8, device=dem.device) if transposed else None
+    L.check(_lib().tg_objmask_known(_p(dem), _p(mask), H, W, int(nodata is not None), 0.0 if nodata is None else float(nodata),
+                                    _p(known), _p(known_t), _stream()), "tg_objmask_known")
+    return known, known_t
+
+
+def objmask_morph(x, radius, op, known=None):
+    """Clipped-window erosion (op MORPH_ERODE) or dilation (MORPH_DILATE) of x [H][W] over the pixels with known != 0
+    (every pixel when known is None) (tg_objmask_morph)."""
+    H, W = _raster_hw(x, "x")
+    _hip(x, torch.float32, (H, W), "x")
+    if known is not None:
+        _hip(known, torch.uint8, (H, W), "known")
+    if op not in (MORPH_ERODE, MORPH_DILATE):
+        raise L.TgError(f"objmask_morph: op {op} is neither MORPH_ERODE nor MORPH_DILATE")
+    tmp, out = torch.empty_like(x), torch.empty_like(x)
+    L.check(_lib().tg_objmask_morph(_p(x), _p(known), H, W, _radius(radius, H, W), int(op), _p(tmp), _p(out), _stream()),
+            "tg_objmask_morph")
+    return out
+
+
+def objmask_pmf_step(s, known, known_t, radius, dh, flags, t0, t1, out):
+    """out = open_r(s) over the known pixels; flags |= known & (s - out > dh) (tg_objmask_pmf_step).  t0, t1: scratch."""
+    H, W = _raster_hw(s, "s")
+    for t, nm in ((s, "s"), (t0, "t0"), (t1, "t1"), (out, "out")):
+        _hip(t, torch.float32, (H, W), nm)
+    _hip(known, torch.uint8, (H, W), "known")
+    _hip(known_t, torch.uint8, (W, H), "known_t")
+    _hip(flags, torch.uint8, (H, W), "flags")
+    L.check(_lib().tg_objmask_pmf_step(_p(s), _p(known), _p(known_t), H, W, _radius(radius, H, W), float(dh), _p(t0), _p(t1),
+                                       _p(out), _p(flags), _stream()), "tg_objmask_pmf_step")
+    return out
+
+
+def objmask_components(flags):
+    """-> (labels int32 [H][W]: smallest linear index of the 8-connected component, -1 off the flags; area int32 [H*W]: the
+    component size at that index) (tg_objmask_components)."""
+    H, W = _raster_hw(flags, "flags")
+    _hip(flags, torch.uint8, (H, W), "flags")
+    labels = torch.empty(H, W, dtype=torch.int32, device=flags.device)
+    area = torch.empty(H * W, dtype=torch.int32, device=flags.device)
+    L.check(_lib().tg_objmask_components(_p(flags), H, W, _p(labels), _p(area), _stream()), "tg_objmask_components")
+    return labels, area
+
+
+def objmask_filter(known, labels, area, min_area, buffer_px):
+    """-> (objects uint8 [H][W], keep float32 [H][W], counts int32 [4] = flagged, kept, removed, object pixels)
+    (tg_objmask_filter)."""
+    H, W = _raster_hw(known, "known")
+    _hip(known, torch.uint8, (H, W), "known")
+    _hip(labels, torch.int32, (H, W), "labels")
+    _hip(area, torch.int32, (H * W,), "area")
+    if not 0 <= int(min_area) < 2 ** 31:
+        raise L.TgError(f"objmask_filter: min_area {min_area} out of range [0, 2^31)")
+    if not 0 <= int(buffer_px) <= OBJMASK_MAX_BUFFER:
+        raise L.TgError(f"objmask_filter: buffer {buffer_px} px out of range [0, {OBJMASK_MAX_BUFFER}]")
+    objects = torch.empty(H, W, dtype=torch.uint8, device=known.device)
+    keep = torch.empty(H, W, dtype=torch.float32, device=known.device)
+    counts = torch.empty(4, dtype=torch.int32, device=known.device)
+    L.check(_lib().tg_objmask_filter(_p(known), _p(labels), _p(area), H, W, int(min_area), int(buffer_px), _p(objects), _p(keep),
+                                     _p(counts), _stream()), "tg_objmask_filter")
+    return objects, keep, counts
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()

@@ -1,0 +1,253 @@
+"""GPU checks of the object detector (csrc/objmask.hip, mvp_gan/src/object_mask.py) against the numpy oracle in
+tests/objmask_oracle.py: morphology, the filter, component labels, object map and keep mask bit for bit; detection quality on
+the seeded synthetic scene; inpaint_raster and RasterWindowLoader with objects; the CLIs."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import objmask_oracle as OR
+from tests.test_object_mask_cpu import spiral
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    from tg_hip import lib
+    lib.load()
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def G(dev):
+    from mvp_gan.src.models import PConvUNet
+    torch.manual_seed(5)
+    return PConvUNet().to(dev)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _dirty(H, W, seed):
+    """Heights with NaN, +-inf, nodata (-9999) and mask holes, an all-unknown row and column when the raster has room."""
+    rng = np.random.default_rng(seed)
+    z = rng.normal(100, 20, (H, W)).astype(np.float32)
+    z[rng.random((H, W)) < 0.02] = np.nan
+    z[rng.random((H, W)) < 0.01] = np.inf
+    z[rng.random((H, W)) < 0.01] = -np.inf
+    z[rng.random((H, W)) < 0.02] = -9999.0
+    z[rng.random((H, W)) < 0.05] = -0.0
+    mask = (rng.random((H, W)) > 0.1).astype(np.float32)
+    if H > 2:
+        mask[H // 2, :] = 0
+    if W > 2:
+        mask[:, W // 3] = 0
+    return z, mask
+
+
+MORPH_SHAPES = [(1, 1), (1, 517), (517, 1), (37, 1031), (4099, 64), (1500, 2100)]
+
+
+@pytest.mark.parametrize("H,W", MORPH_SHAPES)
+def test_morphology_against_oracle(dev, H, W):
+    from tg_hip import ops as O
+    z, mask = _dirty(H, W, H * 7 + W)
+    zd, md = torch.from_numpy(z).to(dev), torch.from_numpy(mask).to(dev)
+    known, known_t = O.objmask_known(zd, md, -9999.0)
+    kn = OR.known_map(z, mask, -9999.0)
+    np.testing.assert_array_equal(known.cpu().numpy(), kn)
+    np.testing.assert_array_equal(known_t.cpu().numpy(), kn.T)
+    for r in (0, 1, 2, 5, 31, 32, 33, 128, max(H, W), 3 * max(H, W) + 7):
+        for op, npop in ((O.MORPH_ERODE, np.minimum), (O.MORPH_DILATE, np.maximum)):
+            got = O.objmask_morph(zd, r, op, known).cpu().numpy()
+            np.testing.assert_array_equal(got, OR.morph(z, kn, r, npop), err_msg=f"{H}x{W} r={r} op={op}")
+    fin = np.nan_to_num(z, nan=1.0, posinf=2.0, neginf=3.0)           # known=None: every pixel counts
+    got = O.objmask_morph(torch.from_numpy(fin).to(dev), 3, O.MORPH_DILATE).cpu().numpy()
+    np.testing.assert_array_equal(got, OR.morph(fin, np.ones(fin.shape, bool), 3, np.maximum))
+
+
+def test_morphology_all_unknown(dev):
+    from tg_hip import ops as O
+    z = np.full((70, 130), np.nan, np.float32)
+    zd = torch.from_numpy(z).to(dev)
+    known, _ = O.objmask_known(zd)
+    assert not known.any()
+    for r in (0, 4, 200):
+        assert torch.isposinf(O.objmask_morph(zd, r, O.MORPH_ERODE, known)).all()
+        assert torch.isneginf(O.objmask_morph(zd, r, O.MORPH_DILATE, known)).all()
+
+
+@pytest.mark.parametrize("spec_kw", [{}, {"max_size_m": 10000.0}])
+def test_pmf_flags_and_surface(dev, spec_kw):
+    from mvp_gan.src.object_mask import ObjectSpec, pmf, schedule
+    from tg_hip import ops as O
+    z, _ = OR.scene(1500, 2100, 4, buildings=60, trees=120)
+    z[200:260, 300:420] = np.nan
+    z[900:903, :] = -9999.0
+    radii, dh, _, _ = schedule(ObjectSpec(**spec_kw), 1.0)
+    if spec_kw:
+        assert radii[-1] > 2100
+    zd = torch.from_numpy(z).to(dev)
+    known, known_t = O.objmask_known(zd, None, -9999.0)
+    flags, s = pmf(zd, known, known_t, radii, dh)
+    kn = OR.known_map(z, None, -9999.0)
+    f_ref, s_ref = OR.pmf(z, kn, radii, dh)
+    np.testing.assert_array_equal(flags.cpu().numpy() != 0, f_ref)
+    np.testing.assert_array_equal(s.cpu().numpy(), s_ref)
+    assert f_ref.any()
+
+
+def _cc_cases():
+    rng = np.random.default_rng(11)
+    cases = []
+    for H, W in ((255, 257), (511, 769), (63, 1025), (1023, 65), (257, 255)):
+        for p in (0.3, 0.45, 0.6):
+            cases.append((f"rand{p}-{H}x{W}", rng.random((H, W)) < p))
+    cases.append(("spiral", spiral(513, 767)))
+    d = np.zeros((300, 500), bool)
+    for j in range(0, 500, 7):
+        i = np.arange(300)
+        c = j + i
+        ok = c < 500
+        d[i[ok], c[ok]] = True                                          # diagonal-only chains
+    cases.append(("diagonals", d))
+    cases.append(("anti-diagonals", d[:, ::-1].copy()))
+    cases.append(("checkerboard", np.indices((257, 321)).sum(0) % 2 == 0))
+    cases.append(("empty", np.zeros((129, 65), bool)))
+    cases.append(("full", np.ones((321, 193), bool)))
+    c = np.zeros((97, 131), bool)
+    c[0, 0] = c[0, -1] = c[-1, 0] = c[-1, -1] = True
+    cases.append(("corners", c))
+    cases.append(("single", np.ones((1, 1), bool)))
+    return cases
+
+
+@pytest.mark.parametrize("name,f", _cc_cases(), ids=[c[0] for c in _cc_cases()])
+def test_component_labels_bitwise(dev, name, f):
+    from tg_hip import ops as O
+    fd = torch.from_numpy(f.astype(np.uint8)).to(dev)
+    labels, area = O.objmask_components(fd)
+    ref = OR.components(f)
+    np.testing.assert_array_equal(labels.cpu().numpy(), ref)
+    np.testing.assert_array_equal(area.cpu().numpy(), OR.areas(ref))
+
+
+def test_object_map_keep_and_info_bitwise(dev):
+    from mvp_gan.src.object_mask import ObjectSpec, object_mask, schedule
+    z, _ = OR.scene(1031, 1537, 6, buildings=60, trees=150)
+    z[400:480, 700:760] = -9999.0
+    mask = np.ones(z.shape, np.float32)
+    mask[50:60, :] = 0
+    spec = ObjectSpec(min_area_m2=9.0, buffer_m=2.0)
+    o, keep, info = object_mask(z, mask, nodata=-9999.0, cellsize=1.0, spec=spec)
+    radii, dh, ma, bp = schedule(spec, 1.0)
+    kn = OR.known_map(z, mask, -9999.0)
+    o_ref, keep_ref, counts, flags, _, _ = OR.object_mask(z, kn, radii, dh, ma, bp)
+    assert o.dtype == torch.uint8 and keep.dtype == torch.float32 and o.is_cuda and keep.is_cuda
+    np.testing.assert_array_equal(o.cpu().numpy(), o_ref)
+    np.testing.assert_array_equal(_bits(keep.cpu().numpy()), _bits(keep_ref))
+    assert [info["flagged"], info["objects"], info["removed"], info["object_pixels"]] == counts
+    assert info["objects"] > 50 and info["removed"] > 0
+    o2, keep2, info2 = object_mask(torch.from_numpy(z).to(dev), torch.from_numpy(mask).to(dev), nodata=-9999.0, cellsize=1.0,
+                                   spec=spec)
+    assert torch.equal(o, o2) and torch.equal(keep, keep2) and info == info2
+
+
+def _quality(o, truth, r_max):
+    o = o != 0
+    ring = OR.morph1d(OR.morph1d(truth.astype(np.float32), 2, 1, np.maximum), 2, 0, np.maximum) > 0
+    inner = np.zeros_like(truth)
+    inner[r_max + 1:-r_max - 1, r_max + 1:-r_max - 1] = True
+    ground = ~ring & inner
+    return (o & truth).sum() / truth.sum(), (o & ground).sum() / ground.sum()
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_quality_on_synthetic_scene(dev, seed):
+    from mvp_gan.src.object_mask import object_mask
+    z, truth = OR.scene(2048, 2048, seed)
+    o, _, info = object_mask(z, cellsize=1.0)
+    recall, flagged_ground = _quality(o.cpu().numpy(), truth, info["radii"][-1])
+    assert recall >= 0.99, recall
+    assert flagged_ground <= 0.005, flagged_ground
+
+
+def test_inpaint_raster_with_objects(dev, G):
+    from mvp_gan.src.inpaint_raster import inpaint_raster
+    from mvp_gan.src.object_mask import ObjectSpec, object_mask
+    z, truth = OR.scene(1024, 1024, 3, buildings=50, trees=100)
+    z[700:730, 100:180] = -9999.0
+    spec = ObjectSpec()
+    o, keep, oinfo = object_mask(z, nodata=-9999.0, cellsize=1.0, spec=spec)
+    a, ia = inpaint_raster(G, z, nodata=-9999.0, window=256, overlap=32, objects=spec, cellsize=1.0)
+    b, ib = inpaint_raster(G, z, keep, nodata=-9999.0, window=256, overlap=32)
+    assert torch.equal(a, b) and ia["objects"] == oinfo and ia["unfilled"] == 0
+    ia.pop("objects")
+    assert ia == ib
+    out, k = a.cpu().numpy(), keep.cpu().numpy() != 0
+    np.testing.assert_array_equal(_bits(out[k]), _bits(z[k]))           # known pixels outside O come back bit for bit
+    top = np.nextafter(np.nextafter(z[k].max(), np.float32(np.inf)), np.float32(np.inf))
+    assert out[~k].max() <= top                          # convex blend over non-object pixels (2 ulp of fp32 blend rounding)
+    assert (o.cpu().numpy() != 0)[truth].mean() >= 0.99
+    with pytest.raises(ValueError, match="cellsize"):
+        inpaint_raster(G, z, objects=spec)
+
+
+def test_loader_never_samples_objects(dev):
+    from mvp_gan.src.object_mask import ObjectSpec, object_mask
+    from mvp_gan.src.utils.raster_dataset import RasterWindowLoader
+    z, _ = OR.scene(768, 768, 5, buildings=30, trees=60)
+    spec = ObjectSpec()
+    o, _, _ = object_mask(z, cellsize=1.0, spec=spec)
+    o = o.cpu().numpy() != 0
+    base = RasterWindowLoader(z, window=64, batch_size=8, seed=1, device=dev)
+    ld = RasterWindowLoader(z, window=64, batch_size=8, seed=1, device=dev, objects=spec, cellsize=1.0)
+    assert "object_fraction" not in base.info
+    assert ld.info["object_fraction"] == o.mean() > 0
+    assert ld.info["admissible_origins"] < base.info["admissible_origins"]
+    for b in range(20):
+        for y0, x0, _ in ld.draw(b)["draws"]:
+            assert not o[y0:y0 + 64, x0:x0 + 64].any()
+    batch = next(iter(ld))
+    assert batch["image"].shape == (8, 1, 64, 64) and torch.isfinite(batch["image"]).all()
+
+
+def test_clis(dev, G, tmp_path):
+    from mvp_gan.src.inpaint_raster import main as inpaint_main
+    from mvp_gan.src.inpaint_raster import read_asc, write_asc
+    from mvp_gan.src.object_mask import main as om_main
+    z, _ = OR.scene(400, 360, 7, buildings=6, trees=10)
+    z[5, 5] = -9999.0
+    hdr = [("ncols", "360"), ("nrows", "400"), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", "1"),
+           ("NODATA_value", "-9999")]
+    write_asc(tmp_path / "in.asc", z, hdr)
+    torch.save({"generator_state_dict": G.state_dict()}, tmp_path / "g.pth")
+    info = om_main(["--dem", str(tmp_path / "in.asc"), "--out", str(tmp_path / "keep.png"), "--objects-out",
+                    str(tmp_path / "obj.asc")])
+    assert info["objects"] >= 5
+    common = ["--dem", str(tmp_path / "in.asc"), "--checkpoint", str(tmp_path / "g.pth"), "--window", "128", "--overlap", "16"]
+    inpaint_main(common + ["--mask", str(tmp_path / "keep.png"), "--out", str(tmp_path / "a.asc")])
+    inpaint_main(common + ["--remove-objects", "--objects-out", str(tmp_path / "obj2.asc"), "--out", str(tmp_path / "b.asc")])
+    a, ha = read_asc(tmp_path / "a.asc")
+    b, hb = read_asc(tmp_path / "b.asc")
+    assert ha == hb == hdr
+    np.testing.assert_array_equal(_bits(a), _bits(b))
+    o1, _ = read_asc(tmp_path / "obj.asc")
+    o2, _ = read_asc(tmp_path / "obj2.asc")
+    np.testing.assert_array_equal(o1, o2)
+    assert o1.sum() == info["object_pixels"]
+
+    env = dict(os.environ, TERRAGAN_ALLOW_STANDIN_VGG="1")
+    r = subprocess.run([sys.executable, "-m", "mvp_gan.src.train_raster", "--dem", str(tmp_path / "in.asc"), "--out",
+                        str(tmp_path / "t.pth"), "--window", "64", "--batch", "2", "--steps", "2", "--epochs", "1", "--block",
+                        "128", "--remove-objects"], cwd=os.path.join(ROOT, "terra-gan_amd"), capture_output=True, text=True,
+                       timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert (tmp_path / "t.pth").exists()
