@@ -516,6 +516,67 @@ int tg_objmask_components(const uint8_t* flags, int H, int W, int32_t* labels, i
 int tg_objmask_filter(const uint8_t* known, const int32_t* labels, const int32_t* area, int H, int W, int min_area,
                       int buffer_px, uint8_t* objects, float* keep, int32_t* counts, tg_stream_t stream);
 
+/* ---- held-out terrain errors of an inpainted raster (mvp_gan/src/evaluate_raster.py; no reference
+ * counterpart: the reference scores 8-bit tiles only) ----
+ * Rasters are row-major [H][W] with 1 <= H, W and H * W < 2^31.  valid: mask != 0 (mask may be NULL), finite, and
+ * (use_nodata) != nodata.  No call allocates or synchronises; every result is bitwise deterministic (integer atomics only,
+ * fp64 sums from per-workgroup partials reduced in a fixed order). */
+/* Evaluation holes of raster rows [row0, row1) (row0 a multiple of tile, row1 <= H): pixel (y, x) lies in cell
+ * (y / tile, x / tile) of a grid of ncy x ncx = ceil(H / tile) x ceil(W / tile) cells; k = cell_of[cy][cx] >= 0 names its
+ * hole mask cell_masks[k][tile][tile] (float, 0 = hole, as tg_hole_masks writes it) read at (y % tile, x % tile); -1 = no
+ * hole.  hole_in [H][W] uint8 (may be NULL) adds the pixels where it is nonzero.  objects [H][W] uint8 may be NULL.
+ * holes [H][W] uint8 = valid && hole && !objects; keep [H][W] float = valid && !hole && !objects.  counts [3] int64 are
+ * ADDED to (the caller zeroes them): valid pixels, holes, valid object pixels. */
+int tg_eval_holes(const float* dem, const float* mask, int use_nodata, float nodata, const uint8_t* objects,
+                  const float* cell_masks, const int32_t* cell_of, const uint8_t* hole_in, int H, int W, int tile, int row0,
+                  int row1, uint8_t* holes, float* keep, int64_t* counts, tg_stream_t stream);
+/* Per-hole table: every root i of labels (labels[i] == i, from tg_objmask_components on the holes) gets a row
+ * s = slot[i] (atomic counter order: the caller sorts by label) of table [cap][TG_HOLE_COLS] int64 =
+ * {label, area, scored 0, fixed-point sum 0, max bits 0, y0, x0, y1, x1}, the bbox set to the root pixel; tg_terrain_errors
+ * adds the rest.  slot [H*W] int32 is written at the roots only and may alias area.  count [1] int32 (zeroed by the call) =
+ * the number of roots; rows past cap are not written. */
+enum { TG_HOLE_COLS = 9 };
+int tg_hole_table(const int32_t* labels, const int32_t* area, int H, int W, int32_t* slot, int64_t* table, int cap,
+                  int32_t* count, tg_stream_t stream);
+/* Area classes of tg_terrain_errors: a hole of area A px is in class c = #{e < n_edges : A >= px[e]} (px nondecreasing). */
+enum { TG_EVAL_MAX_CLASSES = 8 };
+typedef struct {
+    int32_t n_edges, _pad;
+    int64_t px[TG_EVAL_MAX_CLASSES - 1];
+} TgAreaClasses;
+/* fp64 sums (tg_terrain_errors_finish), e = p - z (fp32), a = |e|; S = hole && finite(p); T = S pixels whose 3x3 neighbourhood
+ * lies inside the raster, is valid and has finite p; R = S pixels with an 8-neighbour in keep; dg2 = |grad p - grad z|^2 (Horn,
+ * fp64), ds = slope_p - slope_z in degrees, dl = laplacian_p - laplacian_z: */
+enum {
+    TG_TE_S_E = 0, TG_TE_S_A, TG_TE_S_A2, TG_TE_T_DS, TG_TE_T_DS2, TG_TE_T_DG2, TG_TE_T_DL2, TG_TE_R_A, TG_TE_R_A2,
+    TG_TE_RT_DG2, TG_TE_CLASS /* + 2c: sum a, + 2c + 1: sum a^2 over S pixels of class c */,
+    TG_TE_NSUM = TG_TE_CLASS + 2 * TG_EVAL_MAX_CLASSES
+};
+/* int64 counters (zeroed by tg_terrain_errors): */
+enum {
+    TG_TE_N_VALID = 0, TG_TE_N_HOLES, TG_TE_N_OBJECTS, TG_TE_N_SCORED, TG_TE_N_UNFILLED, TG_TE_N_RING, TG_TE_N_SLOPE,
+    TG_TE_N_RING_SLOPE, TG_TE_N_CLAMPED, TG_TE_MAX_BITS, TG_TE_NCOUNT
+};
+size_t tg_terrain_errors_ws_bytes(int H, int W);
+/* z, p [H][W] float; holes [H][W] uint8 (nonzero = evaluation hole); keep [H][W] float (nonzero = known to the model); labels,
+ * slot, table, nholes from tg_objmask_components + tg_hole_table (nholes <= cap rows).  Per hole (integer atomics at
+ * row slot[labels[i]]): scored += 1, sum += rint(min(a, 2^15) * 2^16), max bits, bbox over all its pixels.  counts
+ * [TG_TE_NCOUNT] int64; sel_a [H*W] = a on S, NaN elsewhere; sel_slope [H*W] = (float)|ds| on T, NaN elsewhere;
+ * ws >= tg_terrain_errors_ws_bytes: per-workgroup partials for tg_terrain_errors_finish. */
+int tg_terrain_errors(const float* z, const float* p, const float* mask, int use_nodata, float nodata, const uint8_t* holes,
+                      const float* keep, const int32_t* labels, const int32_t* slot, int64_t* table, int nholes, int H, int W,
+                      double cellsize, const TgAreaClasses* classes, int64_t* counts, float* sel_a, float* sel_slope,
+                      void* ws, size_t ws_bytes, tg_stream_t stream);
+/* sums [TG_TE_NSUM] double = the partials of the last tg_terrain_errors call of this shape on ws, reduced in a fixed order. */
+int tg_terrain_errors_finish(int H, int W, const void* ws, size_t ws_bytes, double* sums, tg_stream_t stream);
+/* out[j] = the ks[j]-th smallest (0-based) of the values v[0 .. n) whose bits are <= 0x7f800000 (neither NaN nor negative,
+ * -0 included); NaN when ks[j] is out of range.  Exact (radix select on the bits: 11 + 11 + 10), so bitwise equal to
+ * np.sort(v[v >= +0 bits])[k].  ks [nk] int64 device, 1 <= nk <= TG_SELECT_MAX_K, n < 2^31; ws >= tg_select_f32_ws_bytes. */
+enum { TG_SELECT_MAX_K = 8 };
+size_t tg_select_f32_ws_bytes(int64_t n, int nk);
+int tg_select_f32(const float* v, int64_t n, const int64_t* ks, int nk, float* out, void* ws, size_t ws_bytes,
+                  tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

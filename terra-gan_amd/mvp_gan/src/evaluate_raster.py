@@ -1,0 +1,466 @@
+"""Score inpainting on held-out raster blocks: terrain errors in metres on the GPU (csrc/terrain_eval.hip).
+
+The reference scores 8-bit tiles only, and this project's tile metrics (PSNR, SSIM, boundary MSE) are unitless.  Here holes
+are cut into measured terrain of the held-out blocks, the holed raster is inpainted with inpaint_raster unchanged, and the
+result is compared against the truth:
+
+  - valid pixel V: mask != 0, finite, != nodata (the rule of inpaint_raster); Obj: the object_mask map (with `objects`);
+  - hole cells: a grid of `tile`-px cells aligned at (0, 0), block % tile == 0; a cell is eligible when its block (by, bx)
+    has (bx - by) mod 3 == SPLITS[split] (RasterWindowLoader's rule: with the same block, test cells never share a pixel with
+    a training window); split None: every cell;
+  - the holes of a cell are RasterWindowLoader's primitives at side `tile`, drawn from
+    SeedSequence([seed, 7, split tag, cy, cx]) (tag 3 for split None) and rasterised by tg_hole_masks, clipped to the raster;
+    so a cell's holes do not depend on the raster's extent;
+  - Hol = V and cell hole and not Obj; K = V and not Hol and not Obj (the mask inpaint_raster sees); Obj pixels are filled but
+    never scored;
+  - S = Hol and finite(p); e = p - z (fp32), a = |e|; T = S pixels whose 3x3 neighbourhood lies inside the raster, is valid and
+    has finite p: slope (Horn, fp64, degrees), gradient and 5-point Laplacian errors; ring R = S pixels with an 8-neighbour
+    in K;
+  - holes = 8-connected components of Hol (label = smallest linear index); area classes by pixels * cellsize^2;
+  - per-hole sums are sum rint(min(a, 2^15) * 2^16) in int64 (exact, order-independent; < 8 um per pixel);
+  - quantiles by nearest rank: sorted ascending, element ceil(q n) - 1, selected exactly on the GPU.
+
+Two calls on the same inputs return bitwise-equal tensors and an equal report.
+
+CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
+         [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
+         [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
+     python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
+"""
+import argparse
+import json
+import math
+from dataclasses import asdict
+
+import numpy as np
+import torch
+
+from .utils.raster_dataset import SPLITS, HoleSpec, fit_primitives, primitive_draws
+
+MIN_TILE, MAX_TILE = 40, 1024
+AREA_EDGES_M2 = (100.0, 1000.0, 10000.0)
+QUANTILES = (0.5, 0.9, 0.95, 0.99)
+FIX = 2.0 ** 16                       # fixed-point scale of the per-hole sums
+CLAMP = 2.0 ** 15                     # metres: larger per-pixel errors are clamped in the per-hole sums
+MAX_CLASSES = 8
+BATCH_BYTES = 256 << 20               # cell masks rasterised per batch
+HOLE_COLS = ("label", "area", "scored", "sum", "max", "y0", "x0", "y1", "x1")
+SUMS = ("s_e", "s_a", "s_a2", "t_ds", "t_ds2", "t_dg2", "t_dl2", "r_a", "r_a2", "rt_dg2")     # then per class: a, a^2
+COUNTS = ("valid", "holes", "objects", "scored", "unfilled", "ring", "slope_scored", "ring_slope", "clamped", "max_bits")
+
+
+# ---- host-side plan -------------------------------------------------------------------------------------------------
+def _cellsize(c, who):
+    try:
+        v = float(c)
+    except (TypeError, ValueError):
+        v = math.nan
+    if not math.isfinite(v) or v <= 0:
+        raise ValueError(f"{who}: cellsize {c!r} must be finite and > 0")
+    return v
+
+
+def check_plan(H, W, split, block, tile, holes, who="eval_holes"):
+    if split is not None and split not in SPLITS:
+        raise ValueError(f"{who}: split {split!r} must be None or one of {tuple(SPLITS)}")
+    tile, block = int(tile), int(block)
+    if not MIN_TILE <= tile <= MAX_TILE:
+        raise ValueError(f"{who}: tile {tile} out of range [{MIN_TILE}, {MAX_TILE}]")
+    if block < tile or block % tile:
+        raise ValueError(f"{who}: block {block} must be a positive multiple of the tile {tile}")
+    holes.check(tile)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"{who}: raster must be [H, W] with H*W < 2^31, got {H}x{W}")
+    return tile, block
+
+
+def eligible_cells(H, W, split, block, tile):
+    """bool [ceil(H / tile)][ceil(W / tile)]: the cells that get holes."""
+    ncy, ncx = -(-H // tile), -(-W // tile)
+    if split is None:
+        return np.ones((ncy, ncx), bool)
+    by = (np.arange(ncy) * tile // block)[:, None]
+    bx = (np.arange(ncx) * tile // block)[None, :]
+    return (bx - by) % 3 == SPLITS[split]
+
+
+def cell_rng(seed, split, cy, cx):
+    tag = 3 if split is None else SPLITS[split]
+    return np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed), 7, tag, int(cy), int(cx)])))
+
+
+def cell_primitives(seed, split, cells, tile, holes):
+    """-> (prims int32 [P][8], offsets int32 [n+1]) of the cells [(cy, cx)]: draw_primitives(cell_rng(...), 1, tile, holes)
+    per cell, the draws made per cell and fitted in one vectorised pass."""
+    draws = [primitive_draws(cell_rng(seed, split, cy, cx), 1, tile, holes) for cy, cx in cells]
+    d = {k: np.concatenate([x[k] for x in draws]) for k in draws[0]}
+    return fit_primitives(d, tile, holes)
+
+
+def class_px(edges_m2, cellsize):
+    """The smallest area in pixels of each class above the first: min px with px * cellsize^2 >= edge."""
+    c2 = cellsize * cellsize
+    out = []
+    for e in edges_m2:
+        t = max(0, math.floor(e / c2) - 2)
+        while t * c2 < e:
+            t += 1
+        out.append(t)
+    return out
+
+
+def _check_edges(edges):
+    edges = [float(e) for e in edges]
+    if len(edges) > MAX_CLASSES - 1 or any(not math.isfinite(e) or e <= 0 for e in edges) or edges != sorted(edges):
+        raise ValueError(f"terrain_errors: area_edges_m2 {edges} must be at most {MAX_CLASSES - 1} increasing finite values > 0")
+    return edges
+
+
+def _check_quantiles(qs):
+    qs = [float(q) for q in qs]
+    if not 1 <= len(qs) <= 8 or any(not 0 < q <= 1 for q in qs):
+        raise ValueError(f"terrain_errors: quantiles {qs} must be 1 .. 8 values in (0, 1]")
+    return qs
+
+
+def rank(q, n):
+    """0-based nearest rank of quantile q among n sorted values."""
+    return min(max(math.ceil(q * n) - 1, 0), n - 1)
+
+
+# ---- device helpers -------------------------------------------------------------------------------------------------
+def _device():
+    if not torch.cuda.is_available():
+        raise RuntimeError("evaluate_raster: no HIP device visible; this build has no CPU path")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _f32(a, device, what, binary=False):
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError(f"evaluate_raster: {what} is on {a.device}; pass a numpy array or a HIP tensor")
+        if binary and a.dtype != torch.float32:
+            a = a != 0
+        return a.to(device=device, dtype=torch.float32).contiguous()
+    a = np.asarray(a)
+    if binary:
+        a = a != 0
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+def _u8(a, device):
+    if isinstance(a, torch.Tensor) and a.dtype == torch.uint8 and a.device == device and a.is_contiguous():
+        return a                                                # the kernels read nonzero as a hole already
+    if isinstance(a, torch.Tensor):
+        return (a != 0).to(device=device, dtype=torch.uint8).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)).to(device)
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def _nodata(nodata):
+    return None if nodata is None or math.isnan(nodata) else float(nodata)
+
+
+def _inputs(dem, mask, who):
+    shape = _shape(dem)
+    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
+        raise ValueError(f"{who}: dem must be [H, W] with H*W < 2^31, got {shape}")
+    if mask is not None and _shape(mask) != shape:
+        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
+    return shape
+
+
+# ---- evaluation holes -----------------------------------------------------------------------------------------------
+@torch.no_grad()
+def eval_holes(dem, mask=None, *, nodata=None, split="test", block=1024, tile=256, holes=HoleSpec(), seed=0, objects=None,
+               cellsize=None):
+    """-> (holes uint8 [H][W] = Hol, keep float32 [H][W] = K, info) as HIP tensors; info: cells, valid, holes, objects,
+    and with `objects` the object_mask info under "object_mask"."""
+    from tg_hip import ops as O
+    H, W = _inputs(dem, mask, "eval_holes")
+    tile, block = check_plan(H, W, split, block, tile, holes)
+    if objects is not None:
+        cellsize = _cellsize(cellsize, "eval_holes")
+    device = _device()
+    z = _f32(dem, device, "dem")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    nodata = _nodata(nodata)
+    obj, oinfo = None, None
+    if objects is not None:
+        from .object_mask import object_mask
+        obj, _, oinfo = object_mask(z, m, nodata=nodata, cellsize=cellsize, spec=objects)
+    el = eligible_cells(H, W, split, block, tile)
+    ncy, ncx = el.shape
+    cell_of = np.full((ncy, ncx), -1, np.int32)
+    hmap = torch.empty(H, W, dtype=torch.uint8, device=device)
+    keep = torch.empty(H, W, dtype=torch.float32, device=device)
+    counts = torch.zeros(3, dtype=torch.int64, device=device)
+    cap = max(1, min(BATCH_BYTES // (4 * tile * tile), 65535))
+    if int(el.sum(1).max()) > cap:
+        raise ValueError(f"eval_holes: {int(el.sum(1).max())} cells in one row of {tile}-px cells, more than {cap} per batch")
+    cy0 = 0
+    while cy0 < ncy:
+        cy1, n = cy0, 0
+        while cy1 < ncy and n + int(el[cy1].sum()) <= cap:
+            n += int(el[cy1].sum())
+            cy1 += 1
+        cells = np.argwhere(el[cy0:cy1]) + [cy0, 0]
+        masks, cof = None, None
+        if len(cells):
+            cell_of[cells[:, 0], cells[:, 1]] = np.arange(len(cells), dtype=np.int32)
+            prims, offsets = cell_primitives(seed, split, cells.tolist(), tile, holes)
+            pd = torch.from_numpy(prims).to(device)
+            masks = O.hole_masks(pd, torch.from_numpy(offsets).to(device), tile)
+            cof = torch.from_numpy(cell_of).to(device)
+        O.eval_holes(z, m, nodata, obj, masks, cof, tile, cy0 * tile, min(cy1 * tile, H), hmap, keep, counts)
+        cy0 = cy1
+    c = counts.cpu().tolist()
+    info = {"cells": int(el.sum()), "valid": c[0], "holes": c[1], "objects": c[2]}
+    if oinfo is not None:
+        info["object_mask"] = oinfo
+    return hmap, keep, info
+
+
+@torch.no_grad()
+def holes_from_map(dem, hole_map, mask=None, *, nodata=None, objects=None, cellsize=None):
+    """Holes given as a map (nonzero = hole, e.g. the --holes-out of an earlier run) -> (holes uint8, keep float32, info) with
+    the rules of eval_holes: Hol = V and hole and not Obj, K = V and not hole and not Obj."""
+    from tg_hip import ops as O
+    H, W = _inputs(dem, mask, "holes_from_map")
+    if _shape(hole_map) != (H, W):
+        raise ValueError(f"holes_from_map: hole map {_shape(hole_map)} differs from the dem {(H, W)}")
+    if objects is not None:
+        cellsize = _cellsize(cellsize, "holes_from_map")
+    device = _device()
+    z = _f32(dem, device, "dem")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    nodata = _nodata(nodata)
+    obj, oinfo = None, None
+    if objects is not None:
+        from .object_mask import object_mask
+        obj, _, oinfo = object_mask(z, m, nodata=nodata, cellsize=cellsize, spec=objects)
+    hmap = torch.empty(H, W, dtype=torch.uint8, device=device)
+    keep = torch.empty(H, W, dtype=torch.float32, device=device)
+    counts = torch.zeros(3, dtype=torch.int64, device=device)
+    O.eval_holes(z, m, nodata, obj, None, None, MAX_TILE, 0, H, hmap, keep, counts, hole_in=_u8(hole_map, device))
+    c = counts.cpu().tolist()
+    info = {"cells": 0, "valid": c[0], "holes": c[1], "objects": c[2]}
+    if oinfo is not None:
+        info["object_mask"] = oinfo
+    return hmap, keep, info
+
+
+# ---- the report -----------------------------------------------------------------------------------------------------
+def _mean(s, n):
+    return float(s) / n if n else math.nan
+
+
+def _rms(s, n):
+    return math.sqrt(float(s) / n) if n else math.nan
+
+
+def _f32bits(b):
+    return float(np.array([b], np.uint32).view(np.float32)[0])
+
+
+def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantiles, top):
+    """The report from the raw results: counts {COUNTS}, sums {SUMS + class_a / class_a2 lists}, table int64 [n][9] sorted by
+    label, qa: the height quantile values, qs: the slope error p90."""
+    c2 = cellsize * cellsize
+    n = counts
+    ns, nt, nr, nrt = n["scored"], n["slope_scored"], n["ring"], n["ring_slope"]
+    rep = {"pixels": {k: int(n[k]) for k in ("valid", "holes", "scored", "unfilled", "ring", "slope_scored", "objects",
+                                              "clamped")}}
+    h = {"bias": _mean(sums["s_e"], ns), "mae": _mean(sums["s_a"], ns), "rmse": _rms(sums["s_a2"], ns),
+         "max": _f32bits(n["max_bits"]) if ns else math.nan,
+         "quantiles": {repr(q): float(v) for q, v in zip(quantiles, qa)}}
+    h["le90"] = h["quantiles"].get(repr(0.9), math.nan)
+    rep["height"] = h
+    rep["slope_deg"] = {"mae": _mean(sums["t_ds"], nt), "rmse": _rms(sums["t_ds2"], nt), "p90": float(qs),
+                        "gradient_rmse": _rms(sums["t_dg2"], nt), "laplacian_rmse": _rms(sums["t_dl2"], nt)}
+    rep["ring"] = {"mae": _mean(sums["r_a"], nr), "rmse": _rms(sums["r_a2"], nr), "gradient_rmse": _rms(sums["rt_dg2"], nrt)}
+    table = np.asarray(table, np.int64).reshape(-1, len(HOLE_COLS))
+    px = class_px(edges_m2, cellsize)
+    cls = np.zeros(len(table), np.int64)
+    for t in px:
+        cls += table[:, 1] >= t
+    bounds = [0.0] + list(edges_m2) + [math.inf]
+    rep["by_area"] = []
+    for k in range(len(edges_m2) + 1):
+        sel = cls == k
+        npx = int(table[sel, 2].sum())
+        rep["by_area"].append({"lo_m2": bounds[k], "hi_m2": bounds[k + 1], "holes": int(sel.sum()), "pixels": npx,
+                               "mae": _mean(sums["class_a"][k], npx), "rmse": _rms(sums["class_a2"][k], npx)})
+    sc = table[:, 2]
+    mae = np.where(sc > 0, table[:, 3] / FIX / np.maximum(sc, 1), -1.0)
+    order = [i for i in np.lexsort((table[:, 0], -mae)) if sc[i] > 0][:int(top)]
+    rep["holes"] = {"count": int(len(table)), "worst": [
+        {"label": int(table[i, 0]), "bbox": [int(v) for v in table[i, 5:9]], "area_m2": float(table[i, 1]) * c2,
+         "scored": int(sc[i]), "mae": float(mae[i]), "max": _f32bits(table[i, 4])} for i in order]}
+    return rep
+
+
+@torch.no_grad()
+def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
+                   quantiles=QUANTILES, top=10):
+    """The report (a plain dict json.dump can write) of pred against the truth dem on the holes; model-free, so any fill can be
+    scored on the same holes.  holes: nonzero = evaluation hole; keep: nonzero = known to the model."""
+    from tg_hip import ops as O
+    c = _cellsize(cellsize, "terrain_errors")
+    H, W = _inputs(dem, mask, "terrain_errors")
+    for t, nm in ((pred, "pred"), (holes, "holes"), (keep, "keep")):
+        if _shape(t) != (H, W):
+            raise ValueError(f"terrain_errors: {nm} {_shape(t)} differs from the dem {(H, W)}")
+    edges = _check_edges(area_edges_m2)
+    qs = _check_quantiles(quantiles)
+    if int(top) < 0:
+        raise ValueError(f"terrain_errors: top {top} < 0")
+    device = _device()
+    z, p = _f32(dem, device, "dem"), _f32(pred, device, "pred")
+    hm = _u8(holes, device)
+    k = _f32(keep, device, "keep", binary=True)
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    nodata = _nodata(nodata)
+
+    labels, area = O.objmask_components(hm)
+    cap = 4096
+    while True:
+        table, slot, count = O.hole_table(labels, area, cap, slot=None)
+        nh = int(count.item())
+        if nh <= cap:
+            break
+        cap = nh
+    table = table[:nh]
+    sums, counts, sel_a, sel_s = O.terrain_errors(z, p, m, nodata, hm, k, labels, slot, table, c, class_px(edges, c))
+    cn = dict(zip(COUNTS, counts.cpu().tolist()))
+    s = sums.cpu().numpy()
+    sd = dict(zip(SUMS, s[:len(SUMS)].tolist()))
+    ncls = len(edges) + 1
+    sd["class_a"] = s[len(SUMS)::2][:ncls].tolist()
+    sd["class_a2"] = s[len(SUMS) + 1::2][:ncls].tolist()
+    ns, nt = cn["scored"], cn["slope_scored"]
+    qa = O.select_f32(sel_a, [rank(q, ns) for q in qs]).cpu().tolist() if ns else [math.nan] * len(qs)
+    q90 = O.select_f32(sel_s, [rank(0.9, nt)]).cpu().tolist()[0] if nt else math.nan
+    tb = table.cpu().numpy()
+    tb = tb[np.argsort(tb[:, 0], kind="stable")]
+    return assemble_report(cn, sd, tb, qa, q90, cellsize=c, edges_m2=edges, quantiles=qs, top=top)
+
+
+# ---- end to end -----------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
+                    holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
+                    quantiles=QUANTILES, top=10):
+    """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W])."""
+    rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
+                             tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
+                             area_edges_m2=area_edges_m2, quantiles=quantiles, top=top)
+    return rep, pred
+
+
+def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
+              objects, area_edges_m2, quantiles, top):
+    """evaluate_raster, plus the hole map."""
+    from .inpaint_raster import inpaint_raster
+    c = _cellsize(cellsize, "evaluate_raster")
+    H, W = _inputs(dem, mask, "evaluate_raster")
+    check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
+    _check_edges(area_edges_m2)
+    _check_quantiles(quantiles)
+    device = _device()
+    z = _f32(dem, device, "dem")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    hm, keep, hinfo = eval_holes(z, m, nodata=nodata, split=split, block=block, tile=tile, holes=holes, seed=seed,
+                                 objects=objects, cellsize=c)
+    pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch)
+    rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
+                         quantiles=quantiles, top=top)
+    rep.update(params(c, split, block, tile, seed, holes, window, overlap))
+    rep["cells"] = hinfo["cells"]
+    rep["inpaint"] = iinfo
+    return rep, pred, hm
+
+
+def params(cellsize, split, block, tile, seed, holes, window=None, overlap=None):
+    hs = asdict(holes)
+    hs["kinds"] = list(hs["kinds"])
+    return {"cellsize": cellsize, "split": split, "block": int(block), "tile": int(tile), "seed": int(seed), "hole_spec": hs,
+            "window": window, "overlap": overlap}
+
+
+def summary(rep):
+    """One line: height RMSE, LE90, slope MAE, ring RMSE."""
+    return (f"height RMSE {rep['height']['rmse']:.4f} m, LE90 {rep['height']['le90']:.4f} m, slope MAE "
+            f"{rep['slope_deg']['mae']:.3f} deg, ring RMSE {rep['ring']['rmse']:.4f} m over {rep['pixels']['scored']} px in "
+            f"{rep['holes']['count']} holes")
+
+
+# ---- CLI ------------------------------------------------------------------------------------------------------------
+def main(argv=None):
+    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .object_mask import add_spec_args, spec_from_args, write_mask
+    ap = argparse.ArgumentParser(description="Score inpainting of an ESRI ASCII grid DSM on held-out holes, in metres.")
+    ap.add_argument("--dem", required=True, help="truth .asc raster (NODATA_value cells are never scored)")
+    ap.add_argument("--checkpoint", help="generator checkpoint (.pth) to inpaint the holes with")
+    ap.add_argument("--pred", help="scoring mode: an inpainted .asc raster to score instead of running a checkpoint")
+    ap.add_argument("--holes", help="scoring mode: the hole map (.png or .asc, nonzero = hole) of an earlier --holes-out")
+    ap.add_argument("--mask", help="optional mask (.png or .asc) of the raster's size: nonzero = valid")
+    ap.add_argument("--nodata", type=float, help="nodata value (default: the .asc header's NODATA_value)")
+    ap.add_argument("--split", choices=("test", "val", "train", "all"), default="test")
+    ap.add_argument("--block", type=int, default=1024)
+    ap.add_argument("--tile", type=int, default=256)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--window", type=int, default=512)
+    ap.add_argument("--overlap", type=int, default=64)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--remove-objects", action="store_true",
+                    help="find above-ground objects (cellsize from the header): filled but never scored")
+    add_spec_args(ap)
+    ap.add_argument("--json", help="write the report here")
+    ap.add_argument("--pred-out", help="write the prediction (.asc)")
+    ap.add_argument("--holes-out", help="write the evaluation holes (.png or .asc, nonzero = hole)")
+    a = ap.parse_args(argv)
+    if bool(a.checkpoint) == bool(a.pred):
+        ap.error("give exactly one of --checkpoint and --pred")
+    if bool(a.pred) != bool(a.holes):
+        ap.error("--pred and --holes go together")
+    dem, header = read_asc(a.dem)
+    mask = _read_mask(a.mask, dem.shape) if a.mask else None
+    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
+    c = float(asc_value(header, "cellsize"))
+    objects = spec_from_args(a) if a.remove_objects else None
+    split = None if a.split == "all" else a.split
+    if a.checkpoint:
+        rep, pred, hm = _evaluate(a.checkpoint, dem, mask, nodata=nodata, cellsize=c, split=split, block=a.block, tile=a.tile,
+                                  holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
+                                  objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10)
+    else:
+        p, ph = read_asc(a.pred)
+        if p.shape != dem.shape:
+            raise ValueError(f"{a.pred} is {p.shape[0]}x{p.shape[1]}, the dem {dem.shape[0]}x{dem.shape[1]}")
+        pnd = asc_nodata(ph)
+        if pnd is not None:
+            p = np.where(p == np.float32(pnd), np.float32(np.nan), p)     # unfilled cells stay unfilled
+        hm, keep, _ = holes_from_map(dem, _read_mask(a.holes, dem.shape), mask, nodata=nodata, objects=objects, cellsize=c)
+        rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata)
+        rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
+        pred = None
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(rep, f, indent=1)
+    if a.pred_out and pred is not None:
+        out = pred.cpu().numpy()
+        if np.isnan(out).any() and asc_value(header, "NODATA_value") is None:
+            header = header + [("NODATA_value", "-9999")]
+        write_asc(a.pred_out, out, header)
+    if a.holes_out and hm is not None:
+        write_mask(a.holes_out, hm.cpu().numpy(), header)
+    print(summary(rep))
+    return rep
+
+
+if __name__ == "__main__":
+    main()

@@ -6,6 +6,10 @@ Train and validation windows come from RasterWindowLoader (utils/raster_dataset.
 
 CLI: python -m mvp_gan.src.train_raster --dem in.asc [--mask keep.png|keep.asc] [--nodata v] [--init ck.pth] --out ft.pth
          [--window 256 --batch 16 --steps 500 --epochs 4 --seed 0 --norm known|window] [--remove-objects [spec flags]]
+         [--evaluate [--eval-json report.json]]
+
+--evaluate scores the written checkpoint on held-out holes of the test split (mvp_gan/src/evaluate_raster.py) with the same
+block, window (as the hole tile), seed, nodata, mask and objects, prints one line and writes the report to --eval-json.
 
 --remove-objects finds the above-ground objects in the DSM (mvp_gan/src/object_mask.py, cellsize from the header) and never
 samples a window that touches one, so the generator learns bare earth.
@@ -58,8 +62,12 @@ def main(argv=None):
     ap.add_argument("--norm", choices=("known", "window"), default="known")
     ap.add_argument("--remove-objects", action="store_true",
                     help="never sample windows that touch an above-ground object found in the DSM")
+    ap.add_argument("--evaluate", action="store_true", help="score the written checkpoint on held-out holes of the test split")
+    ap.add_argument("--eval-json", help="with --evaluate: write the report here")
     add_spec_args(ap)
     a = ap.parse_args(argv)
+    if a.eval_json and not a.evaluate:
+        ap.error("--eval-json needs --evaluate")
     logging.basicConfig(level=logging.INFO, format="%(message)s")
     if not torch.cuda.is_available():
         raise RuntimeError("train_raster: no HIP device visible; this build has no CPU path")
@@ -87,6 +95,17 @@ def main(argv=None):
     print(f"{a.out}: {a.epochs} epochs x {a.steps} steps of {a.batch} windows {a.window}^2 "
           f"(admissible train {tr.info['admissible_fraction']:.3f}, val {va.info['admissible_fraction']:.3f}), "
           f"init {'+'.join(loaded) or 'random'}, best val g_loss {res['best_val_loss']:.5f}")
+    if a.evaluate:
+        import json
+
+        from .evaluate_raster import evaluate_raster, summary
+        rep, _ = evaluate_raster(a.out, dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")), split="test",
+                                 block=tr.block, tile=a.window, seed=a.seed, objects=common.get("objects"))
+        if a.eval_json:
+            with open(a.eval_json, "w") as f:
+                json.dump(rep, f, indent=1)
+        print(f"test split: {summary(rep)}")
+        res["evaluation"] = rep
     return res
 
 

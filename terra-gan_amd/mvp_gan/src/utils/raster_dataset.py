@@ -72,6 +72,75 @@ def prim_bound(prims):
     return np.where(k == KINDS["stroke"], cap, box)
 
 
+def primitive_draws(rng, n, side, holes):
+    """The random part of draw_primitives: every array it draws from `rng`, in the order it draws them."""
+    K = holes.max_prims
+    d = {"frac": rng.uniform(holes.min_fraction, holes.max_fraction, n)}
+    kinds = np.array([KINDS[k] for k in holes.kinds])
+    d["kind"] = kinds[rng.integers(0, len(kinds), (n, K))]
+    d["share"] = rng.uniform(0.25, 1.0, (n, K))
+    d["cy"], d["cx"] = rng.integers(0, side, (n, K)), rng.integers(0, side, (n, K))
+    d["aspect"], d["lfrac"], d["rfrac"] = rng.uniform(0.2, 1.0, (n, K)), rng.uniform(0.5, 1.0, (n, K)), rng.uniform(0, 1, (n, K))
+    d["ang"] = rng.uniform(0, 2 * math.pi, (n, K))
+    d["uv"] = rng.integers(-16, 17, (n, K, 2))
+    return d
+
+
+def fit_primitives(d, side, holes):
+    """The deterministic part of draw_primitives, elementwise over the windows: draws of several generators concatenated
+    along axis 0 give the concatenation of their results."""
+    w, K = side, holes.max_prims
+    n = d["frac"].shape[0]
+    rem = np.floor(d["frac"] * w * w).astype(np.int64)
+    kind, cy, cx = d["kind"], d["cy"], d["cx"]
+    aspect, lfrac, rfrac, ang = d["aspect"], d["lfrac"], d["rfrac"], d["ang"]
+    share = d["share"].copy()
+    share[:, 0] = 1.0                                        # the first primitive may use the whole budget: >= 1 hole
+    uv = d["uv"].copy()
+    uv[(uv == 0).all(-1)] = (1, 0)
+    rmax = max(1, w // 32)
+    prims = np.zeros((n, K, 8), np.int64)
+    keep = np.zeros((n, K), bool)
+    for k in range(K):
+        if (rem < 16).all():
+            break
+        T = np.floor(rem * share[:, k])
+        # rectangle / ellipse: 4 (a+1) (b+1) <= T with a, b >= 1
+        b1 = np.maximum(2, np.floor(np.sqrt(np.maximum(T, 0) * aspect[:, k] / 4)))
+        a1 = np.floor(T / (4 * b1))
+        a, b = np.clip(a1 - 1, 0, w - 1), np.clip(b1 - 1, 0, w - 1)
+        # segment: r with pi r^2 + pi r + 3 <= T, then a length whose capsule bound stays <= T after rounding the end
+        rfit = np.floor((-math.pi + np.sqrt(math.pi ** 2 + 4 * math.pi * np.maximum(T - 3, 0))) / (2 * math.pi))
+        r = np.minimum(np.floor(rfrac[:, k] * (rmax + 1)), np.minimum(rmax, rfit))
+        lmax = np.maximum(T - math.pi * r * r - math.pi * r - 3, 0) / (2 * r + 1)
+        ln = np.maximum(np.minimum(np.floor(lmax * lfrac[:, k]), w) - 1, 0)
+        y1 = cy[:, k] + np.round(ln * np.sin(ang[:, k])).astype(np.int64)
+        x1 = cx[:, k] + np.round(ln * np.cos(ang[:, k])).astype(np.int64)
+        st = kind[:, k] == KINDS["stroke"]
+        p = prims[:, k]
+        p[:, 0], p[:, 1], p[:, 2] = kind[:, k], cy[:, k], cx[:, k]
+        p[:, 3] = np.where(st, y1, a)
+        p[:, 4] = np.where(st, x1, b)
+        p[:, 5] = np.where(st, r, uv[:, k, 0])
+        p[:, 6] = np.where(st, 0, uv[:, k, 1])
+        bound = prim_bound(p)
+        ok = (T >= 16) & (a1 >= 2) & (bound <= rem)
+        keep[:, k] = ok
+        rem -= np.where(ok, bound, 0)
+    cnt = keep.sum(1)
+    if (cnt == 0).any():
+        raise RuntimeError("RasterWindowLoader: a window got no hole primitive")   # excluded by HoleSpec.check
+    offsets = np.zeros(n + 1, np.int32)
+    np.cumsum(cnt, out=offsets[1:])
+    return prims[keep].astype(np.int32), offsets
+
+
+def draw_primitives(rng, n, side, holes):
+    """-> (prims int32 [P][8], offsets int32 [n+1]): hole primitives of n windows of side `side` within their budgets, drawn
+    from `rng` (RasterWindowLoader's windows, evaluate_raster's cells)."""
+    return fit_primitives(primitive_draws(rng, n, side, holes), side, holes)
+
+
 def _host_f32(a, what):
     if isinstance(a, torch.Tensor):
         if not a.is_cuda:
@@ -212,53 +281,7 @@ class RasterWindowLoader:
 
     def _primitives(self, rng, n):
         """-> (prims int32 [P][8], offsets int32 [n+1]): hole primitives of n windows within their budgets."""
-        hs, w = self.holes, self.window
-        K = hs.max_prims
-        rem = np.floor(rng.uniform(hs.min_fraction, hs.max_fraction, n) * w * w).astype(np.int64)
-        kinds = np.array([KINDS[k] for k in hs.kinds])
-        kind = kinds[rng.integers(0, len(kinds), (n, K))]
-        share = rng.uniform(0.25, 1.0, (n, K))
-        share[:, 0] = 1.0                                        # the first primitive may use the whole budget: >= 1 hole
-        cy, cx = rng.integers(0, w, (n, K)), rng.integers(0, w, (n, K))
-        aspect, lfrac, rfrac = rng.uniform(0.2, 1.0, (n, K)), rng.uniform(0.5, 1.0, (n, K)), rng.uniform(0, 1, (n, K))
-        ang = rng.uniform(0, 2 * math.pi, (n, K))
-        uv = rng.integers(-16, 17, (n, K, 2))
-        uv[(uv == 0).all(-1)] = (1, 0)
-        rmax = max(1, w // 32)
-        prims = np.zeros((n, K, 8), np.int64)
-        keep = np.zeros((n, K), bool)
-        for k in range(K):
-            if (rem < 16).all():
-                break
-            T = np.floor(rem * share[:, k])
-            # rectangle / ellipse: 4 (a+1) (b+1) <= T with a, b >= 1
-            b1 = np.maximum(2, np.floor(np.sqrt(np.maximum(T, 0) * aspect[:, k] / 4)))
-            a1 = np.floor(T / (4 * b1))
-            a, b = np.clip(a1 - 1, 0, w - 1), np.clip(b1 - 1, 0, w - 1)
-            # segment: r with pi r^2 + pi r + 3 <= T, then a length whose capsule bound stays <= T after rounding the end
-            rfit = np.floor((-math.pi + np.sqrt(math.pi ** 2 + 4 * math.pi * np.maximum(T - 3, 0))) / (2 * math.pi))
-            r = np.minimum(np.floor(rfrac[:, k] * (rmax + 1)), np.minimum(rmax, rfit))
-            lmax = np.maximum(T - math.pi * r * r - math.pi * r - 3, 0) / (2 * r + 1)
-            ln = np.maximum(np.minimum(np.floor(lmax * lfrac[:, k]), w) - 1, 0)
-            y1 = cy[:, k] + np.round(ln * np.sin(ang[:, k])).astype(np.int64)
-            x1 = cx[:, k] + np.round(ln * np.cos(ang[:, k])).astype(np.int64)
-            st = kind[:, k] == KINDS["stroke"]
-            p = prims[:, k]
-            p[:, 0], p[:, 1], p[:, 2] = kind[:, k], cy[:, k], cx[:, k]
-            p[:, 3] = np.where(st, y1, a)
-            p[:, 4] = np.where(st, x1, b)
-            p[:, 5] = np.where(st, r, uv[:, k, 0])
-            p[:, 6] = np.where(st, 0, uv[:, k, 1])
-            bound = prim_bound(p)
-            ok = (T >= 16) & (a1 >= 2) & (bound <= rem)
-            keep[:, k] = ok
-            rem -= np.where(ok, bound, 0)
-        cnt = keep.sum(1)
-        if (cnt == 0).any():
-            raise RuntimeError("RasterWindowLoader: a window got no hole primitive")   # excluded by HoleSpec.check
-        offsets = np.zeros(n + 1, np.int32)
-        np.cumsum(cnt, out=offsets[1:])
-        return prims[keep].astype(np.int32), offsets
+        return draw_primitives(rng, n, self.window, self.holes)
 
     def draw(self, b):
         """Host draws of batch b of the current epoch: {'draws' int32 [B][3] = (y0, x0, op), 'prims' int32 [P][8],

@@ -40,6 +40,13 @@ class TgRasterPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("H", "W", "wh", "ww", "overlap", "ny", "nx")]
 
 
+TG_EVAL_MAX_CLASSES = 8
+
+
+class TgAreaClasses(C.Structure):
+    _fields_ = [("n_edges", C.c_int32), ("_pad", C.c_int32), ("px", C.c_int64 * (TG_EVAL_MAX_CLASSES - 1))]
+
+
 class TgError(RuntimeError):
     pass
 
@@ -135,6 +142,13 @@ SIGNATURES = {
     "tg_objmask_pmf_step": (I, [P, P, P, I, I, I, F, P, P, P, P, P]),
     "tg_objmask_components": (I, [P, I, I, P, P, P]),
     "tg_objmask_filter": (I, [P, P, P, I, I, I, I, P, P, P, P]),
+    "tg_eval_holes": (I, [P, P, I, F, P, P, P, P, I, I, I, I, I, P, P, P, P]),
+    "tg_hole_table": (I, [P, P, I, I, P, P, I, P, P]),
+    "tg_terrain_errors_ws_bytes": (SZ, [I, I]),
+    "tg_terrain_errors": (I, [P, P, P, I, F, P, P, P, P, P, I, I, I, D, C.POINTER(TgAreaClasses), P, P, P, P, SZ, P]),
+    "tg_terrain_errors_finish": (I, [I, I, P, SZ, P, P]),
+    "tg_select_f32_ws_bytes": (SZ, [I64, I]),
+    "tg_select_f32": (I, [P, I64, P, I, P, P, SZ, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

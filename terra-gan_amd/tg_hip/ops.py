@@ -1042,6 +1042,99 @@ def objmask_filter(known, labels, area, min_area, buffer_px):
     return objects, keep, counts
 
 
+HOLE_COLS = 9                                     # tg_hole_table rows: label, area, scored, sum, max bits, y0, x0, y1, x1
+TE_NSUM, TE_NCOUNT, SELECT_MAX_K = 10 + 2 * L.TG_EVAL_MAX_CLASSES, 10, 8
+
+
+def eval_holes(dem, mask, nodata, objects, cell_masks, cell_of, tile, row0, row1, holes, keep, counts, hole_in=None):
+    """Evaluation holes of raster rows [row0, row1) into holes uint8 / keep float32 [H][W]; counts int64 [3] (valid, holes,
+    valid object pixels) are added to (tg_eval_holes).  cell_masks [n][tile][tile] / cell_of int32 [ncy][ncx] may be None."""
+    H, W = _raster_hw(dem, "dem")
+    _hip(dem, torch.float32, (H, W), "dem")
+    if mask is not None:
+        _hip(mask, torch.float32, (H, W), "mask")
+    if objects is not None:
+        _hip(objects, torch.uint8, (H, W), "objects")
+    if hole_in is not None:
+        _hip(hole_in, torch.uint8, (H, W), "hole_in")
+    if cell_of is not None:
+        _hip(cell_of, torch.int32, (-(-H // tile), -(-W // tile)), "cell_of")
+        if cell_masks is None or cell_masks.dim() != 3:
+            raise L.TgError("eval_holes: cell_of needs cell_masks [n][tile][tile]")
+        _hip(cell_masks, torch.float32, (cell_masks.shape[0], tile, tile), "cell_masks")
+    _hip(holes, torch.uint8, (H, W), "holes")
+    _hip(keep, torch.float32, (H, W), "keep")
+    _hip(counts, torch.int64, (3,), "counts")
+    L.check(_lib().tg_eval_holes(_p(dem), _p(mask), int(nodata is not None), 0.0 if nodata is None else float(nodata),
+                                 _p(objects), _p(cell_masks) if cell_of is not None else None, _p(cell_of), _p(hole_in), H, W,
+                                 int(tile), int(row0), int(row1), _p(holes), _p(keep), _p(counts), _stream()), "tg_eval_holes")
+
+
+def hole_table(labels, area, cap, slot=None):
+    """-> (table int64 [cap][HOLE_COLS], slot int32 [H*W], count int32 [1]) (tg_hole_table).  slot may be `area` itself."""
+    H, W = _raster_hw(labels, "labels")
+    _hip(labels, torch.int32, (H, W), "labels")
+    _hip(area, torch.int32, (H * W,), "area")
+    slot = torch.empty(H * W, dtype=torch.int32, device=labels.device) if slot is None else slot
+    _hip(slot, torch.int32, (H * W,), "slot")
+    if not 0 <= int(cap) < 2 ** 31:
+        raise L.TgError(f"hole_table: cap {cap} out of range [0, 2^31)")
+    table = torch.empty(max(int(cap), 1), HOLE_COLS, dtype=torch.int64, device=labels.device)
+    count = torch.empty(1, dtype=torch.int32, device=labels.device)
+    L.check(_lib().tg_hole_table(_p(labels), _p(area), H, W, _p(slot), _p(table), int(cap), _p(count), _stream()),
+            "tg_hole_table")
+    return table[:int(cap)], slot, count
+
+
+def terrain_errors(z, p, mask, nodata, holes, keep, labels, slot, table, cellsize, class_px):
+    """-> (sums float64 [TE_NSUM], counts int64 [TE_NCOUNT], sel_a [H*W], sel_slope [H*W]) (tg_terrain_errors and
+    tg_terrain_errors_finish).  table: the rows of hole_table; class_px: the class edges in pixels."""
+    H, W = _raster_hw(z, "z")
+    for t, nm in ((z, "z"), (p, "p"), (keep, "keep")):
+        _hip(t, torch.float32, (H, W), nm)
+    if mask is not None:
+        _hip(mask, torch.float32, (H, W), "mask")
+    _hip(holes, torch.uint8, (H, W), "holes")
+    _hip(labels, torch.int32, (H, W), "labels")
+    _hip(slot, torch.int32, (H * W,), "slot")
+    _hip(table, torch.int64, (table.shape[0], HOLE_COLS), "table")
+    if len(class_px) > L.TG_EVAL_MAX_CLASSES - 1:
+        raise L.TgError(f"terrain_errors: {len(class_px)} class edges, at most {L.TG_EVAL_MAX_CLASSES - 1}")
+    cls = L.TgAreaClasses(len(class_px), 0)
+    for j, v in enumerate(class_px):
+        cls.px[j] = int(v)
+    lib = _lib()
+    dev = z.device
+    counts = torch.empty(TE_NCOUNT, dtype=torch.int64, device=dev)
+    sel_a = torch.empty(H * W, dtype=torch.float32, device=dev)
+    sel_s = torch.empty(H * W, dtype=torch.float32, device=dev)
+    sums = torch.empty(TE_NSUM, dtype=torch.float64, device=dev)
+    nb = lib.tg_terrain_errors_ws_bytes(H, W)
+    ws = workspace(nb)
+    L.check(lib.tg_terrain_errors(_p(z), _p(p), _p(mask), int(nodata is not None), 0.0 if nodata is None else float(nodata),
+                                  _p(holes), _p(keep), _p(labels), _p(slot), _p(table) if table.numel() else None,
+                                  table.shape[0], H, W, float(cellsize), C.byref(cls), _p(counts), _p(sel_a), _p(sel_s),
+                                  _p(ws), ws.numel() * 4, _stream()), "tg_terrain_errors")
+    L.check(lib.tg_terrain_errors_finish(H, W, _p(ws), ws.numel() * 4, _p(sums), _stream()), "tg_terrain_errors_finish")
+    return sums, counts, sel_a, sel_s
+
+
+def select_f32(v, ks):
+    """-> float32 [len(ks)]: the ks[j]-th smallest of the non-NaN, non-negative values of v, NaN for k out of range
+    (tg_select_f32)."""
+    if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+        raise L.TgError("select_f32: expected a contiguous float32 HIP tensor")
+    ks = [int(k) for k in ks]
+    if not 1 <= len(ks) <= SELECT_MAX_K:
+        raise L.TgError(f"select_f32: {len(ks)} ranks, expected 1 .. {SELECT_MAX_K}")
+    kd = torch.tensor(ks, dtype=torch.int64).to(v.device)
+    out = torch.empty(len(ks), dtype=torch.float32, device=v.device)
+    lib = _lib()
+    ws = workspace(lib.tg_select_f32_ws_bytes(v.numel(), len(ks)))
+    L.check(lib.tg_select_f32(_p(v), v.numel(), _p(kd), len(ks), _p(out), _p(ws), ws.numel() * 4, _stream()), "tg_select_f32")
+    return out
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()
