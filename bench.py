@@ -7,19 +7,21 @@ A "step" is one pass of mvp_gan.src.train.train_step over one batch that is alre
 Other BASELINE configs: --size 512 --batch 8 --precision bf16 (configs[2]); --size 1024 --batch 4 --checkpoint
 (configs[4] per GPU); `metric` and `config.workload` are derived from the arguments.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `value` = tiles processed by all ranks / max-over-ranks wall time of exactly K
-steps (barrier + synchronize on both sides).  `roofline` is measured live: an extra instrumented pass after the
-timed region brackets every launch of the dominant kernel (the fp32-MFMA Winograd conv) with hipEvents on
-its launch stream (tg_prof_*), achieved = sum of algorithmic FLOPs / sum of kernel time.  `cpu_baseline` times
-the CPU oracle (oracle/terragan_oracle.py, "port") on the host cores, rank 0 at N=1 only.
+steps (barrier + synchronize on both sides).  A plain run sets up, warms up, times the K steps, dumps (if asked) and
+prints; `roofline` and `cpu_baseline` are null in its line.  `--full` adds two measurements after the timed region.
+`roofline` is measured live: an extra instrumented pass brackets every launch of the dominant kernel (the
+fp32-MFMA Winograd conv) with hipEvents on its launch stream (tg_prof_*), achieved = sum of algorithmic FLOPs / sum
+of kernel time.  `cpu_baseline` times the CPU oracle (oracle/terragan_oracle.py, "port") on the host cores, rank 0
+at N=1 only.  `--no-roofline` / `--no-cpu-baseline` drop either from a `--full` run.
 `--dump-outputs DIR` writes what the last timed step computed (step_outputs) as DIR/<name>.npy right after the timed
 region; the inputs and initial weights are seeded, so two builds run with the same arguments compare output for output.
 
-Roofline fields (every one can be recomputed from profiles/*_conv_launches.csv + *_kernel_stats.csv):
+Roofline fields (--full; every one can be recomputed from profiles/*_conv_launches.csv + *_kernel_stats.csv):
   achieved          EXECUTED MFMA TFLOP/s of the dominant kernel = algorithmic FLOPs / 2.25 / kernel time (Winograd
                     F(2x2,3x3) issues 16 multiplies where the direct convolution has 36; the VGG trunk's F(4x4,3x3) kernel,
                     listed under other_kernels, issues 36 per 16 outputs = 1/4)
@@ -131,26 +133,38 @@ def dump_outputs(arrays, dirpath):
         np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1); ms_per_step = their wall time / steps")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (default: BASELINE config 2)")
     ap.add_argument("--size", type=int, default=TILE)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline (instrumented pass) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the instrumented pass")
     ap.add_argument("--precision", default="f32", choices=["f32", "bf16"],
                     help="conv inner-product arithmetic: f32 (BASELINE config 2, default) or bf16 operands + fp32 accumulate (config 3)")
     ap.add_argument("--checkpoint", action="store_true", help="activation checkpointing in the generator (config 5)")
     ap.add_argument("--graph", action="store_true",
                     help="capture the train step in a hipGraph and replay it (tg_hip.graph; single GPU; pays off at small batches)")
-    ap.add_argument("--prof-dump", default=None, help="write the per-launch table of the instrumented pass to this CSV")
+    ap.add_argument("--prof-dump", default=None,
+                    help="write the per-launch table of the instrumented pass to this CSV (--full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (rank 0; see step_outputs)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    args.roofline = args.full and not args.no_roofline
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    if args.prof_dump and not args.roofline:
+        ap.error("--prof-dump needs the instrumented pass: --full without --no-roofline")
+    return args
+
+
+def main():
+    args = parse_args()
 
     # before the first HIP call (torch.cuda.is_available() initialises the runtime): the host driver only supports dmabuf IPC
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -248,7 +262,7 @@ def main():
         gstep.flush()
         gstep = None            # the instrumented pass below runs eagerly (per-launch events cannot be recorded inside a graph)
     roofline = None
-    if not args.no_roofline:
+    if args.roofline:
         # instrumented pass (outside the timed region): hipEvents around every MFMA conv launch, on its launch stream.
         # Every rank runs the probe steps (they contain the gradient all-reduce); only rank 0 records.
         import csv
@@ -261,7 +275,7 @@ def main():
         torch.cuda.synchronize()
         lib.tg_prof_enable(0)
         _O.PROF_TAGS = False
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.roofline:
         dump = args.prof_dump or os.path.join(tempfile.gettempdir(), f"tg_prof_{os.getpid()}.csv")
         lib.tg_prof_dump(dump.encode())
         rows = list(csv.DictReader(open(dump)))
@@ -366,7 +380,7 @@ def main():
         dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.cpu_baseline:
         cpu = cpu_baseline(args.size, args.batch)
 
     if rank == 0:

@@ -139,6 +139,23 @@ def test_bench_dump_outputs(tmp_path):
         assert np.array_equal(np.load(tmp_path / "dump" / (k + ".npy")), a[k])
 
 
+def test_bench_plain_run_is_lean():
+    """A plain bench.py run only times the steps; the instrumented roofline pass and the CPU baseline run under --full."""
+    import pytest
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and not a.roofline and not a.cpu_baseline
+    a = bench.parse_args(["--full"])
+    assert a.roofline and a.cpu_baseline
+    a = bench.parse_args(["--full", "--no-cpu-baseline", "--prof-dump", "launches.csv"])
+    assert a.roofline and not a.cpu_baseline and a.prof_dump == "launches.csv"
+    a = bench.parse_args(["--full", "--no-roofline"])
+    assert not a.roofline and a.cpu_baseline
+    for argv in (["--prof-dump", "launches.csv"], ["--full", "--no-roofline", "--prof-dump", "launches.csv"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(argv)
+
+
 def test_vgg_trunk_weights_resolution(tmp_path, monkeypatch):
     """losses.py:31-34: the reference loads torchvision's ImageNet VGG16.  Offline that cannot work: the mirror must (i) RAISE
     unless the caller opts in to the stand-in trunk, (ii) load a local vgg16-format state-dict through

@@ -5,12 +5,13 @@ set -e
 out=$1
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-mkdir -p $R/gpurun_out/pmc_pl
-python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --prof-dump $R/gpurun_out/pmc_pl/launches.csv > $R/gpurun_out/pmc_pl/bench.log 2>&1
+W=$(mktemp -d)          # launch table, counter passes and their logs (kept for inspection)
+echo "work directory: $W"
+python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --prof-dump $W/launches.csv > $W/bench.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c -d $R/gpurun_out/pmc_pl/$c -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-roofline > $R/gpurun_out/pmc_pl/$c.log 2>&1
+  rocprofv3 --pmc $c -d $W/$c -o p --output-format csv -- python3 $R/bench.py --steps 2 --warmup 1 > $W/$c.log 2>&1
 done
-python3 - "$R/gpurun_out/pmc_pl" "$R/$out" <<'PY'
+python3 - "$W" "$R/$out" <<'PY'
 import csv, glob, sys
 root, out = sys.argv[1], sys.argv[2]
 names = {"wino_kernel": "4064", "wino22_kernel": "4022", "wino_wgrad_kernel": "4164"}
