@@ -577,6 +577,28 @@ size_t tg_select_f32_ws_bytes(int64_t n, int nk);
 int tg_select_f32(const float* v, int64_t n, const int64_t* ks, int nk, float* out, void* ws, size_t ws_bytes,
                   tg_stream_t stream);
 
+/* ---- harmonic void fill of a DSM (mvp_gan/src/fill_voids.py; no reference counterpart) ----
+ * Rasters are row-major [H][W] with 1 <= H, W and H * W < 2^31.  Known K: mask != 0 (mask may be NULL), finite, and
+ * (use_nodata) != nodata; every other pixel is unknown and solves sum_{q in N4(p) inside the raster} (u_q - u_p) = 0 with
+ * u = z on K.  Masked multigrid: levels halve with ceil until the longer side is at most 16 (tg_vfill_levels); a coarse
+ * cell is fixed when any of its children is.  ws: 256-byte aligned, >= tg_vfill_ws_bytes(H, W), kept between the calls of
+ * one fill.  No call allocates or synchronises; results are bitwise deterministic (integer atomics only). */
+enum { TG_VFILL_MAX_LEVELS = 32 };
+/* stats [TG_VFILL_NSTATS] int64 written by tg_vfill_setup: known and unknown pixels, the float bits of min and max z over K
+ * (0 when K is empty). */
+enum { TG_VFILL_KNOWN = 0, TG_VFILL_UNKNOWN, TG_VFILL_MIN_BITS, TG_VFILL_MAX_BITS, TG_VFILL_NSTATS };
+size_t tg_vfill_ws_bytes(int H, int W);
+int tg_vfill_levels(int H, int W);
+/* Known map, statistics, offset c = (min + max) / 2, initial guess (z - c on K, 0 elsewhere), coarse fixed flags and the
+ * per-level lists of 32 x 64 tiles that hold an unknown cell. */
+int tg_vfill_setup(const float* dem, const float* mask, int use_nodata, float nodata, int H, int W, void* ws, size_t ws_bytes,
+                   int64_t* stats, tg_stream_t stream);
+/* One V-cycle over all levels; change_bits [1] (device, zeroed by the call) = float bits of the largest |change| of u over
+ * the unknown pixels during the cycle. */
+int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t* change_bits, tg_stream_t stream);
+/* out [H][W] = dem at known pixels (bit for bit), the solution at the unknowns; NaN everywhere when K is empty. */
+int tg_vfill_finish(const float* dem, int H, int W, const void* ws, size_t ws_bytes, float* out, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

@@ -1,0 +1,609 @@
+// Harmonic (Laplace) void fill of a DSM by masked multigrid (mvp_gan/src/fill_voids.py).
+//
+//   tg_vfill_setup   known map, count, min / max (integer atomics on order-preserving keys), offset c = (min + max) / 2, the
+//                    initial guess u = z - c at known pixels and 0 elsewhere, the fixed flags of every coarse level (a coarse
+//                    cell is fixed when any of its children is) and per level the list of 32 x 64 tiles that hold an unknown
+//   tg_vfill_cycle   one V-cycle: per level a down pass (2 red-black Gauss-Seidel sweeps staged in LDS with a 5-px halo, the
+//                    residual and its restriction to the next level in the same pass), the coarsest level (at most 16 x 16)
+//                    by red-black SOR in one workgroup, per level an up pass (bilinear prolongation of the coarse correction,
+//                    2 sweeps); the largest change of u over the unknowns goes to change_bits
+//   tg_vfill_finish  known pixels copied bit for bit, u + c at the unknowns, NaN everywhere when nothing is known
+//
+// Level 0 holds v = u - c (known values fixed); coarse levels hold the correction e (0 at fixed cells) with right-hand side f.
+// Every unknown cell p solves f_p + sum_{q in N4(p), inside} (v_q - v_p) = 0; the sums run over neighbour DIFFERENCES, which
+// fp32 keeps accurate for smooth fields, so the cycle converges below the rounding of v itself.  Restriction sums the four
+// children (the unscaled 5-point operator grows by 4 per level), so no level carries an h^2; on a level one cell high or wide a
+// coarse cell has two children and their sum is doubled.
+//
+// Determinism: every value is computed by one thread in a fixed order; tiles are independent (the down and up passes read one
+// buffer and write the other); the change is a maximum on the bits of a non-negative float (integer atomic).  Results are
+// bitwise reproducible.  No kernel uses scratch.
+#include <math.h>
+
+#include "common.h"
+
+static inline hipStream_t S(tg_stream_t s) { return (hipStream_t)s; }
+
+constexpr int VF_TY = 32, VF_TX = 64;              // output tile of the level kernels
+constexpr int VF_HS = 4;                           // half-sweeps per pass (2 red-black sweeps)
+constexpr int VF_HALO = VF_HS + 1;                 // + 1: the residual after the last half-sweep
+constexpr int VF_SY = VF_TY + 2 * VF_HALO, VF_SX = VF_TX + 2 * VF_HALO;
+constexpr int VF_SXP = VF_SX + 2;                  // LDS row stride
+constexpr int VF_CY = VF_TY / 2 + 8, VF_CX = VF_TX / 2 + 8;    // coarse patch of the prolongation (origin y0/2 - 4, x0/2 - 4)
+constexpr int VF_MAX_GRID = 2048;
+constexpr int VF_CMAX = 16;                        // coarsest level: longer side at most 16 (one cell per thread)
+constexpr int VF_ALIGN = 256;
+enum { VF_IN = 1, VF_FIX = 2 };
+
+struct VfHdr {
+    uint32_t lo_key, hi_key;                       // order-preserving keys of min / max z over K
+    unsigned long long known;
+    float c;                                       // offset (min + max) / 2
+    int32_t _pad;
+    int32_t ntiles[TG_VFILL_MAX_LEVELS];           // active tiles per level
+};
+static_assert(sizeof(VfHdr) <= VF_ALIGN, "header fits its slot");
+
+// ---- host-side plan (mirrored by vfill_levels / vfill_layout in mvp_gan/src/fill_voids.py) ---------------------------
+struct VfLevel {
+    int H, W, tiles_x, tiles;
+    size_t flags, list, u0, u1, f;                 // byte offsets; level 0 has no f
+};
+struct VfPlan {
+    int L;
+    VfLevel lv[TG_VFILL_MAX_LEVELS];
+    size_t bytes;
+};
+
+static size_t al(size_t n) { return (n + VF_ALIGN - 1) / VF_ALIGN * VF_ALIGN; }
+
+static void vf_plan(int H, int W, VfPlan* p) {
+    int h = H, w = W, L = 0;
+    size_t off = VF_ALIGN;                         // VfHdr
+    for (;;) {
+        VfLevel& v = p->lv[L];
+        v.H = h; v.W = w;
+        v.tiles_x = cdiv(w, VF_TX);
+        v.tiles = cdiv(h, VF_TY) * v.tiles_x;
+        const size_t n = (size_t)h * w;
+        v.flags = off; off += al(n);
+        v.list = off; off += al((size_t)v.tiles * 4);
+        v.u0 = off; off += al(n * 4);
+        v.u1 = off; off += al(n * 4);
+        if (L > 0) { v.f = off; off += al(n * 4); } else { v.f = 0; }
+        ++L;
+        if ((h > w ? h : w) <= VF_CMAX) break;
+        h = (h + 1) / 2; w = (w + 1) / 2;
+    }
+    p->L = L;
+    p->bytes = off;
+}
+
+// ---- device helpers -----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t f2key(float f) {
+    const uint32_t b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float key2f(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+// ---- setup --------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vf_known_kernel(const float* __restrict__ dem, const float* __restrict__ mask,
+                                                       int use_nodata, float nodata, int64_t n, uint8_t* __restrict__ flags,
+                                                       VfHdr* hdr) {
+    __shared__ uint32_t red[4][3];
+    uint32_t cnt = 0, lo = 0xffffffffu, hi = 0u;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float z = dem[i];
+        bool k = isfinite(z);
+        if (mask) k = k && mask[i] != 0.f;
+        if (use_nodata) k = k && z != nodata;
+        flags[i] = k ? VF_FIX : 0;
+        if (k) {
+            ++cnt;
+            const uint32_t q = f2key(z == 0.f ? 0.f : z);          // -0 and +0 share a key
+            lo = q < lo ? q : lo;
+            hi = q > hi ? q : hi;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        cnt += __shfl_xor(cnt, o, 64);
+        const uint32_t a = __shfl_xor(lo, o, 64), b = __shfl_xor(hi, o, 64);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[w][0] = cnt; red[w][1] = lo; red[w][2] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t c = 0, l = 0xffffffffu, h = 0u;
+        for (int q = 0; q < 4; ++q) {
+            c += red[q][0];
+            l = red[q][1] < l ? red[q][1] : l;
+            h = red[q][2] > h ? red[q][2] : h;
+        }
+        if (c) {
+            atomicAdd(&hdr->known, (unsigned long long)c);
+            atomicMin(&hdr->lo_key, l);
+            atomicMax(&hdr->hi_key, h);
+        }
+    }
+}
+
+// v = z - c at known pixels, 0 elsewhere, into both buffers; block 0 writes the statistics
+__global__ __launch_bounds__(256) void vf_init_kernel(const float* __restrict__ dem, const uint8_t* __restrict__ flags,
+                                                      int64_t n, VfHdr* hdr, float* __restrict__ u0, float* __restrict__ u1,
+                                                      int64_t* __restrict__ stats) {
+    const unsigned long long known = hdr->known;
+    const float lo = key2f(hdr->lo_key), hi = key2f(hdr->hi_key);
+    const float c = known ? __fadd_rn(__fmul_rn(lo, 0.5f), __fmul_rn(hi, 0.5f)) : 0.f;   // no overflow at +-FLT_MAX
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hdr->c = c;
+        stats[TG_VFILL_KNOWN] = (int64_t)known;
+        stats[TG_VFILL_UNKNOWN] = n - (int64_t)known;
+        stats[TG_VFILL_MIN_BITS] = known ? (int64_t)__float_as_uint(lo) : 0;
+        stats[TG_VFILL_MAX_BITS] = known ? (int64_t)__float_as_uint(hi) : 0;
+    }
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float v = (flags[i] & VF_FIX) ? __fsub_rn(dem[i], c) : 0.f;
+        u0[i] = v;
+        u1[i] = v;
+    }
+}
+
+// fixed flags of level l + 1: any fixed child
+__global__ __launch_bounds__(256) void vf_coarsen_kernel(const uint8_t* __restrict__ fine, int Hf, int Wf,
+                                                         uint8_t* __restrict__ coarse, int Hc, int Wc) {
+    const int64_t n = (int64_t)Hc * Wc;
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+        const int Y = (int)(j / Wc), X = (int)(j - (int64_t)Y * Wc);
+        uint8_t f = 0;
+        for (int dy = 0; dy < 2; ++dy)
+            for (int dx = 0; dx < 2; ++dx) {
+                const int y = 2 * Y + dy, x = 2 * X + dx;
+                if (y < Hf && x < Wf) f |= fine[(int64_t)y * Wf + x];
+            }
+        coarse[j] = f & VF_FIX;
+    }
+}
+
+// tiles of a level holding an unknown cell -> list (order of the atomic counter; the passes do not depend on it)
+__global__ __launch_bounds__(256) void vf_tiles_kernel(const uint8_t* __restrict__ flags, int H, int W, int tiles_x, int tiles,
+                                                       int32_t* __restrict__ list, int32_t* __restrict__ count) {
+    __shared__ int any[4];
+    const int w = threadIdx.x >> 6;
+    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const int ty = t / tiles_x, tx = t - ty * tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        int a = 0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int y = y0 + j / VF_TX, x = x0 + (j & (VF_TX - 1));
+            if (y < H && x < W && !(flags[(int64_t)y * W + x] & VF_FIX)) a = 1;
+        }
+        a = __any(a) ? 1 : 0;
+        if ((threadIdx.x & 63) == 0) any[w] = a;
+        __syncthreads();
+        if (threadIdx.x == 0 && (any[0] | any[1] | any[2] | any[3])) list[atomicAdd(count, 1)] = t;
+        __syncthreads();
+    }
+}
+
+// ---- the level passes ---------------------------------------------------------------------------------------------------
+struct VfPass {
+    const float* in;          // level values read with the halo (nullptr: start from 0)
+    float* out;               // the tile's values after the sweeps
+    const float* rhs;         // f of this level (nullptr at level 0)
+    const uint8_t* flags;
+    const int32_t* list;
+    const int32_t* count;
+    int H, W, tiles_x;
+    // down pass: residual restricted to the next level
+    float* f_next;
+    const uint8_t* flags_next;
+    float rscale;             // 4 / children of an interior coarse cell: 1, or 2 on a level one cell high or wide
+    // up pass: correction of the next level, prolongated
+    const float* e_next;
+    int Hn, Wn;
+    uint32_t* change;         // level 0 up pass: max |out_new - out_old| bits over the unknowns
+};
+
+struct VfLds {
+    float u[VF_SY][VF_SXP];
+    float f[VF_SY][VF_SXP];
+    uint8_t fl[VF_SY][VF_SXP];
+    float r[VF_TY][VF_TX];
+    float ec[VF_CY][VF_CX];
+};
+
+// one red-black half-sweep over the LDS cells at distance >= j + 1 from the staged border, colour (gy + gx) & 1 == col
+__device__ __forceinline__ void vf_half_sweep(VfLds& s, int j, int col, int par0) {
+    const int r0 = j + 1, r1 = VF_SY - j - 1, c0 = j + 1, c1 = VF_SX - j - 1;
+    const int nr = r1 - r0, ncp = (c1 - c0 + 1) / 2;            // cells of one colour per row: at most ncp
+    for (int k = threadIdx.x; k < nr * ncp; k += 256) {
+        const int ly = r0 + k / ncp;
+        int lx = c0 + 2 * (k - (k / ncp) * ncp);
+        if (((ly + lx + par0) & 1) != col) ++lx;
+        if (lx >= c1) continue;
+        const uint8_t fl = s.fl[ly][lx];
+        if ((fl & (VF_IN | VF_FIX)) != VF_IN) continue;
+        const float up = s.u[ly][lx];
+        float acc = s.f[ly][lx];
+        int n = 0;
+        if (s.fl[ly - 1][lx] & VF_IN) { acc += s.u[ly - 1][lx] - up; ++n; }
+        if (s.fl[ly + 1][lx] & VF_IN) { acc += s.u[ly + 1][lx] - up; ++n; }
+        if (s.fl[ly][lx - 1] & VF_IN) { acc += s.u[ly][lx - 1] - up; ++n; }
+        if (s.fl[ly][lx + 1] & VF_IN) { acc += s.u[ly][lx + 1] - up; ++n; }
+        if (n) s.u[ly][lx] = up + acc / (float)n;
+    }
+    __syncthreads();
+}
+
+// FINE: level 0, whose right-hand side is 0 (never read)
+template <bool UP, bool FINE>
+__global__ __launch_bounds__(256) void vf_pass_kernel(VfPass P) {
+    __shared__ VfLds s;
+    const int H = P.H, W = P.W;
+    const int ntiles = *P.count;
+    uint32_t mx = 0;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list[t];
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        const int gy0 = y0 - VF_HALO, gx0 = x0 - VF_HALO;
+        const int cy0 = y0 / 2 - 4, cx0 = x0 / 2 - 4;
+        __syncthreads();                                          // the previous tile's readers are done
+        if (UP) {
+            for (int j = threadIdx.x; j < VF_CY * VF_CX; j += 256) {
+                const int r = j / VF_CX, c = j - r * VF_CX;
+                int Y = cy0 + r, X = cx0 + c;
+                Y = Y < 0 ? 0 : (Y >= P.Hn ? P.Hn - 1 : Y);
+                X = X < 0 ? 0 : (X >= P.Wn ? P.Wn - 1 : X);
+                s.ec[r][c] = P.e_next[(int64_t)Y * P.Wn + X];
+            }
+            __syncthreads();
+        }
+        for (int j = threadIdx.x; j < VF_SY * VF_SX; j += 256) {
+            const int r = j / VF_SX, c = j - r * VF_SX;
+            const int y = gy0 + r, x = gx0 + c;
+            float u = 0.f, f = 0.f;
+            uint8_t fl = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const int64_t i = (int64_t)y * W + x;
+                fl = VF_IN | P.flags[i];
+                if (P.in) u = P.in[i];
+                if (!FINE) f = P.rhs[i];
+                if (UP && !(fl & VF_FIX)) {
+                    const int Y = y >> 1, X = x >> 1;
+                    const int ly = Y - cy0, lx = X - cx0;
+                    const int ny = ly + ((y & 1) ? 1 : -1), nx = lx + ((x & 1) ? 1 : -1);
+                    const float e = (9.f * s.ec[ly][lx] + 3.f * s.ec[ny][lx] + 3.f * s.ec[ly][nx] + s.ec[ny][nx]) * 0.0625f;
+                    u += e;
+                }
+            }
+            s.u[r][c] = u;
+            s.f[r][c] = f;
+            s.fl[r][c] = fl;
+        }
+        __syncthreads();
+        const int par0 = (gy0 + gx0) & 1;
+#pragma unroll 1
+        for (int j = 0; j < VF_HS; ++j) vf_half_sweep(s, j, j & 1, par0);
+
+        if (!UP) {
+            // residual at the tile's cells, then its restriction: the 2 x 2 children of a coarse cell lie in one tile
+            for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+                const int r = j / VF_TX, c = j - r * VF_TX;
+                const int ly = r + VF_HALO, lx = c + VF_HALO;
+                const uint8_t fl = s.fl[ly][lx];
+                float acc = 0.f;
+                if ((fl & (VF_IN | VF_FIX)) == VF_IN) {
+                    const float up = s.u[ly][lx];
+                    acc = s.f[ly][lx];
+                    if (s.fl[ly - 1][lx] & VF_IN) acc += s.u[ly - 1][lx] - up;
+                    if (s.fl[ly + 1][lx] & VF_IN) acc += s.u[ly + 1][lx] - up;
+                    if (s.fl[ly][lx - 1] & VF_IN) acc += s.u[ly][lx - 1] - up;
+                    if (s.fl[ly][lx + 1] & VF_IN) acc += s.u[ly][lx + 1] - up;
+                }
+                s.r[r][c] = acc;
+                const int y = y0 + r, x = x0 + c;
+                if (y < H && x < W) P.out[(int64_t)y * W + x] = s.u[ly][lx];
+            }
+            __syncthreads();
+            for (int j = threadIdx.x; j < (VF_TY / 2) * (VF_TX / 2); j += 256) {
+                const int R = j / (VF_TX / 2), Cc = j - R * (VF_TX / 2);
+                const int Y = y0 / 2 + R, X = x0 / 2 + Cc;
+                if (Y >= P.Hn || X >= P.Wn) continue;
+                const int64_t J = (int64_t)Y * P.Wn + X;
+                const float v = (P.flags_next[J] & VF_FIX)
+                                    ? 0.f
+                                    : ((s.r[2 * R][2 * Cc] + s.r[2 * R][2 * Cc + 1]) + (s.r[2 * R + 1][2 * Cc] + s.r[2 * R + 1][2 * Cc + 1])) *
+                                          P.rscale;
+                P.f_next[J] = v;
+            }
+        } else {
+            for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+                const int r = j / VF_TX, c = j - r * VF_TX;
+                const int y = y0 + r, x = x0 + c;
+                if (y >= H || x >= W) continue;
+                const int ly = r + VF_HALO, lx = c + VF_HALO;
+                const int64_t i = (int64_t)y * W + x;
+                const float v = s.u[ly][lx];
+                if (P.change && !(s.fl[ly][lx] & VF_FIX)) {
+                    const uint32_t d = __float_as_uint(fabsf(v - P.out[i]));
+                    mx = d > mx ? d : mx;
+                }
+                P.out[i] = v;
+            }
+        }
+    }
+    if (UP && P.change) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t u = __shfl_xor(mx, o, 64);
+            mx = u > mx ? u : mx;
+        }
+        if ((threadIdx.x & 63) == 0 && mx) atomicMax(P.change, mx);
+    }
+}
+
+// ---- coarsest level: one workgroup, red-black SOR in LDS ----------------------------------------------------------------
+struct VfCoarse {
+    const float* in;          // level 0 only (the grid is the raster): v with the known values; else start from 0
+    float* out;
+    const float* rhs;         // nullptr at level 0
+    const uint8_t* flags;
+    int H, W, sweeps;
+    float omega;
+    uint32_t* change;         // level 0 only
+};
+
+__global__ __launch_bounds__(256) void vf_coarsest_kernel(VfCoarse P) {
+    __shared__ float u[VF_CMAX + 2][VF_CMAX + 2];
+    __shared__ float f[VF_CMAX][VF_CMAX];
+    __shared__ uint8_t fl[VF_CMAX + 2][VF_CMAX + 2];
+    __shared__ uint32_t red[4];
+    const int H = P.H, W = P.W;
+    for (int j = threadIdx.x; j < (VF_CMAX + 2) * (VF_CMAX + 2); j += 256) {
+        const int r = j / (VF_CMAX + 2), c = j - r * (VF_CMAX + 2);
+        const int y = r - 1, x = c - 1;
+        float v = 0.f;
+        uint8_t g = 0;
+        if (y >= 0 && y < H && x >= 0 && x < W) {
+            const int i = y * W + x;
+            g = VF_IN | P.flags[i];
+            if (P.in) v = P.in[i];
+            f[y][x] = P.rhs ? P.rhs[i] : 0.f;
+        }
+        u[r][c] = v;
+        fl[r][c] = g;
+    }
+    __syncthreads();
+    const float om = P.omega;
+    const int half = (W + 1) / 2;
+#pragma unroll 1
+    for (int sw = 0; sw < 2 * P.sweeps; ++sw) {
+        const int col = sw & 1;
+        for (int k = threadIdx.x; k < H * half; k += 256) {
+            const int y = k / half;
+            int x = 2 * (k - y * half);
+            if (((y + x) & 1) != col) ++x;
+            if (x >= W) continue;
+            const int ly = y + 1, lx = x + 1;
+            if ((fl[ly][lx] & (VF_IN | VF_FIX)) != VF_IN) continue;
+            const float up = u[ly][lx];
+            float acc = f[y][x];
+            int n = 0;
+            if (fl[ly - 1][lx] & VF_IN) { acc += u[ly - 1][lx] - up; ++n; }
+            if (fl[ly + 1][lx] & VF_IN) { acc += u[ly + 1][lx] - up; ++n; }
+            if (fl[ly][lx - 1] & VF_IN) { acc += u[ly][lx - 1] - up; ++n; }
+            if (fl[ly][lx + 1] & VF_IN) { acc += u[ly][lx + 1] - up; ++n; }
+            if (n) u[ly][lx] = up + om * (acc / (float)n);
+        }
+        __syncthreads();
+    }
+    uint32_t mx = 0;
+    for (int k = threadIdx.x; k < H * W; k += 256) {
+        const int y = k / W, x = k - y * W;
+        const float v = u[y + 1][x + 1];
+        if (P.change && !(fl[y + 1][x + 1] & VF_FIX)) {
+            const uint32_t d = __float_as_uint(fabsf(v - P.out[k]));
+            mx = d > mx ? d : mx;
+        }
+        P.out[k] = v;
+    }
+    if (P.change) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t t = __shfl_xor(mx, o, 64);
+            mx = t > mx ? t : mx;
+        }
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t m = 0;
+            for (int q = 0; q < 4; ++q) m = red[q] > m ? red[q] : m;
+            if (m) atomicMax(P.change, m);
+        }
+    }
+}
+
+// ---- finish -------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void vf_finish_kernel(const float* __restrict__ dem, const uint8_t* __restrict__ flags,
+                                                        const VfHdr* hdr, const float* __restrict__ u, int64_t n,
+                                                        float* __restrict__ out) {
+    const bool none = hdr->known == 0;
+    const float c = hdr->c;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float v;
+        if (none) v = __int_as_float(0x7fc00000);
+        else if (flags[i] & VF_FIX) v = dem[i];
+        else v = __fadd_rn(u[i], c);
+        out[i] = v;
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+static int vf_size_check(const char* who, int H, int W) {
+    TG_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "%s: raster %dx%d must be non-empty with H*W < 2^31", who,
+               H, W);
+    return TG_OK;
+}
+
+static int vf_ws_check(const char* who, int H, int W, const void* ws, size_t ws_bytes, VfPlan* p) {
+    if (int rc = vf_size_check(who, H, W)) return rc;
+    TG_REQUIRE(ws, "%s: null pointer", who);
+    TG_REQUIRE(((uintptr_t)ws & (VF_ALIGN - 1)) == 0, "%s: workspace must be %d-byte aligned", who, VF_ALIGN);
+    vf_plan(H, W, p);
+    if (ws_bytes < p->bytes) {
+        tg_set_error("%s: workspace %zu bytes < %zu", who, ws_bytes, p->bytes);
+        return TG_ERR_WS;
+    }
+    return TG_OK;
+}
+
+static float vf_omega(int H, int W) {
+    const int n = H > W ? H : W;
+    return (float)(2.0 / (1.0 + sin(M_PI / (2.0 * n + 1.0))));
+}
+static int vf_sweeps(int H, int W) { return 8 * (H > W ? H : W) + 16; }
+
+extern "C" size_t tg_vfill_ws_bytes(int H, int W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    VfPlan p;
+    vf_plan(H, W, &p);
+    return p.bytes;
+}
+
+extern "C" int tg_vfill_levels(int H, int W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    VfPlan p;
+    vf_plan(H, W, &p);
+    return p.L;
+}
+
+extern "C" int tg_vfill_setup(const float* dem, const float* mask, int use_nodata, float nodata, int H, int W, void* ws,
+                              size_t ws_bytes, int64_t* stats, tg_stream_t stream) {
+    VfPlan p;
+    if (int rc = vf_ws_check("tg_vfill_setup", H, W, ws, ws_bytes, &p)) return rc;
+    TG_REQUIRE(dem && stats, "tg_vfill_setup: null pointer");
+    const hipStream_t s = S(stream);
+    char* base = (char*)ws;
+    VfHdr* hdr = (VfHdr*)base;
+    if (hipMemsetAsync(base, 0, p.bytes, s) != hipSuccess) {     // counters, coarse levels and tile counts start at 0
+        tg_set_error("tg_vfill_setup: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    const uint32_t lo_init = 0xffffffffu;
+    if (hipMemsetD32Async((hipDeviceptr_t)&hdr->lo_key, (int)lo_init, 1, s) != hipSuccess) {
+        tg_set_error("tg_vfill_setup: hipMemsetD32Async failed");
+        return TG_ERR_LAUNCH;
+    }
+    const int64_t n = (int64_t)H * W;
+    const VfLevel& l0 = p.lv[0];
+    uint8_t* fl0 = (uint8_t*)(base + l0.flags);
+    hipLaunchKernelGGL(vf_known_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, s, dem, mask, use_nodata, nodata, n, fl0, hdr);
+    TG_CHECK_LAUNCH("vf_known_kernel");
+    hipLaunchKernelGGL(vf_init_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, s, dem, fl0, n, hdr, (float*)(base + l0.u0),
+                       (float*)(base + l0.u1), stats);
+    TG_CHECK_LAUNCH("vf_init_kernel");
+    for (int l = 0; l < p.L; ++l) {
+        const VfLevel& v = p.lv[l];
+        if (l > 0) {
+            const VfLevel& u = p.lv[l - 1];
+            hipLaunchKernelGGL(vf_coarsen_kernel, dim3(ew_grid((int64_t)v.H * v.W, 256)), dim3(256), 0, s,
+                               (const uint8_t*)(base + u.flags), u.H, u.W, (uint8_t*)(base + v.flags), v.H, v.W);
+            TG_CHECK_LAUNCH("vf_coarsen_kernel");
+        }
+        if (l < p.L - 1) {
+            hipLaunchKernelGGL(vf_tiles_kernel, dim3(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID), dim3(256), 0, s,
+                               (const uint8_t*)(base + v.flags), v.H, v.W, v.tiles_x, v.tiles, (int32_t*)(base + v.list),
+                               &hdr->ntiles[l]);
+            TG_CHECK_LAUNCH("vf_tiles_kernel");
+        }
+    }
+    return TG_OK;
+}
+
+extern "C" int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t* change_bits, tg_stream_t stream) {
+    VfPlan p;
+    if (int rc = vf_ws_check("tg_vfill_cycle", H, W, ws, ws_bytes, &p)) return rc;
+    TG_REQUIRE(change_bits, "tg_vfill_cycle: null pointer");
+    const hipStream_t s = S(stream);
+    char* base = (char*)ws;
+    VfHdr* hdr = (VfHdr*)base;
+    if (hipMemsetAsync(change_bits, 0, sizeof(uint32_t), s) != hipSuccess) {
+        tg_set_error("tg_vfill_cycle: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    const int L = p.L;
+    auto F = [&](size_t off) { return (float*)(base + off); };
+    auto U8 = [&](size_t off) { return (const uint8_t*)(base + off); };
+    auto pass = [&](int l) {
+        const VfLevel& v = p.lv[l];
+        VfPass a = {};
+        a.flags = U8(v.flags);
+        a.list = (const int32_t*)(base + v.list);
+        a.count = &hdr->ntiles[l];
+        a.H = v.H; a.W = v.W; a.tiles_x = v.tiles_x;
+        a.rhs = l > 0 ? F(v.f) : nullptr;
+        a.Hn = p.lv[l + 1].H; a.Wn = p.lv[l + 1].W;
+        return a;
+    };
+    // down: level 0 reads u0 and writes u1; coarse levels start from 0 and write u1
+    for (int l = 0; l < L - 1; ++l) {
+        const VfLevel& v = p.lv[l];
+        VfPass a = pass(l);
+        a.in = l == 0 ? F(v.u0) : nullptr;
+        a.out = F(v.u1);
+        a.f_next = F(p.lv[l + 1].f);
+        a.flags_next = U8(p.lv[l + 1].flags);
+        a.rscale = (v.H == 1 || v.W == 1) ? 2.f : 1.f;
+        const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
+        if (l == 0) hipLaunchKernelGGL((vf_pass_kernel<false, true>), g, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((vf_pass_kernel<false, false>), g, dim3(256), 0, s, a);
+        TG_CHECK_LAUNCH("vf_pass_kernel<down>");
+    }
+    {
+        const VfLevel& v = p.lv[L - 1];
+        VfCoarse c;
+        c.in = L == 1 ? F(v.u0) : nullptr;
+        c.out = F(v.u0);
+        c.rhs = L == 1 ? nullptr : F(v.f);
+        c.flags = U8(v.flags);
+        c.H = v.H; c.W = v.W;
+        c.sweeps = vf_sweeps(v.H, v.W);
+        c.omega = vf_omega(v.H, v.W);
+        c.change = L == 1 ? change_bits : nullptr;
+        hipLaunchKernelGGL(vf_coarsest_kernel, dim3(1), dim3(256), 0, s, c);
+        TG_CHECK_LAUNCH("vf_coarsest_kernel");
+    }
+    // up: u1 + prolongated correction of level l + 1 (its u0) -> u0
+    for (int l = L - 2; l >= 0; --l) {
+        const VfLevel& v = p.lv[l];
+        VfPass a = pass(l);
+        a.in = F(v.u1);
+        a.out = F(v.u0);
+        a.e_next = F(p.lv[l + 1].u0);
+        a.change = l == 0 ? change_bits : nullptr;
+        const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
+        if (l == 0) hipLaunchKernelGGL((vf_pass_kernel<true, true>), g, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((vf_pass_kernel<true, false>), g, dim3(256), 0, s, a);
+        TG_CHECK_LAUNCH("vf_pass_kernel<up>");
+    }
+    return TG_OK;
+}
+
+extern "C" int tg_vfill_finish(const float* dem, int H, int W, const void* ws, size_t ws_bytes, float* out,
+                               tg_stream_t stream) {
+    VfPlan p;
+    if (int rc = vf_ws_check("tg_vfill_finish", H, W, ws, ws_bytes, &p)) return rc;
+    TG_REQUIRE(dem && out, "tg_vfill_finish: null pointer");
+    const char* base = (const char*)ws;
+    const int64_t n = (int64_t)H * W;
+    hipLaunchKernelGGL(vf_finish_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, S(stream), dem, (const uint8_t*)(base + p.lv[0].flags),
+                       (const VfHdr*)base, (const float*)(base + p.lv[0].u0), n, out);
+    TG_CHECK_LAUNCH("vf_finish_kernel");
+    return TG_OK;
+}

@@ -22,9 +22,14 @@ result is compared against the truth:
 
 Two calls on the same inputs return bitwise-equal tensors and an equal report.
 
+With baseline="laplace" the same keep mask is also filled by harmonic interpolation (fill_voids) and
+report["baseline"] holds that fill's full terrain_errors report on the same holes, plus "method" and the fill info: the number
+a GAN has to beat.  fallback is passed to inpaint_raster.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
+         [--baseline laplace] [--fallback laplace]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -350,21 +355,50 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
 
 
 # ---- end to end -----------------------------------------------------------------------------------------------------
+BASELINES = ("laplace",)
+
+
+def _check_fill_options(baseline, fallback, who="evaluate_raster"):
+    if baseline is not None and baseline not in BASELINES:
+        raise ValueError(f"{who}: baseline {baseline!r} must be None or one of {BASELINES}")
+    if fallback not in (None, "laplace"):
+        raise ValueError(f"{who}: fallback {fallback!r} must be None or 'laplace'")
+
+
+@torch.no_grad()
+def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
+                    quantiles=QUANTILES, top=10):
+    """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
+    fill info under "fill"."""
+    from .fill_voids import fill_voids
+    device = _device()
+    z = _f32(dem, device, "dem")
+    k = _f32(keep, device, "keep", binary=True)
+    bpred, finfo = fill_voids(z, k, nodata=_nodata(nodata), method=method)
+    rep = terrain_errors(z, bpred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
+                         quantiles=quantiles, top=top)
+    rep["method"] = method
+    rep["fill"] = finfo
+    return rep
+
+
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10):
-    """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W])."""
+                    quantiles=QUANTILES, top=10, baseline=None, fallback=None):
+    """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
+    baseline="laplace" adds report["baseline"]; fallback is passed to inpaint_raster."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
-                             area_edges_m2=area_edges_m2, quantiles=quantiles, top=top)
+                             area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
-              objects, area_edges_m2, quantiles, top):
+              objects, area_edges_m2, quantiles, top, baseline=None, fallback=None):
     """evaluate_raster, plus the hole map."""
     from .inpaint_raster import inpaint_raster
+    _check_fill_options(baseline, fallback)
     c = _cellsize(cellsize, "evaluate_raster")
     H, W = _inputs(dem, mask, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
@@ -375,12 +409,16 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     m = None if mask is None else _f32(mask, device, "mask", binary=True)
     hm, keep, hinfo = eval_holes(z, m, nodata=nodata, split=split, block=block, tile=tile, holes=holes, seed=seed,
                                  objects=objects, cellsize=c)
-    pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch)
+    pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
+                                 fallback=fallback)
     rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top)
     rep.update(params(c, split, block, tile, seed, holes, window, overlap))
     rep["cells"] = hinfo["cells"]
     rep["inpaint"] = iinfo
+    if baseline is not None:
+        rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
+                                          area_edges_m2=area_edges_m2, quantiles=quantiles, top=top)
     return rep, pred, hm
 
 
@@ -422,11 +460,17 @@ def main(argv=None):
     ap.add_argument("--json", help="write the report here")
     ap.add_argument("--pred-out", help="write the prediction (.asc)")
     ap.add_argument("--holes-out", help="write the evaluation holes (.png or .asc, nonzero = hole)")
+    ap.add_argument("--baseline", choices=BASELINES,
+                    help="also score a harmonic interpolation (fill_voids) of the same holes: a second summary line")
+    ap.add_argument("--fallback", choices=("laplace",),
+                    help="checkpoint mode: fill the holes no window reaches by harmonic interpolation")
     a = ap.parse_args(argv)
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
         ap.error("--pred and --holes go together")
+    if a.fallback and a.pred:
+        ap.error("--fallback needs --checkpoint")
     dem, header = read_asc(a.dem)
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
@@ -436,7 +480,8 @@ def main(argv=None):
     if a.checkpoint:
         rep, pred, hm = _evaluate(a.checkpoint, dem, mask, nodata=nodata, cellsize=c, split=split, block=a.block, tile=a.tile,
                                   holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
-                                  objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10)
+                                  objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
+                                  baseline=a.baseline, fallback=a.fallback)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -447,6 +492,8 @@ def main(argv=None):
         hm, keep, _ = holes_from_map(dem, _read_mask(a.holes, dem.shape), mask, nodata=nodata, objects=objects, cellsize=c)
         rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata)
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
+        if a.baseline:
+            rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -459,6 +506,8 @@ def main(argv=None):
     if a.holes_out and hm is not None:
         write_mask(a.holes_out, hm.cpu().numpy(), header)
     print(summary(rep))
+    if "baseline" in rep:
+        print(f"baseline {rep['baseline']['method']}: {summary(rep['baseline'])}")
     return rep
 
 

@@ -1,0 +1,203 @@
+"""Fill the voids of a DSM by harmonic (Laplace) interpolation on the GPU (csrc/voidfill.hip).
+
+The plain interpolation every DEM void-fill tool offers (MATLAB's regionfill solves the same equation): a baseline to score the
+GAN against, and a fill for the voids no inpainting window reaches.
+
+  - known K: mask != 0 (if given), finite, and != nodata (if given; a NaN nodata is ignored), the rule of inpaint_raster; with
+    `objects` (an object_mask.ObjectSpec, which needs `cellsize`) the object_mask keep mask replaces `mask`;
+  - every other pixel p is unknown and satisfies sum_{q in N4(p)} (u_q - u_p) = 0 over its 4-neighbours inside the raster
+    (a natural, Neumann, border), with u = z on K; when K is not empty the solution is unique;
+  - known pixels come back bit for bit; when K is empty every pixel is NaN and info["unfilled"] = H * W;
+  - V-cycles run until the largest change of one cycle over the unknowns is at most `tol` (default 1e-6 x the range of z
+    over K), at most `max_cycles`; running out is not an error: info["converged"] is then False.
+
+Two calls on the same inputs return bitwise-equal rasters and equal info.
+
+CLI: python -m mvp_gan.src.fill_voids --dem in.asc [--mask m.png|m.asc] [--nodata v] [--remove-objects [spec flags]]
+         [--tol t] [--max-cycles n] --out out.asc
+"""
+import argparse
+import math
+
+import numpy as np
+import torch
+
+METHODS = ("laplace",)
+CMAX = 16                      # coarsest level: longer side at most this
+TILE_Y, TILE_X = 32, 64        # tiles of the level passes
+ALIGN = 256
+MAX_LEVELS = 32
+
+
+# ---- host-side mirror of the level plan and workspace layout (tg_vfill_ws_bytes, tg_vfill_levels) ---------------------
+def vfill_levels(H, W):
+    """[(H_l, W_l)]: halve with ceil until the longer side is at most CMAX."""
+    H, W = int(H), int(W)
+    out = [(H, W)]
+    while max(out[-1]) > CMAX:
+        h, w = out[-1]
+        out.append(((h + 1) // 2, (w + 1) // 2))
+    return out
+
+
+def _al(n):
+    return -(-n // ALIGN) * ALIGN
+
+
+def vfill_layout(H, W):
+    """-> (levels [dict: H, W, tiles, flags, list, u0, u1, f byte offsets], total bytes) of the workspace."""
+    off = ALIGN                                         # header: tile counters, statistics, offset
+    out = []
+    for l, (h, w) in enumerate(vfill_levels(H, W)):
+        n = h * w
+        tiles = -(-h // TILE_Y) * -(-w // TILE_X)
+        lv = {"H": h, "W": w, "tiles": tiles}
+        lv["flags"] = off
+        off += _al(n)
+        lv["list"] = off
+        off += _al(4 * tiles)
+        lv["u0"] = off
+        off += _al(4 * n)
+        lv["u1"] = off
+        off += _al(4 * n)
+        lv["f"] = None
+        if l:
+            lv["f"] = off
+            off += _al(4 * n)
+        out.append(lv)
+    return out, off
+
+
+# ---- validation -----------------------------------------------------------------------------------------------------
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
+
+
+def check_args(dem, mask, method, tol, max_cycles, objects, cellsize, who="fill_voids"):
+    """Host-side rejection before any launch; -> (H, W, cellsize or None)."""
+    shape = _shape(dem)
+    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
+        raise ValueError(f"{who}: dem must be [H, W] with H*W < 2^31, got {shape}")
+    if mask is not None and _shape(mask) != shape:
+        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
+    if method not in METHODS:
+        raise ValueError(f"{who}: method {method!r} must be one of {METHODS}")
+    if tol is not None:
+        try:
+            t = float(tol)
+        except (TypeError, ValueError):
+            t = math.nan
+        if not math.isfinite(t) or t < 0:
+            raise ValueError(f"{who}: tol {tol!r} must be finite and >= 0")
+    if isinstance(max_cycles, bool) or not isinstance(max_cycles, (int, np.integer)) or max_cycles < 1:
+        raise ValueError(f"{who}: max_cycles {max_cycles!r} must be an integer >= 1")
+    c = None
+    if objects is not None:
+        from .object_mask import _check_cellsize
+        try:
+            c = _check_cellsize(cellsize)
+        except ValueError:
+            raise ValueError(f"{who}: objects need a cellsize, finite and > 0, got {cellsize!r}") from None
+        objects.check()
+    return shape[0], shape[1], c
+
+
+def _device_f32(a, device, what, binary=False):
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError(f"fill_voids: {what} is on {a.device}; pass a numpy array or a HIP tensor")
+        if binary and a.dtype != torch.float32:
+            a = a != 0
+        return a.to(device=device, dtype=torch.float32).contiguous()
+    a = np.asarray(a)
+    if binary:
+        a = a != 0
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+
+
+def _bits_f32(b):
+    return float(np.array([int(b) & 0xffffffff], np.uint32).view(np.float32)[0])
+
+
+# ---- the fill -------------------------------------------------------------------------------------------------------
+@torch.no_grad()
+def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_cycles=50, objects=None, cellsize=None):
+    """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, nonzero = known (optional).
+    Returns (raster float32 HIP tensor [H][W], info dict: unknown, unfilled, cycles, change, tol, converged, levels, and with
+    objects the object_mask info under "objects")."""
+    from tg_hip import ops as O
+    H, W, c = check_args(dem, mask, method, tol, max_cycles, objects, cellsize)
+    if not torch.cuda.is_available():
+        raise RuntimeError("fill_voids: no HIP device visible; this build has no CPU path")
+    device = torch.device("cuda", torch.cuda.current_device())
+    z = _device_f32(dem, device, "dem")
+    m = None if mask is None else _device_f32(mask, device, "mask", binary=True)
+    if nodata is not None and math.isnan(nodata):
+        nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
+    oinfo = None
+    if objects is not None:
+        from .object_mask import object_mask
+        _, m, oinfo = object_mask(z, m, nodata=nodata, cellsize=c, spec=objects)
+    ws = O.vfill_ws(H, W, device)
+    st = O.vfill_setup(z, m, nodata, ws).cpu().tolist()        # the one sync before the cycles
+    known, unknown = int(st[0]), int(st[1])
+    rng = _bits_f32(st[3]) - _bits_f32(st[2]) if known else 0.0
+    t = 1e-6 * rng if tol is None else float(tol)
+    cycles, change, converged = 0, 0.0, known > 0
+    if known and unknown:
+        converged = False
+        ch = torch.empty(1, dtype=torch.int32, device=device)
+        while cycles < max_cycles:
+            O.vfill_cycle(H, W, ws, ch)
+            cycles += 1
+            change = _bits_f32(ch.item())                       # one read per cycle
+            if change <= t:
+                converged = True
+                break
+    out = O.vfill_finish(z, ws)
+    info = {"unknown": unknown, "unfilled": 0 if known else H * W, "cycles": cycles, "change": change, "tol": t,
+            "converged": converged, "levels": len(vfill_levels(H, W))}
+    if oinfo is not None:
+        info["objects"] = oinfo
+    return out, info
+
+
+# ---- CLI ------------------------------------------------------------------------------------------------------------
+def build_parser():
+    from .object_mask import add_spec_args
+    ap = argparse.ArgumentParser(description="Fill the voids of an ESRI ASCII grid DSM by harmonic (Laplace) interpolation.")
+    ap.add_argument("--dem", required=True, help="input .asc raster (NODATA_value cells are voids)")
+    ap.add_argument("--mask", help="optional mask (.png or .asc) of the raster's size: nonzero = known, 0 = void")
+    ap.add_argument("--nodata", type=float, help="nodata value (default: the .asc header's NODATA_value)")
+    ap.add_argument("--remove-objects", action="store_true",
+                    help="find above-ground objects (cellsize from the header) and fill them too: bare earth")
+    add_spec_args(ap)
+    ap.add_argument("--tol", type=float, help="stop when a cycle changes no void pixel by more (default 1e-6 x range)")
+    ap.add_argument("--max-cycles", type=int, default=50)
+    ap.add_argument("--out", required=True, help="output .asc raster")
+    return ap
+
+
+def main(argv=None):
+    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .object_mask import spec_from_args
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    dem, header = read_asc(a.dem)
+    mask = _read_mask(a.mask, dem.shape) if a.mask else None
+    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
+    objects = spec_from_args(a) if a.remove_objects else None
+    out, info = fill_voids(dem, mask, nodata=nodata, tol=a.tol, max_cycles=a.max_cycles, objects=objects,
+                           cellsize=float(asc_value(header, "cellsize")))
+    if info["unfilled"] and asc_value(header, "NODATA_value") is None:
+        header = header + [("NODATA_value", "-9999")]
+    write_asc(a.out, out.cpu().numpy(), header)
+    print(f"{a.out}: {info['unknown']} void pixels, {info['cycles']} cycles, converged {info['converged']}")
+    if not info["converged"]:
+        print(f"warning: not converged: last change {info['change']:.3g} > tol {info['tol']:.3g} after {info['cycles']} "
+              "cycles" if info["unknown"] and info["unfilled"] == 0 else "warning: nothing is known: every pixel is NaN")
+    return info
+
+
+if __name__ == "__main__":
+    main()

@@ -17,8 +17,12 @@ Semantics:
 With `objects` (an object_mask.ObjectSpec) the above-ground objects are found on the GPU first (mvp_gan/src/object_mask.py)
 and the keep mask, known and not an object, replaces `mask`: the result is bare earth.
 
+With fallback="laplace" the holes no running window covers are filled by fill_voids (mvp_gan/src/fill_voids.py) on the
+blended raster, every finite pixel fixed: known and GAN-filled pixels come back bit for bit, and info["fallback"] reports the
+interpolated pixels, the cycles and whether they converged.  info["unfilled"] counts the holes still NaN at the end.
+
 CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --checkpoint ck.pth --out out.asc
-         [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]]
+         [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]] [--fallback laplace]
 """
 import argparse
 import math
@@ -28,6 +32,7 @@ import numpy as np
 import torch
 
 MIN_SIDE = 40          # smallest window side the generator is tested at (fixture g72x40b3)
+FALLBACK_MAX_CYCLES = 200
 
 Plan = namedtuple("Plan", "H W wh ww overlap ys xs")
 
@@ -149,17 +154,20 @@ def _to_device_f32(a, device, what, binary=False):
 
 @torch.no_grad()
 def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16, objects=None,
-                   cellsize=None):
+                   cellsize=None, fallback=None):
     """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
     objects: an ObjectSpec to remove the above-ground objects first (cellsize, metres per pixel, is then required).
-    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, and with objects the object_mask info
-    under "objects")."""
+    fallback: None or "laplace": fill the holes no running window covers with fill_voids.
+    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, with objects the object_mask info under
+    "objects", with a fallback its pixels, cycles and converged flag under "fallback")."""
     from tg_hip import engine as E
     from tg_hip import ops as O
     if not torch.cuda.is_available():
         raise RuntimeError("inpaint_raster: no HIP device visible; this build has no CPU path")
     if batch < 1:
         raise ValueError(f"inpaint_raster: batch {batch} < 1")
+    if fallback not in (None, "laplace"):
+        raise ValueError(f"inpaint_raster: fallback {fallback!r} must be None or 'laplace'")
     device = torch.device("cuda", torch.cuda.current_device())
     z = _to_device_f32(dem, device, "dem")
     if z.dim() != 2:
@@ -199,6 +207,15 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
     info = {"windows": nwin, "run": int(run.size), "unfilled": int(unfilled.item())}
     if oinfo is not None:
         info["objects"] = oinfo
+    if fallback is not None:
+        info["fallback"] = {"pixels": info["unfilled"], "cycles": 0, "converged": True}
+        if info["unfilled"]:
+            from .fill_voids import fill_voids
+            # every finite pixel fixed: only the NaN holes change.  They are the voids wider than a window, where a V-cycle
+            # contracts the change by about 0.77, hence a larger budget than fill_voids' default
+            out, finfo = fill_voids(out, method=fallback, max_cycles=FALLBACK_MAX_CYCLES)
+            info["fallback"] = {"pixels": finfo["unknown"], "cycles": finfo["cycles"], "converged": finfo["converged"]}
+            info["unfilled"] = finfo["unfilled"]
     return out, info
 
 
@@ -226,6 +243,8 @@ def main(argv=None):
     ap.add_argument("--remove-objects", action="store_true",
                     help="find above-ground objects in the DSM (cellsize from the header) and inpaint them to bare earth")
     ap.add_argument("--objects-out", help="with --remove-objects: write the object map (.png or .asc, nonzero = object)")
+    ap.add_argument("--fallback", choices=("laplace",),
+                    help="fill the holes no window reaches by harmonic interpolation (fill_voids) instead of leaving NaN")
     from .object_mask import add_spec_args, object_mask, spec_from_args, write_mask
     add_spec_args(ap)
     a = ap.parse_args(argv)
@@ -240,11 +259,17 @@ def main(argv=None):
         if a.objects_out:
             write_mask(a.objects_out, objects.cpu().numpy(), header)
         print(f"{oinfo['objects']} objects, {oinfo['object_pixels']} px removed")
-    out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch)
+    out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch,
+                               fallback=a.fallback)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)
     print(f"{a.out}: {info['windows']} windows, {info['run']} run, {info['unfilled']} holes left unfilled")
+    if "fallback" in info:
+        fb = info["fallback"]
+        print(f"fallback {a.fallback}: {fb['pixels']} px, {fb['cycles']} cycles, converged {fb['converged']}")
+        if not fb["converged"]:
+            print("warning: the fallback fill did not converge")
     return info
 
 

@@ -149,6 +149,11 @@ SIGNATURES = {
     "tg_terrain_errors_finish": (I, [I, I, P, SZ, P, P]),
     "tg_select_f32_ws_bytes": (SZ, [I64, I]),
     "tg_select_f32": (I, [P, I64, P, I, P, P, SZ, P]),
+    "tg_vfill_ws_bytes": (SZ, [I, I]),
+    "tg_vfill_levels": (I, [I, I]),
+    "tg_vfill_setup": (I, [P, P, I, F, I, I, P, SZ, P, P]),
+    "tg_vfill_cycle": (I, [I, I, P, SZ, P, P]),
+    "tg_vfill_finish": (I, [P, I, I, P, SZ, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

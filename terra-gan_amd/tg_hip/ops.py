@@ -1135,6 +1135,48 @@ def select_f32(v, ks):
     return out
 
 
+VFILL_NSTATS = 4                                  # tg_vfill_setup stats: known, unknown, min bits, max bits
+
+
+def vfill_ws(H, W, device):
+    """A workspace for one fill of an H x W raster (tg_vfill_ws_bytes; 256-byte aligned by the caching allocator)."""
+    nb = _lib().tg_vfill_ws_bytes(int(H), int(W))
+    if nb == 0:
+        raise L.TgError(f"vfill: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def vfill_setup(dem, mask, nodata, ws):
+    """-> stats int64 [VFILL_NSTATS] (tg_vfill_setup): known map, statistics, initial guess, level flags and tile lists."""
+    H, W = _raster_hw(dem, "dem")
+    _hip(dem, torch.float32, (H, W), "dem")
+    if mask is not None:
+        _hip(mask, torch.float32, (H, W), "mask")
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    stats = torch.empty(VFILL_NSTATS, dtype=torch.int64, device=dem.device)
+    L.check(_lib().tg_vfill_setup(_p(dem), _p(mask), int(nodata is not None), 0.0 if nodata is None else float(nodata), H, W,
+                                  _p(ws), ws.numel(), _p(stats), _stream()), "tg_vfill_setup")
+    return stats
+
+
+def vfill_cycle(H, W, ws, change):
+    """One V-cycle (tg_vfill_cycle); change int32 [1] gets the float bits of the largest change over the unknowns."""
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    _hip(change, torch.int32, (1,), "change")
+    L.check(_lib().tg_vfill_cycle(int(H), int(W), _p(ws), ws.numel(), _p(change), _stream()), "tg_vfill_cycle")
+
+
+def vfill_finish(dem, ws, out=None):
+    """-> out float32 [H][W]: dem at the known pixels, the solution at the unknowns (tg_vfill_finish)."""
+    H, W = _raster_hw(dem, "dem")
+    _hip(dem, torch.float32, (H, W), "dem")
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    out = torch.empty(H, W, dtype=torch.float32, device=dem.device) if out is None else out
+    _hip(out, torch.float32, (H, W), "out")
+    L.check(_lib().tg_vfill_finish(_p(dem), H, W, _p(ws), ws.numel(), _p(out), _stream()), "tg_vfill_finish")
+    return out
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()
