@@ -135,16 +135,40 @@ int tg_maxpool2_bwd_code(const float* dout, const unsigned char* code, int B, in
  * tg_conv_fwd_pool (pool_y only) or tg_conv_fwd_pool_code (both; y unused) of the batch [pred; target]: with sp != NULL the
  * launcher computes only the prediction tiles `sp` marks and copies the target's results into the others -- wherever its
  * planner can honour the map (the fp32 F(2x2,3x3) pipelined kernel in one K split, static walk); any other route runs dense.
- * The results are the same bit for bit either way. */
+ * The results are the same bit for bit either way.
+ *
+ * The same maps serve the trunk's BACKWARD where the gradient at the trunk's input is read only at "needed" pixels.  With
+ * mask != NULL ([nb][H][W]) tg_vgg_sparse_map marks a pixel where the patterns differ OR mask != 1 (the forward then computes those
+ * tiles as well: still exact) and every map carries `pix`, those pixel bits ([nb][H][cdiv(W, 64)] 64-bit words, bit x % 64 of word
+ * x / 64).  Only gradient positions whose feature depends on a needed pixel can reach one, so maps[i] -- the map of conv i's
+ * OUTPUT -- is a superset of what is needed of conv i's input gradient, on the same tile grid:
+ *   tg_conv_dgrad_sparse      tg_conv_dgrad_p (gate_bits == NULL) or tg_conv_dgrad_gbits (x_act == NULL) of a batch of sp->nb
+ *                             images that writes only the tiles `sp` lists, wherever its planner can (the fp32 F(2x2,3x3)
+ *                             pipelined kernel in one K split, static walk); any other route writes every tile.  Listed tiles
+ *                             hold the dense call's values bit for bit provided dy is valid inside the map of the layer above;
+ *                             other tiles may be left UNWRITTEN.  The caller must not ask for F(4x4,3x3) with a partly written
+ *                             dy: there every output mixes the whole input patch.  Cin == 1 (the trunk's first conv; needs
+ *                             sp->pix): EVERY pixel of dx is written -- the dense value where its pix bit is set, exactly 0.0f
+ *                             elsewhere -- so nothing unwritten or non-finite upstream reaches a consumer of dx.
+ *   tg_maxpool2_bwd_code_sparse  tg_maxpool2_bwd_code writing only the full-resolution tiles `sp` lists (the map of the pooled
+ *                             conv); it reads dout only under those tiles. */
 typedef struct TgSparseMap {
     const uint32_t* bits;
     const int32_t* list;
     const int32_t* count;
+    const uint64_t* pix;        /* needed-pixel bits of the trunk's input (NULL: built without a mask) */
     int32_t nb, tiles_y, tiles_x, _pad;
 } TgSparseMap;
 size_t tg_vgg_sparse_map_bytes(int nb, int H, int W, const char* plan);
-int tg_vgg_sparse_map(const float* x, int nb, int H, int W, const char* plan, void* buf, size_t buf_bytes, int* ticket,
-                      TgSparseMap* maps, tg_stream_t stream);
+int tg_vgg_sparse_map(const float* x, const float* mask, int nb, int H, int W, const char* plan, void* buf, size_t buf_bytes,
+                      int* ticket, TgSparseMap* maps, tg_stream_t stream);
+int tg_conv_dgrad_sparse(const TgConv* g, const float* dy, const float* w, const float* wprep, const float* x_act, int act,
+                         float slope, const uint32_t* gate_bits, float* dx, const TgSparseMap* sp, float* ws, size_t ws_bytes,
+                         tg_stream_t stream);
+/* 1: tg_conv_dgrad_sparse writes only the listed tiles for this geometry and gate (0 none, 1 x_act, 2 gate_bits); 0: every tile. */
+int tg_conv_dgrad_sparse_planned(const TgConv* g, int gate, const TgSparseMap* sp);
+int tg_maxpool2_bwd_code_sparse(const float* dout, const unsigned char* code, int B, int Ho, int Wo, int C, float* dx,
+                                const TgSparseMap* sp, tg_stream_t stream);
 int tg_conv_fwd_sparse(const TgConv* g, const float* x, const float* w, const float* wprep, const float* bias, int act,
                        float slope, float* y, float* pool_y, unsigned char* code, const TgSparseMap* sp, float* ws,
                        size_t ws_bytes, tg_stream_t stream);

@@ -1133,17 +1133,19 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
         return wino_launch(kerns[ki], opts[ki], pl.pipe ? W16_PIPE_LDS_BYTES : W16_LDS_BYTES, "wino16_kernel", p, pl.q, pf, true, s);
     }
     typedef void (*WinoKern)(const IGemmParams, const WinoGeom, const float*);
-    static const WinoKern kerns[18] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
+    static const WinoKern kerns[21] = {wino_kernel<false, false, false>, wino_kernel<false, true, false>, wino_kernel<true, false, false>,
                                        wino_kernel<true, true, false>, wino_pipe_kernel<false, false>, wino_pipe_kernel<true, false>,
                                        wino_pipe_kernel<false, false, true>, wino_pipe_kernel<true, false, false, true>,
                                        wino_kernel<false, false, true>, wino_kernel<false, true, true>, wino_kernel<true, false, true>,
                                        wino_kernel<true, true, true>, wino_pipe_kernel<false, true>, wino_pipe_kernel<true, true>,
                                        wino_pipe_kernel<false, true, true>, wino_pipe_kernel<true, true, false, true>,
-                                       wino_pipe_kernel<false, false, false, false, true>, wino_pipe_kernel<false, false, true, false, true>};
-    static LdsOptIn opts[18];
+                                       wino_pipe_kernel<false, false, false, false, 1>, wino_pipe_kernel<false, false, true, false, 1>,
+                                       wino_pipe_kernel<false, false, false, false, 2>, wino_pipe_kernel<true, false, false, false, 2>,
+                                       wino_pipe_kernel<true, false, false, true, 2>};
+    static LdsOptIn opts[21];
     WinoGeom q = pl.q;
     q.qctr = wino_queue_block(s, p.splits, q.total_work);
-    if (pl.sparse && !q.qctr) {
+    if ((pl.sparse || pl.sparse_list) && !q.qctr) {
         const TgSparseMap* sm = p.sparse;
         q.sp_bits = sm->bits; q.sp_list = sm->list; q.sp_count = sm->count;
         q.sp_nb = sm->nb; q.sp_tiles = sm->nb * q.tiles_y * q.tiles_x;
@@ -1177,6 +1179,7 @@ static int launch_igemm(IGemmParams& p, hipStream_t s, size_t ws_floats_avail = 
         p.Ktot = p.TH * p.TW * p.C;
         const double by = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.M * p.N + (double)p.N * p.Ktot);
         ProfScope ps(s, 2, 2.0 * p.M * (double)p.N * p.Ktot, by, p.M, p.N, p.Ktot, p.C, 1, 2000);
+        p.sparse_pix_done = smallconv_to1_map_ok(p) ? 1 : 0;
         return smallconv_fwd_launch(p, s);
     }
     {
@@ -1738,7 +1741,8 @@ extern "C" size_t tg_conv_dgrad_ws_bytes(const TgConv* g) {
 // them; every other route runs ungated and the caller applies the bits.  It steers the route like `gate` (no space-to-depth path).
 static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, float* wprep, int prep, const float* in_mask, float* dx,
                            int accumulate, const float* gate, int gate_act, float gate_slope, float* ws, size_t ws_bytes,
-                           tg_stream_t stream, const uint32_t* gate_bits = nullptr, int* gate_bits_done = nullptr);
+                           tg_stream_t stream, const uint32_t* gate_bits = nullptr, int* gate_bits_done = nullptr,
+                           const TgSparseMap* sparse = nullptr, int* sparse_pix_done = nullptr);
 extern "C" int tg_conv_dgrad(const TgConv* g, const float* dy, const float* w, const float* in_mask, float* dx,
                              int accumulate, float* ws, size_t ws_bytes, tg_stream_t stream) {
     return conv_dgrad_impl(g, dy, w, nullptr, 0, in_mask, dx, accumulate, nullptr, 0, 0.f, ws, ws_bytes, stream);
@@ -1777,6 +1781,50 @@ extern "C" int tg_conv_dgrad_gbits(const TgConv* g, const float* dy, const float
     if (rc || done) return rc;
     return gate_bits_apply_launch(dx, gate_bits, (int64_t)g->B * g->H * g->W, g->Cin, (hipStream_t)stream);
 }
+// tg_conv_dgrad_p / tg_conv_dgrad_gbits of a batch of sp->nb images with the tile map of the conv's output (terragan_hip.h): the
+// launcher decides whether it can honour it (launch_wino: the list-only walk; smallconv: the 64 -> 1 map form); every other route
+// is the dense call.  Cin == 1: whatever the route, every pixel outside sp->pix leaves as 0.0f.
+extern "C" int tg_conv_dgrad_sparse(const TgConv* g, const float* dy, const float* w, const float* wprep, const float* x_act, int act,
+                                    float slope, const uint32_t* gate_bits, float* dx, const TgSparseMap* sp, float* ws, size_t ws_bytes,
+                                    tg_stream_t stream) {
+    int rc = check_conv(g, "tg_conv_dgrad_sparse");
+    if (rc) return rc;
+    TG_REQUIRE(dy && w && dx && ws && sp, "tg_conv_dgrad_sparse: null pointer");
+    TG_REQUIRE(sp->nb == g->B, "tg_conv_dgrad_sparse: the map describes %d images, the batch has %d", sp->nb, g->B);
+    TG_REQUIRE(!(x_act && gate_bits), "tg_conv_dgrad_sparse: x_act and gate_bits are exclusive");
+    TG_REQUIRE(x_act == nullptr || act == TG_ACT_RELU || act == TG_ACT_LEAKY, "tg_conv_dgrad_sparse: a gated dgrad needs a ReLU/LeakyReLU");
+    TG_REQUIRE(g->Cin != 1 || sp->pix, "tg_conv_dgrad_sparse: Cin == 1 needs a map built with a mask (sp->pix)");
+    if (gate_bits) {
+        TG_REQUIRE(g->Cin % 32 == 0, "tg_conv_dgrad_sparse: gate_bits need Cin %% 32 == 0, got %d", g->Cin);
+        TG_REQUIRE((reinterpret_cast<uintptr_t>(gate_bits) & 15) == 0, "tg_conv_dgrad_sparse: pointers must be 16-byte aligned");
+    }
+    const bool usable = wprep != nullptr && !s2d_ok(g);
+    int bits_done = 0, pix_done = 0;
+    rc = conv_dgrad_impl(g, dy, w, usable ? const_cast<float*>(wprep) : nullptr, usable ? 1 : 0, nullptr, dx, 0, x_act,
+                         x_act ? act : TG_ACT_NONE, slope, ws, ws_bytes, stream, gate_bits, &bits_done, sp, &pix_done);
+    if (rc) return rc;
+    // (a dense launch wrote every tile: applying the bits to all of dx touches no unwritten memory that matters -- a product with
+    // 0 or 1 of values nobody reads)
+    if (gate_bits && !bits_done) rc = gate_bits_apply_launch(dx, gate_bits, (int64_t)g->B * g->H * g->W, g->Cin, (hipStream_t)stream);
+    if (rc) return rc;
+    if (g->Cin == 1 && !pix_done) return pix_zero_launch(dx, sp->pix, g->B, g->H, g->W, (hipStream_t)stream);
+    return TG_OK;
+}
+// Will tg_conv_dgrad_sparse write ONLY the listed tiles for this geometry (1), or every tile (0)?  The plan of the launch it
+// would make, with the split-K room the workspace query promises and the static walk (no work-stealing queue); gate: 0 none,
+// 1 fp32 gate, 2 bit gate.  Host only.  (Cin == 1 is not a tile-list launch: 0.)
+extern "C" int tg_conv_dgrad_sparse_planned(const TgConv* g, int gate, const TgSparseMap* sp) {
+    if (!g || !sp || gate < 0 || gate > 2 || check_conv(g, "tg_conv_dgrad_sparse_planned") || !wino_dgrad_geom_ok(g)) return 0;
+    static const float some_gate = 0.f;
+    static const uint32_t some_bits = 0;
+    IGemmParams p = conv_dgrad_s1_params(g);
+    p.act = TG_ACT_NONE;
+    p.gate = gate == 1 ? &some_gate : nullptr; p.gate_act = TG_ACT_RELU;
+    p.gate_bits = gate == 2 ? &some_bits : nullptr;
+    p.sparse = sp;
+    if (wino44_ok(p)) return 0;
+    return wino_plan(p, splitk_room_floats((size_t)g->B * g->H * g->W * g->Cin)).sparse_list ? 1 : 0;
+}
 extern "C" int tg_conv_wprep(const TgConv* g, int mode, const float* w, float* wprep, tg_stream_t stream) {
     TG_REQUIRE(g && w && wprep, "tg_conv_wprep: null pointer");
     TG_REQUIRE(mode == TG_WPREP_FWD || mode == TG_WPREP_DGRAD, "tg_conv_wprep: bad mode %d", mode);
@@ -1813,7 +1861,8 @@ extern "C" int tg_conv_wprep_run(const void* items_dev, int n, tg_stream_t strea
 }
 static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, float* wprep, int prep, const float* in_mask, float* dx,
                            int accumulate, const float* gate, int gate_act, float gate_slope, float* ws, size_t ws_bytes,
-                           tg_stream_t stream, const uint32_t* gate_bits, int* gate_bits_done) {
+                           tg_stream_t stream, const uint32_t* gate_bits, int* gate_bits_done, const TgSparseMap* sparse,
+                           int* sparse_pix_done) {
     int rc = check_conv(g, "tg_conv_dgrad");
     if (rc) return rc;
     TG_REQUIRE(w && (prep < 0 || (dy && dx && ws)), "tg_conv_dgrad: null pointer");
@@ -1874,6 +1923,7 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
         p.wino_u = wt;
         p.wino_ready = prep;
         p.gate_bits = gate_bits;
+        p.sparse = sparse;
         rc = launch_wino_s1(p, ws, dgrad_wt_floats(g), ws2_avail, room, s, "tg_conv_dgrad");
         if (gate_bits_done) *gate_bits_done = p.gate_bits_done;
         return rc;
@@ -1926,6 +1976,7 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
             p.act = TG_ACT_NONE; p.slope = 0.f; p.accumulate = accumulate;
             p.gate = gate; p.gate_act = gate_act; p.gate_slope = gate_slope;
             p.bf16 = g->precision == TG_PREC_BF16;
+            p.sparse = sparse;
             p.Ktot = p.TH * p.TW * p.C; p.nchunks = cdiv(p.C, 32);
             p.T = (p.C % 4) ? cdiv(p.Ktot, 32) : p.TH * p.TW * p.nchunks;
             if (mergeable) {
@@ -1964,6 +2015,7 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
             rc = launch_igemm(cls[i], s, ws2_floats);
             if (rc) return rc;
         }
+        if (sparse_pix_done && ncls == 1) *sparse_pix_done = cls[0].sparse_pix_done;
     }
     return TG_OK;
 }

@@ -55,7 +55,10 @@ struct IGemmParams {
     const uint32_t* gate_bits;
     int gate_bits_done;
     // tg_conv_fwd_sparse: prediction-half tile map of a [pred; target] batch (host side; launch_wino decides whether it applies)
+    // tg_conv_dgrad_sparse: the map of a batch of sparse->nb images.  The 64 -> 1 channel LDS-patch launch that honours it and
+    // zeroes every pixel outside sparse->pix sets sparse_pix_done; otherwise the caller zeroes them (pix_zero_launch)
     const TgSparseMap* sparse;
+    int sparse_pix_done;
 };
 __device__ __forceinline__ float gate_factor(const IGemmParams& p, size_t idx) {
     const float gv = p.gate[idx];
@@ -86,6 +89,9 @@ struct WgradParams {
 // smallconv.hip: bandwidth-bound special cases that would waste >95% of an MFMA tile
 bool smallconv_fwd_applies(const IGemmParams& p);             // C == 1 -> N%64 == 0, or N == 1 <- C%64 == 0
 int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s);
+bool smallconv_to1_map_ok(const IGemmParams& p);              // smallconv_fwd_launch will honour p.sparse (64 -> 1, LDS patch)
+// dx[b][y][x] = 0 where bit x of pix[b][y] is clear (pointwise.hip)
+int pix_zero_launch(float* dx, const uint64_t* pix, int B, int H, int W, hipStream_t s);
 bool smallconv_to1_multi_applies(const IGemmParams* cls, int ncls);   // 64 -> 1 channel, the four 2x2-tap classes of a 4x4 stride-2 dgrad
 int smallconv_to1_multi_launch(const IGemmParams* cls, int ncls, hipStream_t s);
 bool smallconv_wgrad_applies(const WgradParams& p);

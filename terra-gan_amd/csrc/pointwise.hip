@@ -384,6 +384,7 @@ extern "C" int tg_mask_pyramid(const TgMaskPyramid* pm, int B, tg_stream_t strea
 constexpr int VSM_MAX_OPS = 24, VSM_MAX_CONV = 16, VSM_LDS_WORDS = 4096;       // u64 words of one bit image (64 KB of LDS for two)
 struct VggMapArgs {
     const uint32_t* x;
+    const float* mask;                         // optional [nb][H][W]: a pixel with mask != 1 is marked as well (the backward's consumer)
     int nb, H, W, nops, nconv;
     char ops[VSM_MAX_OPS];
     int tiles_y[VSM_MAX_CONV], tiles_x[VSM_MAX_CONV];
@@ -435,18 +436,24 @@ __global__ __launch_bounds__(1024) void vgg_sparse_map_kernel(const VggMapArgs a
         // this slice's rows of the difference image: (row, word) units over the 16 waves, 8 units' loads in flight per wave
         const uint32_t* xp = a.x + (size_t)b * H * W;
         const uint32_t* tp = a.x + ((size_t)a.nb + b) * H * W;
+        const float* mp = a.mask ? a.mask + (size_t)b * H * W : nullptr;
         const int ubeg = blockIdx.x * a.rows_per_slice * WW, uend = min(H, (blockIdx.x + 1) * a.rows_per_slice) * WW;
         for (int u0 = ubeg + wave; u0 < uend; u0 += 16 * 8) {
             uint32_t pv[8], tv[8];
+            float mv[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int u = u0 + 16 * k, y = u / WW, px = (u - y * WW) * 64 + lane;
                 pv[k] = tv[k] = 0;
-                if (u < uend && px < W) { pv[k] = xp[(size_t)y * W + px]; tv[k] = tp[(size_t)y * W + px]; }
+                mv[k] = 1.f;
+                if (u < uend && px < W) {
+                    pv[k] = xp[(size_t)y * W + px]; tv[k] = tp[(size_t)y * W + px];
+                    if (mp) mv[k] = mp[(size_t)y * W + px];
+                }
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const uint64_t m = __ballot(pv[k] != tv[k]);
+                const uint64_t m = __ballot(pv[k] != tv[k] || mv[k] != 1.f);       // (a NaN mask counts as "not 1")
                 if (lane == 0 && u0 + 16 * k < uend) d0[u0 + 16 * k] = m;
             }
         }
@@ -586,14 +593,15 @@ extern "C" size_t tg_vgg_sparse_map_bytes(int nb, int H, int W, const char* plan
     VsmLayout L;
     return vsm_layout(nb, H, W, plan, L) ? L.bytes : 0;
 }
-extern "C" int tg_vgg_sparse_map(const float* x, int nb, int H, int W, const char* plan, void* buf, size_t buf_bytes, int* ticket,
-                                 TgSparseMap* maps, tg_stream_t stream) {
+extern "C" int tg_vgg_sparse_map(const float* x, const float* mask, int nb, int H, int W, const char* plan, void* buf, size_t buf_bytes,
+                                 int* ticket, TgSparseMap* maps, tg_stream_t stream) {
     VsmLayout L;
     TG_REQUIRE(x && buf && ticket && maps, "tg_vgg_sparse_map: null pointer");
     TG_REQUIRE(vsm_layout(nb, H, W, plan, L), "tg_vgg_sparse_map: geometry not supported (tg_vgg_sparse_map_bytes is 0)");
     TG_REQUIRE(buf_bytes >= L.bytes && (reinterpret_cast<uintptr_t>(buf) & 15) == 0, "tg_vgg_sparse_map: buffer too small or unaligned");
     VggMapArgs a = {};
     a.x = reinterpret_cast<const uint32_t*>(x);
+    a.mask = mask;
     a.nb = nb; a.H = H; a.W = W; a.nops = L.nops; a.nconv = L.nconv; a.ticket = ticket;
     for (int i = 0; i < L.nops; ++i) a.ops[i] = plan[i];
     char* base = static_cast<char*>(buf);
@@ -607,7 +615,7 @@ extern "C" int tg_vgg_sparse_map(const float* x, int nb, int H, int W, const cha
         a.bits[i] = reinterpret_cast<uint32_t*>(base + L.bits[i]);
         a.list[i] = reinterpret_cast<int32_t*>(base + L.list[i]);
         a.flags[i] = reinterpret_cast<unsigned char*>(base + L.flags[i]);
-        maps[i] = TgSparseMap{a.bits[i], a.list[i], a.count[i], nb, L.tiles_y[i], L.tiles_x[i], 0};
+        maps[i] = TgSparseMap{a.bits[i], a.list[i], a.count[i], mask ? a.d0 : nullptr, nb, L.tiles_y[i], L.tiles_x[i], 0};
     }
     const size_t lds = 2 * (size_t)H * ((W + 63) / 64) * sizeof(uint64_t);
     static bool opted[64] = {};
@@ -1861,6 +1869,68 @@ extern "C" int tg_maxpool2_bwd_code(const float* dout, const unsigned char* code
     hipLaunchKernelGGL(maxpool2_bwd_code_kernel, dim3(ew_grid((int64_t)B * Ho * Wo * (C / 4), 256)), dim3(256), 0, S(stream), dout, code, B, Ho,
                        Wo, C, dx);
     TG_CHECK_LAUNCH("maxpool2_bwd_code_kernel");
+    return TG_OK;
+}
+// The same for the full-resolution 16x16 tiles a map lists (tg_maxpool2_bwd_code_sparse; the map of the pooled conv): workgroup i
+// takes list entry i -- 8 x 8 pooled pixels -- and leaves when i >= count (read on the device: no host synchronisation).  Tiles
+// outside the list are not written and dout is not read under them.
+__global__ __launch_bounds__(256) void maxpool2_bwd_code_sparse_kernel(const float* __restrict__ dout, const unsigned char* __restrict__ code,
+                                                                       int Ho, int Wo, int C, float* __restrict__ dx,
+                                                                       const int* __restrict__ list, const int* __restrict__ count,
+                                                                       int tiles_y, int tiles_x) {
+    if ((int)blockIdx.x >= *count) return;
+    int tile = list[blockIdx.x];
+    const int tx = tile % tiles_x;
+    tile /= tiles_x;
+    const int ty = tile % tiles_y, b = tile / tiles_y;
+    const int c4n = C >> 2;
+    const int64_t rowpitch = (int64_t)2 * Wo * C;
+    for (int u = threadIdx.x; u < 64 * c4n; u += 256) {
+        const int c = (u % c4n) * 4, pq = u / c4n;
+        const int oy = 8 * ty + (pq >> 3), ox = 8 * tx + (pq & 7);
+        if (oy >= Ho || ox >= Wo) continue;
+        const int64_t pp = ((int64_t)b * Ho + oy) * Wo + ox;
+        const f32x4 d = *reinterpret_cast<const f32x4*>(dout + pp * C + c);
+        const uint32_t cd = *reinterpret_cast<const uint32_t*>(code + pp * C + c);
+        float* base = dx + (((int64_t)b * 2 * Ho + 2 * oy) * 2 * Wo + 2 * ox) * C + c;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t ce = (cd >> (8 * e)) & 0xffu;
+                o[e] = ((ce & 3u) == (uint32_t)k && (ce & 4u)) ? d[e] : 0.f;
+            }
+            *reinterpret_cast<f32x4*>(base + (k >> 1) * rowpitch + (k & 1) * C) = o;
+        }
+    }
+}
+extern "C" int tg_maxpool2_bwd_code_sparse(const float* dout, const unsigned char* code, int B, int Ho, int Wo, int C, float* dx,
+                                           const TgSparseMap* sp, tg_stream_t stream) {
+    TG_REQUIRE(dout && code && dx && B > 0 && Ho > 0 && Wo > 0 && C > 0 && (C % 4) == 0, "tg_maxpool2_bwd_code_sparse: bad arguments");
+    // a map of another grid or batch cannot be honoured: the dense launch, the same values on the listed tiles.  It then reads
+    // ALL of dout, unwritten regions of a sparse dgrad above included -- intended: the pool is pointwise, so those values reach
+    // only pixels nobody needs, and the trunk's 1-channel dgrad zeroes them (tg_conv_dgrad_sparse)
+    if (!sp || !sp->list || !sp->count || sp->nb != B || sp->tiles_y != cdiv(2 * Ho, 16) || sp->tiles_x != cdiv(2 * Wo, 16))
+        return tg_maxpool2_bwd_code(dout, code, B, Ho, Wo, C, dx, stream);
+    hipLaunchKernelGGL(maxpool2_bwd_code_sparse_kernel, dim3(B * sp->tiles_y * sp->tiles_x), dim3(256), 0, S(stream), dout, code, Ho, Wo, C,
+                       dx, sp->list, sp->count, sp->tiles_y, sp->tiles_x);
+    TG_CHECK_LAUNCH("maxpool2_bwd_code_sparse_kernel");
+    return TG_OK;
+}
+// dx[b][y][x] = 0 where bit x of pix[b][y] is clear: the zero guarantee of tg_conv_dgrad_sparse (Cin == 1) behind a launch that
+// could not apply it itself.  A select, not a multiply: what it replaces may be unwritten memory.
+__global__ __launch_bounds__(256) void pix_zero_kernel(float* __restrict__ dx, const uint64_t* __restrict__ pix, int64_t total, int W, int WW) {
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int x = (int)(idx % W);
+        const int64_t row = idx / W;
+        if (!((pix[row * WW + (x >> 6)] >> (x & 63)) & 1ull)) dx[idx] = 0.f;
+    }
+}
+int pix_zero_launch(float* dx, const uint64_t* pix, int B, int H, int W, hipStream_t s) {
+    const int64_t total = (int64_t)B * H * W;
+    hipLaunchKernelGGL(pix_zero_kernel, dim3(ew_grid(total, 256)), dim3(256), 0, s, dx, pix, total, W, (W + 63) / 64);
+    TG_CHECK_LAUNCH("pix_zero_kernel");
     return TG_OK;
 }
 // ReLU gates in one bit per element (tg_relu_gate_pack).  With C % 32 == 0 the words of a row [C/32] are the rows' slice of a

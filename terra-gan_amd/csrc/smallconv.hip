@@ -337,8 +337,15 @@ __device__ __forceinline__ void bn_in_stage(const BnIn& bn, f32x4 (&v)[NIT], int
 }
 // BNIN: the source is act(BN(src)) (IGemmParams::in_bn, no source mask): its own instantiation, with the in-range flags as a bit
 // mask instead of seven floats -- the sixteen per-channel constants then fit without costing a resident wave.
-template <bool BNIN>
-__global__ __launch_bounds__(256) void to1conv64_lds_kernel(const IGemmParams p, int tiles_x, int tiles_y, int sy_min, int sx_min) {
+// MAP (tg_conv_dgrad_sparse, the trunk's first conv: plain dst grid, no accumulation): `mbits` is the tile map of this launch's
+// output grid (16 x 16 tiles: a 4 x 16 tile of this kernel lies inside one) and `pix` its needed-pixel bits.  The source is valid
+// only inside the mapped tiles' windows -- elsewhere it may be UNWRITTEN memory -- so a workgroup whose tile is not mapped reads
+// nothing, and EVERY pixel of the image is stored: the dense value where its pix bit is set, exactly 0.0f elsewhere (a select,
+// never a product: 0 x NaN is NaN).  A set pix bit implies a mapped tile and a 3x3 window inside the map above, so this launch
+// is where the sparse backward's guarantee is established: no unwritten or non-finite value reaches a consumer of dst.
+template <bool BNIN, bool MAP = false>
+__global__ __launch_bounds__(256) void to1conv64_lds_kernel(const IGemmParams p, int tiles_x, int tiles_y, int sy_min, int sx_min,
+                                                            const uint32_t* __restrict__ mbits, const uint64_t* __restrict__ pix) {
     extern __shared__ __attribute__((aligned(16))) float sm[];      // [T1_PH][T1_PW][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int e = lane >> 4, cq = lane & 15;
@@ -347,6 +354,15 @@ __global__ __launch_bounds__(256) void to1conv64_lds_kernel(const IGemmParams p,
     tile /= tiles_x;
     const int tyi = tile % tiles_y, b = tile / tiles_y;
     const int oy0 = tyi * T1_TH, ox0 = txi * T1_TW;
+    if constexpr (MAP) {
+        const int mtx = (p.OW + 15) >> 4, mty = (p.OH + 15) >> 4;
+        const int mt = (b * mty + (oy0 >> 4)) * mtx + (ox0 >> 4);
+        if (!((mbits[mt >> 5] >> (mt & 31)) & 1u)) {                 // workgroup-uniform
+            const int oy = oy0 + wave, ox = ox0 + lane;
+            if (lane < T1_TW && oy < p.OH && ox < p.OW) p.dst[out_pixel(p, b, oy, ox)] = 0.f;
+            return;
+        }
+    }
     f32x4 w[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
@@ -409,6 +425,11 @@ __global__ __launch_bounds__(256) void to1conv64_lds_kernel(const IGemmParams p,
             r = apply_act(r, p.act, p.slope);
             if (p.gate) r *= gate_factor(p, opix);
             if (p.accumulate) r += p.dst[opix];
+            if constexpr (MAP) {
+                const int WW = (p.OW + 63) >> 6;
+                const bool needed = (pix[((size_t)b * p.OH + oy) * WW + (ox >> 6)] >> (ox & 63)) & 1ull;
+                r = needed ? r : 0.f;
+            }
             p.dst[opix] = r;
         }
     }
@@ -579,6 +600,13 @@ static bool to1_fwd_lds_ok(const IGemmParams& p) {
     static const bool no_lds = getenv("TG_NO_TO1LDS") != nullptr;
     return !no_lds && p.TH == 3 && p.TW == 3 && p.ss == 1 && (p.tstep == 1 || p.tstep == -1) && p.OH >= T1_TH && p.OW >= T1_TW;
 }
+// the map form of to1conv64_lds_kernel: a batch of the map's nb images on the plain dst grid, the map's tile grid = the output's
+bool smallconv_to1_map_ok(const IGemmParams& p) {
+    const TgSparseMap* sm = p.sparse;
+    return sm && sm->bits && sm->pix && smallconv_fwd_applies(p) && p.N == 1 && p.C == 64 && !to1w_ok(p) && to1_fwd_lds_ok(p) &&
+           !p.in_bn.mean && !p.accumulate && p.ds == 1 && p.dy0 == 0 && p.dx0 == 0 && p.DH == p.OH && p.DW == p.OW && sm->nb == p.B &&
+           sm->tiles_y == cdiv(p.OH, 16) && sm->tiles_x == cdiv(p.OW, 16);
+}
 bool smallconv_bnin_fwd_ok(const IGemmParams& p) {
     return smallconv_fwd_applies(p) && p.N == 1 && p.C == 64 && !to1w_ok(p) && to1_fwd_lds_ok(p) && !p.amask;
 }
@@ -680,8 +708,13 @@ int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s) {
         const int sy_b = p.sy0 + 2 * p.tstep, sx_b = p.sx0 + 2 * p.tstep;
         const int sy_min = p.sy0 < sy_b ? p.sy0 : sy_b, sx_min = p.sx0 < sx_b ? p.sx0 : sx_b;
         const size_t lds = (size_t)T1_PH * T1_PW * 64 * sizeof(float);
-        if (p.in_bn.mean) hipLaunchKernelGGL(to1conv64_lds_kernel<true>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min);
-        else hipLaunchKernelGGL(to1conv64_lds_kernel<false>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min);
+        const uint32_t* no_bits = nullptr;
+        const uint64_t* no_pix = nullptr;
+        if (smallconv_to1_map_ok(p))
+            hipLaunchKernelGGL((to1conv64_lds_kernel<false, true>), dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min,
+                               sx_min, p.sparse->bits, p.sparse->pix);
+        else if (p.in_bn.mean) hipLaunchKernelGGL(to1conv64_lds_kernel<true>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min, no_bits, no_pix);
+        else hipLaunchKernelGGL(to1conv64_lds_kernel<false>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min, no_bits, no_pix);
         TG_CHECK_LAUNCH("to1conv64_lds_kernel");
         return TG_OK;
     }

@@ -28,7 +28,8 @@ struct WinoGeom {
     int sy_min, sx_min;
     int interleave;     // work distribution, see wino_distribute
     int* qctr;          // work-stealing counter block of this launch (nullptr: static distribution), see WinoWork
-    // prediction-half tile map of a [pred; target] batch (wino_pipe_kernel<.., SPARSE>, TgSparseMap): sp_tiles = nb x tiles
+    // tile map (wino_pipe_kernel<.., SPARSE>, TgSparseMap): sp_tiles = nb x tiles.  SPARSE = 1: the prediction half of a
+    // [pred; target] batch; SPARSE = 2: a batch of nb images of which only the listed tiles are computed
     const uint32_t* sp_bits;
     const int* sp_list;
     const int* sp_count;
@@ -613,7 +614,14 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_kernel(const IGemmParams p,
 // The items are the target half's, dense, followed by `count` list entries of the prediction half (x q.nt, N tile fastest
 // in both parts); a target item whose tile is NOT in the map repeats its stores -- the same registers -- into image b - nb,
 // whose result is that one bit for bit.  Prediction items write only mapped tiles, mirrors only the others: one writer per tile.
-template <bool GATED, bool STEAL, bool POOL = false, bool GBITS = false, bool SPARSE = false>
+// SPARSE = 2 (static walk, one split; gated or not): the batch is nb images and the items are the `count` list entries alone (x q.nt)
+// -- no dense half, no mirror stores; tiles outside the map are not written at all (the trunk's dgrads, tg_conv_dgrad_sparse).  An
+// output pixel of F(2x2,3x3) is a function of its own 3x3 input window (y0 = m0 + m1 + m2 never sees d3, y1 never d0, and the two
+// xi-halves exchange only the sums the partner's rows take), so a listed tile's pixels do not depend on what the rest of the patch
+// holds beyond their windows: bit for bit the dense launch's values wherever those windows are valid.  These forms compile the
+// split-K, row-scale and accumulate paths out, which is what keeps them at 0 bytes of scratch with the list pointer in scalar
+// registers (254 VGPRs, 86-96 SGPRs on ROCm 7): re-check that with --save-temps whenever the compiler changes.
+template <bool GATED, bool STEAL, bool POOL = false, bool GBITS = false, int SPARSE = 0>
 __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmParams p, const WinoGeom q, const float* __restrict__ U) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Vs = smem;                            // [2][16][64][8]
@@ -625,9 +633,9 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
     __shared__ int wq_slot[2];
     WinoWork<STEAL> wk;
     int total = q.total_work;
-    if constexpr (SPARSE) {
+    if constexpr (SPARSE != 0) {
         const int cnt = __builtin_amdgcn_readfirstlane(*q.sp_count);
-        total = (q.sp_tiles + min(max(cnt, 0), q.sp_tiles)) * q.nt;
+        total = ((SPARSE == 1 ? q.sp_tiles : 0) + min(max(cnt, 0), q.sp_tiles)) * q.nt;
     }
     wk.init(total, q.interleave, q.qctr, wq_slot);
 
@@ -638,7 +646,8 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
         r.nt = it % q.nt;
         int tile = it / q.nt;
         r.mirror = 0;
-        if constexpr (SPARSE) {
+        if constexpr (SPARSE == 2) tile = __builtin_amdgcn_readfirstlane(q.sp_list[tile]);
+        if constexpr (SPARSE == 1) {
             if (tile < q.sp_tiles) {             // target image nb + b: mirrored into b where the map leaves the tile out
                 r.mirror = (__builtin_amdgcn_readfirstlane(q.sp_bits[tile >> 5]) >> (tile & 31)) & 1 ? 0 : 1;
                 tile += q.sp_tiles;
@@ -797,11 +806,11 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
         const int e_pix0 = (ci.b * p.DH + p.dy0) * p.DW + p.dx0 + ci.ox0 * p.ds; // + row * e_pitch + (2 (lane >> 3) + j) * ds
         const int e_nb0 = ci.n0 + 32 * e_nw;
         const uint32_t e_lane_px = 2 * (lane >> 3) * p.ds;
-        const bool e_single = p.splits == 1;
+        const bool e_single = SPARSE == 2 || p.splits == 1;      // (the list-only form: one split, no row scales, no accumulation)
         const float act_neg = p.act == TG_ACT_RELU ? 0.f : (p.act == TG_ACT_LEAKY ? p.slope : 1.f);
         const float gate_neg = p.gate_act == TG_ACT_LEAKY ? p.gate_slope : 0.f;
         const auto drsrc = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, (int)((size_t)p.B * p.DH * p.DW * p.N * 4), 0x00020000);
-        const int e_mdelta = SPARSE ? q.sp_nb * p.DH * p.DW * p.N * 4 : 0;       // bytes from image nb + b to image b
+        const int e_mdelta = SPARSE == 1 ? q.sp_nb * p.DH * p.DW * p.N * 4 : 0;       // bytes from image nb + b to image b
         f32x4 bq = {0.f, 0.f, 0.f, 0.f};
         if (p.bias && e_single) bq = *reinterpret_cast<const f32x4*>(p.bias + e_nb0 + 4 * (lane & 7));
         f32x4 pmx[POOL ? 4 : 1];
@@ -811,7 +820,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
             for (int t4 = 0; t4 < 4; ++t4) pmx[t4] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         float rsq[2][4] = {{1.f, 1.f, 1.f, 1.f}, {1.f, 1.f, 1.f, 1.f}};
-        if (p.rowscale && e_single) {
+        if (SPARSE != 2 && p.rowscale && e_single) {
             const auto rrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.rowscale), 0, (int)((size_t)p.B * p.DH * p.DW * 4), 0x00020000);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -882,7 +891,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
 #pragma unroll
                         for (int e = 0; e < 4; ++e) o[e] *= gq[t4][e] > 0.f ? 1.f : gate_neg;
                     }
-                    if (p.accumulate) o += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(drsrc, e_voff, soff, 0));
+                    if (SPARSE != 2 && p.accumulate) o += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(drsrc, e_voff, soff, 0));
                     if constexpr (POOL) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
@@ -899,7 +908,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
                     // (a store of more than 64 bits followed by a write of its data registers) only for stores WITHOUT a
                     // scalar-register offset, as the ISA manual specifies it.
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), drsrc, e_voff + (uint32_t)soff, 0, 0);
-                    if constexpr (SPARSE) {
+                    if constexpr (SPARSE == 1) {
                         if (ci.mirror)
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), drsrc, e_voff + (uint32_t)(soff - e_mdelta), 0, 0);
                     }
@@ -955,7 +964,7 @@ __global__ __launch_bounds__(WINO_THREADS) void wino_pipe_kernel(const IGemmPara
                     const int pix = (ci.b * PH + prow) * PW + (ci.ox0 >> 1);
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), prsrc, p_voff + (uint32_t)((pix * p.N + e_nb0) * 4), 0, 0);
                     if (p.pool_code) __builtin_amdgcn_raw_buffer_store_b32(code, crsrc, c_voff + (uint32_t)(pix * p.N + e_nb0), 0, 0);
-                    if constexpr (SPARSE) {
+                    if constexpr (SPARSE == 1) {
                         if (ci.mirror) {
                             const int mpix = pix - q.sp_nb * PH * PW;
                             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, m), prsrc, p_voff + (uint32_t)((mpix * p.N + e_nb0) * 4), 0, 0);
@@ -1008,8 +1017,11 @@ struct WinoPlan {
     int splits;
     bool fast, pipe, gated, pool, gbits;
     bool sparse;            // the prediction-half tile map can be honoured, by a launch without a work-stealing queue
-    // index into launch_wino's kernel tables: 0-7 the static walk, 8-15 the same with a work-stealing queue, 16-17 the tile map
+    bool sparse_list;       // ... or the list-only form of a batch of nb images (the trunk's dgrads), likewise
+    // index into launch_wino's kernel tables: 0-7 the static walk, 8-15 the same with a work-stealing queue, 16-17 the tile map,
+    // 18-20 its list-only form (plain, fp32 gate, bit gate)
     int kernel(bool queued) const {
+        if (sparse_list && !queued) return gbits ? 20 : gated ? 19 : 18;
         if (sparse && !queued) return pool ? 17 : 16;
         return (queued ? 8 : 0) + (gbits ? 7 : pool ? 6 : pipe ? 4 + gated : (fast ? 2 : 0) + gated);
     }
@@ -1056,6 +1068,11 @@ static WinoPlan wino_plan(const IGemmParams& p, size_t ws_floats_avail) {
     const TgSparseMap* sm = p.sparse;
     pl.sparse = !p.bf16 && sm && pl.pipe && !pl.gated && !pl.gbits && one && !p.rowscale && plain_dst && (pl.pool || !p.pool_dst) &&
                 sm->nb > 0 && p.B == 2 * sm->nb && sm->tiles_y == q.tiles_y && sm->tiles_x == q.tiles_x && sm->bits && sm->list && sm->count;
+    // the list-only form (tg_conv_dgrad_sparse): a batch of exactly the map's nb images, gated or not, no pool; tiles outside the
+    // list stay unwritten.  Splits > 1, a queue walk, row scales, accumulation and bf16 run dense: the same bits on listed tiles
+    pl.sparse_list = !p.bf16 && sm && pl.pipe && one && !p.rowscale && plain_dst && !p.pool_dst && (p.gate == nullptr || pl.gated) &&
+                     (p.gate_bits == nullptr || pl.gbits) && sm->nb > 0 && p.B == sm->nb && sm->tiles_y == q.tiles_y &&
+                     sm->tiles_x == q.tiles_x && sm->list && sm->count;
     return pl;
 }
 

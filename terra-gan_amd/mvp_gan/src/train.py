@@ -152,7 +152,9 @@ def _train_step(generator, discriminator, criterion, optimizer_G, optimizer_D, r
         # (csrc/wino44.inc): that is sound only while no gradient bucket is in flight here -- every bucket of the previous step
         # was waited for by its hip_adam_step, and this step's first bucket is launched inside generator_backward below.
         raise RuntimeError(f"train_step: {grad_sync._inflight} gradient collectives still in flight at the loss stack")
-    g_loss, _parts, dgen = criterion_forward(criterion, gen, real, mask, want_grad=True, both=both, checkpoint=ckpt)   # train.py:188
+    # (holes_only: dgen's one consumer is generator_backward(want_dx=False) below, which multiplies it by 1 - mask)
+    g_loss, _parts, dgen = criterion_forward(criterion, gen, real, mask, want_grad=True, both=both, checkpoint=ckpt,
+                                             holes_only=True)                # train.py:188
     # D(fake) of this step (train.py:202), D(real) and D(fake.detach()) of the discriminator step (train.py:211-212) see the
     # same discriminator weights, and D(real) depends on nothing the generator step produces: the two distinct passes are
     # stacked along the batch and run as ONE grouped forward (convolutions once over 2B images, BatchNorm statistics per

@@ -129,12 +129,16 @@ class _PixelLossFn(torch.autograd.Function):
 
 
 def criterion_forward(crit, pred, target, mask, want_grad, gscale=None, l1_weight=None, w_l1=1.0, scale=1.0, both=None,
-                      checkpoint=False):
+                      checkpoint=False, holes_only=False):
     """Fused value(+gradient) of InpaintingLoss on [B][H][W] tensors.
     Returns (total 1-elem tensor, parts dict of 1-elem tensors, dpred or None).  `scale` multiplies
     the whole loss (HumanGuidedLoss's base_loss_weight).  checkpoint (activation checkpointing, with want_grad): the VGG trunk
     keeps only bit-packed ReLU gates of the prediction half and its pool codes for the backward (vgg_forward(keep="gates")),
-    not its fp32 activations -- the same values bit for bit."""
+    not its fp32 activations -- the same values bit for bit.
+    holes_only (with want_grad): the caller's only use of dpred is a product with (1 - mask) that it forms itself, as
+    generator_backward(want_dx=False) does in sigmoid_composite_bwd.  The perceptual part of dpred is then exact where
+    pred != target or mask != 1 and exactly 0.0 elsewhere (vgg_backward(sparse=True)); every other part is unchanged.  Never set it
+    for a gradient handed to autograd: its consumers are arbitrary."""
     w_p, w_tv, w_b = crit.perceptual_weight, crit.tv_weight, crit.boundary_weight
     out5, dp = O.pixel_losses(pred, target, mask, w_l1 * scale, max(w_tv, 0.0) * scale, max(w_b, 0.0) * scale,
                               l1_weight=l1_weight, gscale=gscale, want_grad=want_grad, eps=crit.boundary_loss.epsilon)
@@ -147,14 +151,15 @@ def criterion_forward(crit, pred, target, mask, want_grad, gscale=None, l1_weigh
             both = torch.empty((2 * B,) + tuple(pred.shape[1:]), dtype=pred.dtype, device=pred.device)
             both[:B].copy_(pred)        # device-to-device memcpy (plumbing)
             both[B:].copy_(target)
-        feats, vctx = E.vgg_forward(V, both, keep=("gates" if checkpoint else True) if want_grad else False, nb=B)
+        feats, vctx = E.vgg_forward(V, both, keep=("gates" if checkpoint else True) if want_grad else False, nb=B,
+                                    bwd_mask=mask if (holes_only and want_grad) else None)
         fp, ft = feats[:B], feats[B:]
         # (the features are ReLU outputs: the L1 gradient comes out already gated by features[15])
         perc, dfeat = O.l1_mean(fp, ft, w_p * scale, gscale=gscale, want_grad=want_grad, relu_gate=True)
         parts["perc"] = perc
         total = O.lincomb(total, 1.0, perc, w_p * scale)
         if want_grad:
-            dperc = E.vgg_backward(vctx, dfeat, nb=B, gated=True)
+            dperc = E.vgg_backward(vctx, dfeat, nb=B, gated=True, sparse=holes_only)
             O.axpby_(dperc, 1.0, 1.0, dp)
     return total, parts, dp
 

@@ -60,6 +60,11 @@ VGG_WINO4_MINCH = int(os.environ.get("TG_VGG_WINO4_MINCH", "128"))
 # no pixel where pred and target differ are not computed -- the target's identical results are stored into them
 # (O.vgg_sparse_map, tg_conv_fwd_sparse).  Bit for bit the dense results.  TG_VGG_SPARSE=0: always dense.
 VGG_SPARSE = os.environ.get("TG_VGG_SPARSE", "1") != "0"
+# Backward of the same batch (vgg_backward(..., sparse=True)): where the caller states that the trunk's input gradient
+# is read only where pred != target or mask != 1, the dgrads below the lowest F(4x4,3x3) layer and the pool backward between them
+# produce only the tiles of the forward's maps, and the last one zeroes every pixel nobody needs.  Bit for bit the dense gradient
+# on the needed pixels.  Needs VGG_SPARSE; TG_VGG_SPARSE_BWD=0: the forward half alone (for A/B runs).
+VGG_SPARSE_BWD = os.environ.get("TG_VGG_SPARSE_BWD", "1") != "0"
 POOL_CODE = os.environ.get("TG_NO_POOL_CODE") is None       # pooled convs of the trunk: pooled tensor + pool code, no full-resolution output
 
 
@@ -476,8 +481,10 @@ def discriminator_replay_running_stats(P, ctx, order=(0,)):
 # --------------------------------------------------------------------------------------------------
 # frozen VGG16 trunk (features[:16]) on a 1-channel image repeated x3 (losses.py:79-90)
 # --------------------------------------------------------------------------------------------------
-def vgg_forward(V, img, keep=True, wino4=None, nb=None):
+def vgg_forward(V, img, keep=True, wino4=None, nb=None, bwd_mask=None):
     """V: {'0.weight','0.bias',...,'0.folded'}; img [B][H][W].  Returns (features, ctx).
+    bwd_mask [nb][H][W] (with nb): the caller will ask vgg_backward(sparse=True), i.e. reads the input gradient only where the two
+    halves differ or bwd_mask != 1 -- the tile maps then cover those pixels too and stay in the context.
     wino4 (forward kernels): None = F(2x2,3x3) unless TG_VGG_WINO4_FWD=1 (see the note at the top of this file); True / False
     force F(4x4,3x3) on (wherever the geometry allows) / off.
     keep: what the context holds for vgg_backward.  True: every conv's ReLU output (fp32, all B images).  False: nothing
@@ -494,14 +501,15 @@ def vgg_forward(V, img, keep=True, wino4=None, nb=None):
     smaps = None
     if VGG_SPARSE and nb is not None and 2 * nb == img.shape[0]:
         # nb prediction images followed by their nb targets: tile maps of every conv from the data (one launch)
-        smaps = O.vgg_sparse_map(img, nb, "".join("M" if it == "M" else "C" for it in VGG_TRUNK))
+        smaps = O.vgg_sparse_map(img, nb, "".join("M" if it == "M" else "C" for it in VGG_TRUNK),
+                                 mask=bwd_mask if (VGG_SPARSE_BWD and keep) else None)
     ci = -1
     for i, item in enumerate(VGG_TRUNK):
         if item == "M":
             # (the conv below has written the pooled tensor with its own output where the sizes are even)
             o = pooled if pooled is not None else O.maxpool2_fwd(h)
             if keep:
-                steps.append(NS(kind="M", x=h if (code is None or not gates) else None, code=code))
+                steps.append(NS(kind="M", x=h if (code is None or not gates) else None, code=code, ci=ci))
             pooled = code = None
         else:
             w = V["0.folded"] if item == 0 else V[f"{item}.weight"]
@@ -522,26 +530,40 @@ def vgg_forward(V, img, keep=True, wino4=None, nb=None):
             if gates:
                 # the input of the next conv (no pool between): its dgrad is gated by this output's ReLU
                 feeds = i + 1 < len(VGG_TRUNK) and VGG_TRUNK[i + 1] != "M"
-                steps.append(NS(kind="C", w=w, x_shape=tuple(h.shape), a=None, bits=O.relu_gate_pack(o, nb) if feeds else None))
+                steps.append(NS(kind="C", w=w, x_shape=tuple(h.shape), a=None, bits=O.relu_gate_pack(o, nb) if feeds else None, ci=ci))
             elif keep:
-                steps.append(NS(kind="C", w=w, x_shape=tuple(h.shape), a=o))
+                steps.append(NS(kind="C", w=w, x_shape=tuple(h.shape), a=o, ci=ci))
         h = o
-    return h, NS(steps=steps)
+    return h, NS(steps=steps, smaps=smaps)
 
 
-def vgg_backward(ctx, dfeat, nb=None, wino4=None, gated=False):
+def vgg_backward(ctx, dfeat, nb=None, wino4=None, gated=False, sparse=False):
     """Input gradient only (weights are frozen, losses.py:33-34) for the first `nb` samples.
     wino4 (dgrad kernels): None = F(4x4,3x3) where it pays (TG_VGG_WINO4=0: never); True / False force.
-    gated: dfeat is already the gradient in front of the trunk's last ReLU (O.l1_mean(..., relu_gate=True))."""
+    gated: dfeat is already the gradient in front of the trunk's last ReLU (O.l1_mean(..., relu_gate=True)).
+    sparse: the caller reads the result only where the forward's two halves differ or its bwd_mask != 1.  Where the context holds
+    maps built for that (vgg_forward(bwd_mask=...)) the result equals the dense one bit for bit on those pixels and is exactly 0.0
+    on all others; intermediate gradients are produced only on the maps' tiles.  The kernel family of a layer does not depend on
+    it.  Sparse launches start below the LOWEST F(4x4,3x3) dgrad: an output of that transform mixes its whole input patch, so
+    it needs a fully written gradient -- F(2x2,3x3) and the direct kernels read a pixel's own 3x3 window only."""
     da = dfeat
     steps = ctx.steps
     w4 = wino4
+    w4s = [st.kind == "C" and _vgg_wino4(st.w, nb if nb is not None else st.x_shape[0], st.x_shape[1], st.x_shape[2], st.x_shape[3],
+                                          w4, VGG_WINO4) for st in steps]
+    smaps = getattr(ctx, "smaps", None)
+    sp_below = 0            # steps [0, sp_below) run on the maps
+    if (sparse and smaps is not None and smaps.for_bwd and nb is not None and smaps.maps[0].nb == nb and steps
+            and steps[0].kind == "C" and steps[0].x_shape[3] == 1):        # (the 1-channel dgrad is what zeroes the unneeded pixels)
+        sp_below = min([i for i, f in enumerate(w4s) if f], default=len(steps))
     for i in range(len(steps) - 1, -1, -1):
         st = steps[i]
+        sp = smaps.maps[st.ci] if i < sp_below else None
         if st.kind == "M":
             # the pooled tensor is a ReLU output: its backward is fused into the pool backward
             if getattr(st, "code", None) is not None:
-                da = O.maxpool2_bwd_code(da, st.code)        # (code of all the forward's images: the first nb are read)
+                # (code of all the forward's images: the first nb are read; sp: the map of the pooled conv, whose dgrad is next)
+                da = O.maxpool2_bwd_code(da, st.code, sparse=sp)
             else:
                 x = st.x if nb is None else st.x[:nb]
                 da = O.maxpool2_bwd(da, x, relu_gate=True)
@@ -556,15 +578,13 @@ def vgg_backward(ctx, dfeat, nb=None, wino4=None, gated=False):
             O.tag(f"vgg{VGG_TRUNK[i]}.dgrad")
             if below is not None and below.kind == "C" and getattr(below, "bits", None) is not None:    # keep="gates"
                 assert below.bits.shape[0] == shp[0], "vgg_backward: the gate bits were packed for another number of images"
-                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, gate_bits=below.bits,
-                                  wino4=_vgg_wino4(st.w, shp[0], shp[1], shp[2], shp[3], w4, VGG_WINO4))
+                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, gate_bits=below.bits, wino4=w4s[i], sparse=sp)
                 gated = True
             elif below is not None and below.kind == "C":    # input of this conv = ReLU output of the conv below
                 ga = below.a if nb is None else below.a[:nb]
-                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, gate=ga, gate_act=O.ACT_RELU,
-                                  wino4=_vgg_wino4(st.w, shp[0], shp[1], shp[2], shp[3], w4, VGG_WINO4))
+                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, gate=ga, gate_act=O.ACT_RELU, wino4=w4s[i], sparse=sp)
                 gated = True
             else:
-                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, wino4=_vgg_wino4(st.w, shp[0], shp[1], shp[2], shp[3], w4, VGG_WINO4))
+                da = O.conv_dgrad(dy, st.w, shp, 3, 1, 1, wino4=w4s[i], sparse=sp)
                 gated = False
     return da.reshape(da.shape[0], da.shape[1], da.shape[2])

@@ -33,7 +33,7 @@ class TgBnAct(C.Structure):
 
 
 class TgSparseMap(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("bits", "list", "count")] + [(n, C.c_int32) for n in ("nb", "tiles_y", "tiles_x", "_pad")]
+    _fields_ = [(n, C.c_void_p) for n in ("bits", "list", "count", "pix")] + [(n, C.c_int32) for n in ("nb", "tiles_y", "tiles_x", "_pad")]
 
 
 class TgRasterPlan(C.Structure):
@@ -77,7 +77,10 @@ SIGNATURES = {
     "tg_conv_fwd_pool_code": (I, [CP, P, P, P, P, P, P, P, SZ, P]),
     "tg_maxpool2_bwd_code": (I, [P, P, I, I, I, I, P, P]),
     "tg_vgg_sparse_map_bytes": (SZ, [I, I, I, C.c_char_p]),
-    "tg_vgg_sparse_map": (I, [P, I, I, I, C.c_char_p, P, SZ, P, C.POINTER(TgSparseMap), P]),
+    "tg_vgg_sparse_map": (I, [P, P, I, I, I, C.c_char_p, P, SZ, P, C.POINTER(TgSparseMap), P]),
+    "tg_conv_dgrad_sparse": (I, [CP, P, P, P, P, I, F, P, P, C.POINTER(TgSparseMap), P, SZ, P]),
+    "tg_conv_dgrad_sparse_planned": (I, [CP, I, C.POINTER(TgSparseMap)]),
+    "tg_maxpool2_bwd_code_sparse": (I, [P, P, I, I, I, I, P, C.POINTER(TgSparseMap), P]),
     "tg_conv_fwd_sparse": (I, [CP, P, P, P, P, I, F, P, P, P, C.POINTER(TgSparseMap), P, SZ, P]),
     "tg_conv_bnin_supported": (I, [CP, I]),
     "tg_conv_fwd_bnin": (I, [CP, P, C.POINTER(TgBnAct), P, P, I, F, P, P, SZ, P]),

@@ -209,19 +209,22 @@ _sparse_tickets = {}
 
 class SparseMaps:
     """Prediction-half tile maps of the VGG trunk for one [pred; target] batch (tg_vgg_sparse_map): maps[i] belongs to the i-th
-    conv of the plan.  Holds the device buffer the maps point into."""
+    conv of the plan.  Holds the device buffer the maps point into.  for_bwd: built with the consumer's mask, so the maps also
+    cover every pixel whose input gradient is read (maps[i].pix) and may steer the trunk's backward."""
 
-    def __init__(self, buf, maps):
-        self.buf, self.maps = buf, maps
+    def __init__(self, buf, maps, for_bwd=False):
+        self.buf, self.maps, self.for_bwd = buf, maps, for_bwd
 
 
-def vgg_sparse_map(x, nb, plan):
+def vgg_sparse_map(x, nb, plan, mask=None):
     """x: the trunk's 1-channel input [2 nb][H][W] (or [2 nb][H][W][1]).  plan: 'C' (3x3 / stride-1 / pad-1 conv) and 'M'
     (2x2 / stride-2 max-pool) in the trunk's order.  Returns SparseMaps, or None where no map can be built (the trunk then
-    runs dense: the same values).  One launch, no host synchronisation."""
-    _chk(x, "x")
+    runs dense: the same values).  One launch, no host synchronisation.  mask [nb][H][W]: pixels with mask != 1 are marked as
+    well (conv_dgrad(sparse=...), maxpool2_bwd_code(sparse=...))."""
+    _chk(x, "x"); _chk(mask, "mask")
     H, W = x.shape[1], x.shape[2]
     assert x.shape[0] == 2 * nb and x.numel() == 2 * nb * H * W, (tuple(x.shape), nb)
+    assert mask is None or (mask.numel() == nb * H * W and mask.shape[0] == nb), (tuple(mask.shape), nb, H, W)
     lib = _lib()
     pb = plan.encode()
     nbytes = lib.tg_vgg_sparse_map_bytes(nb, H, W, pb)
@@ -236,8 +239,8 @@ def vgg_sparse_map(x, nb, plan):
     buf = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
     nconv = plan.count("C")
     maps = (L.TgSparseMap * nconv)()
-    L.check(lib.tg_vgg_sparse_map(_p(x), nb, H, W, pb, _p(buf), nbytes, _p(ticket), maps, _stream()), "tg_vgg_sparse_map")
-    return SparseMaps(buf, maps)
+    L.check(lib.tg_vgg_sparse_map(_p(x), _p(mask), nb, H, W, pb, _p(buf), nbytes, _p(ticket), maps, _stream()), "tg_vgg_sparse_map")
+    return SparseMaps(buf, maps, for_bwd=mask is not None)
 
 
 def conv_fwd(x, w, bias, k, stride, pad, in_mask=None, ratio=None, act=ACT_NONE, slope=0.0, wino4=False, pool=False, sparse=None):
@@ -336,14 +339,29 @@ def conv_fwd_pool_code(x, w, bias, sparse=None):
     return yp, code
 
 
-def maxpool2_bwd_code(dout, code):
-    """Gradient in front of the fused conv's ReLU from the pooled gradient and the pool code: [B][2 Ho][2 Wo][C]."""
-    _chk(dout, "dout")
+def maxpool2_bwd_code(dout, code, sparse=None, out=None):
+    """Gradient in front of the fused conv's ReLU from the pooled gradient and the pool code: [B][2 Ho][2 Wo][C].
+    sparse: the TgSparseMap of the pooled conv -- only the 16x16 tiles it lists are written, the rest of the result is
+    uninitialised memory (tg_maxpool2_bwd_code_sparse)."""
+    _chk(dout, "dout"); _chk(out, "out")
     B, Ho, Wo, Cc = dout.shape
     assert code.dtype == torch.uint8 and code.is_contiguous() and tuple(code.shape[1:]) == (Ho, Wo, Cc) and code.shape[0] >= B
-    dx = empty(B, 2 * Ho, 2 * Wo, Cc, like=dout)
+    dx = out if out is not None else empty(B, 2 * Ho, 2 * Wo, Cc, like=dout)
+    assert tuple(dx.shape) == (B, 2 * Ho, 2 * Wo, Cc)
+    if sparse is not None:
+        L.check(_lib().tg_maxpool2_bwd_code_sparse(_p(dout), C.c_void_p(code.data_ptr()), B, Ho, Wo, Cc, _p(dx), C.byref(sparse), _stream()),
+                "tg_maxpool2_bwd_code_sparse")
+        return dx
     L.check(_lib().tg_maxpool2_bwd_code(_p(dout), C.c_void_p(code.data_ptr()), B, Ho, Wo, Cc, _p(dx), _stream()), "tg_maxpool2_bwd_code")
     return dx
+
+
+def conv_dgrad_sparse_planned(x_shape, cout, sparse, gate=0):
+    """Will conv_dgrad(sparse=...) of a 3x3 / stride-1 / pad-1 layer write only the listed tiles (True) or fall back to the dense
+    launch (False)?  gate: 0 none, 1 `gate`, 2 `gate_bits`.  The launch's own plan; no GPU work."""
+    B, H, W, Cin = x_shape
+    g = L.TgConv(B, H, W, Cin, H, W, cout, 3, 1, 1, _precision)
+    return bool(_lib().tg_conv_dgrad_sparse_planned(C.byref(g), gate, C.byref(sparse)))
 
 
 def relu_gate_pack(a, nb=None):
@@ -359,10 +377,13 @@ def relu_gate_pack(a, nb=None):
 
 
 def conv_dgrad(dy, w, x_shape, k, stride, pad, in_mask=None, out=None, gate=None, gate_act=ACT_RELU, gate_slope=0.0, wino4=False,
-               gate_bits=None):
+               gate_bits=None, sparse=None):
     """dx for an input of shape x_shape=[B,H,W,Cin]; accumulates into `out` when given.  `gate` = output of the
     activation that produced x: its backward is fused into the epilogue (dx *= act'(gate)).  `gate_bits` = relu_gate_pack of a
-    ReLU output in place of `gate` (exclusive with it): the same dx bit for bit (tg_conv_dgrad_gbits)."""
+    ReLU output in place of `gate` (exclusive with it): the same dx bit for bit (tg_conv_dgrad_gbits).
+    sparse: the TgSparseMap of this conv's OUTPUT (vgg_sparse_map with a mask): only the tiles it lists are written where the
+    launch can do so -- the rest of dx is then uninitialised memory -- and `out` is overwritten, not accumulated into; with
+    Cin == 1 every pixel is written, 0.0 outside the map's needed pixels (tg_conv_dgrad_sparse)."""
     _chk(dy, "dy"); _chk(in_mask, "in_mask"); _chk(out, "out"); _chk(gate, "gate")
     wv = weight_view(w)
     B, H, W, Cin = x_shape
@@ -371,6 +392,17 @@ def conv_dgrad(dy, w, x_shape, k, stride, pad, in_mask=None, out=None, gate=None
     dx = out if out is not None else empty(B, H, W, Cin, like=dy)
     lib = _lib()
     ws = workspace(lib.tg_conv_dgrad_ws_bytes(C.byref(g)))
+    if sparse is not None:
+        assert in_mask is None and not wino4 and tuple(dx.shape) == tuple(x_shape)
+        assert gate is None or (gate_bits is None and tuple(gate.shape) == tuple(x_shape))
+        if gate_bits is not None:
+            assert gate_bits.dtype == torch.uint32 and gate_bits.is_contiguous() and tuple(gate_bits.shape) == (B, H, W, Cin // 32), \
+                (gate_bits.dtype, tuple(gate_bits.shape), tuple(x_shape))
+        L.check(lib.tg_conv_dgrad_sparse(C.byref(g), _p(dy), _p(wv), _p(_prepared(w, wv, g, WPREP_DGRAD)), _p(gate),
+                                         gate_act if gate is not None else ACT_NONE, gate_slope,
+                                         C.c_void_p(gate_bits.data_ptr()) if gate_bits is not None else None, _p(dx),
+                                         C.byref(sparse), _p(ws), ws.numel() * 4, _stream()), "tg_conv_dgrad_sparse")
+        return dx
     if gate_bits is not None:
         assert gate is None and out is None, "conv_dgrad: gate_bits is exclusive with gate and does not accumulate"
         assert gate_bits.dtype == torch.uint32 and gate_bits.is_contiguous() and tuple(gate_bits.shape) == (B, H, W, Cin // 32), \
