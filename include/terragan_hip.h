@@ -623,6 +623,22 @@ int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t* change_bit
 /* out [H][W] = dem at known pixels (bit for bit), the solution at the unknowns; NaN everywhere when K is empty. */
 int tg_vfill_finish(const float* dem, int H, int W, const void* ws, size_t ws_bytes, float* out, tg_stream_t stream);
 
+/* ---- seam correction of a filled DSM by a harmonic delta surface (mvp_gan/src/seam_correct.py; no
+ * reference counterpart) ----
+ * Rasters are row-major [H][W] with 1 <= H, W and H * W < 2^31.  Known K as above (mask may be NULL).  A hole pixel is filled
+ * when `filled` is finite there; `filled` at known pixels is never read.  Ring I: filled holes with a known 4-neighbour inside
+ * the raster; interior U': the other filled holes.  No call allocates or synchronises; integer atomics only. */
+enum { TG_SEAM_RING = 0, TG_SEAM_INTERIOR, TG_SEAM_UNFILLED, TG_SEAM_MAX_BITS, TG_SEAM_NCOUNTS };
+/* delta [H][W]: on I the ring target minus the fill, d_p = (sum_dir (e_dir - g_p)) / n over the directions up, left, right,
+ * down whose neighbour q is known, summed in that order in fp32, with e_dir = fma(2, z_q, -z_q2) when order == 1 and
+ * q2 = p + 2 dir is inside and known, else z_q; 0 on K and on unfilled holes; NaN on U'.  counts [TG_SEAM_NCOUNTS] (device
+ * int32, zeroed by the call): pixels of I, of U', unfilled holes, and the float bits of max |d_p|. */
+int tg_seam_delta(const float* dem, const float* mask, int use_nodata, float nodata, const float* filled, int H, int W, int order,
+                  float* delta, int32_t* counts, tg_stream_t stream);
+/* out [H][W] = dem at known pixels (bit for bit), filled + delta_filled (one fp32 add) at filled holes, NaN at unfilled holes. */
+int tg_seam_apply(const float* dem, const float* mask, int use_nodata, float nodata, const float* filled,
+                  const float* delta_filled, int H, int W, float* out, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

@@ -12,24 +12,9 @@
 #include <math.h>
 
 #include "common.h"
+#include "raster_known.h"                // RasterIn, rs_known
 
 static inline hipStream_t S(tg_stream_t s) { return (hipStream_t)s; }
-
-struct RasterIn {
-    const float* dem;
-    const float* mask;     // may be null
-    int use_nodata;
-    float nodata;
-};
-
-// known: mask != 0 (if given), finite, and not the nodata value (if given)
-__device__ __forceinline__ bool rs_known(const RasterIn& in, int64_t i, float& z) {
-    z = in.dem[i];
-    bool k = isfinite(z);
-    if (in.mask) k = k && in.mask[i] != 0.f;
-    if (in.use_nodata) k = k && z != in.nodata;
-    return k;
-}
 
 __device__ __forceinline__ int rs_start(int i, int N, int w, int s) { return min(i * s, N - w); }
 

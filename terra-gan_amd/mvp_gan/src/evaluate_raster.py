@@ -24,12 +24,13 @@ Two calls on the same inputs return bitwise-equal tensors and an equal report.
 
 With baseline="laplace" the same keep mask is also filled by harmonic interpolation (fill_voids) and
 report["baseline"] holds that fill's full terrain_errors report on the same holes, plus "method" and the fill info: the number
-a GAN has to beat.  fallback is passed to inpaint_raster.
+a GAN has to beat.  fallback and seam are passed to inpaint_raster; with seam="harmonic" report["seam"] holds the info of the
+seam correction (mvp_gan/src/seam_correct.py), and the ring errors show what it did.
 
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
-         [--baseline laplace] [--fallback laplace]
+         [--baseline laplace] [--fallback laplace] [--seam harmonic]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -385,20 +386,23 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10, baseline=None, fallback=None):
+                    quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
-    baseline="laplace" adds report["baseline"]; fallback is passed to inpaint_raster."""
+    baseline="laplace" adds report["baseline"]; fallback and seam are passed to inpaint_raster, and seam="harmonic" adds
+    report["seam"]."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
-                             area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback)
+                             area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
+                             seam=seam)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
-              objects, area_edges_m2, quantiles, top, baseline=None, fallback=None):
+              objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None):
     """evaluate_raster, plus the hole map."""
-    from .inpaint_raster import inpaint_raster
+    from .inpaint_raster import check_seam_options, inpaint_raster
     _check_fill_options(baseline, fallback)
+    check_seam_options(seam, 1, who="evaluate_raster")
     c = _cellsize(cellsize, "evaluate_raster")
     H, W = _inputs(dem, mask, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
@@ -410,12 +414,15 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     hm, keep, hinfo = eval_holes(z, m, nodata=nodata, split=split, block=block, tile=tile, holes=holes, seed=seed,
                                  objects=objects, cellsize=c)
     pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
-                                 fallback=fallback)
+                                 fallback=fallback, seam=seam)
+    sinfo = iinfo.get("seam")
     rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top)
     rep.update(params(c, split, block, tile, seed, holes, window, overlap))
     rep["cells"] = hinfo["cells"]
     rep["inpaint"] = iinfo
+    if sinfo is not None:
+        rep["seam"] = sinfo
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top)
@@ -437,9 +444,9 @@ def summary(rep):
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------
-def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
-    from .object_mask import add_spec_args, spec_from_args, write_mask
+def build_parser():
+    from .inpaint_raster import SEAMS
+    from .object_mask import add_spec_args
     ap = argparse.ArgumentParser(description="Score inpainting of an ESRI ASCII grid DSM on held-out holes, in metres.")
     ap.add_argument("--dem", required=True, help="truth .asc raster (NODATA_value cells are never scored)")
     ap.add_argument("--checkpoint", help="generator checkpoint (.pth) to inpaint the holes with")
@@ -464,6 +471,15 @@ def main(argv=None):
                     help="also score a harmonic interpolation (fill_voids) of the same holes: a second summary line")
     ap.add_argument("--fallback", choices=("laplace",),
                     help="checkpoint mode: fill the holes no window reaches by harmonic interpolation")
+    ap.add_argument("--seam", choices=SEAMS,
+                    help="checkpoint mode: correct the filled holes towards the known terrain around them (seam_correct)")
+    return ap
+
+
+def main(argv=None):
+    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .object_mask import spec_from_args, write_mask
+    ap = build_parser()
     a = ap.parse_args(argv)
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
@@ -471,6 +487,8 @@ def main(argv=None):
         ap.error("--pred and --holes go together")
     if a.fallback and a.pred:
         ap.error("--fallback needs --checkpoint")
+    if a.seam and a.pred:
+        ap.error("--seam needs --checkpoint")
     dem, header = read_asc(a.dem)
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
@@ -481,7 +499,7 @@ def main(argv=None):
         rep, pred, hm = _evaluate(a.checkpoint, dem, mask, nodata=nodata, cellsize=c, split=split, block=a.block, tile=a.tile,
                                   holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
-                                  baseline=a.baseline, fallback=a.fallback)
+                                  baseline=a.baseline, fallback=a.fallback, seam=a.seam)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -506,6 +524,10 @@ def main(argv=None):
     if a.holes_out and hm is not None:
         write_mask(a.holes_out, hm.cpu().numpy(), header)
     print(summary(rep))
+    if "seam" in rep:
+        sm = rep["seam"]
+        print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
+              f"{sm['cycles']} cycles, converged {sm['converged']}")
     if "baseline" in rep:
         print(f"baseline {rep['baseline']['method']}: {summary(rep['baseline'])}")
     return rep

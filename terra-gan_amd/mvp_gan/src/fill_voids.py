@@ -102,10 +102,10 @@ def check_args(dem, mask, method, tol, max_cycles, objects, cellsize, who="fill_
     return shape[0], shape[1], c
 
 
-def _device_f32(a, device, what, binary=False):
+def _device_f32(a, device, what, binary=False, who="fill_voids"):
     if isinstance(a, torch.Tensor):
         if not a.is_cuda:
-            raise ValueError(f"fill_voids: {what} is on {a.device}; pass a numpy array or a HIP tensor")
+            raise ValueError(f"{who}: {what} is on {a.device}; pass a numpy array or a HIP tensor")
         if binary and a.dtype != torch.float32:
             a = a != 0
         return a.to(device=device, dtype=torch.float32).contiguous()

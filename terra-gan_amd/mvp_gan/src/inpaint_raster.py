@@ -21,8 +21,13 @@ With fallback="laplace" the holes no running window covers are filled by fill_vo
 blended raster, every finite pixel fixed: known and GAN-filled pixels come back bit for bit, and info["fallback"] reports the
 interpolated pixels, the cycles and whether they converged.  info["unfilled"] counts the holes still NaN at the end.
 
+With seam="harmonic" the blended raster goes through correct_seams (mvp_gan/src/seam_correct.py) with
+the mask the blend used, before any fallback: the filled holes meet the known terrain without a step, and info["seam"] holds
+the correction's info.
+
 CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --checkpoint ck.pth --out out.asc
          [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]] [--fallback laplace]
+         [--seam harmonic [--seam-order 0|1]]
 """
 import argparse
 import math
@@ -33,6 +38,7 @@ import torch
 
 MIN_SIDE = 40          # smallest window side the generator is tested at (fixture g72x40b3)
 FALLBACK_MAX_CYCLES = 200
+SEAMS = ("harmonic",)
 
 Plan = namedtuple("Plan", "H W wh ww overlap ys xs")
 
@@ -152,14 +158,23 @@ def _to_device_f32(a, device, what, binary=False):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
 
 
+def check_seam_options(seam, seam_order, who="inpaint_raster"):
+    if seam is not None and seam not in SEAMS:
+        raise ValueError(f"{who}: seam {seam!r} must be None or one of {SEAMS}")
+    if isinstance(seam_order, bool) or seam_order not in (0, 1):
+        raise ValueError(f"{who}: seam_order {seam_order!r} must be 0 or 1")
+
+
 @torch.no_grad()
 def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16, objects=None,
-                   cellsize=None, fallback=None):
+                   cellsize=None, fallback=None, seam=None, seam_order=1):
     """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
     objects: an ObjectSpec to remove the above-ground objects first (cellsize, metres per pixel, is then required).
     fallback: None or "laplace": fill the holes no running window covers with fill_voids.
+    seam: None or "harmonic": correct the filled holes towards the known terrain around them (correct_seams, seam_order 0 or 1).
     Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, with objects the object_mask info under
-    "objects", with a fallback its pixels, cycles and converged flag under "fallback")."""
+    "objects", with a seam correction its info under "seam", with a fallback its pixels, cycles and converged flag under
+    "fallback")."""
     from tg_hip import engine as E
     from tg_hip import ops as O
     if not torch.cuda.is_available():
@@ -168,6 +183,7 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
         raise ValueError(f"inpaint_raster: batch {batch} < 1")
     if fallback not in (None, "laplace"):
         raise ValueError(f"inpaint_raster: fallback {fallback!r} must be None or 'laplace'")
+    check_seam_options(seam, seam_order)
     device = torch.device("cuda", torch.cuda.current_device())
     z = _to_device_f32(dem, device, "dem")
     if z.dim() != 2:
@@ -207,6 +223,9 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
     info = {"windows": nwin, "run": int(run.size), "unfilled": int(unfilled.item())}
     if oinfo is not None:
         info["objects"] = oinfo
+    if seam is not None:
+        from .seam_correct import correct_seams
+        out, info["seam"] = correct_seams(z, out, m, nodata=nodata, order=seam_order)
     if fallback is not None:
         info["fallback"] = {"pixels": info["unfilled"], "cycles": 0, "converged": True}
         if info["unfilled"]:
@@ -231,7 +250,8 @@ def _read_mask(path, shape):
     return mk != 0
 
 
-def main(argv=None):
+def build_parser():
+    from .object_mask import add_spec_args
     ap = argparse.ArgumentParser(description="Inpaint the holes of an ESRI ASCII grid DSM with a TERRA-GAN generator.")
     ap.add_argument("--dem", required=True, help="input .asc raster (NODATA_value cells are holes)")
     ap.add_argument("--mask", help="optional mask (.png or .asc) of the raster's size: nonzero = keep, 0 = hole")
@@ -245,8 +265,17 @@ def main(argv=None):
     ap.add_argument("--objects-out", help="with --remove-objects: write the object map (.png or .asc, nonzero = object)")
     ap.add_argument("--fallback", choices=("laplace",),
                     help="fill the holes no window reaches by harmonic interpolation (fill_voids) instead of leaving NaN")
-    from .object_mask import add_spec_args, object_mask, spec_from_args, write_mask
+    ap.add_argument("--seam", choices=SEAMS,
+                    help="correct the filled holes towards the known terrain around them: no step at the hole outlines")
+    ap.add_argument("--seam-order", type=int, choices=(0, 1), default=1,
+                    help="with --seam: 1 continues the known slope across the rim, 0 takes the rim value (robust to noise)")
     add_spec_args(ap)
+    return ap
+
+
+def main(argv=None):
+    from .object_mask import object_mask, spec_from_args, write_mask
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.objects_out and not a.remove_objects:
         ap.error("--objects-out needs --remove-objects")
@@ -260,11 +289,17 @@ def main(argv=None):
             write_mask(a.objects_out, objects.cpu().numpy(), header)
         print(f"{oinfo['objects']} objects, {oinfo['object_pixels']} px removed")
     out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch,
-                               fallback=a.fallback)
+                               fallback=a.fallback, seam=a.seam, seam_order=a.seam_order)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)
     print(f"{a.out}: {info['windows']} windows, {info['run']} run, {info['unfilled']} holes left unfilled")
+    if "seam" in info:
+        sm = info["seam"]
+        print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
+              f"{sm['cycles']} cycles, converged {sm['converged']}")
+        if not sm["converged"]:
+            print("warning: the seam correction did not converge")
     if "fallback" in info:
         fb = info["fallback"]
         print(f"fallback {a.fallback}: {fb['pixels']} px, {fb['cycles']} cycles, converged {fb['converged']}")

@@ -1209,6 +1209,42 @@ def vfill_finish(dem, ws, out=None):
     return out
 
 
+SEAM_NCOUNTS = 4                                  # tg_seam_delta counts: ring, interior, unfilled, max |delta| bits
+
+
+def _seam_in(dem, mask, filled, order=None):
+    H, W = _raster_hw(dem, "dem")
+    _hip(dem, torch.float32, (H, W), "dem")
+    if mask is not None:
+        _hip(mask, torch.float32, (H, W), "mask")
+    _hip(filled, torch.float32, (H, W), "filled")
+    if order is not None and (isinstance(order, bool) or order not in (0, 1)):
+        raise L.TgError(f"seam: order {order!r} must be 0 or 1")
+    return H, W
+
+
+def seam_delta(dem, mask, nodata, filled, order=1):
+    """-> (delta float32 [H][W], counts int32 [SEAM_NCOUNTS] device) (tg_seam_delta): the ring targets minus the fill, 0 at the
+    known pixels and the unfilled holes, NaN at the filled holes without a known 4-neighbour."""
+    H, W = _seam_in(dem, mask, filled, order)
+    delta = torch.empty(H, W, dtype=torch.float32, device=dem.device)
+    counts = torch.empty(SEAM_NCOUNTS, dtype=torch.int32, device=dem.device)
+    L.check(_lib().tg_seam_delta(_p(dem), _p(mask), int(nodata is not None), 0.0 if nodata is None else float(nodata),
+                                 _p(filled), H, W, int(order), _p(delta), _p(counts), _stream()), "tg_seam_delta")
+    return delta, counts
+
+
+def seam_apply(dem, mask, nodata, filled, delta_filled):
+    """-> out float32 [H][W]: dem at the known pixels, filled + delta_filled at the filled holes, NaN at the unfilled ones
+    (tg_seam_apply)."""
+    H, W = _seam_in(dem, mask, filled)
+    _hip(delta_filled, torch.float32, (H, W), "delta_filled")
+    out = torch.empty(H, W, dtype=torch.float32, device=dem.device)
+    L.check(_lib().tg_seam_apply(_p(dem), _p(mask), int(nodata is not None), 0.0 if nodata is None else float(nodata),
+                                 _p(filled), _p(delta_filled), H, W, _p(out), _stream()), "tg_seam_apply")
+    return out
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()
