@@ -639,6 +639,32 @@ int tg_seam_delta(const float* dem, const float* mask, int use_nodata, float nod
 int tg_seam_apply(const float* dem, const float* mask, int use_nodata, float nodata, const float* filled,
                   const float* delta_filled, int H, int W, float* out, tg_stream_t stream);
 
+/* ---- raster resampling between cell sizes (mvp_gan/src/resample.py; no reference counterpart) ----
+ * The scale p / q is the output cell size over the source cell size.  Per axis, in units of 1/q source pixel: source pixel i
+ * covers [i q, (i+1) q), output pixel I covers [I p, (I+1) p) clipped to [0, N q), and No = ceil(N q / p); Ho and Wo are
+ * those sizes, or smaller ones for the top-left crop of that grid.  1 <= p, q <= 1024, N q + 2 p < 2^30 per axis.  Known K as
+ * above (mask may be NULL).  out [Ho][Wo] (may be NULL) gets the value, NaN where the output pixel is unknown; out_mask
+ * [Ho][Wo] (may be NULL) 1 / 0; n_nan [1] (device int32, zeroed by the call) the number of unknown output pixels, the NaN
+ * pixels of out; with out and out_mask NULL the call only counts (at p = q = 1: the unknown pixels of dem).  keep_dem / keep_mask [Ho][Wo] (may be NULL): where that pixel is known
+ * under (keep_mask, keep_use_nodata, keep_nodata), out gets its bits and out_mask 1.  No workspace, no allocation, no
+ * synchronisation; bitwise deterministic (one integer atomic per workgroup). */
+/* To a coarser grid, 1 <= p / q <= 16.  The weight of source pixel (i, j) in output pixel (I, J) is the integer overlap of their
+ * intervals along y times that along x.  The output is known iff cov_known > 0 and cov_known * cov_den >= cov_num * cov_total
+ * (int64), the weight sums over the known taps and over all taps of the clipped footprint; 0 <= cov_num <= cov_den <= 1000.
+ * Its value is z0 + (sum w (z - z0)) / cov_known in fp32 over the known taps in row-major order, z0 the first of them (z0
+ * itself when the sum is 0: a footprint of one repeated value returns its bits). */
+int tg_resample_area(const float* dem, const float* mask, int use_nodata, float nodata, int H, int W, int p, int q, int cov_num,
+                     int cov_den, const float* keep_dem, const float* keep_mask, int keep_use_nodata, float keep_nodata, int Ho,
+                     int Wo, float* out, float* out_mask, int32_t* n_nan, tg_stream_t stream);
+/* To a finer grid, 1/16 <= p / q <= 1 (the return trip of every area scale).  The centre of output pixel I lies at source
+ * coordinate ((2 I + 1) p - q) / (2 q) = f + t, f its integer floor; tap indices are clamped to the raster.  The output is known iff the source pixel containing the centre
+ * (f when t < 1/2, else f + 1, clamped) is known; that pixel's value zc is the pivot.  Value: zc + sum w (z - zc) with the
+ * Catmull-Rom (Keys a = -0.5) weights of taps f - 1 .. f + 2 when all 16 are known, else the bilinear weights of taps f, f + 1
+ * renormalised over the known ones (zc itself when the sum is 0). */
+int tg_resample_interp(const float* dem, const float* mask, int use_nodata, float nodata, int H, int W, int p, int q,
+                       const float* keep_dem, const float* keep_mask, int keep_use_nodata, float keep_nodata, int Ho, int Wo,
+                       float* out, float* out_mask, int32_t* n_nan, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

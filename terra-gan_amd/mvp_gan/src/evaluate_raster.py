@@ -30,7 +30,7 @@ seam correction (mvp_gan/src/seam_correct.py), and the ring errors show what it 
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
-         [--baseline laplace] [--fallback laplace] [--seam harmonic]
+         [--baseline laplace] [--fallback laplace] [--seam harmonic] [--model-cellsize 1.0 [--min-coverage 0.5]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -88,6 +88,22 @@ def eligible_cells(H, W, split, block, tile):
     by = (np.arange(ncy) * tile // block)[:, None]
     bx = (np.arange(ncx) * tile // block)[None, :]
     return (bx - by) % 3 == SPLITS[split]
+
+
+def native_cells(block, tile, scale, who="evaluate_raster"):
+    """Block and tile sides counted in working pixels of `scale` (working / native cell size, a Fraction, or None for the
+    native grid itself) -> the same ground lengths in native pixels.  RasterWindowLoader(model_cellsize=...) picks its blocks
+    on the working grid: working block b covers native pixels [b block scale, (b + 1) block scale), so with the block and
+    the tile converted here the native blocks are the loader's, index for index, and eligible_cells keeps its promise that a
+    test cell shares no pixel with the ground of a train or val block.  ValueError when a side is no whole number of native
+    pixels."""
+    if scale is None:
+        return int(block), int(tile)
+    b, t = int(block) * scale, int(tile) * scale
+    if b.denominator != 1 or t.denominator != 1:
+        raise ValueError(f"{who}: block {block} and tile {tile} working pixels at scale {scale} are {b} and {t} native pixels; "
+                         f"both must be whole numbers for the held-out cells to match the training blocks")
+    return int(b), int(t)
 
 
 def cell_rng(seed, split, cy, cx):
@@ -386,24 +402,27 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None):
+                    quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
-    baseline="laplace" adds report["baseline"]; fallback and seam are passed to inpaint_raster, and seam="harmonic" adds
-    report["seam"]."""
+    baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
+    (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
+    checkpoint whose training blocks were picked on the working grid), and seam="harmonic" adds report["seam"]."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
-                             seam=seam)
+                             seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
-              objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None):
+              objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
+              min_coverage=0.5):
     """evaluate_raster, plus the hole map."""
-    from .inpaint_raster import check_seam_options, inpaint_raster
+    from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
     _check_fill_options(baseline, fallback)
     check_seam_options(seam, 1, who="evaluate_raster")
     c = _cellsize(cellsize, "evaluate_raster")
+    check_resample_options(c, model_cellsize, min_coverage, who="evaluate_raster")
     H, W = _inputs(dem, mask, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
@@ -414,7 +433,8 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     hm, keep, hinfo = eval_holes(z, m, nodata=nodata, split=split, block=block, tile=tile, holes=holes, seed=seed,
                                  objects=objects, cellsize=c)
     pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
-                                 fallback=fallback, seam=seam)
+                                 fallback=fallback, seam=seam, cellsize=c, model_cellsize=model_cellsize,
+                                 min_coverage=min_coverage)
     sinfo = iinfo.get("seam")
     rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top)
@@ -473,6 +493,11 @@ def build_parser():
                     help="checkpoint mode: fill the holes no window reaches by harmonic interpolation")
     ap.add_argument("--seam", choices=SEAMS,
                     help="checkpoint mode: correct the filled holes towards the known terrain around them (seam_correct)")
+    ap.add_argument("--model-cellsize", type=float,
+                    help="checkpoint mode: cell size the checkpoint was trained at; the windows run on the raster resampled to "
+                         "it, the scoring stays on the native grid")
+    ap.add_argument("--min-coverage", type=float, default=0.5,
+                    help="with a coarser --model-cellsize: the known share of its footprint a resampled cell needs, in (0, 1]")
     return ap
 
 
@@ -489,6 +514,8 @@ def main(argv=None):
         ap.error("--fallback needs --checkpoint")
     if a.seam and a.pred:
         ap.error("--seam needs --checkpoint")
+    if a.model_cellsize is not None and a.pred:
+        ap.error("--model-cellsize needs --checkpoint")
     dem, header = read_asc(a.dem)
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
@@ -499,7 +526,8 @@ def main(argv=None):
         rep, pred, hm = _evaluate(a.checkpoint, dem, mask, nodata=nodata, cellsize=c, split=split, block=a.block, tile=a.tile,
                                   holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
-                                  baseline=a.baseline, fallback=a.fallback, seam=a.seam)
+                                  baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
+                                  min_coverage=a.min_coverage)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:

@@ -25,9 +25,15 @@ With seam="harmonic" the blended raster goes through correct_seams (mvp_gan/src/
 the mask the blend used, before any fallback: the filled holes meet the known terrain without a step, and info["seam"] holds
 the correction's info.
 
+With model_cellsize (and cellsize) the generator runs at its own ground sampling distance (mvp_gan/src/resample.py, DESIGN.md
+section 8m): after the object removal, the raster and its known pixels are resampled to the working grid of that cell size,
+the windows above run there (window and overlap are then in working pixels), and the result returns to the native grid with
+the known pixels' bits copied through; the seam correction and the fallback then run on the native grid as always.
+info["resample"] holds the scale, the working shape and cell size and the hole counts of both grids.
+
 CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --checkpoint ck.pth --out out.asc
          [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]] [--fallback laplace]
-         [--seam harmonic [--seam-order 0|1]]
+         [--seam harmonic [--seam-order 0|1]] [--model-cellsize 1.0 [--min-coverage 0.5]]
 """
 import argparse
 import math
@@ -165,41 +171,25 @@ def check_seam_options(seam, seam_order, who="inpaint_raster"):
         raise ValueError(f"{who}: seam_order {seam_order!r} must be 0 or 1")
 
 
-@torch.no_grad()
-def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16, objects=None,
-                   cellsize=None, fallback=None, seam=None, seam_order=1):
-    """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
-    objects: an ObjectSpec to remove the above-ground objects first (cellsize, metres per pixel, is then required).
-    fallback: None or "laplace": fill the holes no running window covers with fill_voids.
-    seam: None or "harmonic": correct the filled holes towards the known terrain around them (correct_seams, seam_order 0 or 1).
-    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, with objects the object_mask info under
-    "objects", with a seam correction its info under "seam", with a fallback its pixels, cycles and converged flag under
-    "fallback")."""
+def check_resample_options(cellsize, model_cellsize, min_coverage, who="inpaint_raster"):
+    """-> the scale working / native cell size as a Fraction, or None when nothing is to be resampled."""
+    from .resample import coverage_fraction, resample_scale
+    coverage_fraction(min_coverage)
+    if model_cellsize is None:
+        return None
+    if cellsize is None:
+        raise ValueError(f"{who}: model_cellsize needs cellsize, the raster's metres per pixel")
+    scale = resample_scale(cellsize, model_cellsize)
+    return None if scale == 1 else scale
+
+
+def _inpaint_windows(generator_or_checkpoint, z, m, nodata, window, overlap, batch, device):
+    """The window pipeline on one grid -> (raster, its window count, the windows run, the unfilled counter on the device)."""
     from tg_hip import engine as E
     from tg_hip import ops as O
-    if not torch.cuda.is_available():
-        raise RuntimeError("inpaint_raster: no HIP device visible; this build has no CPU path")
-    if batch < 1:
-        raise ValueError(f"inpaint_raster: batch {batch} < 1")
-    if fallback not in (None, "laplace"):
-        raise ValueError(f"inpaint_raster: fallback {fallback!r} must be None or 'laplace'")
-    check_seam_options(seam, seam_order)
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _to_device_f32(dem, device, "dem")
-    if z.dim() != 2:
-        raise ValueError(f"inpaint_raster: dem must be [H, W], got {tuple(z.shape)}")
-    m = None if mask is None else _to_device_f32(mask, device, "mask", binary=True)
-    if m is not None and m.shape != z.shape:
-        raise ValueError(f"inpaint_raster: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
-    oinfo = None
-    if objects is not None:
-        from .object_mask import object_mask
-        _, m, oinfo = object_mask(z, m, nodata=nodata, cellsize=cellsize, spec=objects)
     pl = plan_windows(*z.shape, window=window, overlap=overlap)
     cp = O.raster_plan(pl.H, pl.W, pl.wh, pl.ww, pl.overlap, len(pl.ys), len(pl.xs))
     nwin = len(pl.ys) * len(pl.xs)
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are holes already
 
     lo, hi, counts = O.raster_window_stats(z, m, cp, nodata)
     c = counts.cpu().numpy()                                    # the one host sync before the result
@@ -220,9 +210,63 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
             x, mk = O.raster_gather(z, m, cp, lo, hi, run_d[b0:b1], nodata, x=xb[:b1 - b0], m=mb[:b1 - b0])
             E.generator_forward(P, x, mk, training=False, out=wout[b0:b1])
     out, unfilled = O.raster_blend(z, m, cp, lo, hi, run_of_d, wout, nodata)
-    info = {"windows": nwin, "run": int(run.size), "unfilled": int(unfilled.item())}
+    return out, nwin, int(run.size), unfilled
+
+
+@torch.no_grad()
+def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16, objects=None,
+                   cellsize=None, fallback=None, seam=None, seam_order=1, model_cellsize=None, min_coverage=0.5):
+    """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
+    objects: an ObjectSpec to remove the above-ground objects first (cellsize, metres per pixel, is then required).
+    fallback: None or "laplace": fill the holes no running window covers with fill_voids.
+    seam: None or "harmonic": correct the filled holes towards the known terrain around them (correct_seams, seam_order 0 or 1).
+    model_cellsize: the cell size the generator was trained at; when it differs from cellsize (then required) the windows run
+    on the raster resampled to it (min_coverage: the known share of its footprint a coarser working pixel needs to be known).
+    Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, with objects the object_mask info under
+    "objects", with a working grid its description under "resample", with a seam correction its info under "seam", with a
+    fallback its pixels, cycles and converged flag under "fallback")."""
+    scale = check_resample_options(cellsize, model_cellsize, min_coverage)
+    if not torch.cuda.is_available():
+        raise RuntimeError("inpaint_raster: no HIP device visible; this build has no CPU path")
+    if batch < 1:
+        raise ValueError(f"inpaint_raster: batch {batch} < 1")
+    if fallback not in (None, "laplace"):
+        raise ValueError(f"inpaint_raster: fallback {fallback!r} must be None or 'laplace'")
+    check_seam_options(seam, seam_order)
+    device = torch.device("cuda", torch.cuda.current_device())
+    z = _to_device_f32(dem, device, "dem")
+    if z.dim() != 2:
+        raise ValueError(f"inpaint_raster: dem must be [H, W], got {tuple(z.shape)}")
+    m = None if mask is None else _to_device_f32(mask, device, "mask", binary=True)
+    if m is not None and m.shape != z.shape:
+        raise ValueError(f"inpaint_raster: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
+    oinfo = None
+    if objects is not None:
+        from .object_mask import object_mask
+        _, m, oinfo = object_mask(z, m, nodata=nodata, cellsize=cellsize, spec=objects)
+    if nodata is not None and math.isnan(nodata):
+        nodata = None                                           # NaN is never a value: non-finite pixels are holes already
+    rinfo = None
+    if scale is None:
+        out, nwin, nrun, unfilled = _inpaint_windows(generator_or_checkpoint, z, m, nodata, window, overlap, batch, device)
+    else:
+        from tg_hip import ops as O
+        from .resample import resample_back, resample_to
+        Hw, Ww = (-(-n * scale.denominator // scale.numerator) for n in z.shape)
+        if min(Hw, Ww) < MIN_SIDE:
+            raise ValueError(f"inpaint_raster: the working grid {Hw}x{Ww} (raster {z.shape[0]}x{z.shape[1]} at scale {scale}) has "
+                             f"a side below {MIN_SIDE} px")
+        zw, _, holes_w = resample_to(z, m, nodata, scale, min_coverage)
+        holes = O.raster_count_unknown(z, m, nodata)               # the native holes: one read of the raster, nothing written
+        outw, nwin, nrun, unfilled_w = _inpaint_windows(generator_or_checkpoint, zw, None, None, window, overlap, batch, device)
+        out, unfilled = resample_back(outw, z, m, nodata=nodata, scale=scale)
+        rinfo = {"scale": f"{scale.numerator}/{scale.denominator}", "shape": (Hw, Ww), "cellsize": float(model_cellsize),
+                 "holes": int(holes.item()), "working_holes": int(holes_w.item()), "working_unfilled": int(unfilled_w.item())}
+    info = {"windows": nwin, "run": nrun, "unfilled": int(unfilled.item())}
     if oinfo is not None:
         info["objects"] = oinfo
+    if rinfo is not None:
+        info["resample"] = rinfo
     if seam is not None:
         from .seam_correct import correct_seams
         out, info["seam"] = correct_seams(z, out, m, nodata=nodata, order=seam_order)
@@ -269,6 +313,11 @@ def build_parser():
                     help="correct the filled holes towards the known terrain around them: no step at the hole outlines")
     ap.add_argument("--seam-order", type=int, choices=(0, 1), default=1,
                     help="with --seam: 1 continues the known slope across the rim, 0 takes the rim value (robust to noise)")
+    ap.add_argument("--model-cellsize", type=float,
+                    help="cell size the checkpoint was trained at: run the windows on the raster resampled to it (the raster's "
+                         "cell size comes from the header); --window and --overlap are then in resampled pixels")
+    ap.add_argument("--min-coverage", type=float, default=0.5,
+                    help="with a coarser --model-cellsize: the known share of its footprint a resampled cell needs, in (0, 1]")
     add_spec_args(ap)
     return ap
 
@@ -289,11 +338,17 @@ def main(argv=None):
             write_mask(a.objects_out, objects.cpu().numpy(), header)
         print(f"{oinfo['objects']} objects, {oinfo['object_pixels']} px removed")
     out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch,
-                               fallback=a.fallback, seam=a.seam, seam_order=a.seam_order)
+                               fallback=a.fallback, seam=a.seam, seam_order=a.seam_order,
+                               cellsize=float(asc_value(header, "cellsize")), model_cellsize=a.model_cellsize,
+                               min_coverage=a.min_coverage)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)
     print(f"{a.out}: {info['windows']} windows, {info['run']} run, {info['unfilled']} holes left unfilled")
+    if "resample" in info:
+        rs = info["resample"]
+        print(f"working grid {rs['shape'][0]}x{rs['shape'][1]} at cellsize {rs['cellsize']:g} (scale {rs['scale']}): "
+              f"{rs['holes']} holes, {rs['working_holes']} on the working grid, {rs['working_unfilled']} left unfilled there")
     if "seam" in info:
         sm = info["seam"]
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "

@@ -6,13 +6,21 @@ Train and validation windows come from RasterWindowLoader (utils/raster_dataset.
 
 CLI: python -m mvp_gan.src.train_raster --dem in.asc [--mask keep.png|keep.asc] [--nodata v] [--init ck.pth] --out ft.pth
          [--window 256 --batch 16 --steps 500 --epochs 4 --seed 0 --norm known|window] [--remove-objects [spec flags]]
-         [--evaluate [--eval-json report.json]]
+         [--model-cellsize 1.0 [--min-coverage 0.5]] [--evaluate [--eval-json report.json]]
 
 --evaluate scores the written checkpoint on held-out holes of the test split (mvp_gan/src/evaluate_raster.py) with the same
 block, window (as the hole tile), seed, nodata, mask and objects, prints one line and writes the report to --eval-json.
 
 --remove-objects finds the above-ground objects in the DSM (mvp_gan/src/object_mask.py, cellsize from the header) and never
 samples a window that touches one, so the generator learns bare earth.
+
+--model-cellsize resamples the raster, the mask and the object keep-mask once to that cell size (mvp_gan/src/resample.py,
+DESIGN.md section 8m; the raster's own comes from the header): the checkpoint is fine-tuned at the cell size it will be used
+at, and --window and --block are in resampled pixels.  --evaluate then scores it with the same model cell size and coverage on
+the native grid, where the holes are cut: block and tile are the same ground squares counted in native pixels (block x
+scale, window x scale; evaluate_raster.native_cells), so a test cell still shares no ground with a train or val block.  That
+needs both products to be whole numbers and the tile within evaluate_raster's range; a run that cannot be scored this way is
+refused before it trains.
 """
 import argparse
 import logging
@@ -44,7 +52,7 @@ def _load_init(path, generator, discriminator, optimizer_G, optimizer_D, device)
     return loaded
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description="Fine-tune a TERRA-GAN generator on windows of one ESRI ASCII grid DSM.")
     ap.add_argument("--dem", required=True, help="input .asc raster in metres (NODATA_value cells are never sampled)")
     ap.add_argument("--mask", help="optional mask (.png or .asc) of the raster's size: nonzero = usable, 0 = never sampled")
@@ -62,9 +70,18 @@ def main(argv=None):
     ap.add_argument("--norm", choices=("known", "window"), default="known")
     ap.add_argument("--remove-objects", action="store_true",
                     help="never sample windows that touch an above-ground object found in the DSM")
+    ap.add_argument("--model-cellsize", type=float,
+                    help="train on the raster resampled to this cell size (the raster's own comes from the header)")
+    ap.add_argument("--min-coverage", type=float, default=0.5,
+                    help="with a coarser --model-cellsize: the known share of its footprint a resampled cell needs, in (0, 1]")
     ap.add_argument("--evaluate", action="store_true", help="score the written checkpoint on held-out holes of the test split")
     ap.add_argument("--eval-json", help="with --evaluate: write the report here")
     add_spec_args(ap)
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.eval_json and not a.evaluate:
         ap.error("--eval-json needs --evaluate")
@@ -79,9 +96,18 @@ def main(argv=None):
     common = dict(nodata=nodata, window=a.window, batch_size=a.batch, block=a.block, norm=a.norm, seed=a.seed, device=device)
     if a.remove_objects:
         common.update(objects=spec_from_args(a), cellsize=float(asc_value(header, "cellsize")))
+    if a.model_cellsize is not None:
+        common.update(model_cellsize=a.model_cellsize, min_coverage=a.min_coverage,
+                      cellsize=float(asc_value(header, "cellsize")))
     tr = RasterWindowLoader(dem, mask, split="train", steps_per_epoch=a.steps, **common)
     va = RasterWindowLoader(dem, mask, split="val", steps_per_epoch=a.val_steps or max(1, a.steps // 10), augment=False,
                             **common)
+    if a.evaluate:                               # the plan of the scoring, checked before the training it would follow
+        from .evaluate_raster import HoleSpec, check_plan, native_cells
+        from .inpaint_raster import check_resample_options
+        scale = check_resample_options(common.get("cellsize"), a.model_cellsize, a.min_coverage, who="train_raster")
+        eval_block, eval_tile = native_cells(tr.block, a.window, scale, who="train_raster --evaluate")
+        check_plan(*dem.shape, "test", eval_block, eval_tile, HoleSpec(), who="train_raster --evaluate")
 
     torch.manual_seed(a.seed)
     G, D = PConvUNet().to(device), Discriminator().to(device)
@@ -100,7 +126,8 @@ def main(argv=None):
 
         from .evaluate_raster import evaluate_raster, summary
         rep, _ = evaluate_raster(a.out, dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")), split="test",
-                                 block=tr.block, tile=a.window, seed=a.seed, objects=common.get("objects"))
+                                 block=eval_block, tile=eval_tile, seed=a.seed, objects=common.get("objects"),
+                                 model_cellsize=a.model_cellsize, min_coverage=a.min_coverage)
         if a.eval_json:
             with open(a.eval_json, "w") as f:
                 json.dump(rep, f, indent=1)

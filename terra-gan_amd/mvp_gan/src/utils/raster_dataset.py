@@ -154,7 +154,8 @@ class RasterWindowLoader:
     metres: image = the normalised window (the target), mask = 1 keep / 0 hole."""
 
     def __init__(self, dem, mask=None, *, nodata=None, window=256, batch_size=16, steps_per_epoch=None, split=None, block=None,
-                 augment=True, norm="known", holes=HoleSpec(), seed=0, rank=0, world=1, device=None, objects=None, cellsize=None):
+                 augment=True, norm="known", holes=HoleSpec(), seed=0, rank=0, world=1, device=None, objects=None, cellsize=None,
+                 model_cellsize=None, min_coverage=0.5):
         if isinstance(window, (tuple, list)):
             if len(window) != 2 or int(window[0]) != int(window[1]):
                 raise ValueError(f"RasterWindowLoader: window {tuple(window)} must be square")
@@ -177,14 +178,15 @@ class RasterWindowLoader:
         if self.block < w:
             raise ValueError(f"RasterWindowLoader: block {self.block} is smaller than the window {w}")
 
+        scale = None
+        if model_cellsize is not None:
+            from ..inpaint_raster import check_resample_options
+            scale = check_resample_options(cellsize, model_cellsize, min_coverage, who="RasterWindowLoader")
         z = _host_f32(dem, "dem")
         if z.ndim != 2:
             raise ValueError(f"RasterWindowLoader: dem must be [H, W], got {z.shape}")
-        self.H, self.W = H, W = z.shape
-        if w > H or w > W:
-            raise ValueError(f"RasterWindowLoader: window {w} is larger than the raster {H}x{W}")
-        if (H + 1) * (W + 1) >= 2 ** 31:
-            raise ValueError(f"RasterWindowLoader: raster {H}x{W} too large for the int32 summed-area table")
+        if scale is None:
+            self._check_size(z.shape)
         valid = np.isfinite(z)
         if mask is not None:
             m = _host_f32(mask, "mask")
@@ -200,6 +202,17 @@ class RasterWindowLoader:
             obj = obj.cpu().numpy() != 0
             object_fraction = float(obj.mean())
             valid &= ~obj
+        if scale is not None:
+            # the keep mask (valid and no object) goes through the resampling with the raster: once, here; everything below
+            # and every window drawn later lives on the working grid
+            from ..resample import resample_raster
+            with torch.cuda.device(device):                     # None: the current device
+                zw, _, _ = resample_raster(z, valid.astype(np.float32), cellsize=cellsize, target_cellsize=model_cellsize,
+                                           min_coverage=min_coverage)
+            dem = z = zw.cpu().numpy()
+            valid = np.isfinite(z)
+            self._check_size(z.shape)
+        self.H, self.W = H, W = z.shape
         sat = np.zeros((H + 1, W + 1), np.int32)                # invalid pixels above and left of (y, x)
         np.cumsum(np.cumsum(~valid, axis=0, dtype=np.int32), axis=1, dtype=np.int32, out=sat[1:, 1:])
         self._sat = sat
@@ -222,6 +235,13 @@ class RasterWindowLoader:
         # upload layout (int32): draws [B][3] | offsets [B+1] | primitives [<= B * max_prims][8]
         self._cap = 4 * self.batch_size + 1 + 8 * self.batch_size * holes.max_prims
         self._pin, self._dev, self._ev = None, None, [None, None]
+
+    def _check_size(self, shape):
+        H, W = shape
+        if self.window > H or self.window > W:
+            raise ValueError(f"RasterWindowLoader: window {self.window} is larger than the raster {H}x{W}")
+        if (H + 1) * (W + 1) >= 2 ** 31:
+            raise ValueError(f"RasterWindowLoader: raster {H}x{W} too large for the int32 summed-area table")
 
     def _device_setup(self):
         if self.device is None:

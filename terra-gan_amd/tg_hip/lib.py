@@ -159,6 +159,8 @@ SIGNATURES = {
     "tg_vfill_finish": (I, [P, I, I, P, SZ, P, P]),
     "tg_seam_delta": (I, [P, P, I, F, P, I, I, I, P, P, P]),
     "tg_seam_apply": (I, [P, P, I, F, P, P, I, I, P, P]),
+    "tg_resample_area": (I, [P, P, I, F, I, I, I, I, I, I, P, P, I, F, I, I, P, P, P, P]),
+    "tg_resample_interp": (I, [P, P, I, F, I, I, I, I, P, P, I, F, I, I, P, P, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

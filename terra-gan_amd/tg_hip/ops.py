@@ -1245,6 +1245,54 @@ def seam_apply(dem, mask, nodata, filled, delta_filled):
     return out
 
 
+def _resample(fn, name, dem, mask, nodata, p, q, keep, extra, out_shape, count_only=False):
+    H, W = _raster_hw(dem, "dem")
+    _hip(dem, torch.float32, (H, W), "dem")
+    if mask is not None:
+        _hip(mask, torch.float32, (H, W), "mask")
+    p, q = int(p), int(q)
+    if p < 1 or q < 1:
+        raise L.TgError(f"{name}: scale {p}/{q} must be positive")
+    Ho, Wo = -(-H * q // p), -(-W * q // p)
+    if out_shape is not None:
+        if not (1 <= out_shape[0] <= Ho and 1 <= out_shape[1] <= Wo):
+            raise L.TgError(f"{name}: output {tuple(out_shape)} is no top-left crop of the {Ho}x{Wo} grid of scale {p}/{q}")
+        Ho, Wo = int(out_shape[0]), int(out_shape[1])
+    kd, km, knd = (None, None, None) if keep is None else keep
+    for t, nm in ((kd, "keep_dem"), (km, "keep_mask")):
+        if t is not None:
+            _hip(t, torch.float32, (Ho, Wo), nm)
+    out = None if count_only else torch.empty(Ho, Wo, dtype=torch.float32, device=dem.device)
+    omask = None if count_only else torch.empty(Ho, Wo, dtype=torch.float32, device=dem.device)
+    n_nan = torch.empty(1, dtype=torch.int32, device=dem.device)
+    L.check(fn(_p(dem), _p(mask), int(nodata is not None), 0.0 if nodata is None else float(nodata), H, W, p, q, *extra,
+               _p(kd), _p(km), int(knd is not None), 0.0 if knd is None else float(knd), Ho, Wo, _p(out), _p(omask), _p(n_nan),
+               _stream()), name)
+    return out, omask, n_nan
+
+
+def resample_area(dem, mask, nodata, p, q, cov_num=1, cov_den=2, keep=None, out_shape=None, count_only=False):
+    """To the coarser grid of scale p / q >= 1 (tg_resample_area) -> (out float32 [Ho][Wo] with NaN at the unknown pixels,
+    known mask float32 1 / 0, n_nan int32 [1] device counter).  An output pixel is known iff its known coverage is positive and
+    at least cov_num / cov_den of its clipped footprint.  keep: None or (dem, mask or None, nodata or None) on the output
+    grid, whose known pixels are copied through bit for bit.  out_shape: a top-left crop of the output grid (the return trip
+    to a native grid).  count_only: write no raster, return (None, None, n_nan)."""
+    return _resample(_lib().tg_resample_area, "tg_resample_area", dem, mask, nodata, p, q, keep, (int(cov_num), int(cov_den)),
+                     out_shape, count_only)
+
+
+def raster_count_unknown(dem, mask, nodata):
+    """-> int32 [1] device counter: the unknown pixels of (dem, mask, nodata).  tg_resample_area at scale 1 with no output:
+    the raster is read once and nothing is written."""
+    return resample_area(dem, mask, nodata, 1, 1, count_only=True)[2]
+
+
+def resample_interp(dem, mask, nodata, p, q, keep=None, out_shape=None):
+    """To the finer grid of scale p / q <= 1 (tg_resample_interp): bicubic where all 16 taps are known, else bilinear over the
+    known ones of the 4 nearest; returns as resample_area does."""
+    return _resample(_lib().tg_resample_interp, "tg_resample_interp", dem, mask, nodata, p, q, keep, (), out_shape)
+
+
 def _dense_layouts(t):
     """Which dense physical orders a tensor's strides describe: 'c' (row-major) and/or 'cl'."""
     out = set()
