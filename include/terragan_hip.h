@@ -622,6 +622,18 @@ int tg_vfill_setup(const float* dem, const float* mask, int use_nodata, float no
 int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t* change_bits, tg_stream_t stream);
 /* out [H][W] = dem at known pixels (bit for bit), the solution at the unknowns; NaN everywhere when K is empty. */
 int tg_vfill_finish(const float* dem, int H, int W, const void* ws, size_t ws_bytes, float* out, tg_stream_t stream);
+/* Conjugate gradients preconditioned by the V-cycle (fill_voids(solver="pcg")): for the large and the
+ * tile-aligned voids on which the plain cycle stalls.  pws: a second workspace, 256-byte aligned, >= tg_vfill_pcg_ws_bytes(H, W)
+ * (0 for the sizes tg_vfill_ws_bytes rejects), kept between the calls of one fill; the layout of ws is unchanged.
+ * tg_vfill_pcg_start runs once after tg_vfill_setup (residual, z = M r, first direction); each tg_vfill_pcg_iter is one
+ * iteration = one V-cycle and stands in for tg_vfill_cycle: change_bits [1] (device, zeroed by the call) = float bits of the
+ * largest |alpha p| over the unknown pixels (+inf when the step was skipped and the direction restarted from p = z),
+ * restarts [1] (device) = directions restarted so far.  The solution ends every iteration in the buffer tg_vfill_finish reads.
+ * Dot products are fp64 sums of per-tile partials in tile order: results are bitwise deterministic. */
+size_t tg_vfill_pcg_ws_bytes(int H, int W);
+int tg_vfill_pcg_start(int H, int W, void* ws, size_t ws_bytes, void* pws, size_t pws_bytes, tg_stream_t stream);
+int tg_vfill_pcg_iter(int H, int W, void* ws, size_t ws_bytes, void* pws, size_t pws_bytes, uint32_t* change_bits,
+                      uint32_t* restarts, tg_stream_t stream);
 
 /* ---- seam correction of a filled DSM by a harmonic delta surface (mvp_gan/src/seam_correct.py; no
  * reference counterpart) ----

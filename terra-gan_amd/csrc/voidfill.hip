@@ -8,6 +8,8 @@
 //                    by red-black SOR in one workgroup, per level an up pass (bilinear prolongation of the coarse correction,
 //                    2 sweeps); the largest change of u over the unknowns goes to change_bits
 //   tg_vfill_finish  known pixels copied bit for bit, u + c at the unknowns, NaN everywhere when nothing is known
+//   tg_vfill_pcg_*   the same cycle as the preconditioner of flexible conjugate gradients (section 8n): start after setup,
+//                    then one iteration per call in place of tg_vfill_cycle; the solution ends every iteration in level 0's u0
 //
 // Level 0 holds v = u - c (known values fixed); coarse levels hold the correction e (0 at fixed cells) with right-hand side f.
 // Every unknown cell p solves f_p + sum_{q in N4(p), inside} (v_q - v_p) = 0; the sums run over neighbour DIFFERENCES, which
@@ -429,6 +431,255 @@ __global__ __launch_bounds__(256) void vf_coarsest_kernel(VfCoarse P) {
     }
 }
 
+// ---- conjugate gradients around the V-cycle (tg_vfill_pcg_*) --------------------------------------
+// A x = b over the unknowns: A is the masked 5-point graph Laplacian, x the level-0 field v.  r = b - A x is the difference-form
+// residual sum_q (x_q - x_p) with the known values in place; A p = -sum_q (p_q - p_p) with p = 0 at the fixed cells.  The
+// vector work runs on level 0's active tiles with a 1-px halo.  Every partial dot product is stored by tile id and the slots
+// are summed in tile-id order by one workgroup, in fp64: the tile list's order (an atomic counter) never reaches a result.
+constexpr int VF_PY = VF_TY + 2, VF_PX = VF_TX + 2, VF_PXP = VF_PX + 1;
+
+struct VfPcgScal {
+    double rho, pap, rz_old, rz_new;               // r.z of the current direction, p.Ap, r'.z, r'.z'
+    float alpha, beta;
+    uint32_t restarts;                             // directions restarted from p = z
+    uint32_t restart;                              // 1: the step is skipped (alpha = 0) and the next beta is 0
+    uint32_t parity;                               // the current p is p[parity]
+    uint32_t _pad;
+};
+static_assert(sizeof(VfPcgScal) <= VF_ALIGN, "scalars fit their slot");
+
+struct VfPcg {
+    const uint8_t* flags;
+    const int32_t* list;      // nullptr on a one-level raster: the single tile 0
+    const int32_t* count;
+    int H, W, tiles_x;
+    VfPcgScal* sc;
+    const float* x_in;        // step: x (u0); dot: x' (u1)
+    float* x_out;             // step: x' (u1); dot: u0
+    float* r;
+    const float* z;
+    float* p0;
+    float* p1;
+    double* part;             // this launch's partials, by tile id
+    uint32_t* change;
+    int init;                 // step: alpha = 0 (the first residual)
+};
+
+// the sum of v over the workgroup in a fixed order; the result is valid in thread 0
+__device__ __forceinline__ double vf_block_sum(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// x' = x + alpha p (halo included) -> x_out, r' = b - A x' -> r, the tile's r'.z_old and the largest |alpha p| over the unknowns
+__global__ __launch_bounds__(256) void vf_pcg_step_kernel(VfPcg P) {
+    __shared__ float sx[VF_PY][VF_PXP];
+    __shared__ uint8_t sf[VF_PY][VF_PXP];
+    __shared__ double red[4];
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    const float alpha = P.init ? 0.f : P.sc->alpha;
+    const float* pin = P.sc->parity ? P.p1 : P.p0;
+    uint32_t mx = 0;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();                                          // the previous tile's readers are done
+        for (int j = threadIdx.x; j < VF_PY * VF_PX; j += 256) {
+            const int r = j / VF_PX, c = j - r * VF_PX;
+            const int y = y0 - 1 + r, x = x0 - 1 + c;
+            float v = 0.f;
+            uint8_t fl = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const int64_t i = (int64_t)y * W + x;
+                fl = VF_IN | P.flags[i];
+                v = P.x_in[i];
+                const bool inner = r >= 1 && r <= VF_TY && c >= 1 && c <= VF_TX;
+                if (!(fl & VF_FIX) && alpha != 0.f) {
+                    const float d = __fmul_rn(alpha, pin[i]);
+                    v = __fadd_rn(v, d);
+                    if (inner) {
+                        const uint32_t b = __float_as_uint(fabsf(d));
+                        mx = b > mx ? b : mx;
+                    }
+                }
+                if (inner) P.x_out[i] = v;
+            }
+            sx[r][c] = v;
+            sf[r][c] = fl;
+        }
+        __syncthreads();
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int ly = r + 1, lx = c + 1;
+            const int64_t i = (int64_t)y * W + x;
+            float acc = 0.f;
+            if (!(sf[ly][lx] & VF_FIX)) {
+                const float up = sx[ly][lx];
+                if (sf[ly - 1][lx] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly - 1][lx], up));
+                if (sf[ly + 1][lx] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly + 1][lx], up));
+                if (sf[ly][lx - 1] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly][lx - 1], up));
+                if (sf[ly][lx + 1] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly][lx + 1], up));
+                sum += (double)acc * (double)P.z[i];
+            }
+            P.r[i] = acc;
+        }
+        sum = vf_block_sum(sum, red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+    if (P.change) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t u = __shfl_xor(mx, o, 64);
+            mx = u > mx ? u : mx;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0 && P.sc->restart) mx = 0x7f800000u;      // a skipped step is not convergence
+        if ((threadIdx.x & 63) == 0 && mx) atomicMax(P.change, mx);
+    }
+}
+
+// the tile's r'.z'; x' moves from u1 back to u0
+__global__ __launch_bounds__(256) void vf_pcg_dot_kernel(VfPcg P) {
+    __shared__ double red[4];
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int64_t i = (int64_t)y * W + x;
+            sum += (double)P.r[i] * (double)P.z[i];               // r is 0 at the fixed cells
+            P.x_out[i] = P.x_in[i];
+        }
+        sum = vf_block_sum(sum, red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+}
+
+// p = z + beta p (halo included) -> the other p buffer, A p in difference form, the tile's p.Ap
+__global__ __launch_bounds__(256) void vf_pcg_dir_kernel(VfPcg P) {
+    __shared__ float sp[VF_PY][VF_PXP];
+    __shared__ uint8_t sf[VF_PY][VF_PXP];
+    __shared__ double red[4];
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    const float beta = P.sc->beta;
+    const bool par = P.sc->parity != 0;
+    const float* pin = par ? P.p1 : P.p0;
+    float* pout = par ? P.p0 : P.p1;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();
+        for (int j = threadIdx.x; j < VF_PY * VF_PX; j += 256) {
+            const int r = j / VF_PX, c = j - r * VF_PX;
+            const int y = y0 - 1 + r, x = x0 - 1 + c;
+            float v = 0.f;
+            uint8_t fl = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const int64_t i = (int64_t)y * W + x;
+                fl = VF_IN | P.flags[i];
+                if (!(fl & VF_FIX)) {
+                    v = P.z[i];
+                    if (beta != 0.f) v = __fadd_rn(v, __fmul_rn(beta, pin[i]));
+                }
+                if (r >= 1 && r <= VF_TY && c >= 1 && c <= VF_TX) pout[i] = v;
+            }
+            sp[r][c] = v;
+            sf[r][c] = fl;
+        }
+        __syncthreads();
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int ly = r + 1, lx = c + 1;
+            if (sf[ly][lx] & VF_FIX) continue;
+            const float up = sp[ly][lx];
+            float acc = 0.f;
+            if (sf[ly - 1][lx] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(up, sp[ly - 1][lx]));
+            if (sf[ly + 1][lx] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(up, sp[ly + 1][lx]));
+            if (sf[ly][lx - 1] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(up, sp[ly][lx - 1]));
+            if (sf[ly][lx + 1] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(up, sp[ly][lx + 1]));
+            sum += (double)up * (double)acc;
+        }
+        sum = vf_block_sum(sum, red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+}
+
+// One workgroup: the partials summed in tile-id order, then the scalars.
+//   BETA:  rho' = sum pa (r'.z'), r'.z = sum pb; beta = (rho' - r'.z) / rho, or 0 at the start, after a restart and at rho = 0
+//   !BETA: p.Ap = sum pa; alpha = rho / p.Ap, or 0 with the restart flag when that is no usable step; p's buffers swap
+template <bool BETA>
+__global__ __launch_bounds__(256) void vf_pcg_scalar_kernel(VfPcgScal* sc, const double* __restrict__ pa,
+                                                            const double* __restrict__ pb, int tiles, int first,
+                                                            uint32_t* restarts_out) {
+    __shared__ double red[2][256];
+    double a = 0.0, b = 0.0;
+    for (int t = threadIdx.x; t < tiles; t += 256) {
+        a += pa[t];
+        if (BETA) b += pb[t];
+    }
+    red[0][threadIdx.x] = a;
+    red[1][threadIdx.x] = b;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    if (BETA) {
+        const double rzn = red[0][0], rzo = red[1][0];
+        float beta = 0.f;
+        if (!first) {
+            if (sc->restart) {
+                sc->restart = 0;
+            } else if (sc->rho != 0.0) {                           // rho = 0: converged, alpha stays 0
+                const float bf = (float)((rzn - rzo) / sc->rho);
+                if (isfinite(bf)) beta = bf;
+                else ++sc->restarts;
+            }
+        }
+        sc->beta = beta;
+        sc->rz_old = rzo;
+        sc->rz_new = rzn;
+        sc->rho = rzn;
+    } else {
+        const double pap = red[0][0], rho = sc->rho;
+        float alpha = 0.f;
+        uint32_t rs = 0;
+        if (rho != 0.0) {                                          // rho = 0: converged, the step is 0
+            const float af = (float)(rho / pap);
+            if (pap > 0.0 && isfinite(af)) alpha = af;
+            else { rs = 1; ++sc->restarts; }
+        }
+        sc->pap = pap;
+        sc->alpha = alpha;
+        sc->restart = rs;
+        sc->parity ^= 1u;
+        if (restarts_out) *restarts_out = sc->restarts;
+    }
+}
+
 // ---- finish -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void vf_finish_kernel(const float* __restrict__ dem, const uint8_t* __restrict__ flags,
                                                         const VfHdr* hdr, const float* __restrict__ u, int64_t n,
@@ -526,17 +777,17 @@ extern "C" int tg_vfill_setup(const float* dem, const float* mask, int use_nodat
     return TG_OK;
 }
 
-extern "C" int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t* change_bits, tg_stream_t stream) {
-    VfPlan p;
-    if (int rc = vf_ws_check("tg_vfill_cycle", H, W, ws, ws_bytes, &p)) return rc;
-    TG_REQUIRE(change_bits, "tg_vfill_cycle: null pointer");
-    const hipStream_t s = S(stream);
-    char* base = (char*)ws;
+// The launches of one V-cycle.  pre == nullptr: the plain cycle on level 0's u0 / u1.  With pre the cycle is the preconditioner
+// of tg_vfill_pcg_*: level 0 is treated as a coarse level (start from 0, right-hand side pre->r, sweeps into pre->d, result
+// in pre->z) and no change is taken.
+struct VfPre {
+    const float* r;
+    float* d;
+    float* z;
+};
+
+static int vf_launch_cycle(const VfPlan& p, char* base, const VfPre* pre, uint32_t* change_bits, hipStream_t s) {
     VfHdr* hdr = (VfHdr*)base;
-    if (hipMemsetAsync(change_bits, 0, sizeof(uint32_t), s) != hipSuccess) {
-        tg_set_error("tg_vfill_cycle: hipMemsetAsync failed");
-        return TG_ERR_LAUNCH;
-    }
     const int L = p.L;
     auto F = [&](size_t off) { return (float*)(base + off); };
     auto U8 = [&](size_t off) { return (const uint8_t*)(base + off); };
@@ -547,7 +798,7 @@ extern "C" int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t*
         a.list = (const int32_t*)(base + v.list);
         a.count = &hdr->ntiles[l];
         a.H = v.H; a.W = v.W; a.tiles_x = v.tiles_x;
-        a.rhs = l > 0 ? F(v.f) : nullptr;
+        a.rhs = l > 0 ? F(v.f) : (pre ? pre->r : nullptr);
         a.Hn = p.lv[l + 1].H; a.Wn = p.lv[l + 1].W;
         return a;
     };
@@ -555,27 +806,27 @@ extern "C" int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t*
     for (int l = 0; l < L - 1; ++l) {
         const VfLevel& v = p.lv[l];
         VfPass a = pass(l);
-        a.in = l == 0 ? F(v.u0) : nullptr;
-        a.out = F(v.u1);
+        a.in = l == 0 && !pre ? F(v.u0) : nullptr;
+        a.out = l == 0 && pre ? pre->d : F(v.u1);
         a.f_next = F(p.lv[l + 1].f);
         a.flags_next = U8(p.lv[l + 1].flags);
         a.rscale = (v.H == 1 || v.W == 1) ? 2.f : 1.f;
         const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
-        if (l == 0) hipLaunchKernelGGL((vf_pass_kernel<false, true>), g, dim3(256), 0, s, a);
+        if (l == 0 && !pre) hipLaunchKernelGGL((vf_pass_kernel<false, true>), g, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((vf_pass_kernel<false, false>), g, dim3(256), 0, s, a);
         TG_CHECK_LAUNCH("vf_pass_kernel<down>");
     }
     {
         const VfLevel& v = p.lv[L - 1];
         VfCoarse c;
-        c.in = L == 1 ? F(v.u0) : nullptr;
-        c.out = F(v.u0);
-        c.rhs = L == 1 ? nullptr : F(v.f);
+        c.in = L == 1 && !pre ? F(v.u0) : nullptr;
+        c.out = L == 1 && pre ? pre->z : F(v.u0);
+        c.rhs = L == 1 ? (pre ? pre->r : nullptr) : F(v.f);
         c.flags = U8(v.flags);
         c.H = v.H; c.W = v.W;
         c.sweeps = vf_sweeps(v.H, v.W);
         c.omega = vf_omega(v.H, v.W);
-        c.change = L == 1 ? change_bits : nullptr;
+        c.change = L == 1 && !pre ? change_bits : nullptr;
         hipLaunchKernelGGL(vf_coarsest_kernel, dim3(1), dim3(256), 0, s, c);
         TG_CHECK_LAUNCH("vf_coarsest_kernel");
     }
@@ -583,16 +834,28 @@ extern "C" int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t*
     for (int l = L - 2; l >= 0; --l) {
         const VfLevel& v = p.lv[l];
         VfPass a = pass(l);
-        a.in = F(v.u1);
-        a.out = F(v.u0);
+        a.in = l == 0 && pre ? pre->d : F(v.u1);
+        a.out = l == 0 && pre ? pre->z : F(v.u0);
         a.e_next = F(p.lv[l + 1].u0);
-        a.change = l == 0 ? change_bits : nullptr;
+        a.change = l == 0 && !pre ? change_bits : nullptr;
         const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
-        if (l == 0) hipLaunchKernelGGL((vf_pass_kernel<true, true>), g, dim3(256), 0, s, a);
+        if (l == 0 && !pre) hipLaunchKernelGGL((vf_pass_kernel<true, true>), g, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((vf_pass_kernel<true, false>), g, dim3(256), 0, s, a);
         TG_CHECK_LAUNCH("vf_pass_kernel<up>");
     }
     return TG_OK;
+}
+
+extern "C" int tg_vfill_cycle(int H, int W, void* ws, size_t ws_bytes, uint32_t* change_bits, tg_stream_t stream) {
+    VfPlan p;
+    if (int rc = vf_ws_check("tg_vfill_cycle", H, W, ws, ws_bytes, &p)) return rc;
+    TG_REQUIRE(change_bits, "tg_vfill_cycle: null pointer");
+    const hipStream_t s = S(stream);
+    if (hipMemsetAsync(change_bits, 0, sizeof(uint32_t), s) != hipSuccess) {
+        tg_set_error("tg_vfill_cycle: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    return vf_launch_cycle(p, (char*)ws, nullptr, change_bits, s);
 }
 
 extern "C" int tg_vfill_finish(const float* dem, int H, int W, const void* ws, size_t ws_bytes, float* out,
@@ -606,4 +869,121 @@ extern "C" int tg_vfill_finish(const float* dem, int H, int W, const void* ws, s
                        (const VfHdr*)base, (const float*)(base + p.lv[0].u0), n, out);
     TG_CHECK_LAUNCH("vf_finish_kernel");
     return TG_OK;
+}
+
+// ---- conjugate gradients: host side ----------------------------------------------------------------------------------------
+// the second workspace (mirrored by vfill_pcg_layout in mvp_gan/src/fill_voids.py)
+struct VfPcgPlan {
+    size_t r, z, p0, p1, d, part[3];               // byte offsets; part: p.Ap, r'.z, r'.z' by tile id
+    size_t bytes;
+};
+
+static void vf_pcg_plan(const VfPlan& p, VfPcgPlan* q) {
+    const size_t n = (size_t)p.lv[0].H * p.lv[0].W;
+    size_t off = VF_ALIGN;                         // VfPcgScal
+    q->r = off; off += al(n * 4);
+    q->z = off; off += al(n * 4);
+    q->p0 = off; off += al(n * 4);
+    q->p1 = off; off += al(n * 4);
+    q->d = off; off += al(n * 4);
+    for (int k = 0; k < 3; ++k) { q->part[k] = off; off += al((size_t)p.lv[0].tiles * 8); }
+    q->bytes = off;
+}
+
+static int vf_pws_check(const char* who, const VfPlan& p, const void* pws, size_t pws_bytes, VfPcgPlan* q) {
+    TG_REQUIRE(pws, "%s: null pointer", who);
+    TG_REQUIRE(((uintptr_t)pws & (VF_ALIGN - 1)) == 0, "%s: pcg workspace must be %d-byte aligned", who, VF_ALIGN);
+    vf_pcg_plan(p, q);
+    if (pws_bytes < q->bytes) {
+        tg_set_error("%s: pcg workspace %zu bytes < %zu", who, pws_bytes, q->bytes);
+        return TG_ERR_WS;
+    }
+    return TG_OK;
+}
+
+extern "C" size_t tg_vfill_pcg_ws_bytes(int H, int W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    VfPlan p;
+    VfPcgPlan q;
+    vf_plan(H, W, &p);
+    vf_pcg_plan(p, &q);
+    return q.bytes;
+}
+
+// step (or the first residual), z = M r, r.z, beta, the new direction and p.Ap, alpha
+static int vf_pcg_launch(const VfPlan& p, const VfPcgPlan& q, char* base, char* pb, bool first,
+                         uint32_t* change_bits, uint32_t* restarts, hipStream_t s) {
+    const VfLevel& v = p.lv[0];
+    VfHdr* hdr = (VfHdr*)base;
+    VfPcgScal* sc = (VfPcgScal*)pb;
+    auto F = [&](size_t off) { return (float*)(pb + off); };
+    auto D = [&](int k) { return (double*)(pb + q.part[k]); };
+    VfPcg a = {};
+    a.flags = (const uint8_t*)(base + v.flags);
+    a.list = p.L > 1 ? (const int32_t*)(base + v.list) : nullptr;
+    a.count = &hdr->ntiles[0];
+    a.H = v.H; a.W = v.W; a.tiles_x = v.tiles_x;
+    a.sc = sc;
+    a.r = F(q.r); a.z = F(q.z); a.p0 = F(q.p0); a.p1 = F(q.p1);
+    const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
+
+    VfPcg st = a;
+    st.x_in = (const float*)(base + v.u0);
+    st.x_out = (float*)(base + v.u1);
+    st.part = D(1);
+    st.change = change_bits;
+    st.init = first ? 1 : 0;
+    hipLaunchKernelGGL(vf_pcg_step_kernel, g, dim3(256), 0, s, st);
+    TG_CHECK_LAUNCH("vf_pcg_step_kernel");
+
+    const VfPre pre = {F(q.r), F(q.d), F(q.z)};
+    if (int rc = vf_launch_cycle(p, base, &pre, nullptr, s)) return rc;
+
+    VfPcg dt = a;
+    dt.x_in = (const float*)(base + v.u1);
+    dt.x_out = (float*)(base + v.u0);
+    dt.part = D(2);
+    hipLaunchKernelGGL(vf_pcg_dot_kernel, g, dim3(256), 0, s, dt);
+    TG_CHECK_LAUNCH("vf_pcg_dot_kernel");
+    hipLaunchKernelGGL((vf_pcg_scalar_kernel<true>), dim3(1), dim3(256), 0, s, sc, (const double*)D(2), (const double*)D(1),
+                       v.tiles, first ? 1 : 0, (uint32_t*)nullptr);
+    TG_CHECK_LAUNCH("vf_pcg_scalar_kernel<beta>");
+
+    VfPcg dr = a;
+    dr.part = D(0);
+    hipLaunchKernelGGL(vf_pcg_dir_kernel, g, dim3(256), 0, s, dr);
+    TG_CHECK_LAUNCH("vf_pcg_dir_kernel");
+    hipLaunchKernelGGL((vf_pcg_scalar_kernel<false>), dim3(1), dim3(256), 0, s, sc, (const double*)D(0), (const double*)nullptr,
+                       v.tiles, 0, restarts);
+    TG_CHECK_LAUNCH("vf_pcg_scalar_kernel<alpha>");
+    return TG_OK;
+}
+
+extern "C" int tg_vfill_pcg_start(int H, int W, void* ws, size_t ws_bytes, void* pws, size_t pws_bytes, tg_stream_t stream) {
+    VfPlan p;
+    VfPcgPlan q;
+    if (int rc = vf_ws_check("tg_vfill_pcg_start", H, W, ws, ws_bytes, &p)) return rc;
+    if (int rc = vf_pws_check("tg_vfill_pcg_start", p, pws, pws_bytes, &q)) return rc;
+    const hipStream_t s = S(stream);
+    // scalars, partials of the inactive tiles, and r, z, p and the down-pass scratch outside the active tiles start at 0
+    if (hipMemsetAsync(pws, 0, q.bytes, s) != hipSuccess) {
+        tg_set_error("tg_vfill_pcg_start: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    return vf_pcg_launch(p, q, (char*)ws, (char*)pws, true, nullptr, nullptr, s);
+}
+
+extern "C" int tg_vfill_pcg_iter(int H, int W, void* ws, size_t ws_bytes, void* pws, size_t pws_bytes, uint32_t* change_bits,
+                                 uint32_t* restarts, tg_stream_t stream) {
+    VfPlan p;
+    VfPcgPlan q;
+    if (int rc = vf_ws_check("tg_vfill_pcg_iter", H, W, ws, ws_bytes, &p)) return rc;
+    if (int rc = vf_pws_check("tg_vfill_pcg_iter", p, pws, pws_bytes, &q)) return rc;
+    TG_REQUIRE(change_bits && restarts, "tg_vfill_pcg_iter: null pointer");
+    const hipStream_t s = S(stream);
+    if (hipMemsetAsync(change_bits, 0, sizeof(uint32_t), s) != hipSuccess) {
+        tg_set_error("tg_vfill_pcg_iter: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    return vf_pcg_launch(p, q, (char*)ws, (char*)pws, false, change_bits, restarts, s);
 }

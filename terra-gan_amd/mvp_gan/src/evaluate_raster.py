@@ -30,7 +30,7 @@ seam correction (mvp_gan/src/seam_correct.py), and the ring errors show what it 
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
-         [--baseline laplace] [--fallback laplace] [--seam harmonic] [--model-cellsize 1.0 [--min-coverage 0.5]]
+         [--baseline laplace] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -384,14 +384,14 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 
 @torch.no_grad()
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10):
+                    quantiles=QUANTILES, top=10, solver="mg"):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
     fill info under "fill"."""
     from .fill_voids import fill_voids
     device = _device()
     z = _f32(dem, device, "dem")
     k = _f32(keep, device, "keep", binary=True)
-    bpred, finfo = fill_voids(z, k, nodata=_nodata(nodata), method=method)
+    bpred, finfo = fill_voids(z, k, nodata=_nodata(nodata), method=method, solver=solver)
     rep = terrain_errors(z, bpred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top)
     rep["method"] = method
@@ -402,24 +402,28 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5):
+                    quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
+                    solver="mg"):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
-    checkpoint whose training blocks were picked on the working grid), and seam="harmonic" adds report["seam"]."""
+    checkpoint whose training blocks were picked on the working grid), and seam="harmonic" adds report["seam"].  solver is the
+    fill_voids solver of the baseline, the seam correction and the fallback ("mg" or "pcg"); "pcg" shows in their infos."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
-                             seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage)
+                             seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
-              min_coverage=0.5):
+              min_coverage=0.5, solver="mg"):
     """evaluate_raster, plus the hole map."""
+    from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
     _check_fill_options(baseline, fallback)
+    check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
     c = _cellsize(cellsize, "evaluate_raster")
     check_resample_options(c, model_cellsize, min_coverage, who="evaluate_raster")
@@ -434,7 +438,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
                                  objects=objects, cellsize=c)
     pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
                                  fallback=fallback, seam=seam, cellsize=c, model_cellsize=model_cellsize,
-                                 min_coverage=min_coverage)
+                                 min_coverage=min_coverage, solver=solver)
     sinfo = iinfo.get("seam")
     rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top)
@@ -445,7 +449,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["seam"] = sinfo
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
-                                          area_edges_m2=area_edges_m2, quantiles=quantiles, top=top)
+                                          area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver)
     return rep, pred, hm
 
 
@@ -491,6 +495,8 @@ def build_parser():
                     help="also score a harmonic interpolation (fill_voids) of the same holes: a second summary line")
     ap.add_argument("--fallback", choices=("laplace",),
                     help="checkpoint mode: fill the holes no window reaches by harmonic interpolation")
+    ap.add_argument("--solver", choices=("mg", "pcg"), default="mg",
+                    help="solver of --baseline, --fallback and --seam: V-cycles, or conjugate gradients around them")
     ap.add_argument("--seam", choices=SEAMS,
                     help="checkpoint mode: correct the filled holes towards the known terrain around them (seam_correct)")
     ap.add_argument("--model-cellsize", type=float,
@@ -527,7 +533,7 @@ def main(argv=None):
                                   holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
-                                  min_coverage=a.min_coverage)
+                                  min_coverage=a.min_coverage, solver=a.solver)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -539,7 +545,8 @@ def main(argv=None):
         rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata)
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
         if a.baseline:
-            rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline)
+            rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
+                                              solver=a.solver)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -557,7 +564,8 @@ def main(argv=None):
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
               f"{sm['cycles']} cycles, converged {sm['converged']}")
     if "baseline" in rep:
-        print(f"baseline {rep['baseline']['method']}: {summary(rep['baseline'])}")
+        how = "" if a.solver == "mg" else f" (solver {a.solver})"
+        print(f"baseline {rep['baseline']['method']}{how}: {summary(rep['baseline'])}")
     return rep
 
 

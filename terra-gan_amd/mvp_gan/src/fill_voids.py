@@ -9,12 +9,16 @@ GAN against, and a fill for the voids no inpainting window reaches.
     (a natural, Neumann, border), with u = z on K; when K is not empty the solution is unique;
   - known pixels come back bit for bit; when K is empty every pixel is NaN and info["unfilled"] = H * W;
   - V-cycles run until the largest change of one cycle over the unknowns is at most `tol` (default 1e-6 x the range of z
-    over K), at most `max_cycles`; running out is not an error: info["converged"] is then False.
+    over K), at most `max_cycles`; running out is not an error: info["converged"] is then False;
+  - solver="pcg" runs flexible conjugate gradients with the same V-cycle as the preconditioner: one
+    iteration is one cycle, and `tol`, `max_cycles`, info["cycles"] and info["change"] (the largest step of an iteration)
+    keep their meaning.  It is the solver for large and for tile-aligned voids (a missing tile of a mosaic), on which the
+    plain cycle converges slowly or not at all; info gains "solver" and "restarts".  The default "mg" is unchanged.
 
 Two calls on the same inputs return bitwise-equal rasters and equal info.
 
 CLI: python -m mvp_gan.src.fill_voids --dem in.asc [--mask m.png|m.asc] [--nodata v] [--remove-objects [spec flags]]
-         [--tol t] [--max-cycles n] --out out.asc
+         [--tol t] [--max-cycles n] [--solver mg|pcg] --out out.asc
 """
 import argparse
 import math
@@ -23,6 +27,7 @@ import numpy as np
 import torch
 
 METHODS = ("laplace",)
+SOLVERS = ("mg", "pcg")
 CMAX = 16                      # coarsest level: longer side at most this
 TILE_Y, TILE_X = 32, 64        # tiles of the level passes
 ALIGN = 256
@@ -66,6 +71,29 @@ def vfill_layout(H, W):
             off += _al(4 * n)
         out.append(lv)
     return out, off
+
+
+def vfill_pcg_layout(H, W):
+    """-> (dict: r, z, p0, p1, d, part (3 offsets: p.Ap, r'.z, r'.z' by tile id) byte offsets, total bytes) of the second
+    workspace of the pcg solver (tg_vfill_pcg_ws_bytes); the scalars sit in the first ALIGN bytes."""
+    n = int(H) * int(W)
+    tiles = -(-int(H) // TILE_Y) * -(-int(W) // TILE_X)
+    off = ALIGN
+    out = {"tiles": tiles}
+    for k in ("r", "z", "p0", "p1", "d"):
+        out[k] = off
+        off += _al(4 * n)
+    out["part"] = []
+    for _ in range(3):
+        out["part"].append(off)
+        off += _al(8 * tiles)
+    return out, off
+
+
+def check_solver(solver, who="fill_voids"):
+    if not isinstance(solver, str) or solver not in SOLVERS:
+        raise ValueError(f"{who}: solver {solver!r} must be one of {SOLVERS}")
+    return solver
 
 
 # ---- validation -----------------------------------------------------------------------------------------------------
@@ -121,12 +149,15 @@ def _bits_f32(b):
 
 # ---- the fill -------------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_cycles=50, objects=None, cellsize=None):
+def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_cycles=50, objects=None, cellsize=None,
+               solver="mg"):
     """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, nonzero = known (optional).
-    Returns (raster float32 HIP tensor [H][W], info dict: unknown, unfilled, cycles, change, tol, converged, levels, and with
-    objects the object_mask info under "objects")."""
+    solver: "mg" (V-cycles) or "pcg" (conjugate gradients around the V-cycle; one iteration counts as one cycle).
+    Returns (raster float32 HIP tensor [H][W], info dict: unknown, unfilled, cycles, change, tol, converged, levels, with
+    objects the object_mask info under "objects", and with solver="pcg" also solver and restarts)."""
     from tg_hip import ops as O
     H, W, c = check_args(dem, mask, method, tol, max_cycles, objects, cellsize)
+    check_solver(solver)
     if not torch.cuda.is_available():
         raise RuntimeError("fill_voids: no HIP device visible; this build has no CPU path")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -143,8 +174,21 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
     known, unknown = int(st[0]), int(st[1])
     rng = _bits_f32(st[3]) - _bits_f32(st[2]) if known else 0.0
     t = 1e-6 * rng if tol is None else float(tol)
-    cycles, change, converged = 0, 0.0, known > 0
-    if known and unknown:
+    cycles, change, converged, restarts = 0, 0.0, known > 0, 0
+    if known and unknown and solver == "pcg":
+        converged = False
+        pws = O.vfill_pcg_ws(H, W, device)
+        O.vfill_pcg_start(H, W, ws, pws)
+        st = torch.zeros(2, dtype=torch.int32, device=device)  # change bits, restarts
+        while cycles < max_cycles:
+            O.vfill_pcg_iter(H, W, ws, pws, st)
+            cycles += 1
+            change = _bits_f32(st[0].item())                    # one read per iteration
+            if change <= t:
+                converged = True
+                break
+        restarts = int(st[1].item())
+    elif known and unknown:
         converged = False
         ch = torch.empty(1, dtype=torch.int32, device=device)
         while cycles < max_cycles:
@@ -157,6 +201,9 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
     out = O.vfill_finish(z, ws)
     info = {"unknown": unknown, "unfilled": 0 if known else H * W, "cycles": cycles, "change": change, "tol": t,
             "converged": converged, "levels": len(vfill_levels(H, W))}
+    if solver == "pcg":
+        info["solver"] = solver
+        info["restarts"] = restarts
     if oinfo is not None:
         info["objects"] = oinfo
     return out, info
@@ -174,6 +221,8 @@ def build_parser():
     add_spec_args(ap)
     ap.add_argument("--tol", type=float, help="stop when a cycle changes no void pixel by more (default 1e-6 x range)")
     ap.add_argument("--max-cycles", type=int, default=50)
+    ap.add_argument("--solver", choices=SOLVERS, default="mg",
+                    help="mg: V-cycles; pcg: conjugate gradients around the V-cycle, for large or tile-aligned voids")
     ap.add_argument("--out", required=True, help="output .asc raster")
     return ap
 
@@ -188,11 +237,11 @@ def main(argv=None):
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
     objects = spec_from_args(a) if a.remove_objects else None
     out, info = fill_voids(dem, mask, nodata=nodata, tol=a.tol, max_cycles=a.max_cycles, objects=objects,
-                           cellsize=float(asc_value(header, "cellsize")))
+                           cellsize=float(asc_value(header, "cellsize")), solver=a.solver)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)
-    print(f"{a.out}: {info['unknown']} void pixels, {info['cycles']} cycles, converged {info['converged']}")
+    print(f"{a.out}: {info['unknown']} void pixels, {info['cycles']} cycles, converged {info['converged']}, solver {a.solver}")
     if not info["converged"]:
         print(f"warning: not converged: last change {info['change']:.3g} > tol {info['tol']:.3g} after {info['cycles']} "
               "cycles" if info["unknown"] and info["unfilled"] == 0 else "warning: nothing is known: every pixel is NaN")

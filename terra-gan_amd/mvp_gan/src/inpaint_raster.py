@@ -32,7 +32,7 @@ the known pixels' bits copied through; the seam correction and the fallback then
 info["resample"] holds the scale, the working shape and cell size and the hole counts of both grids.
 
 CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --checkpoint ck.pth --out out.asc
-         [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]] [--fallback laplace]
+         [--remove-objects [spec flags] [--objects-out objects.png|objects.asc]] [--fallback laplace] [--solver mg|pcg]
          [--seam harmonic [--seam-order 0|1]] [--model-cellsize 1.0 [--min-coverage 0.5]]
 """
 import argparse
@@ -215,17 +215,22 @@ def _inpaint_windows(generator_or_checkpoint, z, m, nodata, window, overlap, bat
 
 @torch.no_grad()
 def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, window=512, overlap=64, batch=16, objects=None,
-                   cellsize=None, fallback=None, seam=None, seam_order=1, model_cellsize=None, min_coverage=0.5):
+                   cellsize=None, fallback=None, seam=None, seam_order=1, model_cellsize=None, min_coverage=0.5,
+                   solver="mg"):
     """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, 1 = keep, 0 = hole (optional).
     objects: an ObjectSpec to remove the above-ground objects first (cellsize, metres per pixel, is then required).
     fallback: None or "laplace": fill the holes no running window covers with fill_voids.
     seam: None or "harmonic": correct the filled holes towards the known terrain around them (correct_seams, seam_order 0 or 1).
+    solver: the fill_voids solver of the seam correction and the fallback, "mg" or "pcg" (DESIGN.md section 8n); with "pcg" the
+    fallback runs with fill_voids' default budget and its info gains solver and restarts.
     model_cellsize: the cell size the generator was trained at; when it differs from cellsize (then required) the windows run
     on the raster resampled to it (min_coverage: the known share of its footprint a coarser working pixel needs to be known).
     Returns (raster float32 HIP tensor [H][W], info dict: windows, run, unfilled, with objects the object_mask info under
     "objects", with a working grid its description under "resample", with a seam correction its info under "seam", with a
     fallback its pixels, cycles and converged flag under "fallback")."""
+    from .fill_voids import check_solver
     scale = check_resample_options(cellsize, model_cellsize, min_coverage)
+    check_solver(solver, who="inpaint_raster")
     if not torch.cuda.is_available():
         raise RuntimeError("inpaint_raster: no HIP device visible; this build has no CPU path")
     if batch < 1:
@@ -269,15 +274,21 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
         info["resample"] = rinfo
     if seam is not None:
         from .seam_correct import correct_seams
-        out, info["seam"] = correct_seams(z, out, m, nodata=nodata, order=seam_order)
+        out, info["seam"] = correct_seams(z, out, m, nodata=nodata, order=seam_order, solver=solver)
     if fallback is not None:
         info["fallback"] = {"pixels": info["unfilled"], "cycles": 0, "converged": True}
         if info["unfilled"]:
             from .fill_voids import fill_voids
             # every finite pixel fixed: only the NaN holes change.  They are the voids wider than a window, where a V-cycle
             # contracts the change by about 0.77, hence a larger budget than fill_voids' default
-            out, finfo = fill_voids(out, method=fallback, max_cycles=FALLBACK_MAX_CYCLES)
+            # with the plain cycle; conjugate gradients need no such budget
+            if solver == "mg":
+                out, finfo = fill_voids(out, method=fallback, max_cycles=FALLBACK_MAX_CYCLES)
+            else:
+                out, finfo = fill_voids(out, method=fallback, solver=solver)
             info["fallback"] = {"pixels": finfo["unknown"], "cycles": finfo["cycles"], "converged": finfo["converged"]}
+            if solver != "mg":
+                info["fallback"].update(solver=solver, restarts=finfo["restarts"])
             info["unfilled"] = finfo["unfilled"]
     return out, info
 
@@ -309,6 +320,8 @@ def build_parser():
     ap.add_argument("--objects-out", help="with --remove-objects: write the object map (.png or .asc, nonzero = object)")
     ap.add_argument("--fallback", choices=("laplace",),
                     help="fill the holes no window reaches by harmonic interpolation (fill_voids) instead of leaving NaN")
+    ap.add_argument("--solver", choices=("mg", "pcg"), default="mg",
+                    help="solver of --fallback and --seam: V-cycles, or conjugate gradients around them (large or aligned voids)")
     ap.add_argument("--seam", choices=SEAMS,
                     help="correct the filled holes towards the known terrain around them: no step at the hole outlines")
     ap.add_argument("--seam-order", type=int, choices=(0, 1), default=1,
@@ -340,7 +353,7 @@ def main(argv=None):
     out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch,
                                fallback=a.fallback, seam=a.seam, seam_order=a.seam_order,
                                cellsize=float(asc_value(header, "cellsize")), model_cellsize=a.model_cellsize,
-                               min_coverage=a.min_coverage)
+                               min_coverage=a.min_coverage, solver=a.solver)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)

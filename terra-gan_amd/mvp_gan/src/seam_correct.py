@@ -20,7 +20,7 @@ neighbour (nothing is known, or no hole is filled) the fill comes back unchanged
 Two calls on the same inputs return bitwise-equal rasters and equal info.
 
 CLI: python -m mvp_gan.src.seam_correct --dem in.asc --filled fill.asc [--mask keep.png|keep.asc] [--nodata v] [--order 0|1]
-         [--tol t] [--max-cycles n] --out out.asc
+         [--tol t] [--max-cycles n] [--solver mg|pcg] --out out.asc
 """
 import argparse
 import math
@@ -28,7 +28,7 @@ import math
 import numpy as np
 import torch
 
-from .fill_voids import _bits_f32, _device_f32, _shape, check_args
+from .fill_voids import SOLVERS, _bits_f32, _device_f32, _shape, check_args, check_solver
 
 ORDERS = (0, 1)
 MAX_CYCLES = 200               # the budget of inpaint_raster's fallback: holes as wide as a window converge slowly
@@ -45,13 +45,14 @@ def check_seam_args(dem, filled, mask, order, tol, max_cycles, who="correct_seam
 
 
 @torch.no_grad()
-def correct_seams(dem, filled, mask=None, *, nodata=None, order=1, tol=None, max_cycles=MAX_CYCLES):
+def correct_seams(dem, filled, mask=None, *, nodata=None, order=1, tol=None, max_cycles=MAX_CYCLES, solver="mg"):
     """dem, filled: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, nonzero = known (optional).
     Returns (raster float32 HIP tensor [H][W], info dict: ring, interior, unfilled, order, max_delta, cycles, change, tol,
-    converged)."""
+    converged; solver: the fill_voids solver of the delta surface, "pcg" adds solver and restarts to the info)."""
     from tg_hip import ops as O
     from .fill_voids import fill_voids
     check_seam_args(dem, filled, mask, order, tol, max_cycles)
+    check_solver(solver, who="correct_seams")
     if not torch.cuda.is_available():
         raise RuntimeError("correct_seams: no HIP device visible; this build has no CPU path")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -64,12 +65,16 @@ def correct_seams(dem, filled, mask=None, *, nodata=None, order=1, tol=None, max
     ring, interior, unfilled, bits = counts.cpu().tolist()      # the one sync before the solve
     info = {"ring": ring, "interior": interior, "unfilled": unfilled, "order": int(order), "max_delta": _bits_f32(bits)}
     if ring:
-        delta, f = fill_voids(delta, tol=tol, max_cycles=max_cycles)
+        delta, f = fill_voids(delta, tol=tol, max_cycles=max_cycles, solver=solver)
         info.update(cycles=f["cycles"], change=f["change"], tol=f["tol"], converged=f["converged"])
+        if solver != "mg":
+            info.update(solver=solver, restarts=f["restarts"])
     else:
         # no rim to correct against: g + (-0) = g bit for bit
         delta = torch.full_like(delta, -0.0)
         info.update(cycles=0, change=0.0, tol=0.0 if tol is None else float(tol), converged=True)
+        if solver != "mg":
+            info.update(solver=solver, restarts=0)
     return O.seam_apply(z, m, nodata, g, delta), info
 
 
@@ -84,6 +89,8 @@ def build_parser():
                     help="1: continue the known slope across the rim (exact on planes); 0: the rim value (robust to noise)")
     ap.add_argument("--tol", type=float, help="stop when a cycle changes no delta by more (default 1e-6 x the delta's range)")
     ap.add_argument("--max-cycles", type=int, default=MAX_CYCLES)
+    ap.add_argument("--solver", choices=SOLVERS, default="mg",
+                    help="solver of the delta surface: V-cycles, or conjugate gradients around them for large or aligned holes")
     ap.add_argument("--out", required=True, help="output .asc raster")
     return ap
 
@@ -100,7 +107,8 @@ def main(argv=None):
         fill = np.where(fill == np.float32(fnd), np.float32(np.nan), fill)       # unfilled cells stay unfilled
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
-    out, info = correct_seams(dem, fill, mask, nodata=nodata, order=a.order, tol=a.tol, max_cycles=a.max_cycles)
+    out, info = correct_seams(dem, fill, mask, nodata=nodata, order=a.order, tol=a.tol, max_cycles=a.max_cycles,
+                              solver=a.solver)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)

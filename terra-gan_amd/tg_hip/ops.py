@@ -1209,6 +1209,31 @@ def vfill_finish(dem, ws, out=None):
     return out
 
 
+def vfill_pcg_ws(H, W, device):
+    """The second workspace of the pcg solver (tg_vfill_pcg_ws_bytes): r, z, p twice, the down-pass scratch, partials, scalars."""
+    nb = _lib().tg_vfill_pcg_ws_bytes(int(H), int(W))
+    if nb == 0:
+        raise L.TgError(f"vfill: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def vfill_pcg_start(H, W, ws, pws):
+    """After vfill_setup: the residual, z = M r, the first direction and its step length (tg_vfill_pcg_start)."""
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    _hip(pws, torch.uint8, (pws.numel(),), "pws")
+    L.check(_lib().tg_vfill_pcg_start(int(H), int(W), _p(ws), ws.numel(), _p(pws), pws.numel(), _stream()), "tg_vfill_pcg_start")
+
+
+def vfill_pcg_iter(H, W, ws, pws, state):
+    """One iteration = one V-cycle (tg_vfill_pcg_iter); state int32 [2] gets the float bits of the largest change over the
+    unknowns and the number of restarted directions."""
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    _hip(pws, torch.uint8, (pws.numel(),), "pws")
+    _hip(state, torch.int32, (2,), "state")
+    L.check(_lib().tg_vfill_pcg_iter(int(H), int(W), _p(ws), ws.numel(), _p(pws), pws.numel(), _p(state), _p(state[1:]),
+                                     _stream()), "tg_vfill_pcg_iter")
+
+
 SEAM_NCOUNTS = 4                                  # tg_seam_delta counts: ring, interior, unfilled, max |delta| bits
 
 
