@@ -373,7 +373,9 @@ int tg_adam(float* p, const float* g, float* m, float* v, int64_t n, double lr, 
 
 /* Multi-tensor form: ONE launch over a device-resident table of segments (whole parameter tensors) and a
  * device-resident work list of int32 pairs (segment index, chunk index); chunk c of a segment covers elements
- * [c*chunk_elems, min(n, (c+1)*chunk_elems)).  All segments share lr/betas/eps/step. */
+ * [c*chunk_elems, min(n, (c+1)*chunk_elems)).  All segments share lr/betas/eps/step.  chunk_elems must be a positive
+ * multiple of 4 (a segment whose four pointers are 16-byte aligned is walked with 16-byte accesses from each chunk's first
+ * element); any other value is refused.  Segments need no alignment: an unaligned one takes the scalar path. */
 typedef struct TgAdamSeg {
     float* p;
     const float* g;

@@ -2231,18 +2231,29 @@ extern "C" int tg_bce_logits(const float* z, int64_t n, float target, float coef
 // =================================================================================================
 // Adam, axpby, lincomb, layout transposes
 // =================================================================================================
+// One element of the update, every rounding written out: tg_adam, the 16-byte loop and the scalar loop of tg_adam_multi all go
+// through it, so the three give the same bits on the same data.  (Left to the compiler, the 16-byte loop fused the multiply-adds
+// of the lerp and of the addcmul and the two scalar loops did not; this is the 16-byte loop's sequence, the one nearly every
+// element of a train step takes.)  g * grad_scale - m is one fused operation in all of them.
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float one_minus_b1, float b2, float one_minus_b2,
+                                          float step_size, float bc2_sqrt, float eps, float grad_scale) {
+#pragma clang fp contract(off)
+    const float gr = g * grad_scale;
+    m = __fmaf_rn(one_minus_b1, __fmaf_rn(g, grad_scale, -m), m);      // exp_avg.lerp_(grad, 1 - beta1)
+    v = __fmaf_rn(v, b2, (one_minus_b2 * gr) * gr);                    // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    const float denom = sqrtf(v) / bc2_sqrt + eps;                     // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+    p = __fmaf_rn(-step_size, m / denom, p);                           // addcdiv_(exp_avg, denom, value=-step_size)
+}
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, int64_t n, float one_minus_b1, float b2,
                                                    float one_minus_b2, float step_size, float bc2_sqrt, float eps,
                                                    float grad_scale) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float gr = g[i] * grad_scale;
-        const float mi = m[i] + one_minus_b1 * (gr - m[i]);       // exp_avg.lerp_(grad, 1 - beta1)
-        const float vi = v[i] * b2 + one_minus_b2 * gr * gr;      // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;           // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+        float pi = p[i], mi = m[i], vi = v[i];
+        adam_elem(pi, g[i], mi, vi, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, grad_scale);
         m[i] = mi;
         v[i] = vi;
-        p[i] = p[i] - step_size * (mi / denom);
+        p[i] = pi;
     }
 }
 // Scalars are taken as doubles and rounded to fp32 exactly where torch.optim.Adam rounds its Python floats
@@ -2276,10 +2287,9 @@ __device__ __forceinline__ void adam_multi_body(const TgAdamSeg* __restrict__ se
             f32x4 m4 = *reinterpret_cast<f32x4*>(sg.m + i), v4 = *reinterpret_cast<f32x4*>(sg.v + i), p4 = *reinterpret_cast<f32x4*>(sg.p + i);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float gr = g4[e] * grad_scale;
-                m4[e] = m4[e] + one_minus_b1 * (gr - m4[e]);
-                v4[e] = v4[e] * b2 + one_minus_b2 * gr * gr;
-                p4[e] = p4[e] - step_size * (m4[e] / (sqrtf(v4[e]) / bc2_sqrt + eps));
+                float pe = p4[e], me = m4[e], ve = v4[e];
+                adam_elem(pe, g4[e], me, ve, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, grad_scale);
+                p4[e] = pe; m4[e] = me; v4[e] = ve;
             }
             *reinterpret_cast<f32x4*>(sg.m + i) = m4;
             *reinterpret_cast<f32x4*>(sg.v + i) = v4;
@@ -2288,13 +2298,11 @@ __device__ __forceinline__ void adam_multi_body(const TgAdamSeg* __restrict__ se
         i = end4;
     }
     for (i += threadIdx.x; i < end; i += 256) {
-        const float gr = sg.g[i] * grad_scale;
-        const float mi = sg.m[i] + one_minus_b1 * (gr - sg.m[i]);
-        const float vi = sg.v[i] * b2 + one_minus_b2 * gr * gr;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        float pi = sg.p[i], mi = sg.m[i], vi = sg.v[i];
+        adam_elem(pi, sg.g[i], mi, vi, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, grad_scale);
         sg.m[i] = mi;
         sg.v[i] = vi;
-        sg.p[i] = sg.p[i] - step_size * (mi / denom);
+        sg.p[i] = pi;
     }
 }
 __global__ __launch_bounds__(256) void adam_multi_kernel(const TgAdamSeg* __restrict__ segs, const int32_t* __restrict__ work,
@@ -2333,6 +2341,7 @@ extern "C" int tg_adam_scalars(double lr, double beta1, double beta2, int step, 
 extern "C" int tg_adam_multi_s(const TgAdamSeg* segs_dev, const int32_t* work_dev, int nwork, int chunk_elems, double beta1,
                                double beta2, double eps, const float* scal_dev, float grad_scale, tg_stream_t stream) {
     TG_REQUIRE(segs_dev && work_dev && scal_dev && nwork > 0 && chunk_elems > 0, "tg_adam_multi_s: bad arguments");
+    TG_REQUIRE(chunk_elems % 4 == 0, "tg_adam_multi_s: chunk_elems=%d is not a multiple of 4 (16-byte accesses start at chunk boundaries)", chunk_elems);
     hipLaunchKernelGGL(adam_multi_s_kernel, dim3(nwork), dim3(256), 0, S(stream), segs_dev, work_dev, chunk_elems, (float)(1.0 - beta1),
                        (float)beta2, (float)(1.0 - beta2), scal_dev, (float)eps, grad_scale);
     TG_CHECK_LAUNCH("adam_multi_s_kernel");
@@ -2341,6 +2350,7 @@ extern "C" int tg_adam_multi_s(const TgAdamSeg* segs_dev, const int32_t* work_de
 extern "C" int tg_adam_multi(const TgAdamSeg* segs_dev, const int32_t* work_dev, int nwork, int chunk_elems, double lr, double beta1,
                              double beta2, double eps, int step, float grad_scale, tg_stream_t stream) {
     TG_REQUIRE(segs_dev && work_dev && nwork > 0 && chunk_elems > 0 && step >= 1, "tg_adam_multi: bad arguments");
+    TG_REQUIRE(chunk_elems % 4 == 0, "tg_adam_multi: chunk_elems=%d is not a multiple of 4 (16-byte accesses start at chunk boundaries)", chunk_elems);
     const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);
     hipLaunchKernelGGL(adam_multi_kernel, dim3(nwork), dim3(256), 0, S(stream), segs_dev, work_dev, chunk_elems, (float)(1.0 - beta1),
                        (float)beta2, (float)(1.0 - beta2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps, grad_scale);

@@ -55,6 +55,19 @@ def _chk(t, name="tensor"):
         raise L.TgError(f"{name}: expected a contiguous tensor, strides {t.stride()}")
 
 
+def _same_numel(ref, ref_name, **others):
+    """Every given tensor (None is skipped) holds as many elements as `ref`: the kernels index them all by ref's count."""
+    for name, t in others.items():
+        if t is not None and t.numel() != ref.numel():
+            raise L.TgError(f"{name}: {t.numel()} elements {tuple(t.shape)}, but {ref_name} has {ref.numel()} {tuple(ref.shape)}")
+
+
+def _chk_scalar(t, name):
+    _chk(t, name)
+    if t is not None and t.numel() != 1:
+        raise L.TgError(f"{name}: expected one float, got {t.numel()} elements")
+
+
 def workspace(nbytes):
     """Stream-ordered scratch shared by all ops on (device, stream); grown on demand."""
     dev = torch.cuda.current_device()
@@ -755,16 +768,17 @@ def upcat_bwd(dout, h, w, Cu, want_skip=True):
 
 
 def sigmoid_composite_fwd(logits, x, mask, out=None):
-    _chk(out, "out")
+    _chk(logits, "logits"); _chk(x, "x"); _chk(mask, "mask"); _chk(out, "out")
     if out is None:
         out = torch.empty_like(x)
-    assert out.shape == x.shape
+    _same_numel(x, "x", logits=logits, mask=mask, out=out)
     L.check(_lib().tg_sigmoid_composite_fwd(_p(logits), _p(x), _p(mask), x.numel(), _p(out), _stream()), "tg_sigmoid_composite_fwd")
     return out
 
 
 def sigmoid_composite_bwd(dout, logits, mask, want_dx=False):
-    _chk(dout, "dout")
+    _chk(dout, "dout"); _chk(logits, "logits"); _chk(mask, "mask")
+    _same_numel(dout, "dout", logits=logits, mask=mask)
     dz = torch.empty_like(logits)
     dx = torch.empty_like(dout) if want_dx else None
     L.check(_lib().tg_sigmoid_composite_bwd(_p(dout), _p(logits), _p(mask), dout.numel(), _p(dz), _p(dx), _stream()),
@@ -789,7 +803,11 @@ def maxpool2_bwd(dout, x, relu_gate=False):
 def pixel_losses(pred, target, mask, w_l1, w_tv, w_bnd, l1_weight=None, gscale=None, dpred=None, accumulate=False,
                  want_grad=True, eps=1e-6):
     """-> (out5 device tensor {l1, tv, boundary, sum(band), total}, dpred or None)."""
-    _chk(pred, "pred"); _chk(target, "target"); _chk(mask, "mask"); _chk(l1_weight, "l1_weight")
+    _chk(pred, "pred"); _chk(target, "target"); _chk(mask, "mask"); _chk(l1_weight, "l1_weight"); _chk(dpred, "dpred")
+    _chk_scalar(gscale, "gscale")
+    if pred.dim() != 3:
+        raise L.TgError(f"pred: expected [B][H][W], got {tuple(pred.shape)}")
+    _same_numel(pred, "pred", target=target, mask=mask, l1_weight=l1_weight, dpred=dpred)
     B, H, W = pred.shape
     out5 = empty(5, like=pred)
     if want_grad and dpred is None:
@@ -1372,11 +1390,18 @@ class AdamScalarArena:
             L.check(lib.tg_write_floats(_p(self.dev), n, C.c_void_p(self.host.ctypes.data), _stream()), "tg_write_floats")
 
 
+def adam_table_key(params, grads, ms, vs):
+    """Everything the cached device table of adam_multi_ is built from: the four pointers AND the element count of every
+    segment (equal pointers with other counts -- views into one buffer, a pointer the allocator handed out again -- are
+    another table)."""
+    return (tuple(t.data_ptr() for ts in (params, grads, ms, vs) for t in ts), tuple(p.numel() for p in params))
+
+
 def adam_multi_(params, grads, ms, vs, lr, beta1, beta2, eps, step, grad_scale=1.0):
     """One-launch Adam over many tensors.  The (p, g, m, v, n) table and the work list live on the device and are
     rebuilt only when a pointer changes (persistent gradient buffers keep them stable step after step)."""
     import numpy as np
-    key = tuple(t.data_ptr() for ts in (params, grads, ms, vs) for t in ts)
+    key = adam_table_key(params, grads, ms, vs)
     ent = _adam_tables.get(key)
     if ent is None:
         lay = None
@@ -1414,6 +1439,8 @@ def axpby_(x, a, b, y):
 
 
 def lincomb(x, a, y, b):
+    _chk(x, "x"); _chk(y, "y")
+    _same_numel(x, "x", y=y)
     out = torch.empty_like(x)
     L.check(_lib().tg_lincomb(_p(x), a, _p(y), b, _p(out), x.numel(), _stream()), "tg_lincomb")
     return out
