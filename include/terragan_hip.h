@@ -685,7 +685,9 @@ int tg_resample_interp(const float* dem, const float* mask, int use_nodata, floa
  * region), returns the totals for `kind` and consumes its records. */
 int tg_prof_enable(int on);
 int tg_prof_summary(int kind, double* total_ms, int64_t* launches, double* flops, double* bytes);
-/* One CSV row per recorded launch (kind,cfg,M,N,K,C,splits,ms,gflop,alg_mb,tag); records are kept. */
+/* One CSV row per recorded launch (kind,cfg,M,N,K,C,splits,ms,gflop,alg_mb,tag,route); records are kept.
+ * route: which small-channel kernel a launch of cfg 2000 / 2001 / 2004 ran (SmallRoute, csrc/igemm_params.h),
+ * 0 for every other kernel.  Read the file by column name: new columns are added at the end. */
 int tg_prof_dump(const char* path);
 /* Label (<= 31 chars, e.g. "dec1.fwd") attached to the launches recorded after it on the calling thread. */
 int tg_prof_tag(const char* tag);

@@ -29,6 +29,7 @@ struct ProfRec {
     int kind;  // 0 = igemm (fwd/dgrad), 1 = wgrad
     double flops, bytes;
     int M, N, K, C, splits, cfg;
+    int route;  // SmallRoute of a small-channel launch (igemm_params.h), 0 for every other kernel
     char tag[32];
 };
 static std::mutex g_prof_mu;
@@ -80,18 +81,18 @@ extern "C" int tg_prof_tag(const char* tag) {
     g_prof_tag[sizeof(g_prof_tag) - 1] = 0;
     return TG_OK;
 }
-// Writes one CSV row per recorded launch (kind,cfg,M,N,K,C,splits,ms,gflop,alg_mb,tag) without consuming the records.
+// Writes one CSV row per recorded launch (kind,cfg,M,N,K,C,splits,ms,gflop,alg_mb,tag,route) without consuming the records.
 extern "C" int tg_prof_dump(const char* path) {
     std::lock_guard<std::mutex> lk(g_prof_mu);
     FILE* f = fopen(path, "w");
     if (!f) { tg_set_error("tg_prof_dump: cannot open %s", path); return TG_ERR_ARG; }
-    fprintf(f, "kind,cfg,M,N,K,C,splits,ms,gflop,alg_mb,tag\n");
+    fprintf(f, "kind,cfg,M,N,K,C,splits,ms,gflop,alg_mb,tag,route\n");
     for (auto& r : g_prof) {
         (void)hipEventSynchronize(r.b);
         float t = 0.f;
         (void)hipEventElapsedTime(&t, r.a, r.b);
-        fprintf(f, "%d,%d,%d,%d,%d,%d,%d,%.5f,%.4f,%.3f,%s\n", r.kind, r.cfg, r.M, r.N, r.K, r.C, r.splits, t, r.flops / 1e9,
-                r.bytes / 1e6, r.tag);
+        fprintf(f, "%d,%d,%d,%d,%d,%d,%d,%.5f,%.4f,%.3f,%s,%d\n", r.kind, r.cfg, r.M, r.N, r.K, r.C, r.splits, t, r.flops / 1e9,
+                r.bytes / 1e6, r.tag, r.route);
     }
     fclose(f);
     return TG_OK;
@@ -1180,7 +1181,7 @@ static int launch_igemm(IGemmParams& p, hipStream_t s, size_t ws_floats_avail = 
         const double by = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.M * p.N + (double)p.N * p.Ktot);
         ProfScope ps(s, 2, 2.0 * p.M * (double)p.N * p.Ktot, by, p.M, p.N, p.Ktot, p.C, 1, 2000);
         p.sparse_pix_done = smallconv_to1_map_ok(p) ? 1 : 0;
-        return smallconv_fwd_launch(p, s);
+        return smallconv_fwd_launch(p, s, &ps.r.route);
     }
     {
         int rc = TG_OK;
@@ -2001,7 +2002,7 @@ static int conv_dgrad_impl(const TgConv* g, const float* dy, const float* w, flo
             }
             by += 4.0 * (double)g->B * g->Ho * g->Wo * g->Cout;
             ProfScope ps(s, 2, fl, by, cls[0].M * ncls, 1, cls[0].TH * cls[0].TW * cls[0].C, cls[0].C, 1, 2004);
-            return smallconv_to1_multi_launch(cls, ncls, s);
+            return smallconv_to1_multi_launch(cls, ncls, s, &ps.r.route);
         }
         if (ncls > 1 && !smallconv_fwd_applies(cls[0])) {
             IGemmParams tmp[4];
@@ -2605,7 +2606,7 @@ static int conv_wgrad_impl(const TgConv* g, const float* x, const float* in_mask
         {
             const double by = 4.0 * ((double)p.B * p.H * p.W * p.C + (double)p.Mpix * p.Cout + (double)p.Cout * p.Ktot);
             ProfScope ps(s, 2, 2.0 * p.Mpix * (double)p.Cout * p.Ktot, by, p.Cout, p.Ktot, p.Mpix, p.C, 1, 2001);
-            rc = smallconv_wgrad_launch(p, dw, ws, ws_floats, s, db, &db_done);
+            rc = smallconv_wgrad_launch(p, dw, ws, ws_floats, s, db, &db_done, &ps.r.route);
         }
         if (rc) return rc;
         if (db && !db_done) {

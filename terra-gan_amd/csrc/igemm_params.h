@@ -86,17 +86,41 @@ struct WgradParams {
     BnIn in_bn;   // (to1wgrad64_lds_kernel only)
 };
 
-// smallconv.hip: bandwidth-bound special cases that would waste >95% of an MFMA tile
+// Which kernel a small-channel launch runs (smallconv.hip).  The three launchers choose it in one function each and switch on it,
+// and the launch records carry it (ProfRec::route, column `route` of tg_prof_dump), so a test can pin the kernel that ran: the
+// records' cfg is 2000 / 2001 / 2004 for all of them.  0 = not a small-channel launch.
+enum SmallRoute {
+    SR_NONE = 0,
+    SR_C1MFMA = 100,                // + taps per side (7 | 4 | 3): c1mfma_kernel<k, k>
+    SR_C1CONV = 110,                // + 7 | 4 | 3, + 0 = the runtime-tap instantiation: c1conv_kernel<k, k>
+    SR_TO1CONVW = 200,              // + 10 k + CQ (k = 3 | 4, CQ = C / 256): to1convw_kernel<k, k, CQ>
+    SR_TO1_LDS = 300,               // to1conv64_lds_kernel<false>
+    SR_TO1_LDS_BNIN = 301,          // to1conv64_lds_kernel<true>: BatchNorm-on-load
+    SR_TO1_LDS_MAP = 302,           // to1conv64_lds_kernel<false, true>: tile map
+    SR_TO1CONV64 = 400,             // + 10 TH + TW: to1conv64_kernel<TH, TW>
+    SR_MULTI22_LDS = 500,           // to1conv64_multi22_lds_kernel
+    SR_MULTI22 = 501,               // to1conv64_multi22_kernel
+    SR_C1WGRAD_MFMA = 600,          // + k (7 | 4 | 3): c1wgrad_mfma_kernel<k> without bias partials
+    SR_C1WGRAD_MFMA_BIAS = 610,     // + k: ... with bias partials
+    SR_C1WGRAD = 620,               // + k: c1wgrad_kernel<k>
+    SR_TO1WGRADW = 700,             // + k (3 | 4): to1wgradw_kernel<k>
+    SR_TO1WGRAD_LDS = 800,          // to1wgrad64_lds_kernel<false>
+    SR_TO1WGRAD_LDS_BNIN = 801,     // to1wgrad64_lds_kernel<true>
+    SR_TO1WGRAD64 = 900,            // + k (3 | 4): to1wgrad64_kernel<k>
+};
+
+// smallconv.hip: bandwidth-bound special cases that would waste >95% of an MFMA tile.  The launchers report the route they took
+// through `route` (a SmallRoute value).
 bool smallconv_fwd_applies(const IGemmParams& p);             // C == 1 -> N%64 == 0, or N == 1 <- C%64 == 0
-int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s);
+int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s, int* route = nullptr);
 bool smallconv_to1_map_ok(const IGemmParams& p);              // smallconv_fwd_launch will honour p.sparse (64 -> 1, LDS patch)
 // dx[b][y][x] = 0 where bit x of pix[b][y] is clear (pointwise.hip)
 int pix_zero_launch(float* dx, const uint64_t* pix, int B, int H, int W, hipStream_t s);
 bool smallconv_to1_multi_applies(const IGemmParams* cls, int ncls);   // 64 -> 1 channel, the four 2x2-tap classes of a 4x4 stride-2 dgrad
-int smallconv_to1_multi_launch(const IGemmParams* cls, int ncls, hipStream_t s);
+int smallconv_to1_multi_launch(const IGemmParams* cls, int ncls, hipStream_t s, int* route = nullptr);
 bool smallconv_wgrad_applies(const WgradParams& p);
 bool smallconv_bnin_fwd_ok(const IGemmParams& p);             // launches that can take IGemmParams::in_bn / WgradParams::in_bn
 bool smallconv_bnin_wgrad_ok(const WgradParams& p);
 size_t smallconv_wgrad_ws_floats(const WgradParams& p);
 int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, size_t ws_floats, hipStream_t s, float* db = nullptr,
-                           int* db_done = nullptr);
+                           int* db_done = nullptr, int* route = nullptr);

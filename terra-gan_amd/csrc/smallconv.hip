@@ -619,50 +619,76 @@ bool smallconv_to1_multi_applies(const IGemmParams* cls, int ncls) {
     }
     return true;
 }
-int smallconv_to1_multi_launch(const IGemmParams* cls, int ncls, hipStream_t s) {
-    IGemmMulti pm = {};
-    for (int i = 0; i < ncls; ++i) pm.c[i] = cls[i];
-    {
-        // one LDS patch for the four classes: they must read the same source tensor within a (T + 2)-pixel window, unmasked
-        static const bool no_lds = getenv("TG_NO_TO1LDS") != nullptr || getenv("TG_NO_TO1_MULTI_LDS") != nullptr;
-        int sy_min = 1 << 30, sx_min = 1 << 30, sy_max = -(1 << 30), sx_max = -(1 << 30);
-        bool ok = !no_lds && cls[0].OH >= T1_TH && cls[0].OW >= T1_TW;
-        for (int i = 0; i < ncls; ++i) {
-            const IGemmParams& p = cls[i];
-            ok = ok && p.src == cls[0].src && p.IH == cls[0].IH && p.IW == cls[0].IW && p.B == cls[0].B && p.ss == 1 && !p.amask &&
-                 (p.tstep == 1 || p.tstep == -1);
-            for (int t = 0; t < 2; ++t) {
-                const int y = p.sy0 + t * p.tstep, x = p.sx0 + t * p.tstep;
-                sy_min = y < sy_min ? y : sy_min; sy_max = y > sy_max ? y : sy_max;
-                sx_min = x < sx_min ? x : sx_min; sx_max = x > sx_max ? x : sx_max;
-            }
-        }
-        if (ok && sy_max - sy_min <= 2 && sx_max - sx_min <= 2) {
-            const int tiles_x = cdiv(cls[0].OW, T1_TW), tiles_y = cdiv(cls[0].OH, T1_TH);
-            const size_t lds = (size_t)T1_PH * T1_PW * 64 * sizeof(float);
-            hipLaunchKernelGGL(to1conv64_multi22_lds_kernel, dim3(tiles_x * tiles_y * cls[0].B), dim3(256), lds, s, pm, tiles_x, tiles_y,
-                               sy_min, sx_min);
-            TG_CHECK_LAUNCH("to1conv64_multi22_lds_kernel");
-            return TG_OK;
+// One LDS patch for the four classes (multi22_lds): they must read the same source tensor within a (T + 2)-pixel window, unmasked.
+// Otherwise the plain merged kernel.  *sy_min / *sx_min: the window's origin (LDS route only).
+static SmallRoute smallconv_to1_multi_route(const IGemmParams* cls, int ncls, int* sy_min_out, int* sx_min_out) {
+    static const bool no_lds = getenv("TG_NO_TO1LDS") != nullptr || getenv("TG_NO_TO1_MULTI_LDS") != nullptr;
+    int sy_min = 1 << 30, sx_min = 1 << 30, sy_max = -(1 << 30), sx_max = -(1 << 30);
+    bool ok = !no_lds && cls[0].OH >= T1_TH && cls[0].OW >= T1_TW;
+    for (int i = 0; i < ncls; ++i) {
+        const IGemmParams& p = cls[i];
+        ok = ok && p.src == cls[0].src && p.IH == cls[0].IH && p.IW == cls[0].IW && p.B == cls[0].B && p.ss == 1 && !p.amask &&
+             (p.tstep == 1 || p.tstep == -1);
+        for (int t = 0; t < 2; ++t) {
+            const int y = p.sy0 + t * p.tstep, x = p.sx0 + t * p.tstep;
+            sy_min = y < sy_min ? y : sy_min; sy_max = y > sy_max ? y : sy_max;
+            sx_min = x < sx_min ? x : sx_min; sx_max = x > sx_max ? x : sx_max;
         }
     }
-    int blocks = cdiv(cls[0].M / 4, 4 * 4);
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(to1conv64_multi22_kernel, dim3(blocks, ncls), dim3(256), 0, s, pm);
-    TG_CHECK_LAUNCH("to1conv64_multi22_kernel");
-    return TG_OK;
+    *sy_min_out = sy_min;
+    *sx_min_out = sx_min;
+    return ok && sy_max - sy_min <= 2 && sx_max - sx_min <= 2 ? SR_MULTI22_LDS : SR_MULTI22;
+}
+int smallconv_to1_multi_launch(const IGemmParams* cls, int ncls, hipStream_t s, int* route) {
+    IGemmMulti pm = {};
+    for (int i = 0; i < ncls; ++i) pm.c[i] = cls[i];
+    int sy_min = 0, sx_min = 0;
+    const SmallRoute r = smallconv_to1_multi_route(cls, ncls, &sy_min, &sx_min);
+    if (route) *route = r;
+    switch (r) {
+    case SR_MULTI22_LDS: {
+        const int tiles_x = cdiv(cls[0].OW, T1_TW), tiles_y = cdiv(cls[0].OH, T1_TH);
+        const size_t lds = (size_t)T1_PH * T1_PW * 64 * sizeof(float);
+        hipLaunchKernelGGL(to1conv64_multi22_lds_kernel, dim3(tiles_x * tiles_y * cls[0].B), dim3(256), lds, s, pm, tiles_x, tiles_y,
+                           sy_min, sx_min);
+        TG_CHECK_LAUNCH("to1conv64_multi22_lds_kernel");
+        return TG_OK;
+    }
+    default: {
+        int blocks = cdiv(cls[0].M / 4, 4 * 4);
+        if (blocks > 2048) blocks = 2048;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(to1conv64_multi22_kernel, dim3(blocks, ncls), dim3(256), 0, s, pm);
+        TG_CHECK_LAUNCH("to1conv64_multi22_kernel");
+        return TG_OK;
+    }
+    }
+}
+
+// The kernel smallconv_fwd_launch runs for p (smallconv_fwd_applies(p) holds); SR_NONE: no to1conv configuration for these taps.
+static SmallRoute smallconv_fwd_route(const IGemmParams& p) {
+    if (p.C == 1) {
+        static const bool no_mfma = getenv("TG_NO_C1MFMA") != nullptr;
+        const bool al16 = ((reinterpret_cast<uintptr_t>(p.dst) | reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.gate)) & 15) == 0;
+        const bool k743 = p.TH == p.TW && (p.TH == 7 || p.TH == 4 || p.TH == 3);
+        if (!no_mfma && al16 && k743) return (SmallRoute)(SR_C1MFMA + p.TH);
+        return (SmallRoute)(SR_C1CONV + (k743 ? p.TH : 0));
+    }
+    if (to1w_ok(p)) return (SmallRoute)(SR_TO1CONVW + 10 * p.TH + p.C / 256);
+    if (to1_fwd_lds_ok(p)) return smallconv_to1_map_ok(p) ? SR_TO1_LDS_MAP : (p.in_bn.mean ? SR_TO1_LDS_BNIN : SR_TO1_LDS);
+    if (to1_cfg_ok(p.TH, p.TW)) return (SmallRoute)(SR_TO1CONV64 + 10 * p.TH + p.TW);
+    return SR_NONE;
 }
 
 #define TO1_CASE(TH_, TW_)                                                                           \
-    if (p.TH == TH_ && p.TW == TW_) {                                                                \
+    case SR_TO1CONV64 + 10 * TH_ + TW_:                                                              \
         hipLaunchKernelGGL((to1conv64_kernel<TH_, TW_>), dim3(blocks), dim3(256), 0, s, p);          \
-        TG_CHECK_LAUNCH("to1conv64_kernel");                                                         \
-        return TG_OK;                                                                                \
-    }
+        break;
 
-int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s) {
+int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s, int* route) {
     TG_REQUIRE(!p.in_bn.mean || smallconv_bnin_fwd_ok(p), "smallconv: BatchNorm-on-load is not available for this geometry");
+    const SmallRoute r = smallconv_fwd_route(p);
+    if (route) *route = r;
     if (p.C == 1) {
         C1Geom q;
         q.tiles_x = cdiv(p.OW, C1_T);
@@ -673,57 +699,61 @@ int smallconv_fwd_launch(const IGemmParams& p, hipStream_t s) {
         q.PH = (C1_T - 1) * p.ss + (p.TH - 1) + 1;
         q.PW = (C1_T - 1) * p.ss + (p.TW - 1) + 1;
         dim3 grid(q.tiles_x * q.tiles_y * p.B, p.N / 64);
-        static const bool no_mfma = getenv("TG_NO_C1MFMA") != nullptr;
-        const bool al16 = ((reinterpret_cast<uintptr_t>(p.dst) | reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.gate)) & 15) == 0;
-        if (!no_mfma && al16 && p.TH == p.TW && (p.TH == 7 || p.TH == 4 || p.TH == 3)) {
-            const int ks = (p.TH * p.TW + 1) / 2;
-            const size_t lds = ((size_t)2 * ks * 68 + 4 * 32 * 36 + (size_t)q.PH * q.PW) * sizeof(float);
-            if (p.TH == 7) hipLaunchKernelGGL((c1mfma_kernel<7, 7>), grid, dim3(256), lds, s, p, q);
-            else if (p.TH == 4) hipLaunchKernelGGL((c1mfma_kernel<4, 4>), grid, dim3(256), lds, s, p, q);
-            else hipLaunchKernelGGL((c1mfma_kernel<3, 3>), grid, dim3(256), lds, s, p, q);
-            TG_CHECK_LAUNCH("c1mfma_kernel");
-            return TG_OK;
-        }
+        const int ks = (p.TH * p.TW + 1) / 2;
+        const size_t lds_mfma = ((size_t)2 * ks * 68 + 4 * 32 * 36 + (size_t)q.PH * q.PW) * sizeof(float);
         const size_t lds = ((size_t)q.PH * q.PW + (size_t)p.TH * p.TW * 64) * sizeof(float);
-        if (p.TH == 7 && p.TW == 7) hipLaunchKernelGGL((c1conv_kernel<7, 7>), grid, dim3(256), lds, s, p, q);
-        else if (p.TH == 4 && p.TW == 4) hipLaunchKernelGGL((c1conv_kernel<4, 4>), grid, dim3(256), lds, s, p, q);
-        else if (p.TH == 3 && p.TW == 3) hipLaunchKernelGGL((c1conv_kernel<3, 3>), grid, dim3(256), lds, s, p, q);
-        else hipLaunchKernelGGL((c1conv_kernel<0, 0>), grid, dim3(256), lds, s, p, q);
-        TG_CHECK_LAUNCH("c1conv_kernel");
+        switch (r) {
+        case SR_C1MFMA + 7: hipLaunchKernelGGL((c1mfma_kernel<7, 7>), grid, dim3(256), lds_mfma, s, p, q); break;
+        case SR_C1MFMA + 4: hipLaunchKernelGGL((c1mfma_kernel<4, 4>), grid, dim3(256), lds_mfma, s, p, q); break;
+        case SR_C1MFMA + 3: hipLaunchKernelGGL((c1mfma_kernel<3, 3>), grid, dim3(256), lds_mfma, s, p, q); break;
+        case SR_C1CONV + 7: hipLaunchKernelGGL((c1conv_kernel<7, 7>), grid, dim3(256), lds, s, p, q); break;
+        case SR_C1CONV + 4: hipLaunchKernelGGL((c1conv_kernel<4, 4>), grid, dim3(256), lds, s, p, q); break;
+        case SR_C1CONV + 3: hipLaunchKernelGGL((c1conv_kernel<3, 3>), grid, dim3(256), lds, s, p, q); break;
+        default: hipLaunchKernelGGL((c1conv_kernel<0, 0>), grid, dim3(256), lds, s, p, q); break;
+        }
+        TG_CHECK_LAUNCH(r >= SR_C1CONV ? "c1conv_kernel" : "c1mfma_kernel");
         return TG_OK;
     }
-    if (to1w_ok(p)) {
+    switch (r) {
+    case SR_TO1CONVW + 31: case SR_TO1CONVW + 32: case SR_TO1CONVW + 41: case SR_TO1CONVW + 42: {
         int blocks = cdiv(p.M, 4 * 3);                 // ~3 outputs per wave: the register-resident weights are amortised
         if (blocks > 1024) blocks = 1024;
         if (blocks < 1) blocks = 1;
-        if (p.TH == 4 && p.C == 512) hipLaunchKernelGGL((to1convw_kernel<4, 4, 2>), dim3(blocks), dim3(256), 0, s, p);
-        else if (p.TH == 4) hipLaunchKernelGGL((to1convw_kernel<4, 4, 1>), dim3(blocks), dim3(256), 0, s, p);
-        else if (p.C == 512) hipLaunchKernelGGL((to1convw_kernel<3, 3, 2>), dim3(blocks), dim3(256), 0, s, p);
+        if (r == SR_TO1CONVW + 42) hipLaunchKernelGGL((to1convw_kernel<4, 4, 2>), dim3(blocks), dim3(256), 0, s, p);
+        else if (r == SR_TO1CONVW + 41) hipLaunchKernelGGL((to1convw_kernel<4, 4, 1>), dim3(blocks), dim3(256), 0, s, p);
+        else if (r == SR_TO1CONVW + 32) hipLaunchKernelGGL((to1convw_kernel<3, 3, 2>), dim3(blocks), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((to1convw_kernel<3, 3, 1>), dim3(blocks), dim3(256), 0, s, p);
         TG_CHECK_LAUNCH("to1convw_kernel");
         return TG_OK;
     }
-    if (to1_fwd_lds_ok(p)) {
+    case SR_TO1_LDS: case SR_TO1_LDS_BNIN: case SR_TO1_LDS_MAP: {
         const int tiles_x = cdiv(p.OW, T1_TW), tiles_y = cdiv(p.OH, T1_TH);
         const int sy_b = p.sy0 + 2 * p.tstep, sx_b = p.sx0 + 2 * p.tstep;
         const int sy_min = p.sy0 < sy_b ? p.sy0 : sy_b, sx_min = p.sx0 < sx_b ? p.sx0 : sx_b;
         const size_t lds = (size_t)T1_PH * T1_PW * 64 * sizeof(float);
         const uint32_t* no_bits = nullptr;
         const uint64_t* no_pix = nullptr;
-        if (smallconv_to1_map_ok(p))
+        if (r == SR_TO1_LDS_MAP)
             hipLaunchKernelGGL((to1conv64_lds_kernel<false, true>), dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min,
                                sx_min, p.sparse->bits, p.sparse->pix);
-        else if (p.in_bn.mean) hipLaunchKernelGGL(to1conv64_lds_kernel<true>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min, no_bits, no_pix);
+        else if (r == SR_TO1_LDS_BNIN) hipLaunchKernelGGL(to1conv64_lds_kernel<true>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min, no_bits, no_pix);
         else hipLaunchKernelGGL(to1conv64_lds_kernel<false>, dim3(tiles_x * tiles_y * p.B), dim3(256), lds, s, p, tiles_x, tiles_y, sy_min, sx_min, no_bits, no_pix);
         TG_CHECK_LAUNCH("to1conv64_lds_kernel");
         return TG_OK;
     }
+    default: break;
+    }
     int blocks = cdiv(p.M / 4, 4 * 4);
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
+    switch (r) {
     TO1_CASE(3, 3) TO1_CASE(2, 2) TO1_CASE(4, 4) TO1_CASE(1, 1) TO1_CASE(2, 1) TO1_CASE(1, 2)
-    tg_set_error("smallconv: no to1conv configuration for taps %dx%d", p.TH, p.TW);
-    return TG_ERR_ARG;
+    default:
+        tg_set_error("smallconv: no to1conv configuration for taps %dx%d", p.TH, p.TW);
+        return TG_ERR_ARG;
+    }
+    TG_CHECK_LAUNCH("to1conv64_kernel");
+    return TG_OK;
 }
 
 // ---- weight gradients ------------------------------------------------------------------------------------
@@ -1176,14 +1206,28 @@ size_t smallconv_wgrad_ws_floats(const WgradParams& p) {
     const size_t blocks = (size_t)smallconv_wgrad_blocks(p);
     return blocks * p.Cout * p.k * p.k * p.C + (p.C == 1 ? blocks * p.Cout : 0) + 64;
 }
+// The kernel smallconv_wgrad_launch runs for p (smallconv_wgrad_applies(p) holds).  want_db: the caller asked for the bias gradient,
+// which the Cin == 1 MFMA kernel produces as partials of its own.  smallconv_wgrad_blocks follows the same order of questions.
+static SmallRoute smallconv_wgrad_route(const WgradParams& p, bool want_db) {
+    if (p.C == 1) {
+        if (getenv("TG_C1WGRAD")) return (SmallRoute)(SR_C1WGRAD + p.k);
+        static const bool no_db = getenv("TG_NO_C1WGRAD_BIAS") != nullptr;       // default: the MFMA kernel
+        return (SmallRoute)((want_db && !no_db ? SR_C1WGRAD_MFMA_BIAS : SR_C1WGRAD_MFMA) + p.k);
+    }
+    if (to1w_wgrad_ok(p)) return (SmallRoute)(SR_TO1WGRADW + p.k);
+    if (to1_wgrad_lds_ok(p)) return p.in_bn.mean ? SR_TO1WGRAD_LDS_BNIN : SR_TO1WGRAD_LDS;
+    return (SmallRoute)(SR_TO1WGRAD64 + p.k);
+}
 // db != nullptr: the launch may produce the bias gradient as well (*db_done = 1: the caller skips its column-sum pass)
-int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, size_t ws_floats, hipStream_t s, float* db, int* db_done) {
+int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, size_t ws_floats, hipStream_t s, float* db, int* db_done, int* route) {
     if (db_done) *db_done = 0;
     float* pdb = nullptr;
     TG_REQUIRE(!p.in_bn.mean || smallconv_bnin_wgrad_ok(p), "smallconv: BatchNorm-on-load is not available for this geometry");
     TG_REQUIRE(ws && ws_floats >= smallconv_wgrad_ws_floats(p), "tg_conv_wgrad: workspace too small for the partial slabs (%zu < %zu floats)",
                ws_floats, smallconv_wgrad_ws_floats(p));
     const int nb = smallconv_wgrad_blocks(p);
+    const SmallRoute r = smallconv_wgrad_route(p, db != nullptr);
+    if (route) *route = r;
     if (p.C == 1) {
         C1Geom q;
         q.tiles_x = cdiv(p.Wo, C1_T);
@@ -1192,37 +1236,44 @@ int smallconv_wgrad_launch(const WgradParams& p, float* dw, float* ws, size_t ws
         q.PH = q.PW = (C1_T - 1) * p.stride + p.k;
         const int ntiles = q.tiles_x * q.tiles_y * p.B;
         dim3 grid(nb, p.Cout / 64);
-        if (!getenv("TG_C1WGRAD")) {                 // default: the MFMA kernel
+        if (r < SR_C1WGRAD) {
             const int ntt = (p.k * p.k + 31) / 32;
             const size_t lds = (((size_t)q.PH * q.PW + 3) / 4 * 4 + (size_t)64 * (ntt * 32 + 1)) * sizeof(float);
-            static const bool no_db = getenv("TG_NO_C1WGRAD_BIAS") != nullptr;
-            if (db && !no_db) pdb = ws + (size_t)nb * p.Cout * p.k * p.k * p.C;
-            if (p.k == 7) hipLaunchKernelGGL((c1wgrad_mfma_kernel<7>), grid, dim3(256), lds, s, p, q, ntiles, ws, pdb);
-            else if (p.k == 4) hipLaunchKernelGGL((c1wgrad_mfma_kernel<4>), grid, dim3(256), lds, s, p, q, ntiles, ws, pdb);
-            else hipLaunchKernelGGL((c1wgrad_mfma_kernel<3>), grid, dim3(256), lds, s, p, q, ntiles, ws, pdb);
+            if (r >= SR_C1WGRAD_MFMA_BIAS) pdb = ws + (size_t)nb * p.Cout * p.k * p.k * p.C;
+            switch (r - (pdb ? SR_C1WGRAD_MFMA_BIAS : SR_C1WGRAD_MFMA)) {
+            case 7: hipLaunchKernelGGL((c1wgrad_mfma_kernel<7>), grid, dim3(256), lds, s, p, q, ntiles, ws, pdb); break;
+            case 4: hipLaunchKernelGGL((c1wgrad_mfma_kernel<4>), grid, dim3(256), lds, s, p, q, ntiles, ws, pdb); break;
+            default: hipLaunchKernelGGL((c1wgrad_mfma_kernel<3>), grid, dim3(256), lds, s, p, q, ntiles, ws, pdb); break;
+            }
             TG_CHECK_LAUNCH("c1wgrad_mfma_kernel");
         } else {
-        const size_t lds = (((size_t)q.PH * q.PW + 3) / 4 * 4 + (size_t)4 * p.k * 64) * sizeof(float);
-        if (p.k == 7) hipLaunchKernelGGL((c1wgrad_kernel<7>), grid, dim3(256), lds, s, p, q, ntiles, ws);
-        else if (p.k == 4) hipLaunchKernelGGL((c1wgrad_kernel<4>), grid, dim3(256), lds, s, p, q, ntiles, ws);
-        else hipLaunchKernelGGL((c1wgrad_kernel<3>), grid, dim3(256), lds, s, p, q, ntiles, ws);
-        TG_CHECK_LAUNCH("c1wgrad_kernel");
+            const size_t lds = (((size_t)q.PH * q.PW + 3) / 4 * 4 + (size_t)4 * p.k * 64) * sizeof(float);
+            switch (r) {
+            case SR_C1WGRAD + 7: hipLaunchKernelGGL((c1wgrad_kernel<7>), grid, dim3(256), lds, s, p, q, ntiles, ws); break;
+            case SR_C1WGRAD + 4: hipLaunchKernelGGL((c1wgrad_kernel<4>), grid, dim3(256), lds, s, p, q, ntiles, ws); break;
+            default: hipLaunchKernelGGL((c1wgrad_kernel<3>), grid, dim3(256), lds, s, p, q, ntiles, ws); break;
+            }
+            TG_CHECK_LAUNCH("c1wgrad_kernel");
         }
-    } else if (to1w_wgrad_ok(p)) {
-        if (p.k == 4) hipLaunchKernelGGL((to1wgradw_kernel<4>), dim3(p.B, p.C / 256, cdiv(p.Ho, 4)), dim3(256), 0, s, p, ws);
-        else hipLaunchKernelGGL((to1wgradw_kernel<3>), dim3(p.B, p.C / 256, cdiv(p.Ho, 4)), dim3(256), 0, s, p, ws);
-        TG_CHECK_LAUNCH("to1wgradw_kernel");
-    } else if (to1_wgrad_lds_ok(p)) {
-        const int tiles_x = cdiv(p.Wo, T1_TW), tiles_y = cdiv(p.Ho, T1_TH), ntiles = tiles_x * tiles_y * p.B;
-        const size_t lds = ((size_t)T1_PH * T1_PW * 64 + T1_TH * T1_TW) * sizeof(float);
-        if (p.in_bn.mean) hipLaunchKernelGGL(to1wgrad64_lds_kernel<true>, dim3(nb), dim3(256), lds, s, p, ws, tiles_x, tiles_y, ntiles);
-        else hipLaunchKernelGGL(to1wgrad64_lds_kernel<false>, dim3(nb), dim3(256), lds, s, p, ws, tiles_x, tiles_y, ntiles);
-        TG_CHECK_LAUNCH("to1wgrad64_lds_kernel");
     } else {
-        const int qpb = cdiv(p.Mpix / 4, to1_wgrad_blocks(p));
-        if (p.k == 4) hipLaunchKernelGGL((to1wgrad64_kernel<4>), dim3(nb), dim3(256), 0, s, p, ws, qpb);
-        else hipLaunchKernelGGL((to1wgrad64_kernel<3>), dim3(nb), dim3(256), 0, s, p, ws, qpb);
-        TG_CHECK_LAUNCH("to1wgrad64_kernel");
+        switch (r) {
+        case SR_TO1WGRADW + 4: hipLaunchKernelGGL((to1wgradw_kernel<4>), dim3(p.B, p.C / 256, cdiv(p.Ho, 4)), dim3(256), 0, s, p, ws); break;
+        case SR_TO1WGRADW + 3: hipLaunchKernelGGL((to1wgradw_kernel<3>), dim3(p.B, p.C / 256, cdiv(p.Ho, 4)), dim3(256), 0, s, p, ws); break;
+        case SR_TO1WGRAD_LDS: case SR_TO1WGRAD_LDS_BNIN: {
+            const int tiles_x = cdiv(p.Wo, T1_TW), tiles_y = cdiv(p.Ho, T1_TH), ntiles = tiles_x * tiles_y * p.B;
+            const size_t lds = ((size_t)T1_PH * T1_PW * 64 + T1_TH * T1_TW) * sizeof(float);
+            if (r == SR_TO1WGRAD_LDS_BNIN) hipLaunchKernelGGL(to1wgrad64_lds_kernel<true>, dim3(nb), dim3(256), lds, s, p, ws, tiles_x, tiles_y, ntiles);
+            else hipLaunchKernelGGL(to1wgrad64_lds_kernel<false>, dim3(nb), dim3(256), lds, s, p, ws, tiles_x, tiles_y, ntiles);
+            break;
+        }
+        default: {
+            const int qpb = cdiv(p.Mpix / 4, to1_wgrad_blocks(p));
+            if (r == SR_TO1WGRAD64 + 4) hipLaunchKernelGGL((to1wgrad64_kernel<4>), dim3(nb), dim3(256), 0, s, p, ws, qpb);
+            else hipLaunchKernelGGL((to1wgrad64_kernel<3>), dim3(nb), dim3(256), 0, s, p, ws, qpb);
+            break;
+        }
+        }
+        TG_CHECK_LAUNCH(r < SR_TO1WGRAD_LDS ? "to1wgradw_kernel" : (r < SR_TO1WGRAD64 ? "to1wgrad64_lds_kernel" : "to1wgrad64_kernel"));
     }
     const size_t n = (size_t)p.Cout * p.k * p.k * p.C;
     hipLaunchKernelGGL(smallconv_slab_reduce, dim3((unsigned)cdiv64((int64_t)n, 4)), dim3(256), 0, s, ws, dw, n, nb);
