@@ -636,6 +636,20 @@ size_t tg_vfill_pcg_ws_bytes(int H, int W);
 int tg_vfill_pcg_start(int H, int W, void* ws, size_t ws_bytes, void* pws, size_t pws_bytes, tg_stream_t stream);
 int tg_vfill_pcg_iter(int H, int W, void* ws, size_t ws_bytes, void* pws, size_t pws_bytes, uint32_t* change_bits,
                       uint32_t* restarts, tg_stream_t stream);
+/* Biharmonic (thin-plate) fill (fill_voids(method="biharmonic")): the unknowns minimise the sum of
+ * D(u)^2 over themselves and their 4-neighbours, D the masked difference sum above; the normal equations D(D(u)) = 0 at the
+ * unknowns are solved by flexible conjugate gradients (x, residual and dots fp64) preconditioned by G(G(r)), G being `inner`
+ * (1..TG_VFILL_BIH_MAX_INNER) conjugate-gradient iterations around the V-cycle (1: one bare cycle).  bws: a third workspace,
+ * 256-byte aligned, >= tg_vfill_bih_ws_bytes(H, W) (0 for the sizes tg_vfill_ws_bytes rejects), kept between the calls of one
+ * fill; the layouts of ws and pws are unchanged and pws is not needed.  tg_vfill_bih_start runs once after tg_vfill_setup;
+ * each tg_vfill_bih_iter is one outer iteration = 2 * inner V-cycles, with the same `inner` as the start.  change_bits and
+ * restarts as for tg_vfill_pcg_iter (restarts counts the inner solves' too); the solution ends every iteration, in fp32, in
+ * the buffer tg_vfill_finish reads.  Bitwise deterministic. */
+enum { TG_VFILL_BIH_MAX_INNER = 8 };
+size_t tg_vfill_bih_ws_bytes(int H, int W);
+int tg_vfill_bih_start(int H, int W, void* ws, size_t ws_bytes, void* bws, size_t bws_bytes, int inner, tg_stream_t stream);
+int tg_vfill_bih_iter(int H, int W, void* ws, size_t ws_bytes, void* bws, size_t bws_bytes, int inner, uint32_t* change_bits,
+                      uint32_t* restarts, tg_stream_t stream);
 
 /* ---- seam correction of a filled DSM by a harmonic delta surface (mvp_gan/src/seam_correct.py; no
  * reference counterpart) ----

@@ -10,6 +10,8 @@
 //   tg_vfill_finish  known pixels copied bit for bit, u + c at the unknowns, NaN everywhere when nothing is known
 //   tg_vfill_pcg_*   the same cycle as the preconditioner of flexible conjugate gradients (section 8n): start after setup,
 //                    then one iteration per call in place of tg_vfill_cycle; the solution ends every iteration in level 0's u0
+//   tg_vfill_bih_*   the biharmonic (thin-plate) fill (section 8q): conjugate gradients on D(D(u)) = 0 in fp64, preconditioned by
+//                    two approximate Laplace solves made of the same cycle; kernels and host code at the end of this file
 //
 // Level 0 holds v = u - c (known values fixed); coarse levels hold the correction e (0 at fixed cells) with right-hand side f.
 // Every unknown cell p solves f_p + sum_{q in N4(p), inside} (v_q - v_p) = 0; the sums run over neighbour DIFFERENCES, which
@@ -986,4 +988,522 @@ extern "C" int tg_vfill_pcg_iter(int H, int W, void* ws, size_t ws_bytes, void* 
         return TG_ERR_LAUNCH;
     }
     return vf_pcg_launch(p, q, (char*)ws, (char*)pws, false, change_bits, restarts, s);
+}
+
+// ---- biharmonic (thin-plate) fill (tg_vfill_bih_*) -------------------------------------------------
+// Minimise sum_{p in S} D(u)_p^2 over the unknowns, D the masked difference sum above and S the unknowns with their
+// 4-neighbours: A x = b with A = D(D(.)) restricted to the unknowns, symmetric positive definite.  Outer loop: the flexible
+// conjugate gradients of section 8n with x, D(x), the residual and every dot product in fp64 (in fp32 the loop stalls above the
+// stop rule), the direction p in fp32.  Preconditioner M r = G(G(r)): G is `inner` iterations of the same conjugate gradients
+// around the V-cycle on -D(e) = f (e = 0 at the fixed cells) from e = 0, all fp32; inner = 1 is one bare cycle.  The outer
+// passes stage a 36 x 68 patch (2-px halo) in LDS, form w = D(.) on its 34 x 66 interior and D(w) on the tile's unknowns: w
+// never goes to memory, and the ring of S that lies in a neighbouring tile without an unknown is covered by the halo.
+constexpr int VF_BY = VF_TY + 4, VF_BX = VF_TX + 4, VF_BXP = VF_BX + 1;
+constexpr int VF_WY = VF_TY + 2, VF_WX = VF_TX + 2, VF_WXP = VF_WX + 1;
+
+struct VfBih {
+    const uint8_t* flags;
+    const int32_t* list;      // nullptr on a one-level raster: the single tile 0
+    const int32_t* count;
+    int H, W, tiles_x;
+    VfPcgScal* sc;
+    const double* x_in;       // step: x (xa); dot: x' (xb)
+    double* x_out;            // step: x' (xb); dot: xa
+    double* r;
+    float* rf;                // the residual in fp32: the preconditioner's input
+    const float* z;
+    float* p0;
+    float* p1;
+    float* u;                 // dot: x' in fp32, the buffer tg_vfill_finish reads
+    double* part;
+    uint32_t* change;
+    int init;                 // step: alpha = 0 (the first residual)
+};
+
+struct VfBihLds {
+    double x[VF_BY][VF_BXP];
+    double w[VF_WY][VF_WXP];
+    uint8_t f[VF_BY][VF_BXP];
+    double red[4];
+};
+
+// w = D(x) on the patch's 34 x 66 interior (0 outside the raster)
+__device__ __forceinline__ void vf_bih_lap(VfBihLds& s) {
+    for (int j = threadIdx.x; j < VF_WY * VF_WX; j += 256) {
+        const int r = j / VF_WX, c = j - r * VF_WX;
+        const int ly = r + 1, lx = c + 1;
+        double acc = 0.0;
+        if (s.f[ly][lx] & VF_IN) {
+            const double up = s.x[ly][lx];
+            if (s.f[ly - 1][lx] & VF_IN) acc += s.x[ly - 1][lx] - up;
+            if (s.f[ly + 1][lx] & VF_IN) acc += s.x[ly + 1][lx] - up;
+            if (s.f[ly][lx - 1] & VF_IN) acc += s.x[ly][lx - 1] - up;
+            if (s.f[ly][lx + 1] & VF_IN) acc += s.x[ly][lx + 1] - up;
+        }
+        s.w[r][c] = acc;
+    }
+    __syncthreads();
+}
+
+// D(w) at the tile cell (r, c), which is not fixed
+__device__ __forceinline__ double vf_bih_lap2(const VfBihLds& s, int r, int c) {
+    const int ly = r + 2, lx = c + 2, wy = r + 1, wx = c + 1;
+    const double wp = s.w[wy][wx];
+    double acc = 0.0;
+    if (s.f[ly - 1][lx] & VF_IN) acc += s.w[wy - 1][wx] - wp;
+    if (s.f[ly + 1][lx] & VF_IN) acc += s.w[wy + 1][wx] - wp;
+    if (s.f[ly][lx - 1] & VF_IN) acc += s.w[wy][wx - 1] - wp;
+    if (s.f[ly][lx + 1] & VF_IN) acc += s.w[wy][wx + 1] - wp;
+    return acc;
+}
+
+__global__ __launch_bounds__(256) void vf_bih_init_kernel(const float* __restrict__ u, int64_t n, double* __restrict__ xa,
+                                                          double* __restrict__ xb) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const double v = (double)u[i];
+        xa[i] = v;
+        xb[i] = v;
+    }
+}
+
+// x' = x + alpha p (halo included) -> x_out, r' = b - A x' = -D(D(x')) -> r and rf, the tile's r'.z_old, the largest |alpha p|
+__global__ __launch_bounds__(256) void vf_bih_step_kernel(VfBih P) {
+    __shared__ VfBihLds s;
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    const double alpha = P.init ? 0.0 : (double)P.sc->alpha;
+    const float* pin = P.sc->parity ? P.p1 : P.p0;
+    uint32_t mx = 0;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();                                          // the previous tile's readers are done
+        for (int j = threadIdx.x; j < VF_BY * VF_BX; j += 256) {
+            const int r = j / VF_BX, c = j - r * VF_BX;
+            const int y = y0 - 2 + r, x = x0 - 2 + c;
+            double v = 0.0;
+            uint8_t fl = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const int64_t i = (int64_t)y * W + x;
+                fl = VF_IN | P.flags[i];
+                v = P.x_in[i];
+                const bool inner = r >= 2 && r < VF_TY + 2 && c >= 2 && c < VF_TX + 2;
+                if (!(fl & VF_FIX) && alpha != 0.0) {
+                    const double d = alpha * (double)pin[i];
+                    v += d;
+                    if (inner) {
+                        const uint32_t b = __float_as_uint(fabsf((float)d));
+                        mx = b > mx ? b : mx;
+                    }
+                }
+                if (inner) P.x_out[i] = v;
+            }
+            s.x[r][c] = v;
+            s.f[r][c] = fl;
+        }
+        __syncthreads();
+        vf_bih_lap(s);
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int64_t i = (int64_t)y * W + x;
+            double acc = 0.0;
+            if (!(s.f[r + 2][c + 2] & VF_FIX)) {
+                acc = -vf_bih_lap2(s, r, c);
+                sum += acc * (double)P.z[i];
+            }
+            P.r[i] = acc;
+            P.rf[i] = (float)acc;
+        }
+        sum = vf_block_sum(sum, s.red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+    if (P.change) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t u = __shfl_xor(mx, o, 64);
+            mx = u > mx ? u : mx;
+        }
+        if (blockIdx.x == 0 && threadIdx.x == 0 && P.sc->restart) mx = 0x7f800000u;      // a skipped step is not convergence
+        if ((threadIdx.x & 63) == 0 && mx) atomicMax(P.change, mx);
+    }
+}
+
+// the tile's r'.z'; x' moves from xb back to xa, and in fp32 to level 0's u0
+__global__ __launch_bounds__(256) void vf_bih_dot_kernel(VfBih P) {
+    __shared__ double red[4];
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int64_t i = (int64_t)y * W + x;
+            sum += P.r[i] * (double)P.z[i];                       // r is 0 at the fixed cells
+            const double v = P.x_in[i];
+            P.x_out[i] = v;
+            P.u[i] = (float)v;
+        }
+        sum = vf_block_sum(sum, red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+}
+
+// p = z + beta p (halo included) -> the other p buffer, A p = D(D(p)) with p = 0 at the fixed cells, the tile's p.Ap
+__global__ __launch_bounds__(256) void vf_bih_dir_kernel(VfBih P) {
+    __shared__ VfBihLds s;
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    const float beta = P.sc->beta;
+    const bool par = P.sc->parity != 0;
+    const float* pin = par ? P.p1 : P.p0;
+    float* pout = par ? P.p0 : P.p1;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();
+        for (int j = threadIdx.x; j < VF_BY * VF_BX; j += 256) {
+            const int r = j / VF_BX, c = j - r * VF_BX;
+            const int y = y0 - 2 + r, x = x0 - 2 + c;
+            float v = 0.f;
+            uint8_t fl = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const int64_t i = (int64_t)y * W + x;
+                fl = VF_IN | P.flags[i];
+                if (!(fl & VF_FIX)) {
+                    v = P.z[i];
+                    if (beta != 0.f) v = __fadd_rn(v, __fmul_rn(beta, pin[i]));
+                }
+                if (r >= 2 && r < VF_TY + 2 && c >= 2 && c < VF_TX + 2) pout[i] = v;
+            }
+            s.x[r][c] = (double)v;
+            s.f[r][c] = fl;
+        }
+        __syncthreads();
+        vf_bih_lap(s);
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            if (s.f[r + 2][c + 2] & VF_FIX) continue;
+            sum += s.x[r + 2][c + 2] * vf_bih_lap2(s, r, c);
+        }
+        sum = vf_block_sum(sum, s.red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+}
+
+// The inner solve G: the passes of section 8n with a right-hand side from an array and 0 at the fixed cells.  Its dot and
+// direction passes are vf_pcg_dot_kernel and vf_pcg_dir_kernel as they stand; the step and the last update are these two.
+struct VfRhs {
+    const uint8_t* flags;
+    const int32_t* list;
+    const int32_t* count;
+    int H, W, tiles_x;
+    const VfPcgScal* sc;
+    const float* rhs;
+    const float* e_in;        // nullptr: e = 0 (the first step of a solve)
+    float* e_out;
+    float* r;
+    const float* z;
+    const float* p0;
+    const float* p1;
+    double* part;
+};
+
+// e' = e + alpha p (halo included) -> e_out, r' = f + D(e') -> r, the tile's r'.z_old
+__global__ __launch_bounds__(256) void vf_rhs_step_kernel(VfRhs P) {
+    __shared__ float sx[VF_PY][VF_PXP];
+    __shared__ uint8_t sf[VF_PY][VF_PXP];
+    __shared__ double red[4];
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    const float alpha = P.sc->alpha;
+    const float* pin = P.sc->parity ? P.p1 : P.p0;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        __syncthreads();                                          // the previous tile's readers are done
+        for (int j = threadIdx.x; j < VF_PY * VF_PX; j += 256) {
+            const int r = j / VF_PX, c = j - r * VF_PX;
+            const int y = y0 - 1 + r, x = x0 - 1 + c;
+            float v = 0.f;
+            uint8_t fl = 0;
+            if (y >= 0 && y < H && x >= 0 && x < W) {
+                const int64_t i = (int64_t)y * W + x;
+                fl = VF_IN | P.flags[i];
+                if (!(fl & VF_FIX)) {
+                    if (P.e_in) v = P.e_in[i];
+                    if (alpha != 0.f) v = __fadd_rn(v, __fmul_rn(alpha, pin[i]));
+                }
+                if (r >= 1 && r <= VF_TY && c >= 1 && c <= VF_TX) P.e_out[i] = v;
+            }
+            sx[r][c] = v;
+            sf[r][c] = fl;
+        }
+        __syncthreads();
+        double sum = 0.0;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int ly = r + 1, lx = c + 1;
+            const int64_t i = (int64_t)y * W + x;
+            float acc = 0.f;
+            if (!(sf[ly][lx] & VF_FIX)) {
+                const float up = sx[ly][lx];
+                acc = P.rhs[i];
+                if (sf[ly - 1][lx] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly - 1][lx], up));
+                if (sf[ly + 1][lx] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly + 1][lx], up));
+                if (sf[ly][lx - 1] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly][lx - 1], up));
+                if (sf[ly][lx + 1] & VF_IN) acc = __fadd_rn(acc, __fsub_rn(sx[ly][lx + 1], up));
+                sum += (double)acc * (double)P.z[i];
+            }
+            P.r[i] = acc;
+        }
+        sum = vf_block_sum(sum, red);
+        if (threadIdx.x == 0) P.part[tile] = sum;
+    }
+}
+
+// the last update of a solve: e + alpha p -> e_out on the active tiles (no residual follows)
+__global__ __launch_bounds__(256) void vf_rhs_final_kernel(VfRhs P) {
+    const int H = P.H, W = P.W;
+    const int ntiles = P.list ? *P.count : 1;
+    const float alpha = P.sc->alpha;
+    const float* pin = P.sc->parity ? P.p1 : P.p0;
+    for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int tile = P.list ? P.list[t] : 0;
+        const int ty = tile / P.tiles_x, tx = tile - ty * P.tiles_x;
+        const int y0 = ty * VF_TY, x0 = tx * VF_TX;
+        for (int j = threadIdx.x; j < VF_TY * VF_TX; j += 256) {
+            const int r = j / VF_TX, c = j - r * VF_TX;
+            const int y = y0 + r, x = x0 + c;
+            if (y >= H || x >= W) continue;
+            const int64_t i = (int64_t)y * W + x;
+            float v = 0.f;
+            if (!(P.flags[i] & VF_FIX)) {
+                if (P.e_in) v = P.e_in[i];
+                if (alpha != 0.f) v = __fadd_rn(v, __fmul_rn(alpha, pin[i]));
+            }
+            P.e_out[i] = v;
+        }
+    }
+}
+
+__global__ void vf_bih_restarts_kernel(const VfPcgScal* outer, const VfPcgScal* inner, uint32_t* restarts) {
+    *restarts = outer->restarts + inner->restarts;
+}
+
+// the third workspace (mirrored by vfill_bih_layout in mvp_gan/src/fill_voids.py)
+enum { VF_BIH_F64 = 3, VF_BIH_F32 = 12, VF_BIH_PARTS = 6 };
+struct VfBihPlan {
+    size_t sc_out, sc_in;
+    size_t xa, xb, r;                              // fp64
+    size_t rf, t, z, p0, p1;                       // fp32, outer
+    size_t e0, e1, ri, zi, q0, q1, d;              // fp32, the inner solve
+    size_t part[VF_BIH_PARTS];                     // outer p.Ap, r'.z, r'.z', then the inner solve's
+    size_t bytes;
+};
+
+static void vf_bih_plan(const VfPlan& p, VfBihPlan* q) {
+    const size_t n = (size_t)p.lv[0].H * p.lv[0].W;
+    size_t off = 0;
+    q->sc_out = off; off += VF_ALIGN;
+    q->sc_in = off; off += VF_ALIGN;
+    size_t* f64[VF_BIH_F64] = {&q->xa, &q->xb, &q->r};
+    for (size_t* o : f64) { *o = off; off += al(n * 8); }
+    size_t* f32[VF_BIH_F32] = {&q->rf, &q->t, &q->z, &q->p0, &q->p1, &q->e0, &q->e1, &q->ri, &q->zi, &q->q0, &q->q1, &q->d};
+    for (size_t* o : f32) { *o = off; off += al(n * 4); }
+    for (int k = 0; k < VF_BIH_PARTS; ++k) { q->part[k] = off; off += al((size_t)p.lv[0].tiles * 8); }
+    q->bytes = off;
+}
+
+static int vf_bws_check(const char* who, const VfPlan& p, const void* bws, size_t bws_bytes, int inner, VfBihPlan* q) {
+    TG_REQUIRE(bws, "%s: null pointer", who);
+    TG_REQUIRE(((uintptr_t)bws & (VF_ALIGN - 1)) == 0, "%s: biharmonic workspace must be %d-byte aligned", who, VF_ALIGN);
+    TG_REQUIRE(inner >= 1 && inner <= TG_VFILL_BIH_MAX_INNER, "%s: inner %d must be in 1..%d", who, inner, TG_VFILL_BIH_MAX_INNER);
+    vf_bih_plan(p, q);
+    if (bws_bytes < q->bytes) {
+        tg_set_error("%s: biharmonic workspace %zu bytes < %zu", who, bws_bytes, q->bytes);
+        return TG_ERR_WS;
+    }
+    return TG_OK;
+}
+
+extern "C" size_t tg_vfill_bih_ws_bytes(int H, int W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    VfPlan p;
+    VfBihPlan q;
+    vf_plan(H, W, &p);
+    vf_bih_plan(p, &q);
+    return q.bytes;
+}
+
+// out = G(f): `inner` cycles
+static int vf_bih_solve(const VfPlan& p, const VfBihPlan& q, char* base, char* bb, const float* f, float* out, int inner,
+                        hipStream_t s) {
+    const VfLevel& v = p.lv[0];
+    VfHdr* hdr = (VfHdr*)base;
+    auto F = [&](size_t off) { return (float*)(bb + off); };
+    auto D = [&](int k) { return (double*)(bb + q.part[3 + k]); };
+    if (inner == 1) {
+        const VfPre pre = {f, F(q.d), out};
+        return vf_launch_cycle(p, base, &pre, nullptr, s);
+    }
+    VfPcgScal* sc = (VfPcgScal*)(bb + q.sc_in);
+    const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
+    VfPcg a = {};
+    a.flags = (const uint8_t*)(base + v.flags);
+    a.list = p.L > 1 ? (const int32_t*)(base + v.list) : nullptr;
+    a.count = &hdr->ntiles[0];
+    a.H = v.H; a.W = v.W; a.tiles_x = v.tiles_x;
+    a.sc = sc;
+    a.z = F(q.zi); a.p0 = F(q.q0); a.p1 = F(q.q1);
+    VfRhs b = {};
+    b.flags = a.flags; b.list = a.list; b.count = a.count;
+    b.H = v.H; b.W = v.W; b.tiles_x = v.tiles_x;
+    b.sc = sc;
+    b.rhs = f;
+    b.z = F(q.zi); b.p0 = F(q.q0); b.p1 = F(q.q1);
+    for (int k = 0; k < inner; ++k) {
+        const float* r = f;                                       // the residual of e = 0
+        if (k > 0) {
+            VfRhs st = b;
+            st.e_in = k > 1 ? F(q.e0) : nullptr;
+            st.e_out = F(q.e1);
+            st.r = F(q.ri);
+            st.part = D(1);
+            hipLaunchKernelGGL(vf_rhs_step_kernel, g, dim3(256), 0, s, st);
+            TG_CHECK_LAUNCH("vf_rhs_step_kernel");
+            r = F(q.ri);
+        }
+        const VfPre pre = {r, F(q.d), F(q.zi)};
+        if (int rc = vf_launch_cycle(p, base, &pre, nullptr, s)) return rc;
+        VfPcg dt = a;
+        dt.r = (float*)r;                                         // read only
+        dt.x_in = k > 0 ? F(q.e1) : F(q.e0);                      // k = 0: e0 onto itself, whatever it holds
+        dt.x_out = F(q.e0);
+        dt.part = D(2);
+        hipLaunchKernelGGL(vf_pcg_dot_kernel, g, dim3(256), 0, s, dt);
+        TG_CHECK_LAUNCH("vf_pcg_dot_kernel");
+        hipLaunchKernelGGL((vf_pcg_scalar_kernel<true>), dim3(1), dim3(256), 0, s, sc, (const double*)D(2), (const double*)D(1),
+                           v.tiles, k == 0 ? 1 : 0, (uint32_t*)nullptr);
+        TG_CHECK_LAUNCH("vf_pcg_scalar_kernel<beta>");
+        VfPcg dr = a;
+        dr.part = D(0);
+        hipLaunchKernelGGL(vf_pcg_dir_kernel, g, dim3(256), 0, s, dr);
+        TG_CHECK_LAUNCH("vf_pcg_dir_kernel");
+        hipLaunchKernelGGL((vf_pcg_scalar_kernel<false>), dim3(1), dim3(256), 0, s, sc, (const double*)D(0),
+                           (const double*)nullptr, v.tiles, 0, (uint32_t*)nullptr);
+        TG_CHECK_LAUNCH("vf_pcg_scalar_kernel<alpha>");
+    }
+    VfRhs fn = b;
+    fn.e_in = inner > 1 ? F(q.e0) : nullptr;
+    fn.e_out = out;
+    hipLaunchKernelGGL(vf_rhs_final_kernel, g, dim3(256), 0, s, fn);
+    TG_CHECK_LAUNCH("vf_rhs_final_kernel");
+    return TG_OK;
+}
+
+// step (or the first residual), z = G(G(r)), r.z, beta, the new direction and p.Ap, alpha
+static int vf_bih_launch(const VfPlan& p, const VfBihPlan& q, char* base, char* bb, bool first, int inner,
+                         uint32_t* change_bits, uint32_t* restarts, hipStream_t s) {
+    const VfLevel& v = p.lv[0];
+    VfHdr* hdr = (VfHdr*)base;
+    VfPcgScal* sc = (VfPcgScal*)(bb + q.sc_out);
+    auto F = [&](size_t off) { return (float*)(bb + off); };
+    auto D = [&](int k) { return (double*)(bb + q.part[k]); };
+    VfBih a = {};
+    a.flags = (const uint8_t*)(base + v.flags);
+    a.list = p.L > 1 ? (const int32_t*)(base + v.list) : nullptr;
+    a.count = &hdr->ntiles[0];
+    a.H = v.H; a.W = v.W; a.tiles_x = v.tiles_x;
+    a.sc = sc;
+    a.r = (double*)(bb + q.r); a.rf = F(q.rf); a.z = F(q.z); a.p0 = F(q.p0); a.p1 = F(q.p1);
+    a.u = (float*)(base + v.u0);
+    const dim3 g(v.tiles < VF_MAX_GRID ? v.tiles : VF_MAX_GRID);
+
+    VfBih st = a;
+    st.x_in = (const double*)(bb + q.xa);
+    st.x_out = (double*)(bb + q.xb);
+    st.part = D(1);
+    st.change = change_bits;
+    st.init = first ? 1 : 0;
+    hipLaunchKernelGGL(vf_bih_step_kernel, g, dim3(256), 0, s, st);
+    TG_CHECK_LAUNCH("vf_bih_step_kernel");
+
+    if (int rc = vf_bih_solve(p, q, base, bb, F(q.rf), F(q.t), inner, s)) return rc;
+    if (int rc = vf_bih_solve(p, q, base, bb, F(q.t), F(q.z), inner, s)) return rc;
+
+    VfBih dt = a;
+    dt.x_in = (const double*)(bb + q.xb);
+    dt.x_out = (double*)(bb + q.xa);
+    dt.part = D(2);
+    hipLaunchKernelGGL(vf_bih_dot_kernel, g, dim3(256), 0, s, dt);
+    TG_CHECK_LAUNCH("vf_bih_dot_kernel");
+    hipLaunchKernelGGL((vf_pcg_scalar_kernel<true>), dim3(1), dim3(256), 0, s, sc, (const double*)D(2), (const double*)D(1),
+                       v.tiles, first ? 1 : 0, (uint32_t*)nullptr);
+    TG_CHECK_LAUNCH("vf_pcg_scalar_kernel<beta>");
+
+    VfBih dr = a;
+    dr.part = D(0);
+    hipLaunchKernelGGL(vf_bih_dir_kernel, g, dim3(256), 0, s, dr);
+    TG_CHECK_LAUNCH("vf_bih_dir_kernel");
+    hipLaunchKernelGGL((vf_pcg_scalar_kernel<false>), dim3(1), dim3(256), 0, s, sc, (const double*)D(0), (const double*)nullptr,
+                       v.tiles, 0, (uint32_t*)nullptr);
+    TG_CHECK_LAUNCH("vf_pcg_scalar_kernel<alpha>");
+    if (restarts) {
+        hipLaunchKernelGGL(vf_bih_restarts_kernel, dim3(1), dim3(1), 0, s, (const VfPcgScal*)sc,
+                           (const VfPcgScal*)(bb + q.sc_in), restarts);
+        TG_CHECK_LAUNCH("vf_bih_restarts_kernel");
+    }
+    return TG_OK;
+}
+
+extern "C" int tg_vfill_bih_start(int H, int W, void* ws, size_t ws_bytes, void* bws, size_t bws_bytes, int inner,
+                                  tg_stream_t stream) {
+    VfPlan p;
+    VfBihPlan q;
+    if (int rc = vf_ws_check("tg_vfill_bih_start", H, W, ws, ws_bytes, &p)) return rc;
+    if (int rc = vf_bws_check("tg_vfill_bih_start", p, bws, bws_bytes, inner, &q)) return rc;
+    const hipStream_t s = S(stream);
+    // scalars, partials of the inactive tiles, and every fp32 vector outside the active tiles start at 0
+    if (hipMemsetAsync(bws, 0, q.bytes, s) != hipSuccess) {
+        tg_set_error("tg_vfill_bih_start: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    const int64_t n = (int64_t)H * W;
+    char* bb = (char*)bws;
+    hipLaunchKernelGGL(vf_bih_init_kernel, dim3(ew_grid(n, 256)), dim3(256), 0, s, (const float*)((char*)ws + p.lv[0].u0), n,
+                       (double*)(bb + q.xa), (double*)(bb + q.xb));
+    TG_CHECK_LAUNCH("vf_bih_init_kernel");
+    return vf_bih_launch(p, q, (char*)ws, bb, true, inner, nullptr, nullptr, s);
+}
+
+extern "C" int tg_vfill_bih_iter(int H, int W, void* ws, size_t ws_bytes, void* bws, size_t bws_bytes, int inner,
+                                 uint32_t* change_bits, uint32_t* restarts, tg_stream_t stream) {
+    VfPlan p;
+    VfBihPlan q;
+    if (int rc = vf_ws_check("tg_vfill_bih_iter", H, W, ws, ws_bytes, &p)) return rc;
+    if (int rc = vf_bws_check("tg_vfill_bih_iter", p, bws, bws_bytes, inner, &q)) return rc;
+    TG_REQUIRE(change_bits && restarts, "tg_vfill_bih_iter: null pointer");
+    const hipStream_t s = S(stream);
+    if (hipMemsetAsync(change_bits, 0, sizeof(uint32_t), s) != hipSuccess) {
+        tg_set_error("tg_vfill_bih_iter: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    return vf_bih_launch(p, q, (char*)ws, (char*)bws, false, inner, change_bits, restarts, s);
 }

@@ -22,7 +22,8 @@ result is compared against the truth:
 
 Two calls on the same inputs return bitwise-equal tensors and an equal report.
 
-With baseline="laplace" the same keep mask is also filled by harmonic interpolation (fill_voids) and
+With baseline="laplace" the same keep mask is also filled by harmonic interpolation (fill_voids; with
+baseline="biharmonic" by the minimum-curvature fill of section 8q, the stronger baseline on slope and curvature) and
 report["baseline"] holds that fill's full terrain_errors report on the same holes, plus "method" and the fill info: the number
 a GAN has to beat.  fallback and seam are passed to inpaint_raster; with seam="harmonic" report["seam"] holds the info of the
 seam correction (mvp_gan/src/seam_correct.py), and the ring errors show what it did.
@@ -30,7 +31,7 @@ seam correction (mvp_gan/src/seam_correct.py), and the ring errors show what it 
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
-         [--baseline laplace] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
+         [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -372,7 +373,7 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
 
 
 # ---- end to end -----------------------------------------------------------------------------------------------------
-BASELINES = ("laplace",)
+BASELINES = ("laplace", "biharmonic")
 
 
 def _check_fill_options(baseline, fallback, who="evaluate_raster"):
@@ -492,7 +493,8 @@ def build_parser():
     ap.add_argument("--pred-out", help="write the prediction (.asc)")
     ap.add_argument("--holes-out", help="write the evaluation holes (.png or .asc, nonzero = hole)")
     ap.add_argument("--baseline", choices=BASELINES,
-                    help="also score a harmonic interpolation (fill_voids) of the same holes: a second summary line")
+                    help="also score a harmonic or a minimum-curvature interpolation (fill_voids) of the same holes: a second "
+                         "summary line")
     ap.add_argument("--fallback", choices=("laplace",),
                     help="checkpoint mode: fill the holes no window reaches by harmonic interpolation")
     ap.add_argument("--solver", choices=("mg", "pcg"), default="mg",

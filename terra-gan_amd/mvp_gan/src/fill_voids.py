@@ -15,10 +15,17 @@ GAN against, and a fill for the voids no inpainting window reaches.
     keep their meaning.  It is the solver for large and for tile-aligned voids (a missing tile of a mosaic), on which the
     plain cycle converges slowly or not at all; info gains "solver" and "restarts".  The default "mg" is unchanged.
 
+  - method="biharmonic" fills with the curvature-minimising (thin-plate, minimum-curvature) surface instead (DESIGN.md
+    section 8q): the unknowns minimise the sum of (sum_q (u_q - u_p))^2 over themselves and their 4-neighbours, so the fill
+    meets the terrain in height and slope and carries ridges and valleys across a void; off the raster border it reproduces
+    every cubic.  Conjugate gradients on the normal equations (the state in fp64), preconditioned by two approximate Laplace
+    solves of `inner` V-cycles each: `max_cycles` (default 200) and info["cycles"] count outer iterations, info["vcycles"]
+    the V-cycles (2 x inner per iteration and for the start); `solver` is validated and unused.
+
 Two calls on the same inputs return bitwise-equal rasters and equal info.
 
 CLI: python -m mvp_gan.src.fill_voids --dem in.asc [--mask m.png|m.asc] [--nodata v] [--remove-objects [spec flags]]
-         [--tol t] [--max-cycles n] [--solver mg|pcg] --out out.asc
+         [--tol t] [--max-cycles n] [--solver mg|pcg] [--method laplace|biharmonic] [--inner k] --out out.asc
 """
 import argparse
 import math
@@ -26,7 +33,10 @@ import math
 import numpy as np
 import torch
 
-METHODS = ("laplace",)
+METHODS = ("laplace", "biharmonic")
+MAX_CYCLES = {"laplace": 50, "biharmonic": 200}    # what max_cycles=None resolves to
+INNER = 3                      # V-cycles of one approximate Laplace solve of the biharmonic preconditioner
+MAX_INNER = 8
 SOLVERS = ("mg", "pcg")
 CMAX = 16                      # coarsest level: longer side at most this
 TILE_Y, TILE_X = 32, 64        # tiles of the level passes
@@ -90,10 +100,42 @@ def vfill_pcg_layout(H, W):
     return out, off
 
 
+def vfill_bih_layout(H, W):
+    """-> (dict: sc_out, sc_in (scalars), xa, xb, r (fp64), rf, t, z, p0, p1 (fp32, outer loop), e0, e1, ri, zi, q0, q1, d (fp32,
+    inner solve), part (6 offsets: the outer p.Ap, r'.z, r'.z' by tile id, then the inner solve's) byte offsets, total bytes)
+    of the workspace of the biharmonic fill (tg_vfill_bih_ws_bytes)."""
+    n = int(H) * int(W)
+    tiles = -(-int(H) // TILE_Y) * -(-int(W) // TILE_X)
+    out = {"tiles": tiles, "sc_out": 0, "sc_in": ALIGN}
+    off = 2 * ALIGN
+    for k in ("xa", "xb", "r"):
+        out[k] = off
+        off += _al(8 * n)
+    for k in ("rf", "t", "z", "p0", "p1", "e0", "e1", "ri", "zi", "q0", "q1", "d"):
+        out[k] = off
+        off += _al(4 * n)
+    out["part"] = []
+    for _ in range(6):
+        out["part"].append(off)
+        off += _al(8 * tiles)
+    return out, off
+
+
 def check_solver(solver, who="fill_voids"):
     if not isinstance(solver, str) or solver not in SOLVERS:
         raise ValueError(f"{who}: solver {solver!r} must be one of {SOLVERS}")
     return solver
+
+
+def check_inner(inner, who="fill_voids"):
+    if isinstance(inner, bool) or not isinstance(inner, (int, np.integer)) or not 1 <= inner <= MAX_INNER:
+        raise ValueError(f"{who}: inner {inner!r} must be an integer in 1..{MAX_INNER}")
+    return int(inner)
+
+
+def resolve_max_cycles(max_cycles, method):
+    """max_cycles=None: 50 V-cycles for "laplace", 200 outer iterations for "biharmonic"."""
+    return MAX_CYCLES[method] if max_cycles is None else max_cycles
 
 
 # ---- validation -----------------------------------------------------------------------------------------------------
@@ -108,8 +150,9 @@ def check_args(dem, mask, method, tol, max_cycles, objects, cellsize, who="fill_
         raise ValueError(f"{who}: dem must be [H, W] with H*W < 2^31, got {shape}")
     if mask is not None and _shape(mask) != shape:
         raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
-    if method not in METHODS:
+    if not isinstance(method, str) or method not in METHODS:
         raise ValueError(f"{who}: method {method!r} must be one of {METHODS}")
+    max_cycles = resolve_max_cycles(max_cycles, method)
     if tol is not None:
         try:
             t = float(tol)
@@ -149,15 +192,21 @@ def _bits_f32(b):
 
 # ---- the fill -------------------------------------------------------------------------------------------------------
 @torch.no_grad()
-def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_cycles=50, objects=None, cellsize=None,
-               solver="mg"):
+def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_cycles=None, objects=None, cellsize=None,
+               solver="mg", inner=INNER):
     """dem: float32 [H][W] in metres (numpy or HIP tensor); mask: same shape, nonzero = known (optional).
+    method: "laplace" (harmonic) or "biharmonic" (thin-plate; `inner` V-cycles per approximate Laplace solve).
     solver: "mg" (V-cycles) or "pcg" (conjugate gradients around the V-cycle; one iteration counts as one cycle).
+    max_cycles: None = 50 for "laplace", 200 (outer iterations) for "biharmonic".
     Returns (raster float32 HIP tensor [H][W], info dict: unknown, unfilled, cycles, change, tol, converged, levels, with
-    objects the object_mask info under "objects", and with solver="pcg" also solver and restarts)."""
+    objects the object_mask info under "objects", with solver="pcg" also solver and restarts, and with method="biharmonic"
+    method, inner, restarts and vcycles)."""
     from tg_hip import ops as O
     H, W, c = check_args(dem, mask, method, tol, max_cycles, objects, cellsize)
     check_solver(solver)
+    inner = check_inner(inner)
+    max_cycles = resolve_max_cycles(max_cycles, method)
+    bih = method == "biharmonic"
     if not torch.cuda.is_available():
         raise RuntimeError("fill_voids: no HIP device visible; this build has no CPU path")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -174,8 +223,23 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
     known, unknown = int(st[0]), int(st[1])
     rng = _bits_f32(st[3]) - _bits_f32(st[2]) if known else 0.0
     t = 1e-6 * rng if tol is None else float(tol)
-    cycles, change, converged, restarts = 0, 0.0, known > 0, 0
-    if known and unknown and solver == "pcg":
+    cycles, change, converged, restarts, vcycles = 0, 0.0, known > 0, 0, 0
+    if known and unknown and bih:
+        converged = False
+        bws = O.vfill_bih_ws(H, W, device)
+        O.vfill_bih_start(H, W, ws, bws, inner)
+        vcycles = 2 * inner
+        st = torch.zeros(2, dtype=torch.int32, device=device)  # change bits, restarts
+        while cycles < max_cycles:
+            O.vfill_bih_iter(H, W, ws, bws, inner, st)
+            cycles += 1
+            vcycles += 2 * inner
+            change = _bits_f32(st[0].item())                    # one read per outer iteration
+            if change <= t:
+                converged = True
+                break
+        restarts = int(st[1].item())
+    elif known and unknown and solver == "pcg":
         converged = False
         pws = O.vfill_pcg_ws(H, W, device)
         O.vfill_pcg_start(H, W, ws, pws)
@@ -201,15 +265,21 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
     out = O.vfill_finish(z, ws)
     info = {"unknown": unknown, "unfilled": 0 if known else H * W, "cycles": cycles, "change": change, "tol": t,
             "converged": converged, "levels": len(vfill_levels(H, W))}
-    if solver == "pcg":
+    if solver == "pcg" and not bih:
         info["solver"] = solver
         info["restarts"] = restarts
+    if bih:
+        info.update(method=method, inner=inner, restarts=restarts, vcycles=vcycles)
     if oinfo is not None:
         info["objects"] = oinfo
     return out, info
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------
+class _Unset(int):
+    """The --max-cycles default: 50 as ever, told apart from a given 50 so that --method decides what it resolves to."""
+
+
 def build_parser():
     from .object_mask import add_spec_args
     ap = argparse.ArgumentParser(description="Fill the voids of an ESRI ASCII grid DSM by harmonic (Laplace) interpolation.")
@@ -220,7 +290,12 @@ def build_parser():
                     help="find above-ground objects (cellsize from the header) and fill them too: bare earth")
     add_spec_args(ap)
     ap.add_argument("--tol", type=float, help="stop when a cycle changes no void pixel by more (default 1e-6 x range)")
-    ap.add_argument("--max-cycles", type=int, default=50)
+    ap.add_argument("--max-cycles", type=int, default=_Unset(MAX_CYCLES["laplace"]),
+                    help="default 50 V-cycles (laplace) or 200 outer iterations (biharmonic)")
+    ap.add_argument("--method", choices=METHODS, default="laplace",
+                    help="laplace: harmonic fill; biharmonic: minimum-curvature (thin-plate) fill")
+    ap.add_argument("--inner", type=int, default=INNER,
+                    help="biharmonic: V-cycles per approximate Laplace solve of the preconditioner (1..8)")
     ap.add_argument("--solver", choices=SOLVERS, default="mg",
                     help="mg: V-cycles; pcg: conjugate gradients around the V-cycle, for large or tile-aligned voids")
     ap.add_argument("--out", required=True, help="output .asc raster")
@@ -236,12 +311,14 @@ def main(argv=None):
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
     objects = spec_from_args(a) if a.remove_objects else None
-    out, info = fill_voids(dem, mask, nodata=nodata, tol=a.tol, max_cycles=a.max_cycles, objects=objects,
-                           cellsize=float(asc_value(header, "cellsize")), solver=a.solver)
+    max_cycles = None if isinstance(a.max_cycles, _Unset) else a.max_cycles
+    out, info = fill_voids(dem, mask, nodata=nodata, tol=a.tol, max_cycles=max_cycles, objects=objects,
+                           cellsize=float(asc_value(header, "cellsize")), solver=a.solver, method=a.method, inner=a.inner)
     if info["unfilled"] and asc_value(header, "NODATA_value") is None:
         header = header + [("NODATA_value", "-9999")]
     write_asc(a.out, out.cpu().numpy(), header)
-    print(f"{a.out}: {info['unknown']} void pixels, {info['cycles']} cycles, converged {info['converged']}, solver {a.solver}")
+    print(f"{a.out}: {info['unknown']} void pixels, {info['cycles']} cycles, converged {info['converged']}, "
+          + (f"method {a.method}, {info['vcycles']} V-cycles" if a.method == "biharmonic" else f"solver {a.solver}"))
     if not info["converged"]:
         print(f"warning: not converged: last change {info['change']:.3g} > tol {info['tol']:.3g} after {info['cycles']} "
               "cycles" if info["unknown"] and info["unfilled"] == 0 else "warning: nothing is known: every pixel is NaN")

@@ -160,6 +160,9 @@ SIGNATURES = {
     "tg_vfill_pcg_ws_bytes": (SZ, [I, I]),
     "tg_vfill_pcg_start": (I, [I, I, P, SZ, P, SZ, P]),
     "tg_vfill_pcg_iter": (I, [I, I, P, SZ, P, SZ, P, P, P]),
+    "tg_vfill_bih_ws_bytes": (SZ, [I, I]),
+    "tg_vfill_bih_start": (I, [I, I, P, SZ, P, SZ, I, P]),
+    "tg_vfill_bih_iter": (I, [I, I, P, SZ, P, SZ, I, P, P, P]),
     "tg_seam_delta": (I, [P, P, I, F, P, I, I, I, P, P, P]),
     "tg_seam_apply": (I, [P, P, I, F, P, P, I, I, P, P]),
     "tg_resample_area": (I, [P, P, I, F, I, I, I, I, I, I, P, P, I, F, I, I, P, P, P, P]),

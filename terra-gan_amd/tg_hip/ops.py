@@ -1252,6 +1252,33 @@ def vfill_pcg_iter(H, W, ws, pws, state):
                                      _stream()), "tg_vfill_pcg_iter")
 
 
+def vfill_bih_ws(H, W, device):
+    """The workspace of the biharmonic fill (tg_vfill_bih_ws_bytes): x twice and the residual in fp64, the fp32 vectors of the
+    outer loop and of the inner solve, partials, scalars."""
+    nb = _lib().tg_vfill_bih_ws_bytes(int(H), int(W))
+    if nb == 0:
+        raise L.TgError(f"vfill: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(nb, dtype=torch.uint8, device=device)
+
+
+def vfill_bih_start(H, W, ws, bws, inner):
+    """After vfill_setup: the residual, z = G(G(r)), the first direction and its step length (tg_vfill_bih_start)."""
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    _hip(bws, torch.uint8, (bws.numel(),), "bws")
+    L.check(_lib().tg_vfill_bih_start(int(H), int(W), _p(ws), ws.numel(), _p(bws), bws.numel(), int(inner), _stream()),
+            "tg_vfill_bih_start")
+
+
+def vfill_bih_iter(H, W, ws, bws, inner, state):
+    """One outer iteration = 2 * inner V-cycles (tg_vfill_bih_iter); state int32 [2] gets the float bits of the largest change
+    over the unknowns and the number of restarted directions."""
+    _hip(ws, torch.uint8, (ws.numel(),), "ws")
+    _hip(bws, torch.uint8, (bws.numel(),), "bws")
+    _hip(state, torch.int32, (2,), "state")
+    L.check(_lib().tg_vfill_bih_iter(int(H), int(W), _p(ws), ws.numel(), _p(bws), bws.numel(), int(inner), _p(state),
+                                     _p(state[1:]), _stream()), "tg_vfill_bih_iter")
+
+
 SEAM_NCOUNTS = 4                                  # tg_seam_delta counts: ring, interior, unfilled, max |delta| bits
 
 

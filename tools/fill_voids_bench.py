@@ -6,9 +6,11 @@ fill_voids calls and back-to-back V-cycles with device
 events after warm-up, and with --evaluate an evaluate_raster(baseline="laplace") call; prints one JSON line per scene: ms per
 call, cycles, ms per cycle, the contraction of the change per cycle, the active tiles per level and the algorithmic bytes of
 the level passes per cycle.  Where mg does not converge within fill_voids' default budget the scene is timed again with
-max_cycles=200 and the line says so ("max_cycles": 200).
+max_cycles=200 and the line says so ("max_cycles": 200).  With --method biharmonic the same scenes are
+filled by the minimum-curvature fill: a line then holds ms per call, the outer iterations ("cycles"), the V-cycles, ms per outer
+iteration and ms per V-cycle, to set next to --solver pcg of the harmonic fill.
 
-    python tools/fill_voids_bench.py [--size 8192] [--holes 0.3 0.02 tiles] [--solver mg pcg] [--reps 3] [--warmup 1] [--evaluate]
+    python tools/fill_voids_bench.py [--size 8192] [--holes 0.3 0.02 tiles] [--solver mg pcg] [--method laplace|biharmonic [--inner 3]] [--reps 3] [--warmup 1] [--evaluate]
     rocprofv3 --kernel-trace --stats -d prof -o p --output-format csv -- python tools/fill_voids_bench.py --holes 0.3
     python tools/fill_voids_bench.py --kstats prof/.../p_kernel_stats.csv --pass-bytes '{"down0": B, ...}'
 (the profiled run's cycles are the launches of vf_coarsest_kernel, one per cycle; setup and finish kernels count per launch)
@@ -66,6 +68,8 @@ def main():
     ap.add_argument("--size", type=int, default=8192)
     ap.add_argument("--holes", nargs="+", default=["0.3", "0.02"], help="shares of disc holes, or 'tiles'")
     ap.add_argument("--solver", nargs="+", choices=("mg", "pcg"), default=["mg"])
+    ap.add_argument("--method", choices=("laplace", "biharmonic"), default="laplace")
+    ap.add_argument("--inner", type=int, default=3, help="biharmonic: V-cycles per approximate Laplace solve")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--evaluate", action="store_true", help="also time evaluate_raster(baseline='laplace') on the 1st scene")
@@ -131,6 +135,33 @@ def main():
     for frac in a.holes:
         z, keep = scene(H, W, frac)
         zd, kd = torch.from_numpy(z).to(dev), torch.from_numpy(keep).to(dev)
+        if a.method == "biharmonic":
+            ms, (out, info) = timed(lambda: fill_voids(zd, kd, method="biharmonic", inner=a.inner), a.reps)
+            ws, bws = O.vfill_ws(H, W, dev), O.vfill_bih_ws(H, W, dev)
+            st = torch.zeros(2, dtype=torch.int32, device=dev)
+            hist = []
+            for timing in (False, True):
+                O.vfill_setup(zd, kd, None, ws)
+                O.vfill_bih_start(H, W, ws, bws, a.inner)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(info["cycles"]):
+                    O.vfill_bih_iter(H, W, ws, bws, a.inner, st)
+                    if not timing:
+                        hist.append(bits(st[0].item()))
+                e1.record()
+                torch.cuda.synchronize()
+            ms_it = e0.elapsed_time(e1) / max(info["cycles"], 1)
+            tiles = np.frombuffer(ws[HDR_TILES:HDR_TILES + 4 * len(levels)].cpu().numpy().tobytes(), np.int32).tolist()
+            print(json.dumps({"what": "fill_voids", "method": "biharmonic", "inner": a.inner, "H": H, "W": W, "holes": frac,
+                              "unknown": info["unknown"], "ms_per_call": round(ms, 3), "cycles": info["cycles"],
+                              "vcycles": info["vcycles"], "ms_per_iteration": round(ms_it, 3),
+                              "ms_per_vcycle": round(ms_it / (2 * a.inner), 3), "converged": info["converged"],
+                              "restarts": info["restarts"], "change": [float("%.3g" % v) for v in hist],
+                              "levels": len(levels), "active_tiles": tiles[:len(levels) - 1],
+                              "workspace_GB": round((ws.numel() + bws.numel()) / 1e9, 3), "reps": a.reps,
+                              "warmup": a.warmup}), flush=True)
+            continue
         for solver in a.solver:
             budget = 50
             ms, (out, info) = timed(lambda: fill_voids(zd, kd, solver=solver), a.reps)
