@@ -693,6 +693,34 @@ int tg_resample_interp(const float* dem, const float* mask, int use_nodata, floa
                        const float* keep_dem, const float* keep_mask, int keep_use_nodata, float keep_nodata, int Ho, int Wo,
                        float* out, float* out_mask, int32_t* n_nan, tg_stream_t stream);
 
+/* ---- Distance to the nearest known pixel; terrain errors by depth (csrc/edt.hip) ---------------- */
+/* Exact Euclidean distance transform.  2 * 32767^2 < 2^31: an int32 holds every squared distance of an admitted raster. */
+enum { TG_EDT_FAR = 0x7fffffff, TG_EDT_MAX_SIDE = 32767 };
+size_t tg_edt_ws_bytes(int H, int W);
+/* seed [H][W] uint8, nonzero = distance 0.  d2 [H][W] int32 = min(exact squared Euclidean distance in pixels to the
+ * nearest seed, cap2); cap2 <= 0: no cap, TG_EDT_FAR where the raster has no seed at all.  dist_m (may be NULL) [H][W] float
+ * = (float)(cellsize * sqrt((double)d2)), +inf at TG_EDT_FAR; cellsize is read only with dist_m.  Integer arithmetic up to
+ * dist_m: bit-exact and deterministic.  ws >= tg_edt_ws_bytes (the band words, the carried rows and the uint16 column
+ * distances); 0 from the query and TG_ERR_ARG from the call for a side outside [1, TG_EDT_MAX_SIDE]. */
+int tg_edt(const uint8_t* seed, int H, int W, int32_t cap2, double cellsize, int32_t* d2, float* dist_m,
+           void* ws, size_t ws_bytes, tg_stream_t stream);
+/* Depth classes of tg_depth_errors: a pixel of squared distance D is in class c = #{e < n_edges : D >= d2[e]}. */
+enum { TG_DEPTH_MAX_CLASSES = 8 };
+typedef struct { int32_t n_edges, _pad; int32_t d2[TG_DEPTH_MAX_CLASSES - 1]; } TgDepthClasses;   /* nondecreasing */
+size_t tg_depth_errors_ws_bytes(int H, int W);
+/* a [H*W]: |error| on the scored pixels, NaN elsewhere (tg_terrain_errors' sel_a, read only).  Pixel i with a[i] not NaN is in
+ * class c = #{e < n_edges : d2[i] >= cls->d2[e]}.  counts [TG_DEPTH_MAX_CLASSES] int64 (zeroed here), max_bits
+ * [TG_DEPTH_MAX_CLASSES] uint32 (zeroed here) = largest a per class as float bits; hole_d2 [nholes] int32 (zeroed here) = max
+ * d2 over ALL pixels of the hole (labels >= 0), at row slot[labels[i]].  Per-workgroup fp64 partials of sum a and sum a*a per
+ * class go to ws (>= tg_depth_errors_ws_bytes); the grid is a function of the shape. */
+int tg_depth_errors(const float* a, const int32_t* d2, const int32_t* labels, const int32_t* slot, int nholes, int H, int W,
+                    const TgDepthClasses* cls, int64_t* counts, uint32_t* max_bits, int32_t* hole_d2,
+                    void* ws, size_t ws_bytes, tg_stream_t stream);
+/* sums [2 * TG_DEPTH_MAX_CLASSES] double: sums[2c] = sum a, sums[2c + 1] = sum a*a over class c, from the partials of the last
+ * tg_depth_errors call of this shape on ws, reduced in a fixed order. */
+int tg_depth_errors_finish(int H, int W, const void* ws, size_t ws_bytes, double* sums /* [2*TG_DEPTH_MAX_CLASSES] */,
+                           tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

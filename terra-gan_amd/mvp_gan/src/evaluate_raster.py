@@ -20,6 +20,12 @@ result is compared against the truth:
   - per-hole sums are sum rint(min(a, 2^15) * 2^16) in int64 (exact, order-independent; < 8 um per pixel);
   - quantiles by nearest rank: sorted ascending, element ceil(q n) - 1, selected exactly on the GPU.
 
+With depth_edges_m (metres, e.g. DEPTH_EDGES_M) the report also says how deep into the holes the errors sit: the exact Euclidean
+distance of every pixel to the nearest pixel of K (csrc/edt.hip; capped at the last edge, beyond which
+every pixel is in the last class anyway) puts each scored pixel into a depth class, report["by_depth"] = {"cap_m", "classes":
+[{"lo_m", "hi_m", "pixels", "mae", "rmse", "max"}]}, and each entry of holes["worst"] gains "depth_m", the hole's largest
+distance to K (saturating at cap_m).  Without it the report has neither key and no further kernel runs.
+
 Two calls on the same inputs return bitwise-equal tensors and an equal report.
 
 With baseline="laplace" the same keep mask is also filled by harmonic interpolation (fill_voids; with
@@ -32,6 +38,7 @@ CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--m
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
+         [--by-depth [E ...]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -47,6 +54,7 @@ from .utils.raster_dataset import SPLITS, HoleSpec, fit_primitives, primitive_dr
 MIN_TILE, MAX_TILE = 40, 1024
 AREA_EDGES_M2 = (100.0, 1000.0, 10000.0)
 QUANTILES = (0.5, 0.9, 0.95, 0.99)
+DEPTH_EDGES_M = (2.0, 5.0, 10.0, 25.0, 50.0)      # --by-depth given bare: class bounds in metres from the known terrain
 FIX = 2.0 ** 16                       # fixed-point scale of the per-hole sums
 CLAMP = 2.0 ** 15                     # metres: larger per-pixel errors are clamped in the per-hole sums
 MAX_CLASSES = 8
@@ -136,6 +144,20 @@ def _check_edges(edges):
     edges = [float(e) for e in edges]
     if len(edges) > MAX_CLASSES - 1 or any(not math.isfinite(e) or e <= 0 for e in edges) or edges != sorted(edges):
         raise ValueError(f"terrain_errors: area_edges_m2 {edges} must be at most {MAX_CLASSES - 1} increasing finite values > 0")
+    return edges
+
+
+def _check_depth_edges(edges):
+    """None, or 1 .. MAX_CLASSES - 1 strictly increasing finite distances in metres > 0."""
+    if edges is None:
+        return None
+    try:
+        edges = [float(e) for e in edges]
+    except (TypeError, ValueError):
+        raise ValueError(f"terrain_errors: depth_edges_m {edges!r} must be a sequence of numbers") from None
+    if not 1 <= len(edges) <= MAX_CLASSES - 1 or any(not math.isfinite(e) or e <= 0 for e in edges) or \
+            any(b <= a for a, b in zip(edges, edges[1:])):
+        raise ValueError(f"terrain_errors: depth_edges_m {edges} must be 1 .. {MAX_CLASSES - 1} increasing finite values > 0")
     return edges
 
 
@@ -289,9 +311,10 @@ def _f32bits(b):
     return float(np.array([b], np.uint32).view(np.float32)[0])
 
 
-def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantiles, top):
+def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantiles, top, depth=None):
     """The report from the raw results: counts {COUNTS}, sums {SUMS + class_a / class_a2 lists}, table int64 [n][9] sorted by
-    label, qa: the height quantile values, qs: the slope error p90."""
+    label, qa: the height quantile values, qs: the slope error p90.  depth (optional): {"edges_m", "cap_d2", "counts",
+    "sum_a", "sum_a2", "max_bits": one per depth class, "hole_d2": the largest squared pixel distance per row of table}."""
     c2 = cellsize * cellsize
     n = counts
     ns, nt, nr, nrt = n["scored"], n["slope_scored"], n["ring"], n["ring_slope"]
@@ -323,14 +346,24 @@ def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantile
     rep["holes"] = {"count": int(len(table)), "worst": [
         {"label": int(table[i, 0]), "bbox": [int(v) for v in table[i, 5:9]], "area_m2": float(table[i, 1]) * c2,
          "scored": int(sc[i]), "mae": float(mae[i]), "max": _f32bits(table[i, 4])} for i in order]}
+    if depth is not None:
+        from .distance import px2_m
+        db = [0.0] + list(depth["edges_m"]) + [math.inf]
+        rep["by_depth"] = {"cap_m": px2_m(depth["cap_d2"], cellsize), "classes": [
+            {"lo_m": db[k], "hi_m": db[k + 1], "pixels": int(depth["counts"][k]),
+             "mae": _mean(depth["sum_a"][k], int(depth["counts"][k])), "rmse": _rms(depth["sum_a2"][k], int(depth["counts"][k])),
+             "max": _f32bits(depth["max_bits"][k]) if depth["counts"][k] else math.nan} for k in range(len(db) - 1)]}
+        for h, i in zip(rep["holes"]["worst"], order):
+            h["depth_m"] = px2_m(int(depth["hole_d2"][i]), cellsize)
     return rep
 
 
 @torch.no_grad()
 def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
-                   quantiles=QUANTILES, top=10):
+                   quantiles=QUANTILES, top=10, depth_edges_m=None):
     """The report (a plain dict json.dump can write) of pred against the truth dem on the holes; model-free, so any fill can be
-    scored on the same holes.  holes: nonzero = evaluation hole; keep: nonzero = known to the model."""
+    scored on the same holes.  holes: nonzero = evaluation hole; keep: nonzero = known to the model.  depth_edges_m: class
+    bounds in metres of the distance to the nearest pixel of K (valid and keep) for "by_depth"; None: no such section."""
     from tg_hip import ops as O
     c = _cellsize(cellsize, "terrain_errors")
     H, W = _inputs(dem, mask, "terrain_errors")
@@ -339,6 +372,12 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
             raise ValueError(f"terrain_errors: {nm} {_shape(t)} differs from the dem {(H, W)}")
     edges = _check_edges(area_edges_m2)
     qs = _check_quantiles(quantiles)
+    dedges = _check_depth_edges(depth_edges_m)
+    if dedges is not None:
+        from .distance import MAX_SIDE, depth_px2
+        if max(H, W) > MAX_SIDE:
+            raise ValueError(f"terrain_errors: depth_edges_m needs sides of at most {MAX_SIDE} px, got {H}x{W}")
+        dpx2 = depth_px2(dedges, c, "terrain_errors: depth_edges_m")
     if int(top) < 0:
         raise ValueError(f"terrain_errors: top {top} < 0")
     device = _device()
@@ -368,8 +407,18 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
     qa = O.select_f32(sel_a, [rank(q, ns) for q in qs]).cpu().tolist() if ns else [math.nan] * len(qs)
     q90 = O.select_f32(sel_s, [rank(0.9, nt)]).cpu().tolist()[0] if nt else math.nan
     tb = table.cpu().numpy()
-    tb = tb[np.argsort(tb[:, 0], kind="stable")]
-    return assemble_report(cn, sd, tb, qa, q90, cellsize=c, edges_m2=edges, quantiles=qs, top=top)
+    by_label = np.argsort(tb[:, 0], kind="stable")
+    tb = tb[by_label]
+    depth = None
+    if dedges is not None:
+        seeds, _ = O.objmask_known(z, k, nodata, transposed=False)          # K: valid and kept
+        d2, _ = O.edt(seeds, dpx2[-1])
+        dsums, dcounts, dmax, hole_d2 = O.depth_errors(sel_a, d2, labels, slot, nh, dpx2)
+        ds = dsums.cpu().numpy()
+        depth = {"edges_m": dedges, "cap_d2": dpx2[-1], "counts": dcounts.cpu().tolist(), "sum_a": ds[0::2].tolist(),
+                 "sum_a2": ds[1::2].tolist(), "max_bits": (dmax.cpu().numpy().view(np.uint32)).tolist(),
+                 "hole_d2": hole_d2.cpu().numpy()[by_label]}
+    return assemble_report(cn, sd, tb, qa, q90, cellsize=c, edges_m2=edges, quantiles=qs, top=top, depth=depth)
 
 
 # ---- end to end -----------------------------------------------------------------------------------------------------
@@ -385,7 +434,7 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 
 @torch.no_grad()
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10, solver="mg"):
+                    quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
     fill info under "fill"."""
     from .fill_voids import fill_voids
@@ -394,7 +443,7 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     k = _f32(keep, device, "keep", binary=True)
     bpred, finfo = fill_voids(z, k, nodata=_nodata(nodata), method=method, solver=solver)
     rep = terrain_errors(z, bpred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
-                         quantiles=quantiles, top=top)
+                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
     rep["method"] = method
     rep["fill"] = finfo
     return rep
@@ -404,22 +453,24 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
-                    solver="mg"):
+                    solver="mg", depth_edges_m=None):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
     checkpoint whose training blocks were picked on the working grid), and seam="harmonic" adds report["seam"].  solver is the
-    fill_voids solver of the baseline, the seam correction and the fallback ("mg" or "pcg"); "pcg" shows in their infos."""
+    fill_voids solver of the baseline, the seam correction and the fallback ("mg" or "pcg"); "pcg" shows in their infos.
+    depth_edges_m adds "by_depth" to the report and, on the same classes, to report["baseline"]."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
-                             seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver)
+                             seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
+                             depth_edges_m=depth_edges_m)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
-              min_coverage=0.5, solver="mg"):
+              min_coverage=0.5, solver="mg", depth_edges_m=None):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
@@ -432,6 +483,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
+    _check_depth_edges(depth_edges_m)
     device = _device()
     z = _f32(dem, device, "dem")
     m = None if mask is None else _f32(mask, device, "mask", binary=True)
@@ -442,7 +494,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
                                  min_coverage=min_coverage, solver=solver)
     sinfo = iinfo.get("seam")
     rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
-                         quantiles=quantiles, top=top)
+                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
     rep.update(params(c, split, block, tile, seed, holes, window, overlap))
     rep["cells"] = hinfo["cells"]
     rep["inpaint"] = iinfo
@@ -450,7 +502,8 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["seam"] = sinfo
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
-                                          area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver)
+                                          area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
+                                          depth_edges_m=depth_edges_m)
     return rep, pred, hm
 
 
@@ -462,10 +515,13 @@ def params(cellsize, split, block, tile, seed, holes, window=None, overlap=None)
 
 
 def summary(rep):
-    """One line: height RMSE, LE90, slope MAE, ring RMSE."""
-    return (f"height RMSE {rep['height']['rmse']:.4f} m, LE90 {rep['height']['le90']:.4f} m, slope MAE "
+    """One line: height RMSE, LE90, slope MAE, ring RMSE; with "by_depth" also the height MAE of each depth class."""
+    line = (f"height RMSE {rep['height']['rmse']:.4f} m, LE90 {rep['height']['le90']:.4f} m, slope MAE "
             f"{rep['slope_deg']['mae']:.3f} deg, ring RMSE {rep['ring']['rmse']:.4f} m over {rep['pixels']['scored']} px in "
             f"{rep['holes']['count']} holes")
+    if "by_depth" in rep:
+        line += "; MAE by depth " + ", ".join(f"{k['lo_m']:g}+ m {k['mae']:.4f}" for k in rep["by_depth"]["classes"])
+    return line
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------
@@ -506,6 +562,9 @@ def build_parser():
                          "it, the scoring stays on the native grid")
     ap.add_argument("--min-coverage", type=float, default=0.5,
                     help="with a coarser --model-cellsize: the known share of its footprint a resampled cell needs, in (0, 1]")
+    ap.add_argument("--by-depth", type=float, nargs="*", metavar="E",
+                    help="also report the height errors by distance to the known terrain: class bounds in metres (given bare: "
+                         + " ".join(f"{e:g}" for e in DEPTH_EDGES_M) + "); the baseline is scored on the same classes")
     return ap
 
 
@@ -530,12 +589,13 @@ def main(argv=None):
     c = float(asc_value(header, "cellsize"))
     objects = spec_from_args(a) if a.remove_objects else None
     split = None if a.split == "all" else a.split
+    depth_edges = None if a.by_depth is None else (tuple(a.by_depth) or DEPTH_EDGES_M)
     if a.checkpoint:
         rep, pred, hm = _evaluate(a.checkpoint, dem, mask, nodata=nodata, cellsize=c, split=split, block=a.block, tile=a.tile,
                                   holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
-                                  min_coverage=a.min_coverage, solver=a.solver)
+                                  min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -544,11 +604,11 @@ def main(argv=None):
         if pnd is not None:
             p = np.where(p == np.float32(pnd), np.float32(np.nan), p)     # unfilled cells stay unfilled
         hm, keep, _ = holes_from_map(dem, _read_mask(a.holes, dem.shape), mask, nodata=nodata, objects=objects, cellsize=c)
-        rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata)
+        rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata, depth_edges_m=depth_edges)
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
-                                              solver=a.solver)
+                                              solver=a.solver, depth_edges_m=depth_edges)
         pred = None
     if a.json:
         with open(a.json, "w") as f:

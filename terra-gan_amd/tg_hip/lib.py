@@ -47,6 +47,13 @@ class TgAreaClasses(C.Structure):
     _fields_ = [("n_edges", C.c_int32), ("_pad", C.c_int32), ("px", C.c_int64 * (TG_EVAL_MAX_CLASSES - 1))]
 
 
+TG_EDT_FAR, TG_EDT_MAX_SIDE, TG_DEPTH_MAX_CLASSES = 0x7fffffff, 32767, 8
+
+
+class TgDepthClasses(C.Structure):
+    _fields_ = [("n_edges", C.c_int32), ("_pad", C.c_int32), ("d2", C.c_int32 * (TG_DEPTH_MAX_CLASSES - 1))]
+
+
 class TgError(RuntimeError):
     pass
 
@@ -167,6 +174,11 @@ SIGNATURES = {
     "tg_seam_apply": (I, [P, P, I, F, P, P, I, I, P, P]),
     "tg_resample_area": (I, [P, P, I, F, I, I, I, I, I, I, P, P, I, F, I, I, P, P, P, P]),
     "tg_resample_interp": (I, [P, P, I, F, I, I, I, I, P, P, I, F, I, I, P, P, P, P]),
+    "tg_edt_ws_bytes": (SZ, [I, I]),
+    "tg_edt": (I, [P, I, I, C.c_int32, D, P, P, P, SZ, P]),
+    "tg_depth_errors_ws_bytes": (SZ, [I, I]),
+    "tg_depth_errors": (I, [P, P, P, P, I, I, I, C.POINTER(TgDepthClasses), P, P, P, P, SZ, P]),
+    "tg_depth_errors_finish": (I, [I, I, P, SZ, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

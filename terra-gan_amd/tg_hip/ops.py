@@ -1185,7 +1185,72 @@ def select_f32(v, ks):
     return out
 
 
-VFILL_NSTATS = 4                                  # tg_vfill_setup stats: known, unknown, min bits, max bits
+EDT_FAR, EDT_MAX_SIDE, DEPTH_MAX_CLASSES = L.TG_EDT_FAR, L.TG_EDT_MAX_SIDE, L.TG_DEPTH_MAX_CLASSES
+
+
+def _edt_hw(t, name):
+    H, W = _raster_hw(t, name)
+    if max(H, W) > EDT_MAX_SIDE:
+        raise L.TgError(f"{name}: raster {H}x{W}: both sides must be at most {EDT_MAX_SIDE} (int32 squared distances)")
+    return H, W
+
+
+def edt(seed, cap2=0, cellsize=None):
+    """-> (d2 int32 [H][W], dist_m float32 [H][W] or None): d2 = min(exact squared Euclidean distance in pixels to the nearest
+    nonzero pixel of seed uint8 [H][W], cap2), EDT_FAR without a seed and without a cap (cap2 <= 0); dist_m =
+    cellsize * sqrt(d2) with a cellsize (tg_edt)."""
+    H, W = _edt_hw(seed, "seed")
+    _hip(seed, torch.uint8, (H, W), "seed")
+    cap2 = int(cap2)
+    if not -2 ** 31 <= cap2 < 2 ** 31:
+        raise L.TgError(f"edt: cap2 {cap2} does not fit an int32")
+    c = 0.0
+    if cellsize is not None:
+        c = float(cellsize)
+        if not (c > 0 and c < float("inf")):
+            raise L.TgError(f"edt: cellsize {cellsize!r} must be finite and > 0")
+    d2 = torch.empty(H, W, dtype=torch.int32, device=seed.device)
+    dist = torch.empty(H, W, dtype=torch.float32, device=seed.device) if cellsize is not None else None
+    lib = _lib()
+    ws = workspace(lib.tg_edt_ws_bytes(H, W))
+    L.check(lib.tg_edt(_p(seed), H, W, cap2, c, _p(d2), _p(dist), _p(ws), ws.numel() * 4, _stream()), "tg_edt")
+    return d2, dist
+
+
+def depth_errors(sel_a, d2, labels, slot, nholes, class_d2):
+    """-> (sums float64 [2 * DEPTH_MAX_CLASSES]: sum a, sum a^2 per class; counts int64 [DEPTH_MAX_CLASSES]; max_bits uint32 as
+    int32 [DEPTH_MAX_CLASSES]; hole_d2 int32 [nholes]: the largest d2 of each hole) (tg_depth_errors and
+    tg_depth_errors_finish).  sel_a [H*W]: terrain_errors' |error| on the scored pixels, NaN elsewhere; class_d2: the class
+    edges as squared pixel distances, nondecreasing."""
+    H, W = _edt_hw(d2, "d2")
+    _hip(d2, torch.int32, (H, W), "d2")
+    _hip(sel_a, torch.float32, (H * W,), "sel_a")
+    _hip(labels, torch.int32, (H, W), "labels")
+    _hip(slot, torch.int32, (H * W,), "slot")
+    nholes = int(nholes)
+    if not 0 <= nholes < 2 ** 31:
+        raise L.TgError(f"depth_errors: nholes {nholes} out of range [0, 2^31)")
+    edges = [int(v) for v in class_d2]
+    if len(edges) > DEPTH_MAX_CLASSES - 1 or any(not 0 <= v < 2 ** 31 for v in edges) or edges != sorted(edges):
+        raise L.TgError(f"depth_errors: class edges {edges} must be at most {DEPTH_MAX_CLASSES - 1} nondecreasing int32 values "
+                        ">= 0")
+    cls = L.TgDepthClasses(len(edges), 0)
+    for j, v in enumerate(edges):
+        cls.d2[j] = v
+    lib = _lib()
+    dev = d2.device
+    counts = torch.empty(DEPTH_MAX_CLASSES, dtype=torch.int64, device=dev)
+    max_bits = torch.empty(DEPTH_MAX_CLASSES, dtype=torch.int32, device=dev)
+    hole_d2 = torch.empty(nholes, dtype=torch.int32, device=dev)
+    sums = torch.empty(2 * DEPTH_MAX_CLASSES, dtype=torch.float64, device=dev)
+    ws = workspace(lib.tg_depth_errors_ws_bytes(H, W))
+    L.check(lib.tg_depth_errors(_p(sel_a), _p(d2), _p(labels), _p(slot), nholes, H, W, C.byref(cls), _p(counts), _p(max_bits),
+                                _p(hole_d2) if nholes else None, _p(ws), ws.numel() * 4, _stream()), "tg_depth_errors")
+    L.check(lib.tg_depth_errors_finish(H, W, _p(ws), ws.numel() * 4, _p(sums), _stream()), "tg_depth_errors_finish")
+    return sums, counts, max_bits, hole_d2
+
+
+VFILL_NSTATS = 4                                 # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
 def vfill_ws(H, W, device):
