@@ -29,7 +29,7 @@ struct ProfRec {
     int kind;  // 0 = igemm (fwd/dgrad), 1 = wgrad
     double flops, bytes;
     int M, N, K, C, splits, cfg;
-    int route;  // SmallRoute of a small-channel launch (igemm_params.h), 0 for every other kernel
+    int route;  // SmallRoute of a small-channel launch, WinoRoute of a Winograd launch (igemm_params.h), 0 for every other kernel
     char tag[32];
 };
 static std::mutex g_prof_mu;
@@ -1120,7 +1120,7 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
     TG_REQUIRE(pl.pool || !(p.pool_code || p.pool_only), "tg_conv_fwd_pool_code: this launch cannot write the pool from its output transform");
     TG_REQUIRE(!p.pool_code || p.act == TG_ACT_RELU, "tg_conv_fwd_pool_code: needs a ReLU output");
     if (pl.gbits) p.gate_bits_done = 1;
-    WinoProf pf = {p.bf16 ? 3 : 0, p.bf16 ? 4016 : 4064, p.M, 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale, 0.0};
+    WinoProf pf = {p.bf16 ? 3 : 0, p.bf16 ? 4016 : 4064, p.M, 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale, 0.0, WR_NONE};
     pf.bytes = 4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.M + (double)p.N * p.Ktot + (double)p.M * p.N +
                       (p.amask ? (double)p.B * p.IH * p.IW : 0.0) + (pl.pool ? 0.25 * (double)p.M * p.N : 0.0)) -
                (p.pool_only ? (4.0 - 0.25) * (double)p.M * p.N : 0.0);      // pool_only: no dst, a code byte per pooled element
@@ -1131,6 +1131,7 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
                                          wino16_pipe_kernel<false, true>, wino16_pipe_kernel<true, false, true>};
         static LdsOptIn opts[8];
         const int ki = pl.kernel(false);
+        pf.route = WR_FIRST + ki;
         return wino_launch(kerns[ki], opts[ki], pl.pipe ? W16_PIPE_LDS_BYTES : W16_LDS_BYTES, "wino16_kernel", p, pl.q, pf, true, s);
     }
     typedef void (*WinoKern)(const IGemmParams, const WinoGeom, const float*);
@@ -1152,6 +1153,7 @@ static int launch_wino(IGemmParams& p, size_t ws_floats_avail, hipStream_t s) {
         q.sp_nb = sm->nb; q.sp_tiles = sm->nb * q.tiles_y * q.tiles_x;
     }
     const int ki = pl.kernel(q.qctr != nullptr);
+    pf.route = WR_FIRST + ki;
     return wino_launch(kerns[ki], opts[ki], (size_t)WINO_LDS_FLOATS * sizeof(float), "wino_kernel", p, q, pf, true, s);
 }
 

@@ -109,6 +109,27 @@ enum SmallRoute {
     SR_TO1WGRAD64 = 900,            // + k (3 | 4): to1wgrad64_kernel<k>
 };
 
+// Which instantiation a Winograd launch runs: the same column of the launch records.  The records' cfg names the family (4064 /
+// 4016 F(2x2,3x3) in fp32 / bf16, 4022 F(2x2,2x2), 4044 F(4x4,3x3), 4164 / 4116 / 4122 their weight gradients); the route is
+// WR_FIRST + the index into the launcher's kernel table, so 0 stays "not recorded".
+//   4064 (launch_wino, WinoPlan::kernel):  1 wino_kernel  2 + gate  3 fast  4 fast + gate  5 wino_pipe_kernel  6 + gate  7 + pool
+//                                          8 + bit gate;  9-16 the same eight with a work-stealing queue;  17 tile map  18 tile map
+//                                          + pool;  19-21 the list-only tile map: plain, gate, bit gate
+//   4016 (launch_wino, bf16):              1-8 as 4064's first eight (wino16_kernel / wino16_pipe_kernel)
+//   4022 (launch_wino22):                  1 + (queue ? 4 : 0) + (fast ? 2 : 0) + gate
+//   4044 (launch_wino44):                  1 plain  2 gate  3 bit gate
+//   4164 / 4116 / 4122:                    1 (one kernel each)
+enum WinoRoute {
+    WR_NONE = 0,
+    WR_FIRST = 1,                   // + kernel-table index
+    WR_PIPE = WR_FIRST + 4,         // wino_pipe_kernel / wino16_pipe_kernel: + gate; + 2 pool; + 3 bit gate
+    WR_QUEUED = WR_FIRST + 8,       // 4064: + the static walk's index
+    WR_MAP = WR_FIRST + 16,         // 4064: + pool
+    WR_MAP_LIST = WR_FIRST + 18,    // 4064: + gate; + 2 bit gate
+    WR_W22_FAST = 2, WR_W22_QUEUED = 4,         // 4022: WR_FIRST + these + gate
+    WR_WGRAD = WR_FIRST,
+};
+
 // smallconv.hip: bandwidth-bound special cases that would waste >95% of an MFMA tile.  The launchers report the route they took
 // through `route` (a SmallRoute value).
 bool smallconv_fwd_applies(const IGemmParams& p);             // C == 1 -> N%64 == 0, or N == 1 <- C%64 == 0

@@ -1097,6 +1097,7 @@ static bool wino_prep(const IGemmParams& p, const TgWprepItem& it, Transform tra
 struct WinoProf {
     int kind, cfg, M;
     double flops, bytes;
+    int route;              // WinoRoute (igemm_params.h): WR_FIRST + the index of `kern` in the launcher's table
 };
 template <class Geom, class UT>
 static int wino_launch(void (*kern)(const IGemmParams, const Geom, const UT*), LdsOptIn& opt, size_t lds, const char* name,
@@ -1104,6 +1105,7 @@ static int wino_launch(void (*kern)(const IGemmParams, const Geom, const UT*), L
     if (int rc = lds_opt_in(opt, reinterpret_cast<const void*>(kern), lds, name)) return rc;
     {
         ProfScope ps(s, pf.kind, pf.flops, pf.bytes, pf.M, p.N, p.Ktot, p.C, p.splits, pf.cfg);
+        ps.r.route = pf.route;
         const int grid = q.total_work < wino_cus() ? q.total_work : wino_cus();
         hipLaunchKernelGGL(kern, dim3(grid, 1, p.splits), dim3(WINO_THREADS), lds, s, p, q, reinterpret_cast<const UT*>(p.wino_u));
     }
@@ -1404,6 +1406,7 @@ static int launch_wino_wgrad(const TgConv* g, const WgradParams& p, float* dw, f
     {
         const double by = 4.0 * ((double)p.B * p.H * p.W * p.C + (double)p.Mpix * p.Cout + (double)p.Cout * p.Ktot);
         ProfScope ps(s, 1, 2.0 * p.Mpix * (double)p.Cout * p.Ktot * g_alg_scale, by, p.Cout, p.Ktot, p.Mpix, p.C, q.splits, 4164);
+        ps.r.route = WR_WGRAD;
         hipLaunchKernelGGL(wino_wgrad_kernel, dim3(q.ntco * q.ntci * q.splits), dim3(WINO_THREADS), lds, s, p, q, ws);
     }
     TG_CHECK_LAUNCH("wino_wgrad_kernel");

@@ -851,6 +851,7 @@ static int launch_wino16_wgrad(const TgConv* g, const WgradParams& p, float* dw,
     {
         const double by = 4.0 * ((double)p.B * p.H * p.W * p.C + (double)p.Mpix * p.Cout + (double)p.Cout * p.Ktot);
         ProfScope ps(s, 3, 2.0 * p.Mpix * (double)p.Cout * p.Ktot * g_alg_scale, by, p.Cout, p.Ktot, p.Mpix, p.C, q.splits, 4116);
+        ps.r.route = WR_WGRAD;
         hipLaunchKernelGGL(wino16_wgrad_kernel, dim3(q.ntco * q.ntci * q.splits), dim3(WINO_THREADS), W16G_LDS_BYTES, s, p, q, ws);
     }
     TG_CHECK_LAUNCH("wino16_wgrad_kernel");

@@ -462,7 +462,7 @@ static int launch_wino22(const TgConv* g, IGemmParams& p, int dgrad, size_t ws_f
     const double mtot = (double)p.M * q.ncls;
     const WinoProf pf = {0, 4022, (int)mtot, 2.0 * mtot * (double)p.N * p.Ktot,              // (direct form: 16 taps)
                          4.0 * ((double)g->B * (dgrad ? g->Ho * g->Wo * g->Cout : g->H * g->W * g->Cin) + 16.0 * g->Cin * g->Cout +
-                                mtot * p.N + (p.rowscale ? mtot : 0.0))};
+                                mtot * p.N + (p.rowscale ? mtot : 0.0)), WR_FIRST + ki};
     // the split-K slabs of the ncls classes are reduced by one launch of the multi-class epilogue
     if ((rc = wino_launch(kerns[ki], opts[ki], (size_t)W22_LDS_FLOATS * sizeof(float), "wino22_kernel", p, q, pf, false, s))) return rc;
     if (p.splits > 1) {
@@ -776,6 +776,7 @@ static int launch_wino22_wgrad(const TgConv* g, const WgradParams& p, float* dw,
     {
         const double by = 4.0 * ((double)p.B * p.H * p.W * p.C + (double)p.Mpix * p.Cout + (double)p.Cout * p.Ktot);
         ProfScope ps(s, 1, 2.0 * p.Mpix * (double)p.Cout * p.Ktot, by, p.Cout, p.Ktot, p.Mpix, p.C, q.splits, 4122);
+        ps.r.route = WR_WGRAD;
         hipLaunchKernelGGL(wino22_wgrad_kernel, dim3(q.ntco * q.ntci * q.splits), dim3(WINO_THREADS), lds, s, p, q, ws);
     }
     TG_CHECK_LAUNCH("wino22_wgrad_kernel");

@@ -446,6 +446,6 @@ static int launch_wino44(IGemmParams& p, hipStream_t s) {
     static const Kern kerns[3] = {wino44_kernel<false>, wino44_kernel<true>, wino44_kernel<true, true>};
     static LdsOptIn opts[3];
     const WinoProf pf = {0, 4044, p.M, 2.0 * p.M * (double)p.N * p.Ktot * g_alg_scale,
-                         4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.N * p.Ktot + (double)p.M * p.N)};
+                         4.0 * ((double)p.B * p.IH * p.IW * p.C + (double)p.N * p.Ktot + (double)p.M * p.N), WR_FIRST + ki};
     return wino_launch(kerns[ki], opts[ki], (size_t)W4_LDS_FLOATS * sizeof(float), "wino44_kernel", p, q, pf, false, s);
 }

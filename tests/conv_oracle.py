@@ -172,7 +172,10 @@ def bound(r, slabs):
 
 
 def exact_ok(r):
-    """Every partial sum of every element is an integer below 2^24 (given integer data): any fp32 order is exact."""
+    """Every partial sum of every element is an integer below 2^24 (given integer data): any fp32 order is exact.  (A result of
+    a Winograd route, WRes: the condition of its algorithm, wino_exact_ok.)"""
+    if hasattr(r, "alg"):
+        return wino_exact_ok(r)
     return float((r.S * np.maximum(r.scale, 1.0) + r.base).max()) < EXACT_LIMIT
 
 
@@ -186,3 +189,216 @@ def worst(x, r, slabs):
     q = np.where(e == 0, 0.0, e / np.where(b > 0, b, 1.0) + np.where(b > 0, 0.0, np.inf))
     i = int(q.argmax())
     return float(q.reshape(-1)[i]), i
+
+
+# ---- the Winograd routes (csrc/wino.inc, wino16.inc, wino22.inc, wino44.inc) ---------------------------------------------------------
+# A Winograd kernel does not add the products x w of the direct form: it adds, per transform point, products of TRANSFORMED operands,
+# Y = At [ sum_k (G g_k Gt) (.) (Bt d_k B) ] A.  Its rounding errors are therefore bounded by the sum of absolute values of THAT
+# expression,
+#     S_w = |At| [ sum_k (|G| |g_k| |Gt|) (.) (|Bt| |d_k| |B|) ] |A|
+# (every partial result of every transform pass and of the contraction is bounded in magnitude by the corresponding partial result
+# of S_w, so the argument of the module docstring goes through term by term), over a chain of n = K + slabs + T + 4 roundings:
+# K = the contraction length of one transform point, T = the sum over the six 1-D transform passes of 2 r - 1, r = the most
+# non-zeros in a row of that pass's matrix (r multiplies and r - 1 adds can each round once).  The VALUE stays the direct oracle's.
+# For a weight gradient the roles turn: dW = Gt [ sum_tiles (A dY At) (.) (Bt X B) ] G, contracted over the tiles.
+_h = 0.5
+WINO = {            # name -> (Bt, G, At)
+    "F23": (np.array([[1, 0, -1, 0], [0, 1, 1, 0], [0, -1, 1, 0], [0, 1, 0, -1]], np.float64),
+            np.array([[1, 0, 0], [_h, _h, _h], [_h, -_h, _h], [0, 0, 1]], np.float64),
+            np.array([[1, 1, 1, 0], [0, 1, -1, -1]], np.float64)),
+    "F22": (np.array([[1, -1, 0], [0, 1, 0], [0, -1, 1]], np.float64),
+            np.array([[1, 0], [1, 1], [0, 1]], np.float64),
+            np.array([[1, 1, 0], [0, 1, 1]], np.float64)),
+    "F43": (np.array([[4, 0, -5, 0, 1, 0], [0, -4, -4, 1, 1, 0], [0, 4, -4, -1, 1, 0], [0, -2, -1, 2, 1, 0], [0, 2, -1, -2, 1, 0],
+                      [0, 4, 0, -5, 0, 1]], np.float64),
+            np.array([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6],
+                      [0, 0, 1]], np.float64),
+            np.array([[1, 1, 1, 1, 1, 0], [0, 1, -1, 2, -2, 0], [0, 1, 1, 4, 4, 0], [0, 1, -1, 8, -8, 1]], np.float64)),
+}
+WINO_SLABS_CONV, WINO_SLABS_WGRAD = 16, 512        # wino_plan / launch_wino22: at most 16 splits; the wgrad plans: at most 512
+# the quantum of every intermediate on integer data: G of F(2x2,3x3) halves twice; F(2x2,2x2) stays in the integers
+WINO_QUANTUM = {"F23": 0.25, "F22": 1.0}
+
+WRes = namedtuple("WRes", Res._fields + ("alg", "vmax", "umax"))
+
+
+def wino_T(alg, wgrad=False):
+    """Roundings of the six 1-D transform passes (two per operand, two on the way out)."""
+    Bt, G, At = WINO[alg]
+    mats = (At.T, Bt, G.T) if wgrad else (Bt, G, At)
+    return int(sum(2 * (2 * int((M != 0).sum(axis=1).max()) - 1) for M in mats))
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _tiles(xp, step, size, ty, tx):
+    """[B][Hp][Wp][C] -> [B][ty][tx][C][size][size]: tile (i, j) starts at (i step, j step); zeros beyond the array."""
+    B, Hp, Wp, C = xp.shape
+    nh, nw = (ty - 1) * step + size, (tx - 1) * step + size
+    xp = np.pad(xp, ((0, 0), (0, max(0, nh - Hp)), (0, max(0, nw - Wp)), (0, 0)))[:, :nh, :nw]
+    v = np.lib.stride_tricks.sliding_window_view(xp, (size, size), axis=(1, 2))
+    return v[:, ::step, ::step][:, :ty, :tx]
+
+
+def wino_corr(xp, w, alg, OH, OW, absolute=False):
+    """y[b][i][j][n] = sum_{u,v,c} xp[b][i + u][j + v][c] w[n][u][v][c] for i < OH, j < OW, evaluated in the Winograd domain of
+    `alg` with tiles that start at (0, 0) -- or, `absolute`, S_w of that evaluation (the arguments are then magnitudes).
+    Returns (y, max |Bt d B|, max |G g Gt|)."""
+    Bt, G, At = (np.abs(M) for M in WINO[alg]) if absolute else WINO[alg]
+    m, a = At.shape[0], Bt.shape[0]
+    assert w.shape[1] == w.shape[2] == G.shape[1] and w.shape[3] == xp.shape[3], (w.shape, xp.shape, alg)
+    ty, tx = _cdiv(OH, m), _cdiv(OW, m)
+    V = Bt @ _tiles(f64(xp), m, a, ty, tx) @ Bt.T                           # [B][ty][tx][C][a][a]
+    Uw = np.einsum("au,nuvc,bv->abnc", G, f64(w), G)                         # [a][a][N][C]
+    B, N = xp.shape[0], w.shape[0]
+    M = np.empty((B, ty, tx, N, a, a))
+    for i in range(a):
+        for j in range(a):
+            M[..., i, j] = V[..., i, j] @ Uw[i, j].T
+    Y = At @ M @ At.T                                                       # [B][ty][tx][N][m][m]
+    y = Y.transpose(0, 1, 4, 2, 5, 3).reshape(B, ty * m, tx * m, N)[:, :OH, :OW]
+    return y, float(np.abs(V).max()), float(np.abs(Uw).max())
+
+
+def wino_wcorr(xp, dy, alg, absolute=False):
+    """dw[n][u][v][c] = sum_{b,i,j} dy[b][i][j][n] xp[b][i + u][j + v][c] in the Winograd domain of `alg` contracted over the tiles
+    of dy (they start at (0, 0)) -- or S_w of it.  Returns (dw, max |Bt X B|, max |A dY At|, number of tiles)."""
+    Bt, G, At = (np.abs(M) for M in WINO[alg]) if absolute else WINO[alg]
+    m, a = At.shape[0], Bt.shape[0]
+    B, OH, OW, N = dy.shape
+    ty, tx = _cdiv(OH, m), _cdiv(OW, m)
+    V = Bt @ _tiles(f64(xp), m, a, ty, tx) @ Bt.T                           # [B][ty][tx][C][a][a]
+    Yt = At.T @ _tiles(f64(dy), m, m, ty, tx) @ At                          # [B][ty][tx][N][a][a]
+    C = xp.shape[3]
+    M = np.empty((a, a, N, C))
+    for i in range(a):
+        for j in range(a):
+            M[i, j] = Yt[..., i, j].reshape(-1, N).T @ V[..., i, j].reshape(-1, C)
+    dw = np.einsum("ua,abnc,bv->nuvc", G.T, M, G)
+    return dw, float(np.abs(V).max()), float(np.abs(Yt).max()), B * ty * tx
+
+
+# the two regroupings that put the stride-2 layers on stride-1 Winograd kernels
+def s2d(x):
+    """x2[b][yy][xx][(dy, dx, c)] = x[b][2 yy + dy][2 xx + dx][c]  (5x5 / stride 2 / pad 2 as 3x3 / stride 1 / pad 1 over 4 C)."""
+    B, H, W, C = x.shape
+    return x.reshape(B, H // 2, 2, W // 2, 2, C).transpose(0, 1, 3, 2, 4, 5).reshape(B, H // 2, W // 2, 4 * C)
+
+
+def d2s(x2):
+    B, H2, W2, C4 = x2.shape
+    C = C4 // 4
+    return x2.reshape(B, H2, W2, 2, 2, C).transpose(0, 1, 3, 2, 4, 5).reshape(B, 2 * H2, 2 * W2, C)
+
+
+def w_regroup(w, t):
+    """w2[co][ty][tx][(dy, dx, c)] = w[co][2 ty + dy][2 tx + dx][c] with t x t taps (0 where the tap does not exist)."""
+    Cout, k, _, C = w.shape
+    wp = np.zeros((Cout, 2 * t, 2 * t, C), w.dtype)
+    wp[:, :k, :k] = w
+    return wp.reshape(Cout, t, 2, t, 2, C).transpose(0, 1, 3, 2, 4, 5).reshape(Cout, t, t, 4 * C)
+
+
+def w_ungroup(w2, k):
+    Cout, t, _, C4 = w2.shape
+    C = C4 // 4
+    return w2.reshape(Cout, t, t, 2, 2, C).transpose(0, 1, 3, 2, 4, 5).reshape(Cout, 2 * t, 2 * t, C)[:, :k, :k]
+
+
+def s2d_shifted(x):
+    """x2[b][yy][xx][(dy, dx, c)] = x[b][2 yy + dy - 1][2 xx + dx - 1][c], yy <= H / 2 (4x4 / stride 2 / pad 1 as 2x2 valid)."""
+    return s2d(_pad(x, 1))
+
+
+def _flip(w):
+    """The correlation weights of a stride-1 dgrad: w'[ci][u][v][co] = w[co][k - 1 - u][k - 1 - v][ci]."""
+    return w[:, ::-1, ::-1, :].transpose(3, 1, 2, 0)
+
+
+def wino_kind(k, s, p):
+    return {(3, 1): "s1", (5, 2): "s2d", (4, 2): "w22"}[(k, s)]
+
+
+# The three functions below reduce every Winograd route to stride-1 problems of wino_corr / wino_wcorr.  `corr` / `wcorr`: another
+# evaluation of those problems with the same signature (tests/test_wino_oracle_cpu.py: an fp32 emulation) in place of the oracle's.
+def _wino_fwd_corr(xin, w, k, s, p, alg, absolute, corr=None):
+    corr = corr or (lambda *a: wino_corr(*a, absolute))
+    B, H, W, Cin = xin.shape
+    Ho, Wo = out_size(H, k, s, p), out_size(W, k, s, p)
+    kind = wino_kind(k, s, p)
+    if kind == "s1":
+        return corr(_pad(xin, p), w, alg, Ho, Wo), Cin
+    if kind == "s2d":
+        assert p == 2 and alg == "F23"
+        return corr(_pad(s2d(xin), 1), w_regroup(w, 3), alg, Ho, Wo), 4 * Cin
+    assert p == 1 and alg == "F22"
+    return corr(s2d_shifted(xin), w_regroup(w, 2), alg, Ho, Wo), 4 * Cin
+
+
+def _wino_dgrad_corr(dy, w, x_shape, k, s, p, alg, absolute, corr=None):
+    corr = corr or (lambda *a: wino_corr(*a, absolute))
+    B, H, W, Cin = x_shape
+    Cout = w.shape[0]
+    kind = wino_kind(k, s, p)
+    if kind == "s1":
+        return corr(_pad(dy, k - 1 - p), _flip(w), alg, H, W)
+    if kind == "s2d":
+        y2, vm, um = corr(_pad(dy, 1), _flip(w_regroup(w, 3)), alg, H // 2, W // 2)
+        return d2s(y2), vm, um
+    # four parity classes: dx[2 y' + 1 - dy][2 x' + 1 - dx][c] = sum w[co][2 ty + dy][2 tx + dx][c] g[y' + 1 - dy - ty][x' + 1 - dx - tx][co]
+    gp = _pad(dy, 1)
+    Ho, Wo = dy.shape[1], dy.shape[2]
+    out, vm, um = np.zeros((B, H, W, Cin), dy.dtype), 0.0, 0.0
+    for cy in range(2):
+        for cx in range(2):
+            wc = w[:, cy::2, cx::2, :][:, ::-1, ::-1, :].transpose(3, 1, 2, 0)          # [c][u = 1 - ty][v = 1 - tx][co]
+            yc, v1, u1 = corr(gp[:, 1 - cy:, 1 - cx:], wc, alg, Ho, Wo)
+            out[:, 1 - cy::2, 1 - cx::2] = yc
+            vm, um = max(vm, v1), max(um, u1)
+    return out, vm, um
+
+
+def wino_fwd(x, w, k, s, p, alg, mask=None, bias=None, ratio=None, act_kind=ACT_NONE, slope=0.0):
+    d = conv_fwd(x, w, k, s, p, mask, bias, ratio, act_kind, slope)
+    xabs = _source(x, mask, None)[1]
+    (S, vm, um), K = _wino_fwd_corr(xabs, np.abs(f64(w)), k, s, p, alg, True)
+    if bias is not None:
+        S = S + np.abs(f64(bias))
+    return WRes(d.val, S, np.full(S.shape, float(K + wino_T(alg))), d.scale, d.base, False, alg, vm, um)
+
+
+def wino_dgrad(dy, w, x_shape, k, s, p, alg, mask=None, gate=None, gate_act=ACT_RELU, gate_slope=0.0, base=None):
+    d = conv_dgrad(dy, w, x_shape, k, s, p, mask, gate, gate_act, gate_slope, base)
+    S, vm, um = _wino_dgrad_corr(np.abs(f64(dy)), np.abs(f64(w)), x_shape, k, s, p, alg, True)
+    return WRes(d.val, S, np.full(S.shape, float(np.shape(w)[0] + wino_T(alg))), d.scale, d.base, False, alg, vm, um)
+
+
+def _wino_wgrad_corr(xin, dy, k, s, p, alg, absolute, wcorr=None):
+    wcorr = wcorr or (lambda *a: wino_wcorr(*a, absolute))
+    kind = wino_kind(k, s, p)
+    if kind == "s1":
+        return wcorr(_pad(xin, p), dy, alg)
+    if kind == "s2d":
+        dw2, vm, ym, nt = wcorr(_pad(s2d(xin), 1), dy, alg)
+        return w_ungroup(dw2, 5), vm, ym, nt
+    dw2, vm, ym, nt = wcorr(s2d_shifted(xin), dy, alg)
+    return w_ungroup(dw2, 4), vm, ym, nt
+
+
+def wino_wgrad(x, dy, k, s, p, alg):
+    """(dW, db): dW through the Winograd weight gradient of `alg` (F23: F(3x3,2x2); F22: F(2x2,2x2)), db the direct column sum."""
+    rw, rb = conv_wgrad(x, dy, k, s, p)
+    S, vm, ym, ntiles = _wino_wgrad_corr(np.abs(f64(x)), np.abs(f64(dy)), k, s, p, alg, True)
+    K = np.full(S.shape, float(ntiles + wino_T(alg, wgrad=True)))
+    return WRes(rw.val, S, K, rw.scale, rw.base, False, alg, vm, ym), rb
+
+
+def wino_exact_ok(r, bf16=False):
+    """Integer data: every intermediate is a multiple of the algorithm's quantum q and bounded by S_w, so with max S_w / q < 2^24
+    every partial sum of every order is an fp32 number.  bf16 operands: the transformed operands (bounded here by their
+    absolute-value twins, which is the stronger demand) must also be bf16 numbers: |V| <= 256 and |U| / q <= 256."""
+    q = WINO_QUANTUM[r.alg]
+    ok = float((r.S * np.maximum(r.scale, 1.0) + r.base).max()) / q < EXACT_LIMIT
+    return ok and (not bf16 or (r.vmax <= 256.0 and r.umax / q <= 256.0))

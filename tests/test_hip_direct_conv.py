@@ -109,22 +109,25 @@ def launch(case, d, mode, dev):
     return out
 
 
-def run_case(case, dev, csv_path):
-    """Both runs of a case; returns [(output name, err / bound of the real run)].  Raises AssertionError on any miss."""
+def run_case(case, dev, csv_path, table=CC, launch_fn=None):
+    """The runs of a case (both, unless the case names its own); returns [(output name, err / bound of the real run)].  Raises
+    AssertionError on any miss.  `table`: the case module (conv_cases, or wino_cases with `launch_fn` its launcher, which sets
+    and restores whatever process-wide state the case asks for around the launch)."""
     from tg_hip import ops as O
-    assert O.get_precision() == "f32", "fp32 only: the bf16 twins have tests/test_hip_bf16.py"
+    assert O.get_precision() == "f32", "fp32 outside the launch: the bf16 twins of the direct kernels have tests/test_hip_bf16.py"
+    launch_fn = launch_fn or launch
     figures = []
-    for mode in ("exact", "real"):
-        d = CC.make_inputs(case, mode)
-        if CC.needs_forward(case, mode):
+    for mode in getattr(case, "runs", ("exact", "real")):
+        d = table.make_inputs(case, mode)
+        if table.needs_forward(case, mode):
             y = _forward(case, d, mode, dev, None)
-            d["dy"] = CC.backward_dy(case, d, mode, y.cpu().numpy())
-        ref = CC.reference(case, d, mode)
+            d["dy"] = table.backward_dy(case, d, mode, y.cpu().numpy())
+        ref = table.reference(case, d, mode)
         with Routes(csv_path) as rt:
-            out = launch(case, d, mode, dev)
+            out = launch_fn(case, d, mode, dev)
         assert rt.rows == case.expect, f"{case.id} ({mode}): launches {rt.rows}, expected {case.expect}"
-        assert CC.splits_ok(case.splits, rt.splits), f"{case.id} ({mode}): splits {rt.splits}, expected {case.splits}"
-        slabs = CC.slab_cap(case, case.expect)
+        assert table.splits_ok(case.splits, rt.splits), f"{case.id} ({mode}): splits {rt.splits}, expected {case.splits}"
+        slabs = table.slab_cap(case, case.expect)
         for name, r in ref.items():
             got = out[name].detach().cpu()
             assert tuple(got.shape) == r.val.shape, (name, tuple(got.shape), r.val.shape)
@@ -151,27 +154,36 @@ def test_direct_conv(dev, case, tmp_path):
     print(f"CASE_SECONDS {case.id} {time.perf_counter() - t0:.2f}")
 
 
-def child_main(env):
-    """Body of the child process of one switch: its cases, a verdict line each, and the closing line the parent looks for."""
+def child_main(env, table=CC, launch_fn=None, marker="DIRECT_CONV_CHILD_OK"):
+    """Body of the child process of one switch (`env`: NAME or NAME=value): its cases, a verdict line each, and the closing line
+    the parent looks for."""
     import tempfile
-    assert os.environ.get(env), env
+    assert os.environ.get(env.split("=")[0]), env
     from tg_hip import lib
     lib.load()
     dev = torch.device("cuda:0")
     with tempfile.TemporaryDirectory() as tmp:
-        for case in (c for c in CC.CASES if c.env == env):
-            run_case(case, dev, os.path.join(tmp, "launches.csv"))
+        for case in (c for c in table.CASES if c.env == env):
+            t0 = time.perf_counter()
+            run_case(case, dev, os.path.join(tmp, "launches.csv"), table, launch_fn)
             print(f"CASE_OK {case.id}")
-    print(f"DIRECT_CONV_CHILD_OK {env}")
+            print(f"CASE_SECONDS {case.id} {time.perf_counter() - t0:.2f}")
+    print(f"{marker} {env}")
+
+
+def run_child(env, module, table, marker):
+    """One fresh child process for the switch `env` (NAME, set to 1, or NAME=value): `module`.child_main(env) runs its cases."""
+    name, _, value = env.partition("=")
+    code = f"import sys; sys.path[:0] = [{ROOT!r}, {os.path.join(ROOT, 'terra-gan_amd')!r}]\n" \
+           f"from tests.{module} import child_main\nchild_main({env!r})\n"
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{name: value or "1"}), cwd=ROOT, capture_output=True,
+                       text=True, timeout=600)
+    print(r.stdout[-6000:])
+    assert r.returncode == 0 and f"{marker} {env}" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert r.stdout.count("CASE_OK ") == sum(1 for c in table.CASES if c.env == env)
 
 
 @pytest.mark.parametrize("env", CC.ENVS)
 def test_direct_conv_behind_switch(dev, env):
     """TG_NO_C1MFMA / TG_C1WGRAD / TG_NO_TO1LDS are read once per process: the plain kernels they select run in a child."""
-    code = f"import sys; sys.path[:0] = [{ROOT!r}, {os.path.join(ROOT, 'terra-gan_amd')!r}]\n" \
-           f"from tests.test_hip_direct_conv import child_main\nchild_main({env!r})\n"
-    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **{env: "1"}), cwd=ROOT, capture_output=True, text=True,
-                       timeout=600)
-    print(r.stdout[-4000:])
-    assert r.returncode == 0 and f"DIRECT_CONV_CHILD_OK {env}" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert r.stdout.count("CASE_OK ") == sum(1 for c in CC.CASES if c.env == env)
+    run_child(env, "test_hip_direct_conv", CC, "DIRECT_CONV_CHILD_OK")

@@ -112,8 +112,11 @@ def _weights(Cout, Cin, seed, dev):
 @pytest.mark.parametrize("kind", ["blobs", "corners", "signed_zero", "empty", "full"])
 @pytest.mark.parametrize("mode", ["plain", "pool", "code"])
 @pytest.mark.parametrize("nb,H,W,Cin,Cout", [(2, 64, 64, 64, 64), (1, 48, 80, 64, 128), (2, 32, 32, 256, 256)])
-def test_sparse_launch_equals_dense(dev, kind, mode, nb, H, W, Cin, Cout):
+def test_sparse_launch_equals_dense(dev, kind, mode, nb, H, W, Cin, Cout, tmp_path):
+    from tests import wino_cases as WC
+    from tests.test_hip_direct_conv import Routes
     from tg_hip import ops as O
+    rt = Routes(tmp_path / "launches.csv")
     a, x1 = _act_pair(nb, H, W, Cin, 100 + H + Cin, kind)
     a, x1 = a.to(dev).contiguous(), x1.to(dev).contiguous()
     w, b = _weights(Cout, Cin, 7 + Cout, dev)
@@ -122,20 +125,30 @@ def test_sparse_launch_equals_dense(dev, kind, mode, nb, H, W, Cin, Cout):
     if mode == "code" and O.conv_pool_code_supported(tuple(a.shape), Cout):
         yp0, c0 = O.conv_fwd_pool_code(a, w, b)
         yp0, c0 = yp0.clone(), c0.clone()
-        yp1, c1 = O.conv_fwd_pool_code(a, w, b, sparse=sp)
+        with rt:
+            yp1, c1 = O.conv_fwd_pool_code(a, w, b, sparse=sp)
         torch.cuda.synchronize()
         assert torch.equal(yp0, yp1) and torch.equal(c0, c1)
     elif mode != "plain":           # (also "code" where the geometry has no pool-code path)
         y0, yp0 = O.conv_fwd(a, w, b, 3, 1, 1, act=O.ACT_RELU, pool=True)
         y0, yp0 = y0.clone(), yp0.clone()
-        y1, yp1 = O.conv_fwd(a, w, b, 3, 1, 1, act=O.ACT_RELU, pool=True, sparse=sp)
+        with rt:
+            y1, yp1 = O.conv_fwd(a, w, b, 3, 1, 1, act=O.ACT_RELU, pool=True, sparse=sp)
         torch.cuda.synchronize()
         assert torch.equal(y0, y1) and torch.equal(yp0, yp1)
     else:
         y0 = O.conv_fwd(a, w, b, 3, 1, 1, act=O.ACT_RELU).clone()
-        y1 = O.conv_fwd(a, w, b, 3, 1, 1, act=O.ACT_RELU, sparse=sp)
+        with rt:
+            y1 = O.conv_fwd(a, w, b, 3, 1, 1, act=O.ACT_RELU, sparse=sp)
         torch.cuda.synchronize()
         assert torch.equal(y0, y1)
+    # ... and where wino_plan's conditions say the map is honoured (the pipelined kernel in one split, with the pool fused where
+    # one is asked for), the launch record must name a tile-map instantiation: equal bits alone would also pass a dense launch
+    pl = WC.wino_plan(2 * nb, H, W, Cin, Cout, pool=mode != "plain")
+    if pl["pipe"] and pl["splits"] == 1 and (mode == "plain" or pl["pool"]):
+        assert rt.rows == [(0, 4064, WC.R_MAP if mode == "plain" else WC.R_MAP_POOL)], rt.rows
+    else:
+        assert len(rt.rows) == 1 and rt.rows[0][:2] == (0, 4064) and rt.rows[0][2] not in WC.MAP_ROUTES, rt.rows
 
 
 @pytest.mark.parametrize("H,W", [(33, 47), (18, 34)])
