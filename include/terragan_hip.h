@@ -721,6 +721,37 @@ int tg_depth_errors(const float* a, const int32_t* d2, const int32_t* labels, co
 int tg_depth_errors_finish(int H, int W, const void* ws, size_t ws_bytes, double* sums /* [2*TG_DEPTH_MAX_CLASSES] */,
                            tg_stream_t stream);
 
+/* ---- Feature transform; directional IDW and nearest-neighbour void fills (csrc/edt.hip, csrc/idw.hip) ------ */
+size_t tg_edt_nearest_ws_bytes(int H, int W);
+/* The feature transform of tg_edt: d2 [H][W] int32 is bit for bit what tg_edt writes for the same seed and cap2; idx [H][W]
+ * int32 = y * W + x of the nearest seed, -1 where d2 is TG_EDT_FAR or, with a cap, d2 >= cap2.  Tie rule (part of the
+ * interface): among the seeds at the smallest squared distance the smallest row, among those the smallest column.  Integer
+ * arithmetic only, no data-dependent order.  Sides, rejections and workspace (>= tg_edt_nearest_ws_bytes) as tg_edt. */
+int tg_edt_nearest(const uint8_t* seed, int H, int W, int32_t cap2, int32_t* d2, int32_t* idx, void* ws, size_t ws_bytes,
+                   tg_stream_t stream);
+size_t tg_rayfill_ws_bytes(int H, int W);
+/* Eight-direction inverse-distance fill.  Directions in this order: N, NE, E, SE, S, SW, W, NW, (dy, dx) = (-1,0), (-1,1),
+ * (0,1), (1,1), (1,0), (1,-1), (0,-1), (-1,-1); s_j = 1 on the axes, 2 on the diagonals.  For an unknown pixel p (known[p] == 0)
+ * k_j is the smallest k >= 1 with p + k d_j inside the raster and known; no hit when the ray leaves the raster first or
+ * k_j^2 s_j > lim2 (lim2 <= 0: no limit).  out[p] = (float)((sum_j w_j z[p + k_j d_j]) / (sum_j w_j)) over the hits in that
+ * order, both sums in fp64 from 0.0 without multiply-add contraction, one fp64 division, one rounding to fp32;
+ * w_j = 1.0 / (double)(k_j^2 s_j) for power == 2, 1.0 / sqrt((double)(k_j^2 s_j)) for power == 1 (every operation correctly
+ * rounded), pow((double)(k_j^2 s_j), -power / 2) for any other power in (0, 8].  Known pixels are copied bit for bit.  An
+ * unknown pixel without a hit takes z[idx[p]] when d2 and idx (tg_edt_nearest's; both or neither) are given, idx[p] >= 0 and
+ * 0 <= d2[p] <= lim2 (no distance condition without a limit); else NaN.  hits (may be NULL) [8][H][W] uint16: k_j, 0 = no
+ * hit, 0 on known pixels.  counts [3] int64 (zeroed here): unknown pixels filled by rays, by the nearest pixel, left NaN.
+ * ws >= tg_rayfill_ws_bytes: per family of lines (columns, rows, both diagonals) a 64-bit word and two int32 carried
+ * positions per 64 pixels of a line.  out must not alias z.  Sides in [1, TG_EDT_MAX_SIDE]. */
+int tg_rayfill(const float* z, const uint8_t* known, int H, int W, int32_t lim2, double power, const int32_t* d2,
+               const int32_t* idx, float* out, uint16_t* hits, int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* out[p] = known[p] ? z[p] : (idx[p] >= 0 ? z[idx[p]] : NaN); counts [2] int64 (zeroed here): filled, left NaN. */
+int tg_gather_fill(const float* z, const uint8_t* known, const int32_t* idx, int H, int W, float* out, int64_t* counts,
+                   tg_stream_t stream);
+/* One Jacobi step of a 3x3 mean on the filled pixels: an unknown, non-NaN pixel becomes the fp64 sum, in row-major order, of
+ * the non-NaN pixels of its 3x3 neighbourhood (itself included, clipped at the raster edge) divided by their count and
+ * rounded to fp32 once; known and NaN pixels are copied.  in and out are distinct. */
+int tg_void_smooth(const float* in, const uint8_t* known, int H, int W, float* out, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

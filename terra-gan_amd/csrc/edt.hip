@@ -7,6 +7,10 @@
 //                        cap), from the band's word by count-leading / count-trailing zeros and the two carried rows
 //   edt_row_kernel       one workgroup per row: the row of g staged in LDS, every lane searches outward from its own x,
 //                        d2 = min over x' of (x - x')^2 + g[x']^2, while k^2 < the best so far (and < cap2)
+//   edt_gs_kernel        (feature transform) the same column distance with the side in bit 15: set when the nearest seed of the
+//                        column lies below (a tie goes to the one above), so its row is y - g or y + g
+//   edt_row_idx_kernel   (feature transform) the row search over (d2, seed row, seed column), lexicographically: d2 as
+//                        edt_row_kernel's, idx = row * W + column of the winner, -1 where nothing is nearer than the cap
 //   depth_errors_kernel  |error| by depth class: per-workgroup fp64 partials, integer counters and maxima, per-hole max d2
 //   depth_errors_finish_kernel   one workgroup reduces the partials in a fixed order
 //
@@ -122,6 +126,80 @@ __global__ __launch_bounds__(256) void edt_row_kernel(const uint16_t* __restrict
         if (dist_m) dist_m[base + x] = best == TG_EDT_FAR ? INFINITY : (float)(cellsize * sqrt((double)best));
     }
 }
+
+// ---- feature transform: which seed is the nearest ---------------------------------------------------
+// Tie rule: among the seeds at the smallest squared distance the smallest row, then the smallest column.  Within a column the
+// seed above wins a tie (its row is smaller); across columns the candidates are compared as (d2, row, column).  A column
+// distance is at most 32766, so bit 15 of g is free for the side and the plane stays 2 B per pixel.
+constexpr uint32_t EDT_BELOW = 0x8000u;
+
+__global__ __launch_bounds__(256) void edt_gs_kernel(const uint64_t* __restrict__ mask, const int32_t* __restrict__ up,
+                                                     const int32_t* __restrict__ down, int H, int W, int glimit,
+                                                     uint16_t* __restrict__ g) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int b = blockIdx.y, y0 = b * EDT_BAND;
+    const int rows = H - y0 < EDT_BAND ? H - y0 : EDT_BAND;
+    const int64_t i = (int64_t)b * W + x;
+    const uint64_t m = mask[i];
+    const int u = up[i], d = down[i];
+    uint16_t* out = g + (int64_t)y0 * W + x;
+#pragma unroll 8
+    for (int r = 0; r < rows; ++r) {
+        const int y = y0 + r;
+        const uint64_t lo = m & (~0ull >> (63 - r));
+        const uint64_t hi = m >> r;
+        const int du = lo ? r - (63 - __clzll((long long)lo)) : (u >= 0 ? y - u : EDT_INF);
+        const int dd = hi ? __ffsll((long long)hi) - 1 : (d >= 0 ? d - y : EDT_INF);
+        const bool below = dd < du;
+        const int v = below ? dd : du;
+        out[(int64_t)r * W] = (uint16_t)(v >= glimit ? EDT_NONE : (uint32_t)v | (below ? EDT_BELOW : 0u));
+    }
+}
+
+// (d2, row, col) < (best, brow, bcol); a candidate that does not get below lim never counts
+#define EDT_CAND(xc, kk2)                                                                          \
+    do {                                                                                           \
+        const uint32_t s_ = sg[xc];                                                                \
+        if (s_ != EDT_NONE) {                                                                      \
+            const int32_t a_ = (int32_t)(s_ & 0x7fffu);                                            \
+            const int32_t c_ = (kk2) + a_ * a_;                                                    \
+            const int32_t r_ = (s_ & EDT_BELOW) ? y + a_ : y - a_;                                 \
+            if (c_ < lim && (c_ < best || (c_ == best && (r_ < brow || (r_ == brow && (xc) < bcol))))) { \
+                best = c_; brow = r_; bcol = (xc);                                                 \
+            }                                                                                      \
+        }                                                                                          \
+    } while (0)
+
+// As edt_row_kernel, but the search goes on while k^2 <= best: a seed at the same distance may have a smaller row or column.
+__global__ __launch_bounds__(256) void edt_row_idx_kernel(const uint16_t* __restrict__ g, int W, int32_t lim,
+                                                          int32_t* __restrict__ d2, int32_t* __restrict__ idx) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t sg[];
+    const int y = blockIdx.x;
+    const int64_t base = (int64_t)y * W;
+    int mine = 0;
+    for (int x = threadIdx.x; x < W; x += 256) {
+        const uint16_t v = g[base + x];
+        sg[x] = v;
+        mine |= v != EDT_NONE;
+    }
+    const int some = __syncthreads_or(mine);
+    for (int x = threadIdx.x; x < W; x += 256) {
+        int32_t best = lim, brow = 0x7fffffff, bcol = 0x7fffffff;
+        if (some) {
+            EDT_CAND(x, 0);
+            const int kmax = x > W - 1 - x ? x : W - 1 - x;
+            for (int k = 1; k <= kmax && k * k <= best && k * k < lim; ++k) {
+                const int32_t k2 = k * k;
+                if (k <= x) EDT_CAND(x - k, k2);
+                if (x + k < W) EDT_CAND(x + k, k2);
+            }
+        }
+        d2[base + x] = best;
+        idx[base + x] = best < lim ? brow * W + bcol : -1;
+    }
+}
+#undef EDT_CAND
 
 // ---- errors by depth ----------------------------------------------------------------------------------------------------
 constexpr int DE_NSUM = 2 * TG_DEPTH_MAX_CLASSES;
@@ -294,6 +372,51 @@ extern "C" int tg_edt(const uint8_t* seed, int H, int W, int32_t cap2, double ce
     hipLaunchKernelGGL(edt_row_kernel, dim3(H), dim3(256), lds, S(stream), g, W, cap2 > 0 ? cap2 : (int32_t)TG_EDT_FAR, cellsize,
                        d2, dist_m);
     TG_CHECK_LAUNCH("edt_row_kernel");
+    return TG_OK;
+}
+
+extern "C" size_t tg_edt_nearest_ws_bytes(int H, int W) { return tg_edt_ws_bytes(H, W); }
+
+extern "C" int tg_edt_nearest(const uint8_t* seed, int H, int W, int32_t cap2, int32_t* d2, int32_t* idx, void* ws,
+                              size_t ws_bytes, tg_stream_t stream) {
+    if (int rc = side_check("tg_edt_nearest", H, W)) return rc;
+    TG_REQUIRE(seed && d2 && idx && ws, "tg_edt_nearest: null pointer");
+    const EdtLayout L = edt_layout(H, W);
+    TG_REQUIRE(ws_bytes >= L.total, "tg_edt_nearest: workspace %zu bytes < %zu", ws_bytes, L.total);
+    int glimit = (int)EDT_NONE;
+    if (cap2 > 0) {                                     // the smallest s with s^2 >= cap2, as in tg_edt
+        int64_t s = (int64_t)sqrt((double)cap2);
+        while (s * s >= cap2 && s > 0) --s;
+        while (s * s < cap2) ++s;
+        if (s < glimit) glimit = (int)s;
+    }
+    static bool opted[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (dev < 0 || dev >= 64 || !opted[dev]) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(edt_row_idx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                EDT_ROW_LDS) != hipSuccess) {
+            tg_set_error("tg_edt_nearest: LDS opt-in failed");
+            return TG_ERR_LAUNCH;
+        }
+        if (dev >= 0 && dev < 64) opted[dev] = true;
+    }
+    char* base = (char*)ws;
+    uint64_t* mask = (uint64_t*)(base + L.mask);
+    int32_t* up = (int32_t*)(base + L.up);
+    int32_t* down = (int32_t*)(base + L.down);
+    uint16_t* g = (uint16_t*)(base + L.g);
+    const int nb = cdiv(H, EDT_BAND), gx = cdiv(W, 256);
+    hipLaunchKernelGGL(edt_mask_kernel, dim3(gx, nb), dim3(256), 0, S(stream), seed, H, W, mask);
+    TG_CHECK_LAUNCH("edt_mask_kernel");
+    hipLaunchKernelGGL(edt_carry_kernel, dim3(gx), dim3(256), 0, S(stream), mask, nb, W, up, down);
+    TG_CHECK_LAUNCH("edt_carry_kernel");
+    hipLaunchKernelGGL(edt_gs_kernel, dim3(gx, nb), dim3(256), 0, S(stream), mask, up, down, H, W, glimit, g);
+    TG_CHECK_LAUNCH("edt_gs_kernel");
+    const size_t lds = ((size_t)W * sizeof(uint16_t) + 15) & ~(size_t)15;
+    hipLaunchKernelGGL(edt_row_idx_kernel, dim3(H), dim3(256), lds, S(stream), g, W, cap2 > 0 ? cap2 : (int32_t)TG_EDT_FAR, d2,
+                       idx);
+    TG_CHECK_LAUNCH("edt_row_idx_kernel");
     return TG_OK;
 }
 

@@ -7,6 +7,9 @@ dist = float32(cellsize * sqrt(float64(d2))).  Known pixels have distance 0; a r
 max_distance (metres) caps the result at the smallest pixel distance that reaches it, which also bounds the cost of the search
 in rasters with large unknown regions.
 
+nearest_known returns the same distance and, per pixel, which known pixel is the nearest (the feature transform, DESIGN.md
+section 8t; mvp_gan/src/interpolate.py fills voids from it).
+
 Two calls on the same inputs return bitwise-equal tensors.
 
 CLI: python -m mvp_gan.src.distance --dem in.asc --out depth.asc [--mask m.png|m.asc] [--nodata v] [--max-distance m]
@@ -103,6 +106,31 @@ def distance_to_known(dem, mask=None, *, nodata=None, cellsize=1.0, max_distance
     info = {"known": known, "unknown": H * W - known, "max_m": px2_m(int(d2.max().item()), c) if known else math.inf,
             "cap_m": px2_m(cap2, c) if cap2 else None, "capped": int((d2 == cap2).count_nonzero().item()) if cap2 else 0}
     return dist, info
+
+
+@torch.no_grad()
+def nearest_known(dem, mask=None, *, nodata=None, cellsize=1.0, max_distance=None):
+    """distance_to_known, plus which known pixel is the nearest (the feature transform, tg_edt_nearest).
+    Returns (dist float32 HIP tensor [H][W] in metres, index int32 HIP tensor [H][W] = y * W + x of the nearest known pixel,
+    the smallest row and then the smallest column among those at the smallest distance, -1 where no known pixel is in reach:
+    none at all, or none nearer than the cap of max_distance; info as distance_to_known's)."""
+    from tg_hip import ops as O
+    from .fill_voids import _device_f32
+    H, W, c, cap2 = check_args(dem, mask, cellsize, max_distance, who="nearest_known")
+    if not torch.cuda.is_available():
+        raise RuntimeError("nearest_known: no HIP device visible; this build has no CPU path")
+    device = torch.device("cuda", torch.cuda.current_device())
+    z = _device_f32(dem, device, "dem", who="nearest_known")
+    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who="nearest_known")
+    if nodata is not None and math.isnan(nodata):
+        nodata = None
+    seed, _ = O.objmask_known(z, m, nodata, transposed=False)
+    d2, index = O.edt_nearest(seed, cap2)
+    dist = torch.where(d2 == FAR, math.inf, c * d2.double().sqrt()).float()      # fp64 sqrt and multiply, rounded once
+    known = int(seed.count_nonzero().item())
+    info = {"known": known, "unknown": H * W - known, "max_m": px2_m(int(d2.max().item()), c) if known else math.inf,
+            "cap_m": px2_m(cap2, c) if cap2 else None, "capped": int((d2 == cap2).count_nonzero().item()) if cap2 else 0}
+    return dist, index, info
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------

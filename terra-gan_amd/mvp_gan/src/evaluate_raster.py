@@ -34,11 +34,15 @@ report["baseline"] holds that fill's full terrain_errors report on the same hole
 a GAN has to beat.  fallback and seam are passed to inpaint_raster; with seam="harmonic" report["seam"] holds the info of the
 seam correction (mvp_gan/src/seam_correct.py), and the ring errors show what it did.
 
+With compare=("idw", "nearest") the same keep mask is also filled by interpolate_voids with its defaults (mvp_gan/src/interpolate.py,
+DESIGN.md section 8t: the cheap end of the baseline ladder) and report["compare"][name] holds that fill's terrain_errors report
+on the same holes and depth classes, plus "method" and the fill info under "fill".  Without it the report has no "compare" key.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
-         [--by-depth [E ...]]
+         [--by-depth [E ...]] [--compare idw nearest]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -449,37 +453,85 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     return rep
 
 
+COMPARES = ("idw", "nearest")
+
+
+def _check_compare(compare, who="evaluate_raster"):
+    """None, or a sequence of distinct names out of COMPARES -> a tuple (empty for None)."""
+    if compare is None:
+        return ()
+    if isinstance(compare, str):
+        compare = (compare,)
+    try:
+        names = tuple(compare)
+    except TypeError:
+        raise ValueError(f"{who}: compare {compare!r} must be None or a sequence out of {COMPARES}") from None
+    if any(n not in COMPARES for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"{who}: compare {compare!r} must be None or distinct names out of {COMPARES}")
+    return names
+
+
+def assemble_compare(reports, infos):
+    """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name."""
+    out = {}
+    for name, rep in reports.items():
+        out[name] = dict(rep)
+        out[name]["method"] = name
+        out[name]["fill"] = infos[name]
+    return out
+
+
+@torch.no_grad()
+def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
+                   quantiles=QUANTILES, top=10, depth_edges_m=None):
+    """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
+    from .interpolate import interpolate_voids
+    device = _device()
+    z = _f32(dem, device, "dem")
+    k = _f32(keep, device, "keep", binary=True)
+    reports, infos = {}, {}
+    for name in _check_compare(names):
+        pred, infos[name] = interpolate_voids(z, k, nodata=_nodata(nodata), method=name, cellsize=cellsize)
+        reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
+                                       area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
+    return assemble_compare(reports, infos)
+
+
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
-                    solver="mg", depth_edges_m=None):
+                    solver="mg", depth_edges_m=None, compare=None):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
     checkpoint whose training blocks were picked on the working grid), and seam="harmonic" adds report["seam"].  solver is the
     fill_voids solver of the baseline, the seam correction and the fallback ("mg" or "pcg"); "pcg" shows in their infos.
-    depth_edges_m adds "by_depth" to the report and, on the same classes, to report["baseline"]."""
+    depth_edges_m adds "by_depth" to the report and, on the same classes, to report["baseline"].  compare: names out of COMPARES,
+    adds report["compare"][name], the interpolate_voids fill of the same keep mask scored on the same holes and classes."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
                              seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
-                             depth_edges_m=depth_edges_m)
+                             depth_edges_m=depth_edges_m, compare=compare)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
-              min_coverage=0.5, solver="mg", depth_edges_m=None):
+              min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
     _check_fill_options(baseline, fallback)
+    compare = _check_compare(compare)
     check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
     c = _cellsize(cellsize, "evaluate_raster")
     check_resample_options(c, model_cellsize, min_coverage, who="evaluate_raster")
     H, W = _inputs(dem, mask, "evaluate_raster")
+    if compare and max(H, W) > 32767:
+        raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
@@ -504,6 +556,9 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
                                           depth_edges_m=depth_edges_m)
+    if compare:
+        rep["compare"] = compare_report(z, hm, keep, compare, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
+                                        quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
     return rep, pred, hm
 
 
@@ -565,6 +620,9 @@ def build_parser():
     ap.add_argument("--by-depth", type=float, nargs="*", metavar="E",
                     help="also report the height errors by distance to the known terrain: class bounds in metres (given bare: "
                          + " ".join(f"{e:g}" for e in DEPTH_EDGES_M) + "); the baseline is scored on the same classes")
+    ap.add_argument("--compare", nargs="+", choices=COMPARES, metavar="NAME",
+                    help="also score these interpolate_voids fills of the same holes (" + ", ".join(COMPARES) + "): one more "
+                         "summary line each")
     return ap
 
 
@@ -595,7 +653,8 @@ def main(argv=None):
                                   holes=HoleSpec(), seed=a.seed, window=a.window, overlap=a.overlap, batch=a.batch,
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
-                                  min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges)
+                                  min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges,
+                                  compare=a.compare)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -609,6 +668,9 @@ def main(argv=None):
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
                                               solver=a.solver, depth_edges_m=depth_edges)
+        if a.compare:
+            rep["compare"] = compare_report(dem, hm, keep, a.compare, cellsize=c, mask=mask, nodata=nodata,
+                                            depth_edges_m=depth_edges)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -628,6 +690,8 @@ def main(argv=None):
     if "baseline" in rep:
         how = "" if a.solver == "mg" else f" (solver {a.solver})"
         print(f"baseline {rep['baseline']['method']}{how}: {summary(rep['baseline'])}")
+    for name, r in rep.get("compare", {}).items():
+        print(f"compare {name}: {summary(r)}")
     return rep
 
 

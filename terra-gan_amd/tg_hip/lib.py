@@ -179,6 +179,12 @@ SIGNATURES = {
     "tg_depth_errors_ws_bytes": (SZ, [I, I]),
     "tg_depth_errors": (I, [P, P, P, P, I, I, I, C.POINTER(TgDepthClasses), P, P, P, P, SZ, P]),
     "tg_depth_errors_finish": (I, [I, I, P, SZ, P, P]),
+    "tg_edt_nearest_ws_bytes": (SZ, [I, I]),
+    "tg_edt_nearest": (I, [P, I, I, C.c_int32, P, P, P, SZ, P]),
+    "tg_rayfill_ws_bytes": (SZ, [I, I]),
+    "tg_rayfill": (I, [P, P, I, I, C.c_int32, D, P, P, P, P, P, P, SZ, P]),
+    "tg_gather_fill": (I, [P, P, P, I, I, P, P, P]),
+    "tg_void_smooth": (I, [P, P, I, I, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -1250,6 +1250,82 @@ def depth_errors(sel_a, d2, labels, slot, nholes, class_d2):
     return sums, counts, max_bits, hole_d2
 
 
+def edt_nearest(seed, cap2=0):
+    """-> (d2 int32 [H][W], idx int32 [H][W]): d2 as edt's; idx = y * W + x of the nearest nonzero pixel of seed (the smallest
+    row, then the smallest column among equals), -1 where d2 is EDT_FAR or, with a cap, d2 >= cap2 (tg_edt_nearest)."""
+    H, W = _edt_hw(seed, "seed")
+    _hip(seed, torch.uint8, (H, W), "seed")
+    cap2 = int(cap2)
+    if not -2 ** 31 <= cap2 < 2 ** 31:
+        raise L.TgError(f"edt_nearest: cap2 {cap2} does not fit an int32")
+    d2 = torch.empty(H, W, dtype=torch.int32, device=seed.device)
+    idx = torch.empty(H, W, dtype=torch.int32, device=seed.device)
+    lib = _lib()
+    ws = workspace(lib.tg_edt_nearest_ws_bytes(H, W))
+    L.check(lib.tg_edt_nearest(_p(seed), H, W, cap2, _p(d2), _p(idx), _p(ws), ws.numel() * 4, _stream()), "tg_edt_nearest")
+    return d2, idx
+
+
+def rayfill(z, known, lim2=0, power=2.0, d2=None, idx=None, want_hits=False):
+    """-> (out float32 [H][W], counts int64 [3]: by rays, by nearest, left NaN; hits uint16 [8][H][W] or None): the
+    eight-direction inverse-distance fill of the pixels with known == 0 (tg_rayfill).  d2, idx: edt_nearest's, for the
+    nearest-neighbour fallback of the pixels no ray serves; both or neither."""
+    H, W = _edt_hw(z, "z")
+    _hip(z, torch.float32, (H, W), "z")
+    _hip(known, torch.uint8, (H, W), "known")
+    lim2 = int(lim2)
+    if not -2 ** 31 <= lim2 < 2 ** 31:
+        raise L.TgError(f"rayfill: lim2 {lim2} does not fit an int32")
+    power = float(power)
+    if not 0.0 < power <= 8.0:
+        raise L.TgError(f"rayfill: power {power!r} must lie in (0, 8]")
+    if (d2 is None) != (idx is None):
+        raise L.TgError("rayfill: d2 and idx go together")
+    if d2 is not None:
+        _hip(d2, torch.int32, (H, W), "d2")
+        _hip(idx, torch.int32, (H, W), "idx")
+    out = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    hits = torch.empty(8, H, W, dtype=torch.uint16, device=z.device) if want_hits else None
+    counts = torch.empty(3, dtype=torch.int64, device=z.device)
+    lib = _lib()
+    ws = workspace(lib.tg_rayfill_ws_bytes(H, W))
+    L.check(lib.tg_rayfill(_p(z), _p(known), H, W, lim2, power, _p(d2), _p(idx), _p(out), _p(hits), _p(counts), _p(ws),
+                           ws.numel() * 4, _stream()), "tg_rayfill")
+    return out, counts, hits
+
+
+def gather_fill(z, known, idx):
+    """-> (out float32 [H][W] = known ? z : z[idx], NaN at idx < 0; counts int64 [2]: filled, left NaN) (tg_gather_fill)."""
+    H, W = _edt_hw(z, "z")
+    _hip(z, torch.float32, (H, W), "z")
+    _hip(known, torch.uint8, (H, W), "known")
+    _hip(idx, torch.int32, (H, W), "idx")
+    out = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    counts = torch.empty(2, dtype=torch.int64, device=z.device)
+    L.check(_lib().tg_gather_fill(_p(z), _p(known), _p(idx), H, W, _p(out), _p(counts), _stream()), "tg_gather_fill")
+    return out, counts
+
+
+def void_smooth(x, known, steps=1):
+    """-> float32 [H][W]: `steps` Jacobi steps of the 3x3 mean over the non-NaN pixels, on the pixels with known == 0 that are
+    not NaN (tg_void_smooth); x is left unchanged."""
+    H, W = _edt_hw(x, "x")
+    _hip(x, torch.float32, (H, W), "x")
+    _hip(known, torch.uint8, (H, W), "known")
+    steps = int(steps)
+    if steps < 0:
+        raise L.TgError(f"void_smooth: steps {steps} < 0")
+    if steps == 0:
+        return x.clone()
+    lib = _lib()
+    a, b = x, torch.empty_like(x)
+    spare = torch.empty_like(x) if steps > 1 else None
+    for _ in range(steps):
+        L.check(lib.tg_void_smooth(_p(a), _p(known), H, W, _p(b), _stream()), "tg_void_smooth")
+        a, b = b, (spare if a is x else a)
+    return a
+
+
 VFILL_NSTATS = 4                                 # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 

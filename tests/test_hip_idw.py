@@ -1,0 +1,449 @@
+"""GPU checks of the feature transform and of the directional inverse-distance, nearest-neighbour and smoothing fills
+(csrc/edt.hip, csrc/idw.hip, mvp_gan/src/distance.py, mvp_gan/src/interpolate.py, mvp_gan/src/evaluate_raster.py) against the
+numpy oracle in tests/idw_oracle.py.  Every comparison is bit for bit, except the fills with a power other than 1 and 2, which
+hold to one ulp of fp32 at the largest contributing height: both pows are within a few ulp of fp64 and the result is a convex
+combination, so the two fp64 quotients differ by less than 2^-48 max|z|, and the one rounding to fp32 moves that by at most one
+ulp."""
+import json
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from tests import edt_oracle as EO
+from tests import idw_oracle as IO
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    from tg_hip import lib
+    lib.load()
+    return torch.device("cuda:0")
+
+
+def _t(dev, a, dtype=None):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(dev)
+
+
+def _random(H, W, p, seed):
+    return (np.random.default_rng(seed).random((H, W)) < p).astype(np.uint8)
+
+
+def _one(H, W, y, x):
+    s = np.zeros((H, W), np.uint8)
+    s[y, x] = 1
+    return s
+
+
+def _capped(want, cap2):
+    d2, idx = want
+    if cap2 <= 0:
+        return d2, idx
+    return np.minimum(d2, cap2), np.where(d2 >= cap2, -1, idx).astype(np.int32)
+
+
+# ---- feature transform -------------------------------------------------------------------------------------------------------
+def _check_ft(dev, seed, cap2=0, want=None):
+    """d2 bitwise tg_edt's, d2 and idx the oracle's (want: the uncapped oracle, when the caller shares it)."""
+    from tg_hip import ops as O
+    s = _t(dev, seed, np.uint8)
+    d2, idx = O.edt_nearest(s, cap2)
+    ref, _ = O.edt(s, cap2)
+    assert d2.dtype == torch.int32 and idx.dtype == torch.int32 and torch.equal(d2, ref)
+    wd2, widx = _capped(IO.nearest(seed) if want is None else want, cap2)
+    np.testing.assert_array_equal(d2.cpu().numpy(), wd2)
+    np.testing.assert_array_equal(idx.cpu().numpy(), widx)
+    if cap2 > 0:
+        np.testing.assert_array_equal(idx.cpu().numpy() == -1, d2.cpu().numpy() >= cap2)
+    return d2, idx
+
+
+def _ft_layouts():
+    out = {"1x1 seed": np.ones((1, 1), np.uint8), "1x1 none": np.zeros((1, 1), np.uint8),
+           "1x300": _random(1, 300, 0.01, 1), "300x1": _random(300, 1, 0.01, 2), "130x67": _random(130, 67, 0.2, 4)}
+    for j, (y, x) in enumerate(((0, 0), (0, 66), (129, 0), (129, 66))):
+        out[f"130x67 corner {j}"] = _one(130, 67, y, x)
+    rows = _one(130, 67, 30, 20)                                # symmetric about row 64: that whole row ties above / below
+    rows[98, 20] = 1
+    out["130x67 tie rows"] = rows
+    cols = _one(130, 67, 70, 3)                                 # symmetric about column 33: that whole column ties left / right
+    cols[70, 63] = 1
+    out["130x67 tie columns"] = cols
+    quad = np.zeros((130, 67), np.uint8)                        # four seeds: the centre ties all of them
+    for y, x in ((30, 3), (30, 63), (98, 3), (98, 63)):
+        quad[y, x] = 1
+    out["130x67 tie four"] = quad
+    out["2x32767"] = _one(2, 32767, 1, 0)
+    return out
+
+
+FT_LAYOUTS = _ft_layouts()
+
+
+@pytest.mark.parametrize("name", list(FT_LAYOUTS))
+def test_feature_transform_layouts(dev, name):
+    seed = FT_LAYOUTS[name]
+    d2, idx = _check_ft(dev, seed)
+    if not seed.any():
+        assert (idx == -1).all() and (d2 == EO.FAR).all()
+    if name == "130x67 tie rows":
+        assert (idx[64] == 30 * 67 + 20).all()                  # the seed above wins the whole tied row
+    if name == "130x67 tie columns":
+        assert (idx[:, 33] == 70 * 67 + 3).all()                # the seed on the left wins the whole tied column
+    if name == "130x67 tie four":
+        assert int(idx[64, 33]) == 30 * 67 + 3
+
+
+@pytest.mark.parametrize("H", [63, 64, 65, 129])
+@pytest.mark.parametrize("W", [255, 256, 257])
+def test_feature_transform_bands(dev, H, W):
+    """One seed in the first band, carried down through every band, and the mirror image, carried up."""
+    seed = _one(H, W, 0, W - 1)
+    _check_ft(dev, seed)
+    _check_ft(dev, seed[::-1].copy())
+
+
+@pytest.fixture(scope="module")
+def big():
+    """257 x 1100 at p = 0.001: searches across several bands and many 256-column strides; the oracle is shared."""
+    seed = _random(257, 1100, 0.001, 7)
+    want = IO.nearest(seed)
+    np.testing.assert_array_equal(want[0], EO.edt_d2(seed))
+    assert want[0].max() > 2000
+    return seed, want
+
+
+def test_feature_transform_big_caps_and_determinism(dev, big):
+    from tg_hip import ops as O
+    seed, want = big
+    a = _check_ft(dev, seed, want=want)
+    for cap2 in (1, 2, 25, 10000):
+        _check_ft(dev, seed, cap2, want=want)
+    b = O.edt_nearest(_t(dev, seed), 0)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+
+def test_feature_transform_all_and_none(dev):
+    from tg_hip import ops as O
+    H, W = 257, 1100
+    d2, idx = O.edt_nearest(torch.ones(H, W, dtype=torch.uint8, device=dev))
+    assert (d2 == 0).all() and torch.equal(idx.flatten(), torch.arange(H * W, dtype=torch.int32, device=dev))
+    for cap2 in (0, 49):
+        d2, idx = O.edt_nearest(torch.zeros(H, W, dtype=torch.uint8, device=dev), cap2)
+        assert (idx == -1).all() and (d2 == (cap2 or EO.FAR)).all()
+
+
+# ---- ray hits -----------------------------------------------------------------------------------------------------------------
+def _check_hits(dev, known, lim2=0):
+    from tg_hip import ops as O
+    H, W = known.shape
+    z = torch.zeros(H, W, device=dev)
+    _, counts, hits = O.rayfill(z, _t(dev, known, np.uint8), lim2, want_hits=True)
+    want = IO.ray_hits(known, lim2)
+    got = hits.cpu().numpy()
+    assert got.dtype == np.uint16 and got.shape == (8, H, W)
+    np.testing.assert_array_equal(got, want)
+    any_hit = (want != 0).any(axis=0)
+    assert counts.cpu().tolist() == [int(any_hit.sum()), 0, int(((known == 0) & ~any_hit).sum())]
+    return want
+
+
+def _hit_layouts():
+    out = dict(FT_LAYOUTS)
+    for H in (63, 64, 65, 129):
+        for W in (255, 256, 257):
+            out[f"{H}x{W} first row"] = _one(H, W, 0, W - 1)
+            out[f"{H}x{W} last row"] = _one(H, W, H - 1, 0)
+    for W in (63, 64, 65, 129):
+        out[f"70x{W}"] = _random(70, W, 0.03, W)
+    out["257x1100"] = _random(257, 1100, 0.001, 7)
+    out["257x1100 all"] = np.ones((257, 1100), np.uint8)
+    out["257x1100 none"] = np.zeros((257, 1100), np.uint8)
+    y, x = np.mgrid[0:66, 0:131]
+    out["checkerboard"] = ((y + x) & 1).astype(np.uint8)
+    out["checkerboard of pairs"] = (~((y % 2 == 0) & (x % 4 < 2))).astype(np.uint8)     # unknown: pairs (x, x + 1) on even rows
+    out["65x130 corner"] = _one(65, 130, 64, 0)
+    last_row = np.zeros((200, 150), np.uint8)
+    last_row[199] = 1
+    out["only the last row"] = last_row
+    last_col = np.zeros((150, 200), np.uint8)
+    last_col[:, 199] = 1
+    out["only the last column"] = last_col
+    return out
+
+
+HIT_LAYOUTS = _hit_layouts()
+
+
+@pytest.mark.parametrize("name", list(HIT_LAYOUTS))
+def test_ray_hits(dev, name):
+    known = HIT_LAYOUTS[name]
+    want = _check_hits(dev, known)
+    if name.startswith("checkerboard"):
+        inner = known == 0
+        inner[[0, -1]] = False
+        inner[:, [0, -1]] = False
+    if name == "checkerboard":
+        assert (want[0::2][:, inner] == 1).all() and not want[1::2].any()   # axis neighbours known, diagonals all unknown
+    if name == "checkerboard of pairs":
+        assert (want[1::2][:, inner] == 1).all()                        # every diagonal hit is at k = 1
+        assert (want[0][inner] == 1).all() and (want[4][inner] == 1).all()
+        first = inner & (np.arange(131)[None, :] % 4 == 0)              # the axis hits along the row alternate: 1 and 2
+        assert (want[2][first] == 2).all() and (want[6][first] == 1).all()
+        second = inner & ~first
+        second[:, 1] = False                                            # from column 1 the ray to the west leaves the raster
+        assert (want[2][second] == 1).all() and (want[6][second] == 2).all() and not want[6][:, 1].any()
+    if name == "65x130 corner":
+        hit = np.argwhere(want != 0)
+        assert {int(j) for j in hit[:, 0]} == {4, 5, 6}                 # S along the column, SW along the diagonal, W along the row
+        assert want[5, 0, 64] == 64 and want[4, 0, 0] == 64 and want[6, 64, 129] == 129
+
+
+@pytest.mark.parametrize("lim2", [1, 2, 25, 10000])
+def test_ray_hits_with_a_limit(dev, lim2):
+    for known in (_random(130, 67, 0.05, 11), _random(257, 300, 0.002, 12)):
+        want = _check_hits(dev, known, lim2)
+        if lim2 == 1:
+            assert not want[1::2].any() and set(np.unique(want[0::2])) <= {0, 1}
+        if lim2 == 2:
+            assert set(np.unique(want)) <= {0, 1} and want[1::2].any()
+
+
+# ---- values ---------------------------------------------------------------------------------------------------------------------
+def _heights(H, W, seed):
+    """~1000 m with metre-scale relief: the fp32 inputs carry ~1e-4 m, so a sum that is not carried in fp64 shows."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:H, 0:W]
+    return (1000.0 + 30.0 * np.sin(x / 17.0) * np.cos(y / 23.0) + rng.normal(0, 1.5, (H, W))).astype(np.float32)
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    """(z, known, lim2) with dense and sparse seeds; a limit that leaves no-hit pixels; one seed only (almost no ray hits)."""
+    out = [(_heights(130, 67, 1), _random(130, 67, 0.2, 21), 0), (_heights(65, 130, 2), _random(65, 130, 0.02, 22), 0),
+           (_heights(65, 130, 3), _random(65, 130, 0.02, 23), 25), (_heights(70, 90, 4), _one(70, 90, 33, 41), 0)]
+    return [(z, k, lim2, IO.ray_hits(k, lim2), IO.nearest(k, lim2 + 1 if lim2 else 0)) for z, k, lim2 in out]
+
+
+def _fill(dev, z, known, lim2, power, ft=None):
+    from tg_hip import ops as O
+    d2, idx = (None, None) if ft is None else (_t(dev, ft[0]), _t(dev, ft[1]))
+    out, counts, _ = O.rayfill(_t(dev, z), _t(dev, known, np.uint8), lim2, power, d2, idx)
+    return out.cpu().numpy(), counts.cpu().tolist()
+
+
+@pytest.mark.parametrize("power", [2.0, 1.0])
+def test_fill_is_bitwise_the_oracle(dev, scenes, power):
+    saw_near = saw_left = False
+    for z, known, lim2, hits, ft in scenes:
+        unknown = int((known == 0).sum())
+        for fb in (None, ft):
+            want, wc, lo, hi = IO.rayfill(z, known, lim2, power, *(fb or (None, None)), hits=hits)
+            got, counts = _fill(dev, z, known, lim2, power, fb)
+            np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))
+            assert counts == wc and sum(counts) == unknown
+            saw_near, saw_left = saw_near or wc[1] > 0, saw_left or (fb is not None and wc[2] > 0)
+            kn = known != 0
+            np.testing.assert_array_equal(got[kn].view(np.int32), z[kn].view(np.int32))       # known pixels bit for bit
+            rays = ~np.isnan(lo)
+            assert (got[rays] >= lo[rays]).all() and (got[rays] <= hi[rays]).all()
+            nohit = ~kn & ~rays
+            if fb is None:
+                assert np.isnan(got[nohit]).all() and counts[1] == 0
+            else:
+                ok = nohit & (ft[1] >= 0)
+                np.testing.assert_array_equal(got[ok], z.ravel()[ft[1][ok]])
+                assert np.isnan(got[nohit & (ft[1] < 0)]).all()
+            again, c2 = _fill(dev, z, known, lim2, power, fb)
+            assert np.array_equal(again.view(np.int32), got.view(np.int32)) and c2 == counts
+    assert saw_near and saw_left                  # the scenes reach the fallback, and pixels beyond the limit despite it
+
+
+@pytest.mark.parametrize("power", [1.5, 3.0])
+def test_fill_general_power_within_one_ulp(dev, scenes, power):
+    for z, known, lim2, hits, ft in scenes:
+        want, wc, lo, hi = IO.rayfill(z, known, lim2, power, *ft, hits=hits)
+        got, counts = _fill(dev, z, known, lim2, power, ft)
+        assert counts == wc
+        rays = ~np.isnan(lo)
+        ulp = np.spacing(np.maximum(np.abs(lo[rays]), np.abs(hi[rays])).astype(np.float32))
+        err = np.abs(got[rays].astype(np.float64) - want[rays].astype(np.float64))
+        print(f"power {power}: max |out - oracle| / ulp = {(err / ulp).max():.3g} over {int(rays.sum())} px")
+        assert (err <= ulp).all()
+        assert (got[rays] >= lo[rays]).all() and (got[rays] <= hi[rays]).all()
+        np.testing.assert_array_equal(got[~rays].view(np.int32), want[~rays].view(np.int32))
+
+
+@pytest.mark.parametrize("power", [2.0, 1.0, 1.5])
+def test_constant_field_comes_back_constant(dev, power):
+    known = _random(130, 67, 0.03, 31)
+    z = np.full((130, 67), 1234.5678, np.float32)
+    got, counts = _fill(dev, z, known, 0, power, IO.nearest(known))
+    assert counts[0] > 8000 and counts[2] == 0 and (got == z).all()
+
+
+def test_gather_fill(dev, scenes):
+    from tg_hip import ops as O
+    for z, known, lim2, _, ft in scenes:
+        out, counts = O.gather_fill(_t(dev, z), _t(dev, known, np.uint8), _t(dev, ft[1]))
+        want, wc = IO.gather_fill(z, known, ft[1])
+        np.testing.assert_array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
+        assert counts.cpu().tolist() == wc and sum(wc) == int((known == 0).sum())
+
+
+# ---- smoothing -----------------------------------------------------------------------------------------------------------------
+def test_smoothing_steps(dev, scenes):
+    from tg_hip import ops as O
+    z, known, lim2, hits, _ = scenes[2]
+    filled, wc, _, _ = IO.rayfill(z, known, lim2, 2.0, hits=hits)               # fallback None: NaN islands stay
+    assert wc[2] > 0 and wc[0] > 0
+    x, k = _t(dev, filled), _t(dev, known, np.uint8)
+    for steps in (1, 2, 5):
+        got = O.void_smooth(x, k, steps).cpu().numpy()
+        want = IO.smooth(filled, known, steps)
+        np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))
+        kn = known != 0
+        np.testing.assert_array_equal(got[kn].view(np.int32), z[kn].view(np.int32))
+        np.testing.assert_array_equal(np.isnan(got), np.isnan(filled))
+        assert (got != filled)[~kn & ~np.isnan(filled)].any()
+    assert np.array_equal(x.cpu().numpy().view(np.int32), filled.view(np.int32))           # the input is left alone
+
+
+# ---- the public API and the CLI ------------------------------------------------------------------------------------------------
+def _dirty_raster(H, W, seed):
+    rng = np.random.default_rng(seed)
+    z = _heights(H, W, seed)
+    mask = np.ones((H, W), np.float32)
+    mask[20:60, 30:90] = 0                                  # a masked block
+    z[70:90, 10:25] = np.nan                                # a NaN hole
+    z[5:15, 100:140] = -9999.0                              # a nodata hole
+    z[rng.random((H, W)) < 0.01] = np.nan
+    return z, mask
+
+
+def test_nearest_known(dev):
+    from mvp_gan.src.distance import distance_to_known, nearest_known
+    H, W = 100, 150
+    z, mask = _dirty_raster(H, W, 31)
+    K = (mask != 0) & np.isfinite(z) & (z != np.float32(-9999.0))
+    want = IO.nearest(K)
+    for c, md in ((0.5, None), (0.25, 1.3), (2.5, 12.0)):
+        dist, index, info = nearest_known(z, mask, nodata=-9999.0, cellsize=c, max_distance=md)
+        ref, rinfo = distance_to_known(z, mask, nodata=-9999.0, cellsize=c, max_distance=md)
+        assert torch.equal(dist, ref) and info == rinfo and index.dtype == torch.int32
+        cap2 = EO.depth_px2([md], c)[0] if md else 0
+        wd2, widx = _capped(want, cap2)
+        np.testing.assert_array_equal(index.cpu().numpy(), widx)
+        np.testing.assert_array_equal(dist.cpu().numpy().view(np.int32), EO.metres(wd2, c).view(np.int32))
+        if md:
+            assert (widx == -1).any() and info["capped"] == int((widx == -1).sum())
+    dist, index, info = nearest_known(np.full((9, 11), np.nan, np.float32), cellsize=2.0)
+    assert (index == -1).all() and np.isposinf(dist.cpu().numpy()).all() and info["known"] == 0
+
+
+@pytest.mark.parametrize("c,md", [(1.0, None), (0.25, 1.3), (2.5, 12.0)])
+def test_interpolate_voids(dev, c, md):
+    from mvp_gan.src.interpolate import interpolate_voids
+    H, W = 100, 150
+    z, mask = _dirty_raster(H, W, 32)
+    K = (mask != 0) & np.isfinite(z) & (z != np.float32(-9999.0))
+    unknown = int((~K).sum())
+    lim2 = IO.ray_px2(md, c) if md else 0
+    if md:
+        assert c * math.sqrt(lim2) <= md < c * math.sqrt(lim2 + 1)
+    ft = IO.nearest(K, lim2 + 1 if lim2 else 0)
+    base = {"unknown": unknown, "smooth": 0, "max_distance": md, "lim2": lim2 or None}
+    # nearest
+    out, info = interpolate_voids(z, mask, nodata=-9999.0, method="nearest", cellsize=c, max_distance=md)
+    want, wc = IO.gather_fill(z, K, ft[1])
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
+    assert info == dict(base, filled=wc[0], by_nearest=wc[0], unfilled=wc[1], method="nearest", power=2.0)
+    assert (wc[1] > 0) == bool(md)
+    # idw with and without the fallback, device tensors in
+    for fb, power in (("nearest", 2.0), (None, 1.0)):
+        out, info = interpolate_voids(_t(dev, z), _t(dev, mask), nodata=-9999.0, cellsize=c, max_distance=md, power=power,
+                                      fallback=fb)
+        want, wc, _, _ = IO.rayfill(z, K, lim2, power, *(ft if fb else (None, None)))
+        np.testing.assert_array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
+        assert info == dict(base, filled=wc[0] + wc[1], by_nearest=wc[1], unfilled=wc[2], method="idw", power=power)
+    # smoothing applies to both methods; a NaN nodata is no value
+    out, info = interpolate_voids(z, mask, nodata=-9999.0, cellsize=c, max_distance=md, smooth=3)
+    want = IO.smooth(IO.rayfill(z, K, lim2, 2.0, *ft)[0], K, 3)
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
+    assert info["smooth"] == 3
+    out, info = interpolate_voids(z, mask, nodata=-9999.0, method="nearest", cellsize=c, max_distance=md, smooth=2)
+    want = IO.smooth(IO.gather_fill(z, K, ft[1])[0], K, 2)
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.int32), want.view(np.int32))
+    out, info = interpolate_voids(z, nodata=math.nan, method="nearest")
+    K2 = np.isfinite(z)
+    np.testing.assert_array_equal(out.cpu().numpy().view(np.int32), IO.gather_fill(z, K2, IO.nearest(K2)[1])[0].view(np.int32))
+    out, info = interpolate_voids(np.full((9, 11), np.nan, np.float32))
+    assert np.isnan(out.cpu().numpy()).all() and (info["unknown"], info["filled"], info["unfilled"]) == (99, 0, 99)
+
+
+def test_cli_round_trip(dev, tmp_path):
+    from mvp_gan.src.inpaint_raster import read_asc
+    from tests.test_hip_terrain_eval import _write_asc
+    H, W, c = 100, 150, 0.5
+    z, mask = _dirty_raster(H, W, 33)
+    z[np.isnan(z)] = -9999.0
+    dem, mpath, out = (str(tmp_path / n) for n in ("dem.asc", "mask.asc", "filled.asc"))
+    _write_asc(dem, z, c, -9999)
+    _write_asc(mpath, mask, c)
+    zr, _ = read_asc(dem)                                   # the heights as the text round trip leaves them
+    K = (mask != 0) & (zr != np.float32(-9999.0))
+    cwd = os.path.join(ROOT, "terra-gan_amd")
+    run = lambda args: subprocess.run([sys.executable, "-m", "mvp_gan.src.interpolate", "--dem", dem, "--out", out] + args,
+                                      cwd=cwd, capture_output=True, text=True, timeout=600)
+    r = run(["--mask", mpath])
+    assert r.returncode == 0, r.stderr
+    assert f"{int((~K).sum())} void pixels" in r.stdout
+    got, hdr = read_asc(out)
+    want = IO.rayfill(zr, K, 0, 2.0, *IO.nearest(K))[0]
+    np.testing.assert_array_equal(got.view(np.int32), want.view(np.int32))     # 9 digits: float32 reads back bit for bit
+    assert dict(hdr)["cellsize"] == str(c) and not (got == -9999.0).any()
+    r = run(["--mask", mpath, "--method", "nearest", "--max-distance", "2", "--smooth", "1"])
+    assert r.returncode == 0, r.stderr
+    got, _ = read_asc(out)
+    lim2 = IO.ray_px2(2.0, c)
+    assert lim2 == 16
+    want = IO.smooth(IO.gather_fill(zr, K, IO.nearest(K, lim2 + 1)[1])[0], K, 1)
+    assert np.isnan(want).any()
+    np.testing.assert_array_equal(got.view(np.int32), np.where(np.isnan(want), np.float32(-9999.0), want).view(np.int32))
+
+
+def test_evaluate_raster_compare(dev):
+    """End to end on the small scene of tests/test_hip_edt.py: the GAN, the harmonic baseline and both interpolators on the same
+    holes and depth classes; compare=None is the call without the keyword."""
+    from mvp_gan.src.evaluate_raster import evaluate_raster, summary
+    from mvp_gan.src.models import PConvUNet
+    from tests.test_hip_terrain_eval import _terrain
+    torch.manual_seed(7)
+    G = PConvUNet().to(dev)
+    H, W, c = 400, 520, 2.0
+    z = _terrain(H, W, c, 8)
+    kw = dict(cellsize=c, block=160, tile=80, window=128, overlap=16, baseline="laplace", depth_edges_m=(2, 5, 10))
+    rep, pred = evaluate_raster(G, z, compare=("idw", "nearest"), **kw)
+    none, pred1 = evaluate_raster(G, z, compare=None, **kw)
+    plain, pred0 = evaluate_raster(G, z, **kw)
+    assert torch.equal(pred, pred0) and torch.equal(pred1, pred0)
+    assert "compare" not in plain and json.dumps(none) == json.dumps(plain)
+    assert json.dumps({k: v for k, v in rep.items() if k != "compare"}) == json.dumps(plain)
+    assert list(rep["compare"]) == ["idw", "nearest"]
+    key = lambda r: [(k["lo_m"], k["hi_m"], k["pixels"]) for k in r["by_depth"]["classes"]]
+    for name, r in rep["compare"].items():
+        assert r["method"] == name and r["fill"]["method"] == name and r["fill"]["unfilled"] == 0
+        assert r["fill"]["unknown"] == r["fill"]["filled"] >= rep["pixels"]["holes"]
+        assert r["pixels"] == dict(rep["baseline"]["pixels"]) and r["pixels"]["scored"] == rep["pixels"]["scored"] > 0
+        assert r["holes"]["count"] == rep["holes"]["count"] == rep["baseline"]["holes"]["count"]
+        assert key(r) == key(rep) == key(rep["baseline"]) and r["by_depth"]["cap_m"] == 10.0
+        assert math.isfinite(r["height"]["rmse"]) and "by depth" in summary(r)
+    assert rep["compare"]["nearest"]["fill"]["by_nearest"] == rep["compare"]["nearest"]["fill"]["filled"]
