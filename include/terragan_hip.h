@@ -752,6 +752,38 @@ int tg_gather_fill(const float* z, const uint8_t* known, const int32_t* idx, int
  * rounded to fp32 once; known and NaN pixels are copied.  in and out are distinct. */
 int tg_void_smooth(const float* in, const uint8_t* known, int H, int W, float* out, tg_stream_t stream);
 
+/* ---- Depression filling (pit removal) (csrc/depfill.hip) ------------------------------------------------------
+ * Known pixels: known[p] != 0 (tg_objmask_known's map).  Connectivity conn = 8 or 4.  An outlet is a known pixel on the raster's
+ * edge or with an unknown conn-neighbour.  For a known pixel p, W(p) = min over conn-connected paths of known pixels from p to
+ * an outlet of the max of z along the path: exact (comparisons, fminf and fmaxf only), independent of the order of the sweeps.
+ * Sides as tg_objmask_known (H, W >= 1, H * W < 2^31).  One workspace ws >= tg_depfill_ws_bytes(H, W) serves all calls: 256
+ * control bytes, two dirty planes of one byte per 64x64 tile (each rounded up to 256 bytes), then 40 bytes per workgroup of the
+ * statistics, min(1024, ceil(H * W / 4096)) of them (rounded up to 256 bytes).  0 for sides out of range. */
+size_t tg_depfill_ws_bytes(int H, int W);
+/* w [H][W] = z at outlets, +inf at the other known pixels, NaN at unknown ones; every tile of ws is marked dirty. */
+int tg_depfill_init(const float* z, const uint8_t* known, int H, int W, int conn, float* w, void* ws, size_t ws_bytes,
+                    tg_stream_t stream);
+/* Enqueues n sweeps, 1 <= n <= 2^20, of w (after tg_depfill_init on the same z, known, conn, w and ws): every dirty tile is relaxed,
+ * W(p) <- max(z(p), min(W(p), min over the neighbours W)), to a fixed point against its one-pixel halo (or to a cap on the inner
+ * rounds; it stays dirty then); a tile is dirty in a sweep when it changed in the one before or a neighbour tile lowered a
+ * value on its rim.  changed [1] int32 (zeroed here): the workgroup visits of the LAST of the n sweeps that lowered a value; 0
+ * means w is the answer.  visits [1] int64 is added to (the caller zeroes it): tiles visited.  Every value of w is at all times
+ * an upper bound of the answer and the bits of some known z, or +inf (not reached yet).  The raster at the fixed point does not
+ * depend on the order of the visits; the number of sweeps to it may. */
+int tg_depfill_sweep(const float* z, const uint8_t* known, int H, int W, int conn, int n, float* w, int32_t* changed,
+                     int64_t* visits, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* Over the known pixels, with sel (uint8 [H][W], may be NULL) only those with sel != 0: counts [3] int64 = pixels with w > z,
+ * pixels with w == +inf (among the former), pixels counted; sums [2] double = the sum of (double)w - (double)z over the pixels
+ * with z < w < +inf, in a fixed order (per-workgroup partials, then one ordered pass: two calls agree bitwise), and the largest
+ * such difference (exact).  Uses only the statistics part of ws: the state of the sweeps is kept. */
+int tg_depfill_stats(const float* z, const float* w, const uint8_t* known, const uint8_t* sel, int H, int W, int64_t* counts,
+                     double* sums, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* out [H][W] = w where z < w < +inf, z's own bits where w <= z, NaN at unknown pixels and where w == +inf.  depth (may be
+ * NULL) = out - z in fp32: 0 where not raised, NaN where out is.  flags (uint8, may be NULL) = 1 on the known pixels with
+ * w > z, else 0 (tg_objmask_components' input). */
+int tg_depfill_finish(const float* z, const float* w, const uint8_t* known, int H, int W, float* out, float* depth,
+                      uint8_t* flags, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

@@ -38,11 +38,17 @@ With compare=("idw", "nearest") the same keep mask is also filled by interpolate
 DESIGN.md section 8t: the cheap end of the baseline ladder) and report["compare"][name] holds that fill's terrain_errors report
 on the same holes and depth classes, plus "method" and the fill info under "fill".  Without it the report has no "compare" key.
 
+With sinks=True the report also says whether a fill drains (sink_errors; mvp_gan/src/fill_depressions.py):
+the depressions of the truth and of the fill are filled over the same known pixels, and report["sinks"] = {"truth", "pred":
+{"cells", "volume_m3", "max_depth_m", "depressions", "converged"}, "excess_volume_m3", "excess_cells"} counts the closed pits
+inside the holes; report["baseline"] and every report["compare"][name] gain the same key for their fills.  Without it the report
+has no "sinks" key and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
-         [--by-depth [E ...]] [--compare idw nearest]
+         [--by-depth [E ...]] [--compare idw nearest] [--sinks]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -438,9 +444,9 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 
 @torch.no_grad()
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None):
+                    quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None, sinks=False):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
-    fill info under "fill"."""
+    fill info under "fill"; with sinks also sink_errors' dict under "sinks"."""
     from .fill_voids import fill_voids
     device = _device()
     z = _f32(dem, device, "dem")
@@ -450,6 +456,8 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
                          quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
     rep["method"] = method
     rep["fill"] = finfo
+    if sinks:
+        rep["sinks"] = sink_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata)
     return rep
 
 
@@ -471,55 +479,117 @@ def _check_compare(compare, who="evaluate_raster"):
     return names
 
 
-def assemble_compare(reports, infos):
-    """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name."""
+def assemble_compare(reports, infos, sinks=None):
+    """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name; with sinks
+    ({name: sink_errors' dict}) also "sinks"."""
     out = {}
     for name, rep in reports.items():
         out[name] = dict(rep)
         out[name]["method"] = name
         out[name]["fill"] = infos[name]
+        if sinks is not None:
+            out[name]["sinks"] = sinks[name]
     return out
 
 
 @torch.no_grad()
 def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
-                   quantiles=QUANTILES, top=10, depth_edges_m=None):
+                   quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False):
     """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
     from .interpolate import interpolate_voids
     device = _device()
     z = _f32(dem, device, "dem")
     k = _f32(keep, device, "keep", binary=True)
-    reports, infos = {}, {}
+    reports, infos, snk = {}, {}, {}
     for name in _check_compare(names):
         pred, infos[name] = interpolate_voids(z, k, nodata=_nodata(nodata), method=name, cellsize=cellsize)
         reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
                                        area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
-    return assemble_compare(reports, infos)
+        if sinks:
+            snk[name] = sink_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata)
+    return assemble_compare(reports, infos, snk if sinks else None)
+
+
+# ---- sinks: does a fill drain ---------------------------------------------------------------------------------------------
+def assemble_sinks(truth, pred):
+    """The sinks dict from two sides' raw numbers, each {"counts": tg_depfill_stats' [raised, unreached, counted], "sums":
+    [depth sum in m, largest depth in m], "depressions", "converged", "cellsize"} (pure: no GPU)."""
+    from .fill_depressions import stats_dict
+
+    def side(r):
+        st = stats_dict(r["counts"], r["sums"], float(r["cellsize"]))
+        return {"cells": st["cells"], "volume_m3": st["volume_m3"], "max_depth_m": st["max_depth_m"],
+                "depressions": int(r["depressions"]), "converged": bool(r["converged"])}
+    t, p = side(truth), side(pred)
+    return {"truth": t, "pred": p, "excess_volume_m3": p["volume_m3"] - t["volume_m3"], "excess_cells": p["cells"] - t["cells"]}
+
+
+@torch.no_grad()
+def sink_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, connectivity=8):
+    """The closed pits a fill put into the holes, against those the true terrain has there.  The depressions of dem and of
+    pred are filled (fill_depressions' iteration) over one known mask, the pixels known in both, so both have the same outlets;
+    the raised pixels are counted inside holes (nonzero = hole).  -> {"truth": {...}, "pred": {...}, "excess_volume_m3",
+    "excess_cells"}; a side holds cells (raised pixels in the holes), volume_m3, max_depth_m, depressions (8-connected
+    components of the raised pixels in the holes) and converged."""
+    from tg_hip import ops as O
+    from .fill_depressions import CONNECTIVITIES, count_depressions, relax
+    who = "sink_errors"
+    c = _cellsize(cellsize, who)
+    _inputs(dem, mask, who)
+    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
+        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES:
+        raise ValueError(f"{who}: connectivity {connectivity!r} must be 8 or 4")
+    device = _device()
+    z = _f32(dem, device, "dem")
+    p = _f32(pred, device, "pred")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    sel = _u8(holes, device)
+    nd = _nodata(nodata)
+    kz, _ = O.objmask_known(z, m, nd, transposed=False)
+    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
+    known = kz & kp
+    raw = []
+    for surf in (z, p):
+        w, _, _, _, converged = relax(surf, known, connectivity)
+        counts, sums = O.depfill_stats(surf, w, known, sel)
+        _, _, flags = O.depfill_finish(surf, w, known, want_flags=True)
+        raw.append({"counts": counts.cpu().tolist(), "sums": sums.cpu().tolist(), "converged": converged, "cellsize": c,
+                    "depressions": count_depressions(flags & (sel != 0))})
+    return assemble_sinks(*raw)
+
+
+def sinks_summary(s):
+    """One line for a sinks dict."""
+    return (f"sinks: {s['pred']['cells']} px / {s['pred']['volume_m3']:.6g} m3 in {s['pred']['depressions']} pits (truth "
+            f"{s['truth']['cells']} px / {s['truth']['volume_m3']:.6g} m3 in {s['truth']['depressions']}), excess "
+            f"{s['excess_volume_m3']:.6g} m3")
 
 
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
-                    solver="mg", depth_edges_m=None, compare=None):
+                    solver="mg", depth_edges_m=None, compare=None, sinks=False):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
     checkpoint whose training blocks were picked on the working grid), and seam="harmonic" adds report["seam"].  solver is the
     fill_voids solver of the baseline, the seam correction and the fallback ("mg" or "pcg"); "pcg" shows in their infos.
     depth_edges_m adds "by_depth" to the report and, on the same classes, to report["baseline"].  compare: names out of COMPARES,
-    adds report["compare"][name], the interpolate_voids fill of the same keep mask scored on the same holes and classes."""
+    adds report["compare"][name], the interpolate_voids fill of the same keep mask scored on the same holes and classes.
+    sinks=True adds sink_errors' dict under "sinks" to the report, to report["baseline"] and to every report["compare"][name]."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
                              seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
-                             depth_edges_m=depth_edges_m, compare=compare)
+                             depth_edges_m=depth_edges_m, compare=compare, sinks=sinks)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
-              min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None):
+              min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
@@ -552,13 +622,15 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     rep["inpaint"] = iinfo
     if sinfo is not None:
         rep["seam"] = sinfo
+    if sinks:
+        rep["sinks"] = sink_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata)
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
-                                          depth_edges_m=depth_edges_m)
+                                          depth_edges_m=depth_edges_m, sinks=bool(sinks))
     if compare:
         rep["compare"] = compare_report(z, hm, keep, compare, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
-                                        quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
+                                        quantiles=quantiles, top=top, depth_edges_m=depth_edges_m, sinks=bool(sinks))
     return rep, pred, hm
 
 
@@ -623,6 +695,9 @@ def build_parser():
     ap.add_argument("--compare", nargs="+", choices=COMPARES, metavar="NAME",
                     help="also score these interpolate_voids fills of the same holes (" + ", ".join(COMPARES) + "): one more "
                          "summary line each")
+    ap.add_argument("--sinks", action="store_true",
+                    help="also fill the depressions of the truth and of every scored fill and report the closed pits each fill "
+                         "put into the holes (cells, volume, count): one more summary line per fill")
     return ap
 
 
@@ -654,7 +729,7 @@ def main(argv=None):
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
                                   min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges,
-                                  compare=a.compare)
+                                  compare=a.compare, sinks=a.sinks)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -665,12 +740,14 @@ def main(argv=None):
         hm, keep, _ = holes_from_map(dem, _read_mask(a.holes, dem.shape), mask, nodata=nodata, objects=objects, cellsize=c)
         rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata, depth_edges_m=depth_edges)
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
+        if a.sinks:
+            rep["sinks"] = sink_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata)
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
-                                              solver=a.solver, depth_edges_m=depth_edges)
+                                              solver=a.solver, depth_edges_m=depth_edges, sinks=a.sinks)
         if a.compare:
             rep["compare"] = compare_report(dem, hm, keep, a.compare, cellsize=c, mask=mask, nodata=nodata,
-                                            depth_edges_m=depth_edges)
+                                            depth_edges_m=depth_edges, sinks=a.sinks)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -683,6 +760,8 @@ def main(argv=None):
     if a.holes_out and hm is not None:
         write_mask(a.holes_out, hm.cpu().numpy(), header)
     print(summary(rep))
+    if "sinks" in rep:
+        print(sinks_summary(rep["sinks"]))
     if "seam" in rep:
         sm = rep["seam"]
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
@@ -690,8 +769,12 @@ def main(argv=None):
     if "baseline" in rep:
         how = "" if a.solver == "mg" else f" (solver {a.solver})"
         print(f"baseline {rep['baseline']['method']}{how}: {summary(rep['baseline'])}")
+        if "sinks" in rep["baseline"]:
+            print(f"baseline {rep['baseline']['method']} {sinks_summary(rep['baseline']['sinks'])}")
     for name, r in rep.get("compare", {}).items():
         print(f"compare {name}: {summary(r)}")
+        if "sinks" in r:
+            print(f"compare {name} {sinks_summary(r['sinks'])}")
     return rep
 
 

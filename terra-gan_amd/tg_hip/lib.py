@@ -185,6 +185,11 @@ SIGNATURES = {
     "tg_rayfill": (I, [P, P, I, I, C.c_int32, D, P, P, P, P, P, P, SZ, P]),
     "tg_gather_fill": (I, [P, P, P, I, I, P, P, P]),
     "tg_void_smooth": (I, [P, P, I, I, P, P]),
+    "tg_depfill_ws_bytes": (SZ, [I, I]),
+    "tg_depfill_init": (I, [P, P, I, I, I, P, P, SZ, P]),
+    "tg_depfill_sweep": (I, [P, P, I, I, I, I, P, P, P, P, SZ, P]),
+    "tg_depfill_stats": (I, [P, P, P, P, I, I, P, P, P, SZ, P]),
+    "tg_depfill_finish": (I, [P, P, P, I, I, P, P, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -1326,6 +1326,88 @@ def void_smooth(x, known, steps=1):
     return a
 
 
+DEPFILL_CONNS = (8, 4)
+
+
+def _depfill_in(z, known, w, conn, who):
+    H, W = _raster_hw(z, "z")
+    _hip(z, torch.float32, (H, W), "z")
+    _hip(known, torch.uint8, (H, W), "known")
+    if w is not None:
+        _hip(w, torch.float32, (H, W), "w")
+        if w.data_ptr() == z.data_ptr():
+            raise L.TgError(f"{who}: w must not alias z")
+    if conn is not None and (isinstance(conn, bool) or conn not in DEPFILL_CONNS):
+        raise L.TgError(f"{who}: connectivity {conn!r} must be 8 or 4")
+    return H, W
+
+
+def depfill_ws(H, W, device):
+    """The workspace of one depression fill: uint8 [tg_depfill_ws_bytes]; it carries the dirty tiles from depfill_init through
+    the depfill_sweep calls, so it is the caller's and not the shared one."""
+    n = _lib().tg_depfill_ws_bytes(int(H), int(W))
+    if n == 0:
+        raise L.TgError(f"depfill: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _depfill_ws_chk(ws, H, W):
+    need = _lib().tg_depfill_ws_bytes(H, W)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need):
+        raise L.TgError(f"depfill: ws must be a contiguous uint8 HIP tensor of at least {need} bytes (depfill_ws)")
+
+
+def depfill_init(z, known, conn, ws):
+    """-> w float32 [H][W]: z at the outlets (known pixels on the edge or with an unknown conn-neighbour), +inf at the other
+    known pixels, NaN at unknown ones; every tile of ws dirty (tg_depfill_init)."""
+    H, W = _depfill_in(z, known, None, conn, "depfill_init")
+    _depfill_ws_chk(ws, H, W)
+    w = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    L.check(_lib().tg_depfill_init(_p(z), _p(known), H, W, int(conn), _p(w), _p(ws), ws.numel(), _stream()), "tg_depfill_init")
+    return w
+
+
+def depfill_sweep(z, known, conn, n, w, changed, visits, ws):
+    """n >= 1 sweeps of w in place; changed int32 [1] = visits of the last sweep that lowered a value (0: a fixed point);
+    visits int64 [1] is added to (tg_depfill_sweep)."""
+    H, W = _depfill_in(z, known, w, conn, "depfill_sweep")
+    _depfill_ws_chk(ws, H, W)
+    _hip(changed, torch.int32, (1,), "changed")
+    _hip(visits, torch.int64, (1,), "visits")
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
+        raise L.TgError(f"depfill_sweep: n {n!r} must be an integer in [1, 2^20]")
+    L.check(_lib().tg_depfill_sweep(_p(z), _p(known), H, W, int(conn), n, _p(w), _p(changed), _p(visits), _p(ws), ws.numel(),
+                                    _stream()), "tg_depfill_sweep")
+
+
+def depfill_stats(z, w, known, sel=None):
+    """-> (counts int64 [3]: pixels with w > z, of those still +inf, pixels counted; sums float64 [2]: the depth sum over the
+    raised finite pixels in a fixed order, the largest depth) over the known pixels, with sel (uint8 [H][W]) those with
+    sel != 0 (tg_depfill_stats)."""
+    H, W = _depfill_in(z, known, w, None, "depfill_stats")
+    if sel is not None:
+        _hip(sel, torch.uint8, (H, W), "sel")
+    counts = torch.empty(3, dtype=torch.int64, device=z.device)
+    sums = torch.empty(2, dtype=torch.float64, device=z.device)
+    lib = _lib()
+    ws = workspace(lib.tg_depfill_ws_bytes(H, W))
+    L.check(lib.tg_depfill_stats(_p(z), _p(w), _p(known), _p(sel), H, W, _p(counts), _p(sums), _p(ws), ws.numel() * 4, _stream()),
+            "tg_depfill_stats")
+    return counts, sums
+
+
+def depfill_finish(z, w, known, want_depth=False, want_flags=False):
+    """-> (out float32 [H][W]: w where raised, z's bits elsewhere, NaN at unknown and unreached pixels; depth float32 or None:
+    out - z; flags uint8 or None: 1 where w > z) (tg_depfill_finish)."""
+    H, W = _depfill_in(z, known, w, None, "depfill_finish")
+    out = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    depth = torch.empty(H, W, dtype=torch.float32, device=z.device) if want_depth else None
+    flags = torch.empty(H, W, dtype=torch.uint8, device=z.device) if want_flags else None
+    L.check(_lib().tg_depfill_finish(_p(z), _p(w), _p(known), H, W, _p(out), _p(depth), _p(flags), _stream()),
+            "tg_depfill_finish")
+    return out, depth, flags
+
+
 VFILL_NSTATS = 4                                 # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
