@@ -784,6 +784,51 @@ int tg_depfill_stats(const float* z, const float* w, const uint8_t* known, const
 int tg_depfill_finish(const float* z, const float* w, const uint8_t* known, int H, int W, float* out, float* depth,
                       uint8_t* flags, tg_stream_t stream);
 
+/* ---- D8 flow directions, flat resolution, flow accumulation (csrc/flow.hip) -----------------------------------
+ * Known pixels: known[p] != 0 (tg_objmask_known's map); w [H][W] is any fp32 surface, usually tg_depfill_finish's out at
+ * connectivity 8.  Sides as tg_objmask_known (H, W >= 1, H * W < 2^31).  A direction code is one uint8: 0 unknown; 1..8 the
+ * receiver E, SE, S, SW, W, NW, N, NE (the ESRI code is 1 << (code - 1)); TG_FLOW_OUT, an outlet that drains off the raster or
+ * into a void; TG_FLOW_PIT, no receiver; TG_FLOW_UNDECIDED only between tg_flow_slope and tg_flow_flat_dir.  Equal candidates
+ * are taken in the order of preference E, S, W, N, SE, SW, NW, NE.  An outlet is a known pixel on the raster's edge or with an
+ * unknown 8-neighbour.
+ * One workspace ws >= tg_flow_ws_bytes(H, W) serves all calls: 256 control bytes, two dirty planes of one byte per 64x64 tile
+ * (each rounded up to 256 bytes), then four int32 planes of H * W words (each rounded up to 256 bytes): the pointers and the sums
+ * of the accumulation, both double-buffered, 16 bytes per pixel.  0 for sides out of range. */
+#define TG_FLOW_OUT 9
+#define TG_FLOW_UNDECIDED 254
+#define TG_FLOW_PIT 255
+#define TG_FLOW_FAR 0x7fffffff
+#define TG_FLOW_MAX_ROUNDS 32
+size_t tg_flow_ws_bytes(int H, int W);
+/* The slope step.  For a known pixel p and a known 8-neighbour n: d = w(p) - w(n) in fp32, s = d for a cardinal n and
+ * d * 0x1.6a09e6p-1f (one fp32 multiply, nothing fused) for a diagonal one.  If some s > 0, dir(p) is the neighbour with the
+ * largest s; otherwise TG_FLOW_OUT if p is an outlet, else TG_FLOW_UNDECIDED.  D [H][W] int32 = 0 where decided, TG_FLOW_FAR
+ * where undecided, -1 at unknown pixels.  counts [2] int64 (zeroed here) = known pixels, outlets.  Every tile of ws is marked
+ * dirty and its sweep counter zeroed. */
+int tg_flow_slope(const float* w, const uint8_t* known, int H, int W, uint8_t* dir, int32_t* D, int64_t* counts, void* ws,
+                  size_t ws_bytes, tg_stream_t stream);
+/* Enqueues n sweeps, 1 <= n <= 2^20, of D (after tg_flow_slope on the same w, D and ws): every dirty tile is relaxed,
+ * D(p) <- min(D(p), 1 + min over the known 8-neighbours n with w(n) == w(p) of D(n)), to a fixed point against its one-pixel halo
+ * (or to a cap on the inner rounds; it stays dirty then).  The fixed point is, for an undecided pixel, the smallest number of
+ * 8-connected steps through pixels of its own height to a decided pixel of that height, TG_FLOW_FAR if there is none.  changed,
+ * visits and the dirty tiles as tg_depfill_sweep.  Every value of D is at all times the length of such a path or TG_FLOW_FAR;
+ * the plane at the fixed point does not depend on the order of the visits. */
+int tg_flow_flat_sweep(const float* w, int H, int W, int n, int32_t* D, int32_t* changed, int64_t* visits, void* ws,
+                       size_t ws_bytes, tg_stream_t stream);
+/* Every TG_FLOW_UNDECIDED pixel of dir gets its code: with 0 < D(p) < TG_FLOW_FAR the known neighbour n with w(n) == w(p) and the
+ * smallest D(n) < D(p) (at the fixed point of the sweeps that is D(p) - 1), else TG_FLOW_PIT.  counts [2] int64 (zeroed here) =
+ * pixels that got a flat code, pits.  Along every edge (w, D) decreases lexicographically, converged or not: a forest. */
+int tg_flow_flat_dir(const float* w, const int32_t* D, int H, int W, uint8_t* dir, int64_t* counts, tg_stream_t stream);
+/* Flow accumulation A(p) = 1 + sum of A(q) over the pixels q whose receiver is p, int32, 0 at unknown pixels, by pointer
+ * doubling in ws.  _init: next(p) = the receiver's linear index (-1 for every other code), S = 1 on the pixels with dir != 0.
+ * tg_flow_accum enqueues rounds k0 .. k0 + n - 1 (k0 = the rounds enqueued before, k0 + n <= TG_FLOW_MAX_ROUNDS): in round k
+ * every pixel adds its S to itself and to S[next(p)] in the other plane by integer atomics (exact in any order) and takes
+ * next(next(p)); a round that finds no pointer left does nothing.  state [2] int32 = pointers left after these rounds (0: done),
+ * rounds that ran.  _finish(rounds = state[1]) copies the sums to acc [H][W] and writes their maximum to amax [1]. */
+int tg_flow_accum_init(const uint8_t* dir, int H, int W, void* ws, size_t ws_bytes, tg_stream_t stream);
+int tg_flow_accum(int H, int W, int k0, int n, int32_t* state, void* ws, size_t ws_bytes, tg_stream_t stream);
+int tg_flow_accum_finish(int H, int W, int rounds, int32_t* acc, int32_t* amax, void* ws, size_t ws_bytes, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

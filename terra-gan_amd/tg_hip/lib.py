@@ -54,6 +54,9 @@ class TgDepthClasses(C.Structure):
     _fields_ = [("n_edges", C.c_int32), ("_pad", C.c_int32), ("d2", C.c_int32 * (TG_DEPTH_MAX_CLASSES - 1))]
 
 
+TG_FLOW_OUT, TG_FLOW_UNDECIDED, TG_FLOW_PIT, TG_FLOW_FAR, TG_FLOW_MAX_ROUNDS = 9, 254, 255, 0x7fffffff, 32
+
+
 class TgError(RuntimeError):
     pass
 
@@ -190,6 +193,13 @@ SIGNATURES = {
     "tg_depfill_sweep": (I, [P, P, I, I, I, I, P, P, P, P, SZ, P]),
     "tg_depfill_stats": (I, [P, P, P, P, I, I, P, P, P, SZ, P]),
     "tg_depfill_finish": (I, [P, P, P, I, I, P, P, P, P]),
+    "tg_flow_ws_bytes": (SZ, [I, I]),
+    "tg_flow_slope": (I, [P, P, I, I, P, P, P, P, SZ, P]),
+    "tg_flow_flat_sweep": (I, [P, I, I, I, P, P, P, P, SZ, P]),
+    "tg_flow_flat_dir": (I, [P, P, I, I, P, P, P]),
+    "tg_flow_accum_init": (I, [P, I, I, P, SZ, P]),
+    "tg_flow_accum": (I, [I, I, I, I, P, P, SZ, P]),
+    "tg_flow_accum_finish": (I, [I, I, I, P, P, P, SZ, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -1408,6 +1408,96 @@ def depfill_finish(z, w, known, want_depth=False, want_flags=False):
     return out, depth, flags
 
 
+def flow_ws(H, W, device):
+    """The workspace of one flow routing: uint8 [tg_flow_ws_bytes]; it carries the dirty tiles of the flat sweeps and the planes
+    of the accumulation from call to call, so it is the caller's and not the shared one."""
+    n = _lib().tg_flow_ws_bytes(int(H), int(W))
+    if n == 0:
+        raise L.TgError(f"flow: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _flow_ws_chk(ws, H, W):
+    need = _lib().tg_flow_ws_bytes(H, W)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need):
+        raise L.TgError(f"flow: ws must be a contiguous uint8 HIP tensor of at least {need} bytes (flow_ws)")
+
+
+def _flow_count(v, lo, hi, name, who):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise L.TgError(f"{who}: {name} {v!r} must be an integer in [{lo}, {hi}]")
+    return v
+
+
+def flow_slope(w, known, ws):
+    """-> (dir uint8 [H][W]: 1..8 towards the steepest positive drop, TG_FLOW_OUT, TG_FLOW_UNDECIDED, 0 at unknown pixels;
+    D int32 [H][W]: 0 decided, TG_FLOW_FAR undecided, -1 unknown; counts int64 [2]: known pixels, outlets); every tile of ws dirty
+    (tg_flow_slope)."""
+    H, W = _raster_hw(w, "w")
+    _hip(w, torch.float32, (H, W), "w")
+    _hip(known, torch.uint8, (H, W), "known")
+    _flow_ws_chk(ws, H, W)
+    d = torch.empty(H, W, dtype=torch.uint8, device=w.device)
+    D = torch.empty(H, W, dtype=torch.int32, device=w.device)
+    counts = torch.empty(2, dtype=torch.int64, device=w.device)
+    L.check(_lib().tg_flow_slope(_p(w), _p(known), H, W, _p(d), _p(D), _p(counts), _p(ws), ws.numel(), _stream()), "tg_flow_slope")
+    return d, D, counts
+
+
+def flow_flat_sweep(w, n, D, changed, visits, ws):
+    """n >= 1 sweeps of D in place; changed int32 [1] = visits of the last sweep that lowered a value (0: a fixed point);
+    visits int64 [1] is added to (tg_flow_flat_sweep)."""
+    H, W = _raster_hw(w, "w")
+    _hip(w, torch.float32, (H, W), "w")
+    _hip(D, torch.int32, (H, W), "D")
+    _flow_ws_chk(ws, H, W)
+    _hip(changed, torch.int32, (1,), "changed")
+    _hip(visits, torch.int64, (1,), "visits")
+    _flow_count(n, 1, 1 << 20, "n", "flow_flat_sweep")
+    L.check(_lib().tg_flow_flat_sweep(_p(w), H, W, n, _p(D), _p(changed), _p(visits), _p(ws), ws.numel(), _stream()),
+            "tg_flow_flat_sweep")
+
+
+def flow_flat_dir(w, D, d):
+    """The undecided pixels of d (uint8 [H][W], in place) get their flat code or TG_FLOW_PIT from D -> counts int64 [2]: flat
+    pixels, pits (tg_flow_flat_dir)."""
+    H, W = _raster_hw(w, "w")
+    _hip(w, torch.float32, (H, W), "w")
+    _hip(D, torch.int32, (H, W), "D")
+    _hip(d, torch.uint8, (H, W), "dir")
+    counts = torch.empty(2, dtype=torch.int64, device=w.device)
+    L.check(_lib().tg_flow_flat_dir(_p(w), _p(D), H, W, _p(d), _p(counts), _stream()), "tg_flow_flat_dir")
+    return counts
+
+
+def flow_accum_init(d, ws):
+    """The pointers and unit sums of the accumulation from the codes d (uint8 [H][W]) into ws (tg_flow_accum_init)."""
+    H, W = _raster_hw(d, "dir")
+    _hip(d, torch.uint8, (H, W), "dir")
+    _flow_ws_chk(ws, H, W)
+    L.check(_lib().tg_flow_accum_init(_p(d), H, W, _p(ws), ws.numel(), _stream()), "tg_flow_accum_init")
+
+
+def flow_accum(H, W, k0, n, state, ws):
+    """Rounds k0 .. k0 + n - 1 of the pointer doubling; state int32 [2] = pointers left, rounds that ran (tg_flow_accum)."""
+    _flow_ws_chk(ws, int(H), int(W))
+    _hip(state, torch.int32, (2,), "state")
+    _flow_count(k0, 0, L.TG_FLOW_MAX_ROUNDS, "k0", "flow_accum")
+    _flow_count(n, 1, L.TG_FLOW_MAX_ROUNDS - k0, "n", "flow_accum")
+    L.check(_lib().tg_flow_accum(int(H), int(W), k0, n, _p(state), _p(ws), ws.numel(), _stream()), "tg_flow_accum")
+
+
+def flow_accum_finish(H, W, rounds, ws):
+    """-> (acc int32 [H][W], amax int32 [1]) after `rounds` rounds (tg_flow_accum_finish)."""
+    _flow_ws_chk(ws, int(H), int(W))
+    _flow_count(rounds, 0, L.TG_FLOW_MAX_ROUNDS, "rounds", "flow_accum_finish")
+    acc = torch.empty(int(H), int(W), dtype=torch.int32, device=ws.device)
+    amax = torch.empty(1, dtype=torch.int32, device=ws.device)
+    L.check(_lib().tg_flow_accum_finish(int(H), int(W), rounds, _p(acc), _p(amax), _p(ws), ws.numel(), _stream()),
+            "tg_flow_accum_finish")
+    return acc, amax
+
+
 VFILL_NSTATS = 4                                 # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 

@@ -1,0 +1,356 @@
+"""CPU checks of the flow routing (csrc/flow.hip, mvp_gan/src/flow_routing.py): the two forms of D and of
+the accumulation in tests/flow_oracle.py against each other and against the defining properties, the conditions the GPU scenes
+must meet, host-side rejection by the seven C entry points, the ops and the Python API, the workspace query, the CLI parser,
+to_esri and streams, all without a GPU.  Every comparison is exact."""
+import ctypes as C
+import inspect
+import math
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import depfill_oracle as DO
+from tests import flow_oracle as FO
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("tg_flow_ws_bytes", "tg_flow_slope", "tg_flow_flat_sweep", "tg_flow_flat_dir", "tg_flow_accum_init", "tg_flow_accum",
+         "tg_flow_accum_finish")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def contract():
+    """The oracle implements what include/terragan_hip.h states."""
+    txt = " ".join(open(os.path.join(ROOT, "include", "terragan_hip.h")).read().replace("* ", "").split())
+    for name in NAMES:
+        assert name + "(" in txt, name
+    assert "An outlet is a known pixel on the raster's edge or with an unknown 8-neighbour" in txt
+    assert "in the order of preference E, S, W, N, SE, SW, NW, NE" in txt
+    assert "0x1.6a09e6p-1f (one fp32 multiply, nothing fused)" in txt
+    for name, v in (("TG_FLOW_OUT", FO.OUT), ("TG_FLOW_UNDECIDED", FO.UNDECIDED), ("TG_FLOW_PIT", FO.PIT),
+                    ("TG_FLOW_FAR", "0x7fffffff"), ("TG_FLOW_MAX_ROUNDS", 32)):
+        assert f"#define {name} {v} " in txt, name
+    return txt
+
+
+def _rasters():
+    """40 rasters up to 30x30, integer-rounded heights (plateaus and ties), voids at 0 and 5 %, and one with real heights."""
+    rng = np.random.default_rng(43)
+    out = []
+    for i in range(40):
+        H, W = (int(v) for v in rng.integers(1, 31, 2))
+        z = np.rint(1000 + rng.normal(0, 1.5 if i % 4 < 2 else 3, (H, W))).astype(np.float32)
+        if i % 2:
+            z[rng.random((H, W)) < 0.05] = np.nan
+        out.append(z)
+    out.append((1000 + rng.normal(0, 3, (30, 30))).astype(np.float32))
+    return out
+
+
+def _edges_decrease(r):
+    """Along every edge (w, D) decreases lexicographically; receivers are known pixels inside the raster."""
+    code, w, D = r["dir"], r["w"], r["D"]
+    H, W = code.shape
+    for c in range(1, 9):
+        ys, xs = np.nonzero(code == c)
+        yy, xx = ys + FO.DY[c - 1], xs + FO.DX[c - 1]
+        assert ((yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)).all()
+        assert r["known"][yy, xx].all()
+        lower = w[yy, xx] < w[ys, xs]
+        flat = (w[yy, xx] == w[ys, xs]) & (D[yy, xx] == D[ys, xs] - 1)
+        assert (lower | flat).all() and (D[ys, xs][lower] == 0).all()
+
+
+def test_two_forms_of_distance_and_accumulation_agree():
+    n = plateaus = 0
+    for z in _rasters():
+        known = DO.known_map(z)
+        for fill in (False, True):
+            r = FO.route(z, fill=fill)
+            code0, D0 = FO.slope_step(r["w"], known)
+            D2, _ = FO.flat_distance_relax(r["w"], D0)
+            np.testing.assert_array_equal(r["D"], D2)
+            a2, rounds = FO.accumulate_doubling(r["dir"])
+            np.testing.assert_array_equal(r["acc"], a2)
+            assert rounds == r["rounds"]
+            np.testing.assert_array_equal(FO.flat_dirs(r["w"], code0, r["D"], exact=False), r["dir"])   # the same thing at the fixed point
+            _edges_decrease(r)
+            roots = (r["dir"] == FO.OUT) | (r["dir"] == FO.PIT)
+            assert int(r["acc"][roots].sum()) == int(known.sum())
+            assert (r["acc"][~known] == 0).all() and (r["dir"][~known] == 0).all() and (r["D"][~known] == -1).all()
+            assert (r["acc"][known] >= 1).all() and not (r["dir"] == FO.UNDECIDED).any()
+            assert r["flat_cells"] + r["pits"] == int((code0 == FO.UNDECIDED).sum())
+            if fill:
+                assert r["pits"] == 0                                    # the drainage argument of DESIGN 8v
+            plateaus += r["flat_cells"]
+            n += 1
+    assert n >= 80 and plateaus > 500
+
+
+def test_hand_made_cases():
+    # equal slopes: the order of preference decides
+    z = np.full((3, 3), 1010.0, np.float32)
+    z[1, 2] = 1009.0                                                     # E of the centre: s = 1
+    z[1, 0] = 1009.0                                                     # W: s = 1 as well: E comes first
+    r = FO.route(z, fill=False)
+    assert r["dir"][1, 1] == 1
+    z = np.full((3, 3), 1010.0, np.float32)
+    z[2, 1] = 1009.0                                                     # S and N tie: S
+    z[0, 1] = 1009.0
+    assert FO.route(z, fill=False)["dir"][1, 1] == 3
+    # a cardinal and a diagonal with the same fp32 slope: d = 1 against d' with d' * c == 1 in float32
+    c = FO.DIAG
+    d = np.float32(1.0)
+    dd = np.float32(1.0) / c
+    cand = [np.nextafter(dd, np.float32(0)), dd, np.nextafter(dd, np.float32(2))]
+    dd = [v for v in cand if np.float32(v * c) == d]
+    assert dd, "no fp32 drop whose diagonal slope is exactly 1"
+    z = np.full((3, 3), 8.0, np.float32)
+    z[1, 1] = 4.0
+    z[0, 1] = np.float32(4.0) - d                                        # N, cardinal
+    z[2, 2] = np.float32(4.0) - dd[0]                                    # SE, diagonal, first in the order of codes
+    assert np.float32(np.float32(z[1, 1] - z[2, 2]) * c) == np.float32(z[1, 1] - z[0, 1])
+    assert FO.route(z, fill=False)["dir"][1, 1] == 7                     # the cardinal wins the tie
+    # the 3x3 pit
+    pit = np.array([[1003, 1002, 1004], [1001, 990, 1005], [1006, 1002.5, 1007]], np.float32)
+    r = FO.route(pit, fill=False)
+    assert int((r["dir"] == FO.PIT).sum()) == 1 and r["dir"][1, 1] == FO.PIT and r["acc"][1, 1] == 9 and r["pits"] == 1
+    assert r["D"][1, 1] == FO.FAR
+    r = FO.route(pit, fill=True)
+    assert r["pits"] == 0 and r["dir"][1, 1] == 5 and r["D"][1, 1] == 1  # filled to 1001: a flat with its spill, W of it
+    # a constant raster: every edge pixel OUT, D = the Chebyshev distance to the edge
+    flat = np.full((7, 9), 1000.5, np.float32)
+    r = FO.route(flat, fill=True)
+    y, x = np.mgrid[0:7, 0:9]
+    np.testing.assert_array_equal(r["D"], np.minimum(np.minimum(y, 6 - y), np.minimum(x, 8 - x)))
+    assert (r["dir"][r["D"] == 0] == FO.OUT).all() and r["pits"] == 0 and r["flat_cells"] == 5 * 7
+    assert r["dir"][3, 1] == 5 and r["dir"][1, 4] == 7 and r["dir"][3, 4] == 3    # W; N; the centre: S before N
+    # a void inside is an outlet
+    flat[3, 4] = np.nan
+    r = FO.route(flat, fill=False)
+    assert r["dir"][3, 4] == 0 and r["dir"][3, 3] == FO.OUT and r["acc"][3, 4] == 0 and r["outlets"] == 28 + 8
+
+
+def test_scene_conditions():
+    z, order = FO.serpentine()
+    r = FO.route(z, fill=False)
+    assert z.shape == (130, 130) and r["longest"] > 4096 and r["rounds"] >= 13 and r["pits"] == 0
+    on = order >= 0
+    assert (np.diff(z[on][np.argsort(order[on])]) < 0).all()             # strictly descending along the channel
+    mouth = np.unravel_index(np.argmax(order), order.shape)
+    assert r["dir"][mouth] == FO.OUT and r["acc"][mouth] > 16000         # nearly everything leaves through the mouth
+    z, channel = FO.spiral_flat()
+    r = FO.route(z, fill=False)
+    assert z.shape == (130, 130) and (z[channel] == 1000).all() and r["pits"] == 0
+    assert r["D"][channel].max() > 4096 and (r["D"][channel] < FO.FAR).all()
+    z, lake = FO.lake_scene()
+    r = FO.route(z, fill=False)
+    assert r["pits"] == 0 and r["flat_cells"] == int(lake.sum()) and r["dir"][64, 64] == 1
+    assert r["acc"][64, 64] >= int(lake.sum()) + 1 and (r["D"][lake] >= 1).all() and r["D"][63, 63] == 1
+
+
+# ---- host-side rejection ---------------------------------------------------------------------------------------------------
+def _lib():
+    import __graft_entry__ as ge
+    ge.build()
+    from tg_hip import lib as L
+    return L, L.load()
+
+
+def test_c_entry_points_reject_without_gpu():
+    L, lib = _lib()
+    f = [C.c_void_p(0x1000 * (i + 1)) for i in range(12)]
+    big = 1 << 40
+
+    def err(rc, msg):
+        assert rc == -1 and msg in lib.tg_last_error(), (rc, lib.tg_last_error())
+
+    slope = lambda H, W, w=f[0], kn=f[1], d=f[2], D=f[3], cnt=f[4], ws=f[5], nb=big: \
+        lib.tg_flow_slope(w, kn, H, W, d, D, cnt, ws, nb, None)
+    sweep = lambda H, W, w=f[0], n=1, D=f[3], ch=f[6], vis=f[7], ws=f[5], nb=big: \
+        lib.tg_flow_flat_sweep(w, H, W, n, D, ch, vis, ws, nb, None)
+    fdir = lambda H, W, w=f[0], D=f[3], d=f[2], cnt=f[4]: lib.tg_flow_flat_dir(w, D, H, W, d, cnt, None)
+    ainit = lambda H, W, d=f[2], ws=f[5], nb=big: lib.tg_flow_accum_init(d, H, W, ws, nb, None)
+    acc = lambda H, W, k0=0, n=1, st=f[8], ws=f[5], nb=big: lib.tg_flow_accum(H, W, k0, n, st, ws, nb, None)
+    fin = lambda H, W, rounds=0, a=f[9], mx=f[10], ws=f[5], nb=big: lib.tg_flow_accum_finish(H, W, rounds, a, mx, ws, nb, None)
+    for H, W in ((0, 5), (5, 0), (-1, 5), (5, -1), (1 << 16, 1 << 15), (1 << 30, 2)):
+        for call in (slope, sweep, fdir, ainit, acc, fin):
+            err(call(H, W), b"must be non-empty with H*W < 2^31")
+        assert lib.tg_flow_ws_bytes(H, W) == 0
+    for kw in ({"w": None}, {"kn": None}, {"d": None}, {"D": None}, {"cnt": None}, {"ws": None}):
+        err(slope(8, 8, **kw), b"null pointer")
+    for kw in ({"w": None}, {"D": None}, {"ch": None}, {"vis": None}, {"ws": None}):
+        err(sweep(8, 8, **kw), b"null pointer")
+    for kw in ({"w": None}, {"D": None}, {"d": None}, {"cnt": None}):
+        err(fdir(8, 8, **kw), b"null pointer")
+    for kw in ({"d": None}, {"ws": None}):
+        err(ainit(8, 8, **kw), b"null pointer")
+    for kw in ({"st": None}, {"ws": None}):
+        err(acc(8, 8, **kw), b"null pointer")
+    for kw in ({"a": None}, {"mx": None}, {"ws": None}):
+        err(fin(8, 8, **kw), b"null pointer")
+    err(slope(8, 8, d=f[1]), b"alias")
+    err(slope(8, 8, D=f[0]), b"alias")
+    err(sweep(8, 8, D=f[0]), b"alias")
+    for n in (0, -1, (1 << 20) + 1):
+        err(sweep(8, 8, n=n), b"sweeps")
+    for k0, n in ((-1, 1), (0, 0), (0, 33), (32, 1), (20, 13), (33, 1), (0, -1)):
+        err(acc(8, 8, k0=k0, n=n), b"rounds")
+    for rounds in (-1, 33):
+        err(fin(8, 8, rounds=rounds), b"rounds")
+    for H, W in ((8, 8), (129, 4097), (32767, 32767)):
+        short = lib.tg_flow_ws_bytes(H, W) - 1
+        for call in (slope, sweep, ainit, acc, fin):
+            err(call(H, W, nb=short), b"workspace")
+
+
+def test_ws_query_covers_the_layout_and_grows():
+    """256 control bytes, two dirty planes of a byte per 64x64 tile, four int32 planes of H W words (16 bytes per pixel); each part
+    rounded up to 256 bytes."""
+    L, lib = _lib()
+    up = lambda n: -(-n // 256) * 256
+    shapes = [(1, 1), (1, 2049), (2049, 1), (63, 65), (64, 64), (65, 63), (257, 1101), (1501, 2099), (4097, 513), (8191, 8193),
+              (32767, 3), (3, 32767), (32767, 32767), (46340, 46340), (1, (1 << 31) - 1)]
+    for H, W in shapes:
+        tiles = -(-H // 64) * -(-W // 64)
+        assert lib.tg_flow_ws_bytes(H, W) == 256 + 2 * up(tiles) + 4 * up(4 * H * W)
+    for H, W in shapes[:-3]:
+        for dh, dw in ((1, 0), (0, 1), (64, 0), (0, 255), (2, 2)):
+            assert lib.tg_flow_ws_bytes(H + dh, W + dw) >= lib.tg_flow_ws_bytes(H, W)
+    P, I, SZ = C.c_void_p, C.c_int, C.c_size_t
+    assert L.SIGNATURES["tg_flow_ws_bytes"] == (SZ, [I, I])
+    assert L.SIGNATURES["tg_flow_slope"] == (I, [P, P, I, I, P, P, P, P, SZ, P])
+    assert L.SIGNATURES["tg_flow_flat_sweep"] == (I, [P, I, I, I, P, P, P, P, SZ, P])
+    assert L.SIGNATURES["tg_flow_flat_dir"] == (I, [P, P, I, I, P, P, P])
+    assert L.SIGNATURES["tg_flow_accum_init"] == (I, [P, I, I, P, SZ, P])
+    assert L.SIGNATURES["tg_flow_accum"] == (I, [I, I, I, I, P, P, SZ, P])
+    assert L.SIGNATURES["tg_flow_accum_finish"] == (I, [I, I, I, P, P, P, SZ, P])
+    assert (L.TG_FLOW_OUT, L.TG_FLOW_UNDECIDED, L.TG_FLOW_PIT, L.TG_FLOW_FAR, L.TG_FLOW_MAX_ROUNDS) == \
+        (FO.OUT, FO.UNDECIDED, FO.PIT, FO.FAR, 32)
+
+
+def test_python_rejects_bad_arguments():
+    from mvp_gan.src import flow_routing as FR
+    z = np.zeros((8, 8), np.float32)
+    with pytest.raises(ValueError, match="H, W"):
+        FR.flow_routing(np.zeros((2, 3, 4), np.float32))
+    with pytest.raises(ValueError, match="H, W"):
+        FR.flow_routing(np.zeros((0, 4), np.float32))
+    with pytest.raises(ValueError, match="2\\^31"):
+        FR.flow_routing(np.broadcast_to(np.float32(0), (1 << 16, 1 << 15)))
+    with pytest.raises(ValueError, match="mask"):
+        FR.flow_routing(z, np.ones((8, 9)))
+    for c in (0.0, -1.0, math.nan, math.inf, None, "x"):
+        with pytest.raises(ValueError, match="cellsize"):
+            FR.flow_routing(z, cellsize=c)
+    for n in (0, -1, 1.5, "3", None, True, (1 << 20) + 1):
+        with pytest.raises(ValueError, match="max_sweeps"):
+            FR.flow_routing(z, max_sweeps=n)
+        with pytest.raises(ValueError, match="check_every"):
+            FR.flow_routing(z, check_every=n)
+    for f in (0, 1, None, "yes"):
+        with pytest.raises(ValueError, match="fill"):
+            FR.flow_routing(z, fill=f)
+    with pytest.raises(ValueError, match="flow_routing"):
+        FR.flow_routing(z, cellsize=0.0)                                 # the message names this function
+    sig = inspect.signature(FR.flow_routing).parameters
+    assert list(sig)[:2] == ["dem", "mask"] and sig["mask"].default is None
+    assert all(sig[k].kind is inspect.Parameter.KEYWORD_ONLY for k in list(sig)[2:])
+    assert [(k, sig[k].default) for k in list(sig)[2:]] == [("nodata", None), ("cellsize", 1.0), ("fill", True),
+                                                            ("max_sweeps", 4096), ("check_every", 8)]
+    assert (FR.OUT, FR.PIT, FR.UNKNOWN, FR.FAR) == (FO.OUT, FO.PIT, 0, FO.FAR)
+
+
+def test_no_cpu_path(monkeypatch):
+    import torch
+    from mvp_gan.src.flow_routing import flow_routing
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        flow_routing(np.zeros((8, 8), np.float32))
+
+
+def test_ops_reject_before_any_launch():
+    import torch
+    from tg_hip import lib as L
+    from tg_hip import ops as O
+    w, k = torch.zeros(4, 4), torch.zeros(4, 4, dtype=torch.uint8)
+    D, d = torch.zeros(4, 4, dtype=torch.int32), torch.zeros(4, 4, dtype=torch.uint8)
+    ws = torch.zeros(4096, dtype=torch.uint8)
+    ch, vis, st = torch.zeros(1, dtype=torch.int32), torch.zeros(1, dtype=torch.int64), torch.zeros(2, dtype=torch.int32)
+    for call in (lambda: O.flow_slope(w, k, ws), lambda: O.flow_flat_sweep(w, 1, D, ch, vis, ws), lambda: O.flow_flat_dir(w, D, d),
+                 lambda: O.flow_accum_init(d, ws), lambda: O.flow_accum(4, 4, 0, 1, st, ws), lambda: O.flow_accum_finish(4, 4, 0, ws),
+                 lambda: O.flow_slope(np.zeros((4, 4), np.float32), k, ws)):
+        with pytest.raises(L.TgError):
+            call()
+    with pytest.raises(L.TgError, match="2\\^31"):
+        O.flow_ws(1 << 16, 1 << 15, "cpu")
+    assert O.flow_ws(130, 70, "cpu").numel() == _lib()[1].tg_flow_ws_bytes(130, 70)
+
+
+# ---- helpers and the CLI -----------------------------------------------------------------------------------------------------
+def test_to_esri_and_streams():
+    import torch
+    from mvp_gan.src.flow_routing import streams, to_esri
+    d = np.array([[0, 1, 2, 3, 4], [5, 6, 7, 8, 9], [255, 1, 8, 9, 0]], np.uint8)
+    want = np.array([[255, 1, 2, 4, 8], [16, 32, 64, 128, 0], [0, 1, 128, 0, 255]], np.uint8)
+    got = to_esri(d)
+    assert got.dtype == np.uint8
+    np.testing.assert_array_equal(got, want)
+    gt = to_esri(torch.from_numpy(d))
+    assert gt.dtype == torch.uint8
+    np.testing.assert_array_equal(gt.numpy(), want)
+    for c in range(1, 9):
+        assert int(to_esri(np.array([c], np.uint8))[0]) == 1 << (c - 1)
+    with pytest.raises(ValueError, match="uint8"):
+        to_esri(d.astype(np.int32))
+    with pytest.raises(ValueError, match="uint8"):
+        to_esri(torch.from_numpy(d.astype(np.int32)))
+    a = np.array([[0, 1, 5], [99, 100, 2 ** 31 - 1]], np.int32)
+    s = streams(a, 100)
+    assert s.dtype == np.uint8
+    np.testing.assert_array_equal(s, [[0, 0, 0], [0, 1, 1]])
+    np.testing.assert_array_equal(streams(a, 1), [[0, 1, 1], [1, 1, 1]])
+    st = streams(torch.from_numpy(a), 5)
+    assert st.dtype == torch.uint8
+    np.testing.assert_array_equal(st.numpy(), [[0, 0, 1], [1, 1, 1]])
+    for bad in (0, -3, 1.5, "4", None, True):
+        with pytest.raises(ValueError, match="min_cells"):
+            streams(a, bad)
+
+
+def test_cli_parser(tmp_path):
+    from mvp_gan.src.flow_routing import build_parser, parse_args, write_int_asc
+    from mvp_gan.src.inpaint_raster import read_asc
+    base = ["--dem", "in.asc", "--dir-out", "d.asc", "--acc-out", "a.asc"]
+    a = parse_args(base)
+    assert (a.dem, a.dir_out, a.acc_out, a.mask, a.nodata, a.no_fill, a.esri, a.streams_out, a.min_cells, a.max_sweeps) == \
+        ("in.asc", "d.asc", "a.asc", None, None, False, False, None, None, 4096)
+    a = parse_args(base + ["--mask", "m.png", "--nodata", "-9999", "--no-fill", "--esri", "--streams-out", "s.asc", "--min-cells",
+                           "250", "--max-sweeps", "17"])
+    assert (a.mask, a.nodata, a.no_fill, a.esri, a.streams_out, a.min_cells, a.max_sweeps) == \
+        ("m.png", -9999.0, True, True, "s.asc", 250, 17)
+    for bad in (["--dem", "in.asc"], ["--dem", "in.asc", "--dir-out", "d.asc"], ["--dir-out", "d.asc", "--acc-out", "a.asc"],
+                base + ["--streams-out", "s.asc"], base + ["--min-cells", "5"], base + ["--streams-out", "s.asc", "--min-cells", "0"],
+                base + ["--min-cells", "x", "--streams-out", "s.asc"], base + ["--no-fill", "yes"]):
+        with pytest.raises(SystemExit):
+            parse_args(bad)
+    assert build_parser().parse_args(base).esri is False
+    cwd = os.path.join(ROOT, "terra-gan_amd")
+    r = subprocess.run([sys.executable, "-m", "mvp_gan.src.flow_routing", "--help"], cwd=cwd, capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0, r.stderr
+    for flag in ("--dem", "--dir-out", "--acc-out", "--mask", "--nodata", "--no-fill", "--esri", "--streams-out", "--min-cells"):
+        assert flag in r.stdout
+    # integer grids are written exactly, above 2^24 too, and without a NODATA_value (every code is a value)
+    hdr = [("ncols", "3"), ("nrows", "2"), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", "0.5"), ("NODATA_value", "-9999")]
+    a = np.array([[0, 1, 16777217], [255, 9, 2 ** 31 - 1]], np.int32)
+    p = str(tmp_path / "a.asc")
+    write_int_asc(p, a, hdr)
+    lines = open(p).read().split("\n")
+    assert lines[5:7] == ["0 1 16777217", "255 9 2147483647"] and not any("NODATA" in ln for ln in lines)
+    got, h2 = read_asc(p)
+    assert got.shape == (2, 3) and dict(h2)["cellsize"] == "0.5"
+    with pytest.raises(ValueError, match="header"):
+        write_int_asc(p, a.T, hdr)
