@@ -829,6 +829,50 @@ int tg_flow_accum_init(const uint8_t* dir, int H, int W, void* ws, size_t ws_byt
 int tg_flow_accum(int H, int W, int k0, int n, int32_t* state, void* ws, size_t ws_bytes, tg_stream_t stream);
 int tg_flow_accum_finish(int H, int W, int rounds, int32_t* acc, int32_t* amax, void* ws, size_t ws_bytes, tg_stream_t stream);
 
+/* ---- Watersheds, flow length, drainage comparison (csrc/drainage.hip) ------------------------------------------
+ * dir [H][W] uint8 is a direction grid of the section above without TG_FLOW_UNDECIDED (the caller's to check: it needs a read of
+ * the grid).  next0(p) = the receiver's linear index for the codes 1..8, else -1.  pour (may be NULL) [H][W] uint8, nonzero = pour
+ * point: a pixel with pour != 0 and dir != 0 is a terminal whatever its code (next0 = -1); a pour point on a pixel with dir == 0
+ * is ignored.  T(p) is the last pixel of p's path (T(p) = p for a terminal), nc(p) and nd(p) the cardinal and diagonal steps
+ * from p to T(p); pixels with dir == 0 have T = -1, nc = nd = 0.  Sides as tg_objmask_known (H, W >= 1, H * W < 2^31).
+ * Gather-only pointer doubling: a pixel's state is one 16-byte record (next, last, nc, nd), start (next0, p, c0, d0) with
+ * (c0, d0) = (1, 0) for a cardinal code, (0, 1) for a diagonal one, else (0, 0); in round k a pixel with q = next(p) >= 0 takes
+ * (next(q), last(q), nc(p) + nc(q), nd(p) + nd(q)), every word of q from the state before the round; any other pixel copies its
+ * record.  No atomics on the rasters: exact, bitwise reproducible.
+ * One workspace ws >= tg_flow_basin_ws_bytes(H, W) serves the three calls: 256 control bytes, then two planes of H * W records
+ * of 16 bytes (each rounded up to 256 bytes), 32 bytes per pixel; round k reads plane k & 1 and writes the other.  ws is aligned
+ * to 16 bytes.  0 for sides out of range. */
+#define TG_FLOW_BASIN_COUNTS 3
+#define TG_FLOW_COMPARE_COUNTS 19
+size_t tg_flow_basin_ws_bytes(int H, int W);
+/* The start state in plane 0, live[0].  counts [2] int64 (zeroed here) = pour points that became terminals, pour points ignored. */
+int tg_flow_basin_init(const uint8_t* dir, const uint8_t* pour /* may be NULL */, int H, int W, int64_t* counts, void* ws,
+                       size_t ws_bytes, tg_stream_t stream);
+/* Enqueues rounds k0 .. k0 + n - 1 (k0 = the rounds enqueued before, k0 + n <= TG_FLOW_MAX_ROUNDS); a round that finds no pointer
+ * left does nothing.  state [2] int32 = pointers left after these rounds (0: done), rounds that ran. */
+int tg_flow_basin(int H, int W, int k0, int n, int32_t* state, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* From the plane of `rounds` (= state[1]) rounds: basin [H][W] int32 = last (T at the end, -1 where dir == 0); nc, nd (int32,
+ * may be NULL); length_m (may be NULL) = (float)(cellsize * ((double)nc + 1.4142135623730951 * (double)nd)): one fp64 multiply,
+ * one add, one multiply, nothing fused, one rounding to fp32.  counts [TG_FLOW_BASIN_COUNTS] int64 (zeroed here) = terminals
+ * (pixels with last == p), the largest nc + nd, the bits of the largest length_m (computed with or without the plane; a
+ * non-negative float's bits order as integers).  cellsize finite and > 0. */
+int tg_flow_basin_finish(int H, int W, int rounds, double cellsize, int32_t* basin, int32_t* nc, int32_t* nd, float* length_m,
+                         int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* Two routings of one raster compared in integers, over the pixels with sel != 0, dir_t != 0 and dir_p != 0 (t = truth, p = the
+ * fill).  basin_*: tg_flow_basin_finish's; acc_*: tg_flow_accum_finish's; a pixel is a stream of a side when acc >= stream_cells
+ * (>= 1); d2_t, d2_p: tg_edt's squared distances to the truth's and the fill's stream masks, so sides in [1, TG_EDT_MAX_SIDE];
+ * 0 <= tol2 < TG_EDT_FAR.  counts [TG_FLOW_COMPARE_COUNTS] int64 (zeroed here), exact in any order (per-wave shuffles, one 64-bit integer
+ * atomic per wave and counter):
+ *   0 cells; 1 dir_equal (the codes are equal); 2 dir_routed (both codes in 1..8); 3 dir_within_45 (both in 1..8 and their
+ *   cyclic difference <= 1); 4 same_outlet (basin_t == basin_p); 5 outlet_d2_sum, 6 outlet_d2_max: the squared pixel distance
+ *   between the two terminals (0 where a basin is negative); 7 area_octave_sum: sum of |floor(log2 acc_t) - floor(log2 acc_p)|
+ *   (an acc < 1 counts as 1); 8 streams_truth, 9 streams_pred, 10 streams_both; over the fill's stream pixels: 11 matched
+ *   (d2_t <= tol2), 12 far (d2_t == TG_EDT_FAR; not in the next two), 13 d2_sum, 14 d2_max; over the truth's stream pixels the
+ *   same four from d2_p: 15, 16, 17, 18. */
+int tg_flow_compare(const uint8_t* sel, const uint8_t* dir_t, const uint8_t* dir_p, const int32_t* basin_t, const int32_t* basin_p,
+                    const int32_t* acc_t, const int32_t* acc_p, const int32_t* d2_t, const int32_t* d2_p, int H, int W,
+                    int32_t stream_cells, int32_t tol2, int64_t* counts, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

@@ -1,0 +1,342 @@
+// Watersheds, flow length and the drainage comparison of two routings (mvp_gan/src/flow_routing.py watersheds,
+// mvp_gan/src/evaluate_raster.py drainage_errors).
+//
+// A pixel's state is one 16-byte record (next, last, nc, nd): the pixel 2^k steps downstream (-1: the path has ended), the last
+// pixel reached, and the cardinal and diagonal steps taken to it.  Two planes of records in the workspace: round k reads plane
+// k & 1 and writes the other, so no record a round reads is written by it, and the four words of q = next(p) come from one
+// iterate in one 16-byte load.
+//
+//   basin_init_kernel     the start state (next0, p, c0, d0) into plane 0; (-1, -1, 0, 0) at unknown pixels; live[0]; pour counts
+//   basin_round_kernel    a live pixel takes (next(q), last(q), nc + nc(q), nd + nd(q)); any other pixel copies its record, so the
+//                         plane of every later round holds its final record; live[k + 1]
+//   basin_state_kernel    one thread: the live count after the rounds enqueued and the number of rounds that ran
+//   basin_finish_kernel   last -> basin, nc, nd, the length in metres; terminals, the largest nc + nd and length
+//   flow_compare_kernel   the 19 integer counters of two routings over the selected pixels
+//
+// A round moves 32 bytes per pixel (its record read and written) and 16 more per pixel whose pointer is live (the gather).
+//
+// Determinism: gathers and plain stores only on the rasters; the counters are sums and maxima of integers by integer atomics,
+// exact in any order.
+#include "common.h"
+
+static inline hipStream_t S(tg_stream_t s) { return (hipStream_t)s; }
+
+typedef unsigned long long ull;
+
+// length_m is one fp64 multiply, one add, one multiply, one rounding to fp32: nothing is fused in this file.
+#pragma clang fp contract(off)
+
+constexpr int DR_CTL_BYTES = 256;        // int32 [8 .. 40]: live[k] of the doubling
+constexpr int DR_LIVE = 8;               // first word of live[0 .. 32]
+constexpr int DR_MAX_ROUNDS = TG_FLOW_MAX_ROUNDS;
+constexpr int DR_NCMP = TG_FLOW_COMPARE_COUNTS;
+
+static size_t dr_al256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+struct DrLayout {
+    size_t ctl, rec[2], total;
+};
+
+static DrLayout dr_layout(int H, int W) {
+    DrLayout L;
+    const size_t px = dr_al256((size_t)H * W * 16);
+    size_t o = 0;
+    L.ctl = o; o += DR_CTL_BYTES;
+    L.rec[0] = o; o += px;
+    L.rec[1] = o; o += px;
+    L.total = o;
+    return L;
+}
+
+// code - 1 -> (dy, dx): E, SE, S, SW, W, NW, N, NE (flow.hip's tables)
+__host__ __device__ constexpr int dr_dy(int k) { return ((0x01a9 >> (2 * k)) & 3) - 1; }     // 0, 1, 1, 1, 0, -1, -1, -1
+__host__ __device__ constexpr int dr_dx(int k) { return ((0x901a >> (2 * k)) & 3) - 1; }     // 1, 1, 0, -1, -1, -1, 0, 1
+static_assert(dr_dy(0) == 0 && dr_dy(1) == 1 && dr_dy(2) == 1 && dr_dy(3) == 1 && dr_dy(4) == 0 && dr_dy(5) == -1 &&
+              dr_dy(6) == -1 && dr_dy(7) == -1, "dy");
+static_assert(dr_dx(0) == 1 && dr_dx(1) == 1 && dr_dx(2) == 0 && dr_dx(3) == -1 && dr_dx(4) == -1 && dr_dx(5) == -1 &&
+              dr_dx(6) == 0 && dr_dx(7) == 1, "dx");
+
+__device__ __forceinline__ void dr_count_live(int alive, int32_t* dst) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) alive += __shfl_xor(alive, o, 64);
+    if ((threadIdx.x & 63) == 0 && alive) atomicAdd(dst, alive);
+}
+
+// ---- the doubling -------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void basin_init_kernel(const uint8_t* __restrict__ dir, const uint8_t* __restrict__ pour, int H,
+                                                         int W, int4* __restrict__ rec, int32_t* __restrict__ live,
+                                                         ull* __restrict__ counts) {
+    const int64_t n = (int64_t)H * W;
+    int alive = 0, used = 0, ignored = 0;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+        const int code = dir[p];
+        const bool pp = pour && pour[p] != 0;
+        int4 r = make_int4(-1, code ? (int32_t)p : -1, 0, 0);
+        if (pp) {
+            if (code) ++used;
+            else ++ignored;
+        } else if (code >= 1 && code <= 8) {
+            const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
+            const int yy = y + dr_dy(code - 1), xx = x + dr_dx(code - 1);
+            if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
+                r.x = (int32_t)((int64_t)yy * W + xx);
+                r.z = (code & 1) ? 1 : 0;                           // codes 1, 3, 5, 7 are E, S, W, N
+                r.w = (code & 1) ? 0 : 1;
+            }
+        }
+        rec[p] = r;
+        alive += r.x >= 0;
+    }
+    dr_count_live(alive, live);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        used += __shfl_xor(used, o, 64);
+        ignored += __shfl_xor(ignored, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (used) atomicAdd(counts, (ull)used);
+        if (ignored) atomicAdd(counts + 1, (ull)ignored);
+    }
+}
+
+// live points at live[k]: round k runs only while a pointer is left, and counts those left after it into live[k + 1]
+__global__ __launch_bounds__(256) void basin_round_kernel(int64_t n, const int4* __restrict__ in, int4* __restrict__ out,
+                                                          int32_t* live) {
+    if (live[0] == 0) return;                                       // uniform: every path has ended
+    int alive = 0;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+        int4 r = in[p];
+        if ((uint32_t)r.x < (uint32_t)n) {                          // a receiver's index (n < 2^31; -1 is not below it)
+            const int4 q = in[r.x];                                 // one 16-byte load: the four words of one iterate
+            r.x = q.x;
+            r.y = q.y;
+            r.z += q.z;
+            r.w += q.w;
+        }
+        out[p] = r;
+        alive += r.x >= 0;
+    }
+    dr_count_live(alive, live + 1);
+}
+
+__global__ void basin_state_kernel(const int32_t* __restrict__ live, int k_end, int32_t* __restrict__ state) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    int k = 0;
+    while (k < k_end && live[k] != 0) ++k;                          // round k ran iff live[k] != 0
+    state[0] = live[k];
+    state[1] = k;
+}
+
+__global__ __launch_bounds__(256) void basin_finish_kernel(const int4* __restrict__ rec, int64_t n, double cellsize,
+                                                           int32_t* __restrict__ basin, int32_t* __restrict__ nc,
+                                                           int32_t* __restrict__ nd, float* __restrict__ length_m,
+                                                           ull* __restrict__ counts) {
+    int term = 0;
+    uint32_t steps = 0, bits = 0;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+        const int4 r = rec[p];
+        basin[p] = r.y;
+        if (nc) nc[p] = r.z;
+        if (nd) nd[p] = r.w;
+        const double diag = 1.4142135623730951 * (double)r.w;
+        const double sum = (double)r.z + diag;
+        const float len = (float)(cellsize * sum);
+        if (length_m) length_m[p] = len;
+        term += (int64_t)r.y == p;
+        const uint32_t s = (uint32_t)r.z + (uint32_t)r.w, b = __float_as_uint(len);
+        steps = s > steps ? s : steps;
+        bits = b > bits ? b : bits;                                 // len >= 0: its bits order as integers
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        term += __shfl_xor(term, o, 64);
+        const uint32_t s2 = __shfl_xor(steps, o, 64), b2 = __shfl_xor(bits, o, 64);
+        steps = s2 > steps ? s2 : steps;
+        bits = b2 > bits ? b2 : bits;
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (term) atomicAdd(counts, (ull)term);
+        if (steps) atomicMax(counts + 1, (ull)steps);
+        if (bits) atomicMax(counts + 2, (ull)bits);
+    }
+}
+
+// ---- the comparison -----------------------------------------------------------------------------------------------------
+// counters 6, 14 and 18 are maxima, the others sums
+__host__ __device__ constexpr bool dr_is_max(int i) { return i == 6 || i == 14 || i == 18; }
+
+__global__ __launch_bounds__(256) void flow_compare_kernel(const uint8_t* __restrict__ sel, const uint8_t* __restrict__ dir_t,
+                                                           const uint8_t* __restrict__ dir_p, const int32_t* __restrict__ basin_t,
+                                                           const int32_t* __restrict__ basin_p, const int32_t* __restrict__ acc_t,
+                                                           const int32_t* __restrict__ acc_p, const int32_t* __restrict__ d2_t,
+                                                           const int32_t* __restrict__ d2_p, int64_t n, int W, int32_t stream_cells,
+                                                           int32_t tol2, ull* __restrict__ counts) {
+    ull c[DR_NCMP];
+#pragma unroll
+    for (int i = 0; i < DR_NCMP; ++i) c[i] = 0;
+    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+        if (!sel[p]) continue;
+        const int ct = dir_t[p], cp = dir_p[p];
+        if (!ct || !cp) continue;
+        c[0] += 1;
+        c[1] += ct == cp;
+        if (ct <= 8 && cp <= 8) {
+            c[2] += 1;
+            int d = ct - cp;
+            d = d < 0 ? -d : d;
+            d = d > 4 ? 8 - d : d;
+            c[3] += d <= 1;
+        }
+        const int32_t bt = basin_t[p], bp = basin_p[p];
+        c[4] += bt == bp;
+        if (bt >= 0 && bp >= 0 && bt != bp) {
+            const int64_t yt = bt / W, yp = bp / W;
+            const int64_t dy = yt - yp, dx = (bt - yt * W) - (bp - yp * W);
+            const ull d2 = (ull)(dy * dy + dx * dx);
+            c[5] += d2;
+            c[6] = d2 > c[6] ? d2 : c[6];
+        }
+        const int32_t at = acc_t[p], ap = acc_p[p];
+        const int ot = 31 - __clz(at < 1 ? 1 : at), op = 31 - __clz(ap < 1 ? 1 : ap);
+        c[7] += (ull)(ot > op ? ot - op : op - ot);
+        const bool st = at >= stream_cells, sp = ap >= stream_cells;
+        c[8] += st;
+        c[9] += sp;
+        c[10] += st && sp;
+        if (sp) {
+            const int32_t d = d2_t[p];
+            c[11] += d <= tol2;
+            if (d == TG_EDT_FAR) {
+                c[12] += 1;
+            } else {
+                c[13] += (ull)d;
+                c[14] = (ull)d > c[14] ? (ull)d : c[14];
+            }
+        }
+        if (st) {
+            const int32_t d = d2_p[p];
+            c[15] += d <= tol2;
+            if (d == TG_EDT_FAR) {
+                c[16] += 1;
+            } else {
+                c[17] += (ull)d;
+                c[18] = (ull)d > c[18] ? (ull)d : c[18];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < DR_NCMP; ++i) {
+        ull v = c[i];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const ull v2 = __shfl_xor(v, o, 64);
+            v = dr_is_max(i) ? (v2 > v ? v2 : v) : v + v2;
+        }
+        if ((threadIdx.x & 63) == 0 && v) {
+            if (dr_is_max(i)) atomicMax(counts + i, v);
+            else atomicAdd(counts + i, v);
+        }
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------
+static int dr_size_check(const char* who, int H, int W) {
+    TG_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "%s: raster %dx%d must be non-empty with H*W < 2^31", who,
+               H, W);
+    return TG_OK;
+}
+
+extern "C" size_t tg_flow_basin_ws_bytes(int H, int W) {
+    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    return dr_layout(H, W).total;
+}
+
+extern "C" int tg_flow_basin_init(const uint8_t* dir, const uint8_t* pour, int H, int W, int64_t* counts, void* ws,
+                                  size_t ws_bytes, tg_stream_t stream) {
+    if (int rc = dr_size_check("tg_flow_basin_init", H, W)) return rc;
+    TG_REQUIRE(dir && counts && ws, "tg_flow_basin_init: null pointer");
+    const DrLayout L = dr_layout(H, W);
+    TG_REQUIRE(ws_bytes >= L.total, "tg_flow_basin_init: workspace %zu bytes < %zu", ws_bytes, L.total);
+    TG_REQUIRE(((uintptr_t)ws & 15) == 0, "tg_flow_basin_init: workspace must be aligned to 16 bytes");
+    const hipStream_t s = S(stream);
+    char* base = (char*)ws;
+    int32_t* live = (int32_t*)(base + L.ctl) + DR_LIVE;
+    if (hipMemsetAsync(base + L.ctl, 0, DR_CTL_BYTES, s) != hipSuccess ||
+        hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s) != hipSuccess) {
+        tg_set_error("tg_flow_basin_init: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    hipLaunchKernelGGL(basin_init_kernel, dim3(ew_grid((int64_t)H * W, 256)), dim3(256), 0, s, dir, pour, H, W,
+                       (int4*)(base + L.rec[0]), live, reinterpret_cast<ull*>(counts));
+    TG_CHECK_LAUNCH("basin_init_kernel");
+    return TG_OK;
+}
+
+extern "C" int tg_flow_basin(int H, int W, int k0, int n, int32_t* state, void* ws, size_t ws_bytes, tg_stream_t stream) {
+    if (int rc = dr_size_check("tg_flow_basin", H, W)) return rc;
+    TG_REQUIRE(state && ws, "tg_flow_basin: null pointer");
+    TG_REQUIRE(k0 >= 0 && n >= 1 && k0 <= DR_MAX_ROUNDS && n <= DR_MAX_ROUNDS - k0,
+               "tg_flow_basin: rounds k0 = %d, n = %d must satisfy k0 >= 0, n >= 1, k0 + n <= %d", k0, n, DR_MAX_ROUNDS);
+    const DrLayout L = dr_layout(H, W);
+    TG_REQUIRE(ws_bytes >= L.total, "tg_flow_basin: workspace %zu bytes < %zu", ws_bytes, L.total);
+    TG_REQUIRE(((uintptr_t)ws & 15) == 0, "tg_flow_basin: workspace must be aligned to 16 bytes");
+    const hipStream_t s = S(stream);
+    char* base = (char*)ws;
+    int32_t* live = (int32_t*)(base + L.ctl) + DR_LIVE;
+    const int64_t px = (int64_t)H * W;
+    const dim3 grid(ew_grid(px, 256));
+    for (int k = k0; k < k0 + n; ++k) {
+        const int a = k & 1, b = a ^ 1;
+        hipLaunchKernelGGL(basin_round_kernel, grid, dim3(256), 0, s, px, (const int4*)(base + L.rec[a]), (int4*)(base + L.rec[b]),
+                           live + k);
+        TG_CHECK_LAUNCH("basin_round_kernel");
+    }
+    hipLaunchKernelGGL(basin_state_kernel, dim3(1), dim3(64), 0, s, live, k0 + n, state);
+    TG_CHECK_LAUNCH("basin_state_kernel");
+    return TG_OK;
+}
+
+extern "C" int tg_flow_basin_finish(int H, int W, int rounds, double cellsize, int32_t* basin, int32_t* nc, int32_t* nd,
+                                    float* length_m, int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream) {
+    if (int rc = dr_size_check("tg_flow_basin_finish", H, W)) return rc;
+    TG_REQUIRE(basin && counts && ws, "tg_flow_basin_finish: null pointer");
+    TG_REQUIRE(rounds >= 0 && rounds <= DR_MAX_ROUNDS, "tg_flow_basin_finish: rounds = %d must lie in [0, %d]", rounds,
+               DR_MAX_ROUNDS);
+    TG_REQUIRE(cellsize > 0 && cellsize * 0.0 == 0.0, "tg_flow_basin_finish: cellsize %g must be finite and > 0", cellsize);
+    const DrLayout L = dr_layout(H, W);
+    TG_REQUIRE(ws_bytes >= L.total, "tg_flow_basin_finish: workspace %zu bytes < %zu", ws_bytes, L.total);
+    TG_REQUIRE(((uintptr_t)ws & 15) == 0, "tg_flow_basin_finish: workspace must be aligned to 16 bytes");
+    const hipStream_t s = S(stream);
+    if (hipMemsetAsync(counts, 0, TG_FLOW_BASIN_COUNTS * sizeof(int64_t), s) != hipSuccess) {
+        tg_set_error("tg_flow_basin_finish: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    const int64_t px = (int64_t)H * W;
+    hipLaunchKernelGGL(basin_finish_kernel, dim3(ew_grid(px, 256)), dim3(256), 0, s,
+                       (const int4*)((char*)ws + L.rec[rounds & 1]), px, cellsize, basin, nc, nd, length_m,
+                       reinterpret_cast<ull*>(counts));
+    TG_CHECK_LAUNCH("basin_finish_kernel");
+    return TG_OK;
+}
+
+extern "C" int tg_flow_compare(const uint8_t* sel, const uint8_t* dir_t, const uint8_t* dir_p, const int32_t* basin_t,
+                               const int32_t* basin_p, const int32_t* acc_t, const int32_t* acc_p, const int32_t* d2_t,
+                               const int32_t* d2_p, int H, int W, int32_t stream_cells, int32_t tol2, int64_t* counts,
+                               tg_stream_t stream) {
+    TG_REQUIRE(H >= 1 && W >= 1 && H <= TG_EDT_MAX_SIDE && W <= TG_EDT_MAX_SIDE,
+               "tg_flow_compare: raster %dx%d: both sides must lie in [1, %d]", H, W, (int)TG_EDT_MAX_SIDE);
+    TG_REQUIRE(sel && dir_t && dir_p && basin_t && basin_p && acc_t && acc_p && d2_t && d2_p && counts,
+               "tg_flow_compare: null pointer");
+    TG_REQUIRE(stream_cells >= 1, "tg_flow_compare: stream_cells = %d must be >= 1", stream_cells);
+    TG_REQUIRE(tol2 >= 0 && tol2 < TG_EDT_FAR, "tg_flow_compare: tol2 = %d must lie in [0, TG_EDT_FAR)", tol2);
+    const hipStream_t s = S(stream);
+    if (hipMemsetAsync(counts, 0, DR_NCMP * sizeof(int64_t), s) != hipSuccess) {
+        tg_set_error("tg_flow_compare: hipMemsetAsync failed");
+        return TG_ERR_LAUNCH;
+    }
+    const int64_t px = (int64_t)H * W;
+    hipLaunchKernelGGL(flow_compare_kernel, dim3(ew_grid(px, 256)), dim3(256), 0, s, sel, dir_t, dir_p, basin_t, basin_p, acc_t,
+                       acc_p, d2_t, d2_p, px, W, stream_cells, tol2, reinterpret_cast<ull*>(counts));
+    TG_CHECK_LAUNCH("flow_compare_kernel");
+    return TG_OK;
+}

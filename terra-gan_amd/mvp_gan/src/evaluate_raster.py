@@ -44,11 +44,17 @@ the depressions of the truth and of the fill are filled over the same known pixe
 inside the holes; report["baseline"] and every report["compare"][name] gain the same key for their fills.  Without it the report
 has no "sinks" key and nothing more runs.
 
+With drainage=True the report also says whether water crosses a fill the way it crosses the true terrain (drainage_errors;
+mvp_gan/src/flow_routing.py): both surfaces are routed over the same known pixels, and report["drainage"]
+compares their D8 directions, outlets, contributing areas and stream networks (accumulation >= stream_cells) inside the holes, in
+integers; report["baseline"] and every report["compare"][name] gain the same key.  Without it the report has no "drainage" key
+and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
-         [--by-depth [E ...]] [--compare idw nearest] [--sinks]
+         [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -444,9 +450,10 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 
 @torch.no_grad()
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
-                    quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None, sinks=False):
+                    quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
+                    stream_tol_m=None):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
-    fill info under "fill"; with sinks also sink_errors' dict under "sinks"."""
+    fill info under "fill"; with sinks also sink_errors' dict under "sinks", with drainage drainage_errors' under "drainage"."""
     from .fill_voids import fill_voids
     device = _device()
     z = _f32(dem, device, "dem")
@@ -458,6 +465,9 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     rep["fill"] = finfo
     if sinks:
         rep["sinks"] = sink_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata)
+    if drainage:
+        rep["drainage"] = drainage_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                          stream_tol_m=stream_tol_m)
     return rep
 
 
@@ -479,9 +489,9 @@ def _check_compare(compare, who="evaluate_raster"):
     return names
 
 
-def assemble_compare(reports, infos, sinks=None):
+def assemble_compare(reports, infos, sinks=None, drainage=None):
     """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name; with sinks
-    ({name: sink_errors' dict}) also "sinks"."""
+    ({name: sink_errors' dict}) also "sinks", with drainage ({name: drainage_errors' dict}) also "drainage"."""
     out = {}
     for name, rep in reports.items():
         out[name] = dict(rep)
@@ -489,25 +499,31 @@ def assemble_compare(reports, infos, sinks=None):
         out[name]["fill"] = infos[name]
         if sinks is not None:
             out[name]["sinks"] = sinks[name]
+        if drainage is not None:
+            out[name]["drainage"] = drainage[name]
     return out
 
 
 @torch.no_grad()
 def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
-                   quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False):
+                   quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
+                   stream_tol_m=None):
     """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
     from .interpolate import interpolate_voids
     device = _device()
     z = _f32(dem, device, "dem")
     k = _f32(keep, device, "keep", binary=True)
-    reports, infos, snk = {}, {}, {}
+    reports, infos, snk, drn = {}, {}, {}, {}
     for name in _check_compare(names):
         pred, infos[name] = interpolate_voids(z, k, nodata=_nodata(nodata), method=name, cellsize=cellsize)
         reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
                                        area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
         if sinks:
             snk[name] = sink_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata)
-    return assemble_compare(reports, infos, snk if sinks else None)
+        if drainage:
+            drn[name] = drainage_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                        stream_tol_m=stream_tol_m)
+    return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None)
 
 
 # ---- sinks: does a fill drain ---------------------------------------------------------------------------------------------
@@ -566,11 +582,122 @@ def sinks_summary(s):
             f"{s['excess_volume_m3']:.6g} m3")
 
 
+# ---- drainage: does water cross a fill as it crosses the truth -----------------------------------------------------------
+def stream_tolerance(cellsize, stream_tol_m=None, who="drainage_errors"):
+    """-> (tolerance in metres, tol2 = floor((tolerance / cellsize)^2) in pixels^2).  None means 3 cells: 3.0 * cellsize and
+    tol2 = 9 exactly.  Otherwise tol2 is computed in exact rational arithmetic on the two doubles as given (fractions.Fraction),
+    so no rounding can move it across an integer; it must be below 2^31 - 1."""
+    from fractions import Fraction
+    c = _cellsize(cellsize, who)
+    if stream_tol_m is None:
+        return 3.0 * c, 9
+    try:
+        t = float(stream_tol_m)
+    except (TypeError, ValueError):
+        t = math.nan
+    if isinstance(stream_tol_m, bool) or not (t >= 0 and t < math.inf):
+        raise ValueError(f"{who}: stream_tol_m {stream_tol_m!r} must be None or a finite number >= 0")
+    tol2 = math.floor((Fraction(t) / Fraction(c)) ** 2)
+    if tol2 >= 2 ** 31 - 1:
+        raise ValueError(f"{who}: stream_tol_m {t!r} is {tol2} px^2 at cellsize {c!r}: must be below 2^31 - 1")
+    return t, tol2
+
+
+def _check_stream_cells(n, who):
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n < 2 ** 31:
+        raise ValueError(f"{who}: stream_cells {n!r} must be an integer in [1, 2^31)")
+    return n
+
+
+def assemble_drainage(counts, truth, pred, *, cellsize, stream_cells, stream_tol_m):
+    """The drainage dict from tg_flow_compare's counters (a sequence of FLOW_COMPARE_COUNTS integers, ops.FLOW_COMPARE_NAMES)
+    and the two sides' routing numbers, each {"pits", "flat_cells", "converged", "rounds"} (pure: no GPU).  Shares are taken
+    of the cells compared, within_45 of the cells both sides route (codes 1..8); distances are cellsize * sqrt(an exact
+    integer or a ratio of two); a share or mean with a zero denominator is None."""
+    (cells, dir_equal, dir_routed, dir_within, same, od2_sum, od2_max, oct_sum, st_t, st_p, st_b, p_match, p_far, p_sum, p_max,
+     t_match, t_far, t_sum, t_max) = (int(v) for v in counts)
+    c = float(cellsize)
+    ratio = lambda a, b: a / b if b else None
+    rms = lambda s2, n: c * math.sqrt(s2 / n) if n else None
+    dist = lambda d2, n: c * math.sqrt(d2) if n else None
+    side = lambda r: {"pits": int(r["pits"]), "flat_cells": int(r["flat_cells"]), "converged": bool(r["converged"]),
+                      "rounds": int(r["rounds"])}
+    return {"cells": cells, "stream_cells": int(stream_cells), "stream_tol_m": float(stream_tol_m),
+            "direction": {"equal": ratio(dir_equal, cells), "within_45": ratio(dir_within, dir_routed), "routed": dir_routed},
+            "outlet": {"same": ratio(same, cells), "shift_rms_m": rms(od2_sum, cells), "shift_max_m": dist(od2_max, cells)},
+            "area": {"octave_mae": ratio(oct_sum, cells)},
+            "streams": {"truth_cells": st_t, "pred_cells": st_p, "both_cells": st_b,
+                        "precision": ratio(p_match, st_p), "recall": ratio(t_match, st_t),
+                        "pred_to_truth_rms_m": rms(p_sum, st_p - p_far), "pred_to_truth_max_m": dist(p_max, st_p - p_far),
+                        "truth_to_pred_rms_m": rms(t_sum, st_t - t_far), "truth_to_pred_max_m": dist(t_max, st_t - t_far),
+                        "pred_far": p_far, "truth_far": t_far},
+            "truth": side(truth), "pred": side(pred)}
+
+
+@torch.no_grad()
+def drainage_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, stream_cells=1000, stream_tol_m=None):
+    """drainage_errors' measurement -> (counts: tg_flow_compare's counters as a list of ints, [truth side, pred side], tolerance in
+    metres, tol2)."""
+    from tg_hip import ops as O
+    from .flow_routing import route_known, streams, watersheds
+    who = "drainage_errors"
+    c = _cellsize(cellsize, who)
+    H, W = _inputs(dem, mask, who)
+    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
+        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    if max(H, W) > 32767:
+        raise ValueError(f"{who}: needs sides of at most 32767 px (exact int32 squared distances), got {H}x{W}")
+    _check_stream_cells(stream_cells, who)
+    tol_m, tol2 = stream_tolerance(c, stream_tol_m, who)
+    device = _device()
+    z = _f32(dem, device, "dem")
+    p = _f32(pred, device, "pred")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    sel = _u8(holes, device)
+    kz, _ = O.objmask_known(z, m, _nodata(nodata), transposed=False)
+    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
+    known = kz & kp
+    sides, grids = [], []
+    for surf in (z, p):
+        direction, acc, info = route_known(surf, known, c, fill=True)
+        basin, _, winfo = watersheds(direction, cellsize=c)
+        d2, _ = O.edt(streams(acc, stream_cells))
+        grids.append((direction, basin, acc, d2))
+        sides.append({"pits": info["pits"], "flat_cells": info["flat_cells"], "converged": info["converged"],
+                      "rounds": winfo["rounds"]})
+    (dt, bt, at, d2t), (dp, bp, ap, d2p) = grids
+    counts = O.flow_compare(sel, dt, dp, bt, bp, at, ap, d2t, d2p, stream_cells, tol2)
+    return counts.cpu().tolist(), sides, tol_m, tol2
+
+
+def drainage_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, stream_cells=1000, stream_tol_m=None):
+    """How water crosses a fill, against how it crosses the true terrain.  dem and pred are routed (flow_routing's chain with
+    fill=True) over one known mask, the pixels known in both, so both have the same outlets; watersheds gives every pixel its
+    outlet, the pixels with an accumulation >= stream_cells are a side's streams, and tg_edt gives the exact squared distance
+    to each side's streams.  Inside holes (nonzero = hole) one pass counts, in integers: equal and near-equal directions,
+    equal outlets and the distance between the two, the octaves between the two contributing areas, and the stream pixels of
+    each side within stream_tol_m (None: 3 cells; stream_tolerance) of the other's.  -> assemble_drainage's dict."""
+    counts, sides, tol_m, _ = drainage_raw(dem, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata,
+                                           stream_cells=stream_cells, stream_tol_m=stream_tol_m)
+    return assemble_drainage(counts, sides[0], sides[1], cellsize=_cellsize(cellsize, "drainage_errors"),
+                             stream_cells=stream_cells, stream_tol_m=tol_m)
+
+
+def drainage_summary(d):
+    """One line for a drainage dict."""
+    f = lambda v, spec: "n/a" if v is None else format(v, spec)
+    s = d["streams"]
+    return (f"drainage: {f(d['direction']['equal'], '.3f')} equal directions, {f(d['outlet']['same'], '.3f')} same outlet (shift rms "
+            f"{f(d['outlet']['shift_rms_m'], '.4g')} m) over {d['cells']} px; streams >= {d['stream_cells']} cells: precision "
+            f"{f(s['precision'], '.3f')}, recall {f(s['recall'], '.3f')} within {d['stream_tol_m']:g} m, largest displacement "
+            f"{f(s['pred_to_truth_max_m'], '.4g')} m")
+
+
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
-                    solver="mg", depth_edges_m=None, compare=None, sinks=False):
+                    solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -578,18 +705,22 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     fill_voids solver of the baseline, the seam correction and the fallback ("mg" or "pcg"); "pcg" shows in their infos.
     depth_edges_m adds "by_depth" to the report and, on the same classes, to report["baseline"].  compare: names out of COMPARES,
     adds report["compare"][name], the interpolate_voids fill of the same keep mask scored on the same holes and classes.
-    sinks=True adds sink_errors' dict under "sinks" to the report, to report["baseline"] and to every report["compare"][name]."""
+    sinks=True adds sink_errors' dict under "sinks" to the report, to report["baseline"] and to every report["compare"][name];
+    drainage=True adds drainage_errors' dict (streams of stream_cells cells, matched within stream_tol_m) under "drainage" to the
+    same three places."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
                              seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
-                             depth_edges_m=depth_edges_m, compare=compare, sinks=sinks)
+                             depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
+                             stream_cells=stream_cells, stream_tol_m=stream_tol_m)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
-              min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False):
+              min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
+              stream_tol_m=None):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
@@ -602,6 +733,11 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     H, W = _inputs(dem, mask, "evaluate_raster")
     if compare and max(H, W) > 32767:
         raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
+    if drainage:
+        if max(H, W) > 32767:
+            raise ValueError(f"evaluate_raster: drainage needs sides of at most 32767 px, got {H}x{W}")
+        _check_stream_cells(stream_cells, "evaluate_raster")
+        stream_tolerance(c, stream_tol_m, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
@@ -624,13 +760,17 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["seam"] = sinfo
     if sinks:
         rep["sinks"] = sink_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata)
+    drn = {"drainage": bool(drainage), "stream_cells": stream_cells, "stream_tol_m": stream_tol_m}
+    if drainage:
+        rep["drainage"] = drainage_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, stream_cells=stream_cells,
+                                          stream_tol_m=stream_tol_m)
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
-                                          depth_edges_m=depth_edges_m, sinks=bool(sinks))
+                                          depth_edges_m=depth_edges_m, sinks=bool(sinks), **drn)
     if compare:
         rep["compare"] = compare_report(z, hm, keep, compare, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
-                                        quantiles=quantiles, top=top, depth_edges_m=depth_edges_m, sinks=bool(sinks))
+                                        quantiles=quantiles, top=top, depth_edges_m=depth_edges_m, sinks=bool(sinks), **drn)
     return rep, pred, hm
 
 
@@ -698,6 +838,14 @@ def build_parser():
     ap.add_argument("--sinks", action="store_true",
                     help="also fill the depressions of the truth and of every scored fill and report the closed pits each fill "
                          "put into the holes (cells, volume, count): one more summary line per fill")
+    ap.add_argument("--drainage", action="store_true",
+                    help="also route the truth and every scored fill (D8 after a depression fill) and compare directions, "
+                         "outlets, contributing areas and stream networks inside the holes: one more summary line per fill")
+    ap.add_argument("--stream-cells", type=int, default=1000,
+                    help="with --drainage: a cell is a stream when its contributing area is at least this many cells")
+    ap.add_argument("--stream-tol", type=float, metavar="M",
+                    help="with --drainage: a stream cell is matched when the other side has one within this many metres "
+                         "(default: 3 cells)")
     return ap
 
 
@@ -706,6 +854,10 @@ def main(argv=None):
     from .object_mask import spec_from_args, write_mask
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.stream_cells < 1:
+        ap.error("--stream-cells must be >= 1")
+    if a.stream_tol is not None and not (a.stream_tol >= 0 and a.stream_tol < math.inf):
+        ap.error("--stream-tol must be finite and >= 0")
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
@@ -729,7 +881,8 @@ def main(argv=None):
                                   objects=objects, area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10,
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
                                   min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges,
-                                  compare=a.compare, sinks=a.sinks)
+                                  compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
+                                  stream_tol_m=a.stream_tol)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -742,12 +895,16 @@ def main(argv=None):
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
         if a.sinks:
             rep["sinks"] = sink_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata)
+        drn = {"drainage": a.drainage, "stream_cells": a.stream_cells, "stream_tol_m": a.stream_tol}
+        if a.drainage:
+            rep["drainage"] = drainage_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, stream_cells=a.stream_cells,
+                                              stream_tol_m=a.stream_tol)
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
-                                              solver=a.solver, depth_edges_m=depth_edges, sinks=a.sinks)
+                                              solver=a.solver, depth_edges_m=depth_edges, sinks=a.sinks, **drn)
         if a.compare:
             rep["compare"] = compare_report(dem, hm, keep, a.compare, cellsize=c, mask=mask, nodata=nodata,
-                                            depth_edges_m=depth_edges, sinks=a.sinks)
+                                            depth_edges_m=depth_edges, sinks=a.sinks, **drn)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -762,6 +919,8 @@ def main(argv=None):
     print(summary(rep))
     if "sinks" in rep:
         print(sinks_summary(rep["sinks"]))
+    if "drainage" in rep:
+        print(drainage_summary(rep["drainage"]))
     if "seam" in rep:
         sm = rep["seam"]
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
@@ -771,10 +930,14 @@ def main(argv=None):
         print(f"baseline {rep['baseline']['method']}{how}: {summary(rep['baseline'])}")
         if "sinks" in rep["baseline"]:
             print(f"baseline {rep['baseline']['method']} {sinks_summary(rep['baseline']['sinks'])}")
+        if "drainage" in rep["baseline"]:
+            print(f"baseline {rep['baseline']['method']} {drainage_summary(rep['baseline']['drainage'])}")
     for name, r in rep.get("compare", {}).items():
         print(f"compare {name}: {summary(r)}")
         if "sinks" in r:
             print(f"compare {name} {sinks_summary(r['sinks'])}")
+        if "drainage" in r:
+            print(f"compare {name} {drainage_summary(r['drainage'])}")
     return rep
 
 

@@ -28,8 +28,13 @@ the others follow a decreasing D, and direction is still a forest.
 info: known, unknown, outlets, flat_cells (pixels that got their code from D), pits, max_accumulation, max_area_m2 = cellsize^2 *
 max_accumulation, flat_sweeps, tile_visits (both may differ between runs; the rasters do not), acc_rounds, converged, filled.
 
+watersheds(direction, pour_points) follows every pixel's path to its end by a gather-only pointer doubling (csrc/drainage.hip,
+DESIGN.md section 8w): the basin of every pixel (the pixel its water ends at, or a pour point on the way) and the length of the
+path there in metres, exact and bitwise reproducible.
+
 CLI: python -m mvp_gan.src.flow_routing --dem in.asc --dir-out d.asc --acc-out a.asc [--mask m.png|m.asc] [--nodata v]
          [--no-fill] [--esri] [--streams-out s.asc --min-cells n] [--max-sweeps n]       (cellsize from the header)
+         [--basins-out b.asc [--pour p.png|p.asc] [--compact]] [--length-out l.asc]
 """
 import argparse
 import math
@@ -108,7 +113,6 @@ def flow_routing(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, max_sw
     """dem: float32 [H][W] (numpy or HIP tensor); mask: same shape, nonzero = known (optional).  Returns (direction uint8 HIP
     tensor [H][W], accumulation int32 HIP tensor [H][W], info)."""
     from tg_hip import ops as O
-    from .fill_depressions import relax
     from .fill_voids import _device_f32
     who = "flow_routing"
     H, W, c = check_args(dem, mask, cellsize, 8, max_sweeps, check_every, who=who)
@@ -122,6 +126,17 @@ def flow_routing(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, max_sw
     if nodata is not None and math.isnan(nodata):
         nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
     known, _ = O.objmask_known(z, m, nodata, transposed=False)
+    return route_known(z, known, c, fill=fill, max_sweeps=max_sweeps, check_every=check_every)
+
+
+def route_known(z, known, cellsize, *, fill=True, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY):
+    """flow_routing's body on device tensors with a ready known mask: z float32 [H][W], known uint8 [H][W] (tg_objmask_known's
+    map, or the intersection of two) -> (direction, accumulation, info)."""
+    from tg_hip import ops as O
+    from .fill_depressions import relax
+    H, W = z.shape
+    c = cellsize
+    device = z.device
     converged = True
     if fill:
         state, _, _, _, converged = relax(z, known, 8, max_sweeps, check_every)
@@ -141,6 +156,100 @@ def flow_routing(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, max_sw
     return direction, acc, info
 
 
+# ---- watersheds and flow length ---------------------------------------------------------------------------------------
+SQRT2 = 1.4142135623730951
+
+
+def _bits_f32(b):
+    return float(np.array([int(b) & 0xffffffff], np.uint32).view(np.float32)[0])
+
+
+def _device_u8(a, device, what, who, nonzero=False):
+    """A direction grid (uint8 as given) or a pour raster (any numeric type, nonzero -> 1) as a uint8 HIP tensor."""
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError(f"{who}: {what} is on {a.device}; pass a numpy array or a HIP tensor")
+        a = (a != 0) if nonzero else a
+        return a.to(device=device, dtype=torch.uint8).contiguous()
+    a = np.asarray(a)
+    a = (a != 0) if nonzero else a
+    return torch.from_numpy(np.array(a, dtype=np.uint8, order="C")).to(device)      # a copy: the input may be read-only
+
+
+def check_watershed_args(direction, pour_points, cellsize, compact, check_every, who="watersheds"):
+    """Host-side rejection before any launch; -> (H, W, cellsize)."""
+    from .fill_depressions import _cellsize, _count, _shape
+    shape = _shape(direction)
+    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
+        raise ValueError(f"{who}: direction must be [H, W], non-empty with H*W < 2^31, got {shape}")
+    dt = direction.dtype if isinstance(direction, (torch.Tensor, np.ndarray)) else None
+    if dt not in (torch.uint8, np.dtype(np.uint8)):
+        raise ValueError(f"{who}: direction must be a uint8 grid of flow_routing's codes, got {dt}")
+    if pour_points is not None and _shape(pour_points) != shape:
+        raise ValueError(f"{who}: pour_points {_shape(pour_points)} differs from the direction grid {shape}")
+    if not isinstance(compact, bool):
+        raise ValueError(f"{who}: compact {compact!r} must be True or False")
+    _count(check_every, 1, "check_every", who)
+    return shape[0], shape[1], _cellsize(cellsize, who)
+
+
+def basin_doubling(d, pour, ws, check_every=CHECK_EVERY):
+    """The doubling on device tensors (d uint8 [H][W], pour uint8 [H][W] or None) -> (rounds, pour points used, ignored); the
+    records stay in ws for ops.flow_basin_finish.  One host sync per check_every rounds."""
+    from tg_hip import ops as O
+    H, W = d.shape
+    pc = O.flow_basin_init(d, pour, ws)
+    state = torch.empty(2, dtype=torch.int32, device=d.device)
+    k, left, rounds = 0, 1, 0
+    while left and k < ACC_MAX_ROUNDS:
+        n = min(check_every, ACC_MAX_ROUNDS - k)
+        O.flow_basin(H, W, k, n, state, ws)
+        k += n
+        left, rounds = state.cpu().tolist()
+    if left:
+        raise RuntimeError("watersheds: the direction grid has a cycle")
+    used, ignored = pc.cpu().tolist()
+    return rounds, used, ignored
+
+
+def compact_labels(basin):
+    """basin int32 [H][W] of terminal indices (-1 unknown) -> the rank 1..n of the terminal in raster order, 0 where unknown."""
+    flat = basin.reshape(-1)
+    idx = torch.arange(flat.numel(), dtype=torch.int32, device=flat.device)
+    rank = torch.cumsum((flat == idx).to(torch.int32), 0, dtype=torch.int32)
+    out = rank[flat.clamp(min=0).long()]
+    return torch.where(flat >= 0, out, torch.zeros_like(out)).reshape(basin.shape)
+
+
+@torch.no_grad()
+def watersheds(direction, pour_points=None, *, cellsize=1.0, compact=False, check_every=CHECK_EVERY):
+    """direction: uint8 [H][W] of flow_routing's codes (numpy or HIP tensor); pour_points: same shape, nonzero = pour point
+    (optional).  Every pixel's path is followed to its last pixel T: an OUT, a PIT, a pour point, or a pixel whose receiver
+    lies off the raster.  Returns (basin int32 HIP tensor [H][W]: T as y * W + x, -1 where unknown; with compact=True the rank
+    1..n of T in raster order, 0 where unknown; length_m float32 HIP tensor [H][W] = float32(cellsize * (nc + sqrt(2) nd)) for
+    nc cardinal and nd diagonal steps to T, in float64 with SQRT2; info: basins, rounds, longest_steps, max_length_m,
+    pour_points, pour_ignored).  Exact and bitwise reproducible (csrc/drainage.hip)."""
+    from tg_hip import ops as O
+    who = "watersheds"
+    H, W, c = check_watershed_args(direction, pour_points, cellsize, compact, check_every, who)
+    if not torch.cuda.is_available():
+        raise RuntimeError("watersheds: no HIP device visible; this build has no CPU path")
+    device = torch.device("cuda", torch.cuda.current_device())
+    d = _device_u8(direction, device, "direction", who)
+    if bool(torch.any(d == 254)):
+        raise ValueError(f"{who}: the direction grid holds the code 254 (undecided): route it to the end first")
+    pour = None if pour_points is None else _device_u8(pour_points, device, "pour_points", who, nonzero=True)
+    ws = O.flow_basin_ws(H, W, device)
+    rounds, used, ignored = basin_doubling(d, pour, ws, check_every)
+    basin, _, _, length, counts = O.flow_basin_finish(H, W, rounds, ws, c)
+    terminals, longest, bits = counts.cpu().tolist()
+    if compact:
+        basin = compact_labels(basin)
+    info = {"basins": terminals, "rounds": rounds, "longest_steps": longest, "max_length_m": _bits_f32(bits),
+            "pour_points": used, "pour_ignored": ignored}
+    return basin, length, info
+
+
 # ---- CLI ------------------------------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(description="D8 flow directions and flow accumulation of an ESRI ASCII grid DEM: depressions "
@@ -155,6 +264,13 @@ def build_parser():
                                                                        "sweeps each even if not converged")
     ap.add_argument("--streams-out", help="also write the stream mask (.asc): 1 where the accumulation >= --min-cells")
     ap.add_argument("--min-cells", type=int, help="stream threshold in cells (required with --streams-out)")
+    ap.add_argument("--basins-out", help="also write the watershed labels (.asc): the linear index y * ncols + x of the pixel each "
+                                         "cell drains to, -1 = void")
+    ap.add_argument("--pour", help="pour points for --basins-out (.png or .asc of the raster's size): nonzero = a cell where "
+                                   "paths end, so that its upstream area is a basin of its own")
+    ap.add_argument("--compact", action="store_true", help="with --basins-out: number the basins 1..n in raster order of their "
+                                                           "outlets, 0 = void")
+    ap.add_argument("--length-out", help="also write the flow length to the outlet in metres (.asc, full float32 precision)")
     ap.add_argument("--dir-out", required=True, help="output .asc raster of direction codes")
     ap.add_argument("--acc-out", required=True, help="output .asc raster of the flow accumulation in cells")
     return ap
@@ -167,6 +283,10 @@ def parse_args(argv=None):
         ap.error("--streams-out and --min-cells go together")
     if a.min_cells is not None and a.min_cells < 1:
         ap.error("--min-cells must be >= 1")
+    if a.compact and not a.basins_out:
+        ap.error("--compact needs --basins-out")
+    if a.pour and not (a.basins_out or a.length_out):
+        ap.error("--pour needs --basins-out or --length-out")
     return a
 
 
@@ -185,7 +305,7 @@ def write_int_asc(path, arr, header):
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc
+    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
     a = parse_args(argv)
     dem, header = read_asc(a.dem)
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
@@ -196,6 +316,17 @@ def main(argv=None):
     write_int_asc(a.acc_out, acc.cpu().numpy(), header)
     if a.streams_out:
         write_int_asc(a.streams_out, streams(acc, a.min_cells).cpu().numpy(), header)
+    if a.basins_out or a.length_out:
+        pour = _read_mask(a.pour, dem.shape) if a.pour else None
+        basin, length, winfo = watersheds(direction, pour, cellsize=float(asc_value(header, "cellsize")), compact=a.compact)
+        if a.basins_out:
+            write_int_asc(a.basins_out, basin.cpu().numpy(), header)
+        if a.length_out:
+            write_asc(a.length_out, length.cpu().numpy(), [(k, v) for k, v in header if k.lower() != "nodata_value"])
+        info["watersheds"] = winfo
+        print(f"{a.basins_out or a.length_out}: {winfo['basins']} basins, longest path {winfo['longest_steps']} steps = "
+              f"{winfo['max_length_m']:.9g} m, {winfo['rounds']} rounds, {winfo['pour_points']} pour points"
+              + (f" ({winfo['pour_ignored']} on voids ignored)" if winfo["pour_ignored"] else ""))
     how = "" if info["converged"] else f" (NOT converged after {info['flat_sweeps']} flat sweeps: unresolved flat cells are pits)"
     print(f"{a.dir_out}: {info['known']} cells, {info['outlets']} outlets, {info['flat_cells']} flat cells, {info['pits']} pits, "
           f"largest contributing area {info['max_accumulation']} cells = {info['max_area_m2']:.6g} m2, "

@@ -55,6 +55,7 @@ class TgDepthClasses(C.Structure):
 
 
 TG_FLOW_OUT, TG_FLOW_UNDECIDED, TG_FLOW_PIT, TG_FLOW_FAR, TG_FLOW_MAX_ROUNDS = 9, 254, 255, 0x7fffffff, 32
+TG_FLOW_BASIN_COUNTS, TG_FLOW_COMPARE_COUNTS = 3, 19
 
 
 class TgError(RuntimeError):
@@ -200,6 +201,11 @@ SIGNATURES = {
     "tg_flow_accum_init": (I, [P, I, I, P, SZ, P]),
     "tg_flow_accum": (I, [I, I, I, I, P, P, SZ, P]),
     "tg_flow_accum_finish": (I, [I, I, I, P, P, P, SZ, P]),
+    "tg_flow_basin_ws_bytes": (SZ, [I, I]),
+    "tg_flow_basin_init": (I, [P, P, I, I, P, P, SZ, P]),
+    "tg_flow_basin": (I, [I, I, I, I, P, P, SZ, P]),
+    "tg_flow_basin_finish": (I, [I, I, I, D, P, P, P, P, P, P, SZ, P]),
+    "tg_flow_compare": (I, [P, P, P, P, P, P, P, P, P, I, I, C.c_int32, C.c_int32, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

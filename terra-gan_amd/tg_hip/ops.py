@@ -1498,7 +1498,91 @@ def flow_accum_finish(H, W, rounds, ws):
     return acc, amax
 
 
-VFILL_NSTATS = 4                                 # tg_vfill_setup stats: known, unknown, min bits, max bits
+FLOW_BASIN_COUNTS, FLOW_COMPARE_COUNTS = L.TG_FLOW_BASIN_COUNTS, L.TG_FLOW_COMPARE_COUNTS
+# tg_flow_compare's counters in order
+FLOW_COMPARE_NAMES = ("cells", "dir_equal", "dir_routed", "dir_within_45", "same_outlet", "outlet_d2_sum", "outlet_d2_max",
+                      "area_octave_sum", "streams_truth", "streams_pred", "streams_both", "pred_matched", "pred_far", "pred_d2_sum",
+                      "pred_d2_max", "truth_matched", "truth_far", "truth_d2_sum", "truth_d2_max")
+
+
+def flow_basin_ws(H, W, device):
+    """The workspace of one watershed labelling: uint8 [tg_flow_basin_ws_bytes]; it carries the two planes of records from
+    flow_basin_init through the flow_basin calls to flow_basin_finish, so it is the caller's and not the shared one."""
+    n = _lib().tg_flow_basin_ws_bytes(int(H), int(W))
+    if n == 0:
+        raise L.TgError(f"flow_basin: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _flow_basin_ws_chk(ws, H, W):
+    need = _lib().tg_flow_basin_ws_bytes(H, W)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+            and ws.data_ptr() % 16 == 0):
+        raise L.TgError(f"flow_basin: ws must be a contiguous uint8 HIP tensor of at least {need} bytes, aligned to 16 "
+                        "(flow_basin_ws)")
+
+
+def flow_basin_init(d, pour, ws):
+    """The start records of the watershed doubling from the codes d (uint8 [H][W], without TG_FLOW_UNDECIDED) and the pour
+    points (uint8 [H][W], nonzero = terminal, or None) into ws -> counts int64 [2]: pour points that became terminals, pour
+    points ignored on unknown pixels (tg_flow_basin_init)."""
+    H, W = _raster_hw(d, "dir")
+    _hip(d, torch.uint8, (H, W), "dir")
+    if pour is not None:
+        _hip(pour, torch.uint8, (H, W), "pour")
+    _flow_basin_ws_chk(ws, H, W)
+    counts = torch.empty(2, dtype=torch.int64, device=d.device)
+    L.check(_lib().tg_flow_basin_init(_p(d), _p(pour), H, W, _p(counts), _p(ws), ws.numel(), _stream()), "tg_flow_basin_init")
+    return counts
+
+
+def flow_basin(H, W, k0, n, state, ws):
+    """Rounds k0 .. k0 + n - 1 of the watershed doubling; state int32 [2] = pointers left, rounds that ran (tg_flow_basin)."""
+    _flow_basin_ws_chk(ws, int(H), int(W))
+    _hip(state, torch.int32, (2,), "state")
+    _flow_count(k0, 0, L.TG_FLOW_MAX_ROUNDS, "k0", "flow_basin")
+    _flow_count(n, 1, L.TG_FLOW_MAX_ROUNDS - k0, "n", "flow_basin")
+    L.check(_lib().tg_flow_basin(int(H), int(W), k0, n, _p(state), _p(ws), ws.numel(), _stream()), "tg_flow_basin")
+
+
+def flow_basin_finish(H, W, rounds, ws, cellsize=1.0, want_steps=False, want_length=True):
+    """-> (basin int32 [H][W]: the last pixel reached, -1 at unknown pixels; nc, nd int32 [H][W] or None: cardinal and diagonal
+    steps; length_m float32 [H][W] or None; counts int64 [FLOW_BASIN_COUNTS]: terminals, the largest nc + nd, the bits of the
+    largest length) after `rounds` rounds (tg_flow_basin_finish)."""
+    H, W = int(H), int(W)
+    _flow_basin_ws_chk(ws, H, W)
+    _flow_count(rounds, 0, L.TG_FLOW_MAX_ROUNDS, "rounds", "flow_basin_finish")
+    c = float(cellsize)
+    if not (c > 0 and c < float("inf")):
+        raise L.TgError(f"flow_basin_finish: cellsize {cellsize!r} must be finite and > 0")
+    dev = ws.device
+    basin = torch.empty(H, W, dtype=torch.int32, device=dev)
+    nc = torch.empty(H, W, dtype=torch.int32, device=dev) if want_steps else None
+    nd = torch.empty(H, W, dtype=torch.int32, device=dev) if want_steps else None
+    length = torch.empty(H, W, dtype=torch.float32, device=dev) if want_length else None
+    counts = torch.empty(FLOW_BASIN_COUNTS, dtype=torch.int64, device=dev)
+    L.check(_lib().tg_flow_basin_finish(H, W, rounds, c, _p(basin), _p(nc), _p(nd), _p(length), _p(counts), _p(ws), ws.numel(),
+                                        _stream()), "tg_flow_basin_finish")
+    return basin, nc, nd, length, counts
+
+
+def flow_compare(sel, dir_t, dir_p, basin_t, basin_p, acc_t, acc_p, d2_t, d2_p, stream_cells, tol2):
+    """-> counts int64 [FLOW_COMPARE_COUNTS] (FLOW_COMPARE_NAMES) of two routings over the pixels with sel != 0 and both
+    directions != 0 (tg_flow_compare).  sel, dir_*: uint8 [H][W]; basin_*, acc_*, d2_*: int32 [H][W]; sides at most EDT_MAX_SIDE."""
+    H, W = _edt_hw(sel, "sel")
+    for t, name in ((sel, "sel"), (dir_t, "dir_t"), (dir_p, "dir_p")):
+        _hip(t, torch.uint8, (H, W), name)
+    for t, name in ((basin_t, "basin_t"), (basin_p, "basin_p"), (acc_t, "acc_t"), (acc_p, "acc_p"), (d2_t, "d2_t"), (d2_p, "d2_p")):
+        _hip(t, torch.int32, (H, W), name)
+    _flow_count(stream_cells, 1, 2 ** 31 - 1, "stream_cells", "flow_compare")
+    _flow_count(tol2, 0, EDT_FAR - 1, "tol2", "flow_compare")
+    counts = torch.empty(FLOW_COMPARE_COUNTS, dtype=torch.int64, device=sel.device)
+    L.check(_lib().tg_flow_compare(_p(sel), _p(dir_t), _p(dir_p), _p(basin_t), _p(basin_p), _p(acc_t), _p(acc_p), _p(d2_t),
+                                   _p(d2_p), H, W, stream_cells, tol2, _p(counts), _stream()), "tg_flow_compare")
+    return counts
+
+
+VFILL_NSTATS = 4                                # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
 def vfill_ws(H, W, device):
