@@ -873,6 +873,64 @@ int tg_flow_compare(const uint8_t* sel, const uint8_t* dir_t, const uint8_t* dir
                     const int32_t* acc_t, const int32_t* acc_p, const int32_t* d2_t, const int32_t* d2_p, int H, int W,
                     int32_t stream_cells, int32_t tol2, int64_t* counts, tg_stream_t stream);
 
+/* ---- Stream classes, links, Strahler order, height above the nearest drainage, flood comparison (csrc/drainage.hip, DESIGN.md
+ * 8x) ------------------------------------------------------------------------------------------------------------------------
+ * dir [H][W] uint8 as in the section above; acc [H][W] int32 is any accumulation plane (it need not belong to dir).  A stream
+ * pixel has dir != 0 and acc >= min_cells (>= 1).  A stream donor of p is a stream pixel with a code 1..8 whose receiver is p; sd(p)
+ * is their number.  Class (uint8): 0 not a stream, TG_STREAM_HEAD (sd = 0), TG_STREAM_INTERIOR (sd = 1), TG_STREAM_JUNCTION
+ * (sd >= 2).  up(p) is the one stream donor of an interior pixel, -1 elsewhere; top(p) is the end of p's up chain (top(p) = p for
+ * heads and junctions): the upstream end of p's link.  Strahler order: 1 for a head, the donor's for an interior pixel, for a
+ * junction max(m1, m2 + 1) with m1 >= m2 the two largest orders among its stream donors; constant along a link.
+ * Sides as tg_objmask_known (H, W >= 1, H * W < 2^31). */
+#define TG_STREAM_HEAD 1
+#define TG_STREAM_INTERIOR 2
+#define TG_STREAM_JUNCTION 3
+#define TG_STREAM_ORDER_BINS 15
+#define TG_STREAM_ORDER_COUNTS (1 + 2 * TG_STREAM_ORDER_BINS)
+#define TG_FLOOD_MAX_STAGES 8
+#define TG_FLOOD_COUNTS (6 + 3 * TG_FLOOD_MAX_STAGES)
+typedef struct {
+    float s[TG_FLOOD_MAX_STAGES];
+} tg_flood_stages;
+/* One pass: cls [H][W] uint8; order [H][W] int32 = 1 on stream pixels, 0 elsewhere (the start of tg_stream_order); and the start
+ * records of the upstream doubling in plane 0 of a tg_flow_basin workspace (ws >= tg_flow_basin_ws_bytes(H, W), aligned to 16
+ * bytes) with live[0]: (up, p, c, d) for an interior pixel, (c, d) = (1, 0) for a cardinal code of the donor and (0, 1) for a
+ * diagonal one; (-1, p, 0, 0) for heads and junctions; (-1, -1, 0, 0) off the streams.  After it tg_flow_basin's rounds and
+ * tg_flow_basin_finish give top (as basin; -1 off the streams), the cardinal and diagonal steps from top(p) down to p and their
+ * length.  counts [4] int64 (zeroed here) = stream pixels, heads, junctions, stream terminals (stream pixels whose receiver is
+ * not a stream pixel). */
+int tg_stream_class(const uint8_t* dir, const int32_t* acc, int H, int W, int32_t min_cells, uint8_t* cls, int32_t* order,
+                    int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* Enqueues n >= 1 rounds over the junctions [nj] int32 (the linear indices of the pixels of class TG_STREAM_JUNCTION, in any
+ * order; nj = 0 launches nothing).  In a round junction j reads order[top(q)] of its stream donors q (the neighbours with
+ * cls != 0 whose code points at j) and raises order[j] to max(m1, m2 + 1) if that is larger: in place, relaxed atomic loads at
+ * agent scope and atomicMax, so a round may see values of its own; the update is monotone and every iterate is a lower bound of
+ * the order, so any schedule ends at the same plane.  changed [1] int32 (zeroed here) = raises of the last of the n rounds (0: a
+ * fixed point).  An index junctions[i] or top[q] outside [0, H * W) is skipped. */
+int tg_stream_order(const uint8_t* dir, const uint8_t* cls, const int32_t* top, const int32_t* junctions, int nj, int H, int W,
+                    int n, int32_t* order, int32_t* changed, tg_stream_t stream);
+/* out [H][W] uint8 = order[top(p)] on stream pixels (at most 255), 0 elsewhere.  counts [TG_STREAM_ORDER_COUNTS] int64 (zeroed
+ * here) = the largest order; cells of order 1 .. TG_STREAM_ORDER_BINS; links (heads and junctions) of order 1 ..
+ * TG_STREAM_ORDER_BINS; higher orders go into the last bin. */
+int tg_stream_order_finish(const uint8_t* cls, const int32_t* top, const int32_t* order, int H, int W, uint8_t* out,
+                           int64_t* counts, tg_stream_t stream);
+/* Height above the nearest drainage.  w [H][W] fp32 is the routed surface, basin [H][W] int32 tg_flow_basin_finish's terminals
+ * with the drainage mask smask [H][W] uint8 as pour points.  p is drained when T = basin(p) lies in [0, H * W) and smask(T) != 0:
+ * hand(p) = w(p) - w(T), one fp32 subtract; NaN (0x7fc00000) elsewhere.  With length_m and distance_m (both or neither NULL)
+ * distance_m(p) = length_m(p) where drained, NaN elsewhere.  counts [4] int64 (zeroed here) = drained pixels, undrained pixels
+ * (basin >= 0, not drained), drainage pixels (smask != 0 and basin >= 0), the bits of the largest hand > 0. */
+int tg_hand(const float* w, const int32_t* basin, const uint8_t* smask, const float* length_m, int H, int W, float* hand,
+            float* distance_m, int64_t* counts, tg_stream_t stream);
+/* Two HAND planes compared over the pixels with sel != 0 (t = truth, p = the fill), stages s[0] < ... < s[k - 1], 1 <= k <=
+ * TG_FLOOD_MAX_STAGES, each finite and > 0.  counts [TG_FLOOD_COUNTS] int64 (zeroed here), exact in any order (per-wave shuffles,
+ * one 64-bit integer atomic per wave and non-zero counter):
+ *   0 cells (neither hand NaN); 1 undrained_t, 2 undrained_p (that side's hand NaN); over the cells: 3 abs_q10 = sum of
+ *   rint((double)|hp - ht| * 1024) with the difference and the absolute value in fp32 and the rounding half-to-even, 4 bias_q10 =
+ *   the same of hp - ht, signed; 5 abs_max_bits, the bits of the largest |hp - ht|; for stage i: 6 + 3 i wet_t (ht <= s[i]),
+ *   7 + 3 i wet_p, 8 + 3 i wet_both. */
+int tg_flood_compare(const uint8_t* sel, const float* hand_t, const float* hand_p, int H, int W, tg_flood_stages stages, int k,
+                     int64_t* counts, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

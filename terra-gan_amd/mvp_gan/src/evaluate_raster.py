@@ -50,11 +50,18 @@ compares their D8 directions, outlets, contributing areas and stream networks (a
 integers; report["baseline"] and every report["compare"][name] gain the same key.  Without it the report has no "drainage" key
 and nothing more runs.
 
+With flood=True the report also says whether a flood map made from a fill wets the ground that one made from the true terrain
+wets (flood_errors; DESIGN.md section 8x): both surfaces are routed as above, each side's height above its nearest drainage (HAND;
+streams of stream_cells cells) is taken, and report["flood"] compares the two HAND planes and the flood extents HAND <= stage at
+flood_stages_m inside the holes, in integers; report["baseline"] and every report["compare"][name] gain the same key.  Without it
+the report has no "flood" key and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
+         [--flood [--flood-stages s ...]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -439,6 +446,8 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
 
 # ---- end to end -----------------------------------------------------------------------------------------------------
 BASELINES = ("laplace", "biharmonic")
+FLOOD_STAGES_M = (0.5, 1.0, 2.0, 5.0)                  # the default stages of flood_errors
+FLOOD_MAX_STAGES = 8                                   # TG_FLOOD_MAX_STAGES
 
 
 def _check_fill_options(baseline, fallback, who="evaluate_raster"):
@@ -451,9 +460,10 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 @torch.no_grad()
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
-                    stream_tol_m=None):
+                    stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
-    fill info under "fill"; with sinks also sink_errors' dict under "sinks", with drainage drainage_errors' under "drainage"."""
+    fill info under "fill"; with sinks also sink_errors' dict under "sinks", with drainage drainage_errors' under "drainage",
+    with flood flood_errors' under "flood"."""
     from .fill_voids import fill_voids
     device = _device()
     z = _f32(dem, device, "dem")
@@ -468,6 +478,9 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     if drainage:
         rep["drainage"] = drainage_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
                                           stream_tol_m=stream_tol_m)
+    if flood:
+        rep["flood"] = flood_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                    stages_m=flood_stages_m)
     return rep
 
 
@@ -489,9 +502,10 @@ def _check_compare(compare, who="evaluate_raster"):
     return names
 
 
-def assemble_compare(reports, infos, sinks=None, drainage=None):
+def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None):
     """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name; with sinks
-    ({name: sink_errors' dict}) also "sinks", with drainage ({name: drainage_errors' dict}) also "drainage"."""
+    ({name: sink_errors' dict}) also "sinks", with drainage ({name: drainage_errors' dict}) also "drainage", with flood ({name:
+    flood_errors' dict}) also "flood"."""
     out = {}
     for name, rep in reports.items():
         out[name] = dict(rep)
@@ -501,19 +515,21 @@ def assemble_compare(reports, infos, sinks=None, drainage=None):
             out[name]["sinks"] = sinks[name]
         if drainage is not None:
             out[name]["drainage"] = drainage[name]
+        if flood is not None:
+            out[name]["flood"] = flood[name]
     return out
 
 
 @torch.no_grad()
 def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
                    quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
-                   stream_tol_m=None):
+                   stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M):
     """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
     from .interpolate import interpolate_voids
     device = _device()
     z = _f32(dem, device, "dem")
     k = _f32(keep, device, "keep", binary=True)
-    reports, infos, snk, drn = {}, {}, {}, {}
+    reports, infos, snk, drn, fld = {}, {}, {}, {}, {}
     for name in _check_compare(names):
         pred, infos[name] = interpolate_voids(z, k, nodata=_nodata(nodata), method=name, cellsize=cellsize)
         reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
@@ -523,7 +539,10 @@ def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None,
         if drainage:
             drn[name] = drainage_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
                                         stream_tol_m=stream_tol_m)
-    return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None)
+        if flood:
+            fld[name] = flood_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                     stages_m=flood_stages_m)
+    return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None, fld if flood else None)
 
 
 # ---- sinks: does a fill drain ---------------------------------------------------------------------------------------------
@@ -693,11 +712,106 @@ def drainage_summary(d):
             f"{f(s['pred_to_truth_max_m'], '.4g')} m")
 
 
+# ---- flood: does a flood map made from a fill wet the ground the truth's does -----------------------------------------------
+def check_flood_stages(stages_m, who="flood_errors"):
+    """1 to 8 stages in metres, each finite and > 0 and strictly increasing, also after the rounding to float32 the kernel gets
+    them in -> a tuple of floats (the float32 values)."""
+    try:
+        vals = [float(v) for v in stages_m]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: flood stages {stages_m!r} must be a sequence of numbers") from None
+    if any(isinstance(v, bool) for v in stages_m) or not 1 <= len(vals) <= FLOOD_MAX_STAGES:
+        raise ValueError(f"{who}: flood stages {stages_m!r} must be 1 to {FLOOD_MAX_STAGES} numbers")
+    with np.errstate(over="ignore"):
+        f = np.array(vals, np.float64).astype(np.float32)
+    if not (np.isfinite(f).all() and (f > 0).all()):
+        raise ValueError(f"{who}: flood stages {stages_m!r} must be finite and > 0")
+    if not (np.diff(f) > 0).all():
+        raise ValueError(f"{who}: flood stages {stages_m!r} must be strictly increasing")
+    return tuple(float(v) for v in f)
+
+
+def assemble_flood(counts, stages_m, *, stream_cells):
+    """The flood dict from tg_flood_compare's counters (a sequence of at least 6 + 3 * len(stages_m) integers) (pure: no GPU).
+    hand: mean absolute, mean signed (fill minus truth) and largest difference of the two HAND planes over the cells compared,
+    from the exact integer sums in 1/1024 m; per stage the cells each side wets (HAND <= stage), those both wet, the critical
+    success index both / (truth + pred - both), precision both / pred and recall both / truth; None on a zero denominator."""
+    c = [int(v) for v in counts]
+    stages = [float(s) for s in stages_m]
+    if len(c) < 6 + 3 * len(stages):
+        raise ValueError(f"assemble_flood: {len(c)} counters for {len(stages)} stages")
+    cells, und_t, und_p, abs_q, bias_q, max_bits = c[:6]
+    ratio = lambda a, b: a / b if b else None
+    out = {"cells": cells, "stream_cells": int(stream_cells), "undrained_truth": und_t, "undrained_pred": und_p,
+           "hand": {"mae_m": ratio(abs_q / 1024, cells), "bias_m": ratio(bias_q / 1024, cells),
+                    "max_m": _f32bits(max_bits) if cells else None},
+           "stages": []}
+    for i, s in enumerate(stages):
+        t, p, b = c[6 + 3 * i:9 + 3 * i]
+        out["stages"].append({"stage_m": s, "truth_cells": t, "pred_cells": p, "both_cells": b, "csi": ratio(b, t + p - b),
+                              "precision": ratio(b, p), "recall": ratio(b, t)})
+    return out
+
+
+@torch.no_grad()
+def flood_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, stream_cells=1000, stages_m=FLOOD_STAGES_M):
+    """flood_errors' measurement -> (counts: tg_flood_compare's counters as a list of ints, the stages as given to the kernel,
+    [truth side, pred side]: each hand_from_routing's info)."""
+    from tg_hip import ops as O
+    from .flow_routing import hand_from_routing, route_known
+    who = "flood_errors"
+    c = _cellsize(cellsize, who)
+    _inputs(dem, mask, who)
+    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
+        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    _check_stream_cells(stream_cells, who)
+    stages = check_flood_stages(stages_m, who)
+    device = _device()
+    z = _f32(dem, device, "dem")
+    p = _f32(pred, device, "pred")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    sel = _u8(holes, device)
+    kz, _ = O.objmask_known(z, m, _nodata(nodata), transposed=False)
+    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
+    known = kz & kp
+    hands, sides = [], []
+    for surf in (z, p):
+        direction, acc, _, w = route_known(surf, known, c, fill=True, return_surface=True)
+        stream = ((acc >= stream_cells) & (direction != 0)).to(torch.uint8)
+        h, _, hinfo = hand_from_routing(w, direction, stream, c)
+        hands.append(h)
+        sides.append(hinfo)
+    counts = O.flood_compare(sel, hands[0], hands[1], stages)
+    return counts.cpu().tolist(), stages, sides
+
+
+def flood_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, stream_cells=1000, stages_m=FLOOD_STAGES_M):
+    """Does a flood map made from a fill wet the ground that one made from the true terrain wets.  dem and pred are routed
+    (flow_routing's chain with fill=True) over one known mask, the pixels known in both; each side's height above the nearest
+    drainage (flow_routing.hand_from_routing) is taken against its own streams (accumulation >= stream_cells); the flood extent
+    of a side at stage s is HAND <= s.  Inside holes (nonzero = hole) one pass counts in integers, over the pixels where both
+    sides are drained: the HAND differences, and per stage the cells each side wets and those both wet.  -> assemble_flood's
+    dict."""
+    counts, stages, _ = flood_raw(dem, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                  stages_m=stages_m)
+    return assemble_flood(counts, stages, stream_cells=stream_cells)
+
+
+def flood_summary(d):
+    """One line for a flood dict."""
+    f = lambda v, spec: "n/a" if v is None else format(v, spec)
+    st = ", ".join(f"{s['stage_m']:g} m {f(s['csi'], '.3f')}" for s in d["stages"])
+    return (f"flood: HAND MAE {f(d['hand']['mae_m'], '.4g')} m, bias {f(d['hand']['bias_m'], '.4g')} m, max "
+            f"{f(d['hand']['max_m'], '.4g')} m over {d['cells']} px (streams >= {d['stream_cells']} cells; undrained "
+            f"{d['undrained_truth']} truth / {d['undrained_pred']} fill); CSI by stage: {st}")
+
+
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
-                    solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None):
+                    solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
+                    flood=False, flood_stages_m=FLOOD_STAGES_M):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -707,20 +821,21 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     adds report["compare"][name], the interpolate_voids fill of the same keep mask scored on the same holes and classes.
     sinks=True adds sink_errors' dict under "sinks" to the report, to report["baseline"] and to every report["compare"][name];
     drainage=True adds drainage_errors' dict (streams of stream_cells cells, matched within stream_tol_m) under "drainage" to the
-    same three places."""
+    same three places; flood=True adds flood_errors' dict (HAND against streams of stream_cells cells, flood extents at
+    flood_stages_m) under "flood" to the same three places."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
                              seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
                              depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
-                             stream_cells=stream_cells, stream_tol_m=stream_tol_m)
+                             stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
-              stream_tol_m=None):
+              stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
@@ -738,6 +853,9 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
             raise ValueError(f"evaluate_raster: drainage needs sides of at most 32767 px, got {H}x{W}")
         _check_stream_cells(stream_cells, "evaluate_raster")
         stream_tolerance(c, stream_tol_m, "evaluate_raster")
+    if flood:
+        _check_stream_cells(stream_cells, "evaluate_raster")
+        check_flood_stages(flood_stages_m, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
@@ -760,10 +878,14 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["seam"] = sinfo
     if sinks:
         rep["sinks"] = sink_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata)
-    drn = {"drainage": bool(drainage), "stream_cells": stream_cells, "stream_tol_m": stream_tol_m}
+    drn = {"drainage": bool(drainage), "stream_cells": stream_cells, "stream_tol_m": stream_tol_m, "flood": bool(flood),
+           "flood_stages_m": flood_stages_m}
     if drainage:
         rep["drainage"] = drainage_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, stream_cells=stream_cells,
                                           stream_tol_m=stream_tol_m)
+    if flood:
+        rep["flood"] = flood_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, stream_cells=stream_cells,
+                                    stages_m=flood_stages_m)
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
@@ -846,6 +968,13 @@ def build_parser():
     ap.add_argument("--stream-tol", type=float, metavar="M",
                     help="with --drainage: a stream cell is matched when the other side has one within this many metres "
                          "(default: 3 cells)")
+    ap.add_argument("--flood", action="store_true",
+                    help="also compare flood maps: the height above the nearest drainage (streams of --stream-cells cells) of the "
+                         "truth and of every scored fill, and the flood extents at --flood-stages inside the holes: one more "
+                         "summary line per fill")
+    ap.add_argument("--flood-stages", type=float, nargs="+", metavar="S", default=list(FLOOD_STAGES_M),
+                    help="with --flood: 1 to 8 water stages above the drainage in metres, increasing (default: "
+                         + " ".join(f"{s:g}" for s in FLOOD_STAGES_M) + ")")
     return ap
 
 
@@ -858,6 +987,10 @@ def main(argv=None):
         ap.error("--stream-cells must be >= 1")
     if a.stream_tol is not None and not (a.stream_tol >= 0 and a.stream_tol < math.inf):
         ap.error("--stream-tol must be finite and >= 0")
+    try:
+        check_flood_stages(a.flood_stages, "--flood-stages")
+    except ValueError as e:
+        ap.error(str(e))
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
@@ -882,7 +1015,7 @@ def main(argv=None):
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
                                   min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges,
                                   compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
-                                  stream_tol_m=a.stream_tol)
+                                  stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages))
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -895,10 +1028,14 @@ def main(argv=None):
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
         if a.sinks:
             rep["sinks"] = sink_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata)
-        drn = {"drainage": a.drainage, "stream_cells": a.stream_cells, "stream_tol_m": a.stream_tol}
+        drn = {"drainage": a.drainage, "stream_cells": a.stream_cells, "stream_tol_m": a.stream_tol, "flood": a.flood,
+               "flood_stages_m": tuple(a.flood_stages)}
         if a.drainage:
             rep["drainage"] = drainage_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, stream_cells=a.stream_cells,
                                               stream_tol_m=a.stream_tol)
+        if a.flood:
+            rep["flood"] = flood_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, stream_cells=a.stream_cells,
+                                        stages_m=tuple(a.flood_stages))
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
                                               solver=a.solver, depth_edges_m=depth_edges, sinks=a.sinks, **drn)
@@ -921,6 +1058,8 @@ def main(argv=None):
         print(sinks_summary(rep["sinks"]))
     if "drainage" in rep:
         print(drainage_summary(rep["drainage"]))
+    if "flood" in rep:
+        print(flood_summary(rep["flood"]))
     if "seam" in rep:
         sm = rep["seam"]
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
@@ -932,12 +1071,16 @@ def main(argv=None):
             print(f"baseline {rep['baseline']['method']} {sinks_summary(rep['baseline']['sinks'])}")
         if "drainage" in rep["baseline"]:
             print(f"baseline {rep['baseline']['method']} {drainage_summary(rep['baseline']['drainage'])}")
+        if "flood" in rep["baseline"]:
+            print(f"baseline {rep['baseline']['method']} {flood_summary(rep['baseline']['flood'])}")
     for name, r in rep.get("compare", {}).items():
         print(f"compare {name}: {summary(r)}")
         if "sinks" in r:
             print(f"compare {name} {sinks_summary(r['sinks'])}")
         if "drainage" in r:
             print(f"compare {name} {drainage_summary(r['drainage'])}")
+        if "flood" in r:
+            print(f"compare {name} {flood_summary(r['flood'])}")
     return rep
 
 

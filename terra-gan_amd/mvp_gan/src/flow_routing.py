@@ -32,9 +32,14 @@ watersheds(direction, pour_points) follows every pixel's path to its end by a ga
 DESIGN.md section 8w): the basin of every pixel (the pixel its water ends at, or a pour point on the way) and the length of the
 path there in metres, exact and bitwise reproducible.
 
+stream_network(direction, accumulation, min_cells) gives the streams their structure: the class of every
+stream pixel (head, interior, junction), the link it belongs to and its Strahler order; hand(dem, ...) the height of every pixel
+above the drainage pixel its water reaches first and the flow length to it.  Exact and bitwise reproducible as well.
+
 CLI: python -m mvp_gan.src.flow_routing --dem in.asc --dir-out d.asc --acc-out a.asc [--mask m.png|m.asc] [--nodata v]
          [--no-fill] [--esri] [--streams-out s.asc --min-cells n] [--max-sweeps n]       (cellsize from the header)
          [--basins-out b.asc [--pour p.png|p.asc] [--compact]] [--length-out l.asc]
+         [--order-out o.asc] [--links-out l.asc] [--hand-out h.asc [--hand-distance-out d.asc] [--min-order k]]   (with --min-cells)
 """
 import argparse
 import math
@@ -112,26 +117,31 @@ def accumulate(direction, ws, check_every=CHECK_EVERY):
 def flow_routing(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY):
     """dem: float32 [H][W] (numpy or HIP tensor); mask: same shape, nonzero = known (optional).  Returns (direction uint8 HIP
     tensor [H][W], accumulation int32 HIP tensor [H][W], info)."""
+    return route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, "flow_routing")[:3]
+
+
+def route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who):
+    """flow_routing's checks, upload and known mask -> (direction, accumulation, info, w: the surface that was routed)."""
     from tg_hip import ops as O
     from .fill_voids import _device_f32
-    who = "flow_routing"
     H, W, c = check_args(dem, mask, cellsize, 8, max_sweeps, check_every, who=who)
     if not isinstance(fill, bool):
         raise ValueError(f"{who}: fill {fill!r} must be True or False")
     if not torch.cuda.is_available():
-        raise RuntimeError("flow_routing: no HIP device visible; this build has no CPU path")
+        raise RuntimeError(f"{who}: no HIP device visible; this build has no CPU path")
     device = torch.device("cuda", torch.cuda.current_device())
     z = _device_f32(dem, device, "dem", who=who)
     m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who=who)
     if nodata is not None and math.isnan(nodata):
         nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
     known, _ = O.objmask_known(z, m, nodata, transposed=False)
-    return route_known(z, known, c, fill=fill, max_sweeps=max_sweeps, check_every=check_every)
+    return route_known(z, known, c, fill=fill, max_sweeps=max_sweeps, check_every=check_every, return_surface=True)
 
 
-def route_known(z, known, cellsize, *, fill=True, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY):
+def route_known(z, known, cellsize, *, fill=True, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY, return_surface=False):
     """flow_routing's body on device tensors with a ready known mask: z float32 [H][W], known uint8 [H][W] (tg_objmask_known's
-    map, or the intersection of two) -> (direction, accumulation, info)."""
+    map, or the intersection of two) -> (direction, accumulation, info); with return_surface=True also w, the surface that was
+    routed (the filled one with fill=True, else z itself)."""
     from tg_hip import ops as O
     from .fill_depressions import relax
     H, W = z.shape
@@ -153,6 +163,8 @@ def route_known(z, known, cellsize, *, fill=True, max_sweeps=MAX_SWEEPS, check_e
     info = {"known": nknown, "unknown": H * W - nknown, "outlets": outlets, "flat_cells": flat_cells, "pits": pits,
             "max_accumulation": amax, "max_area_m2": c * c * amax, "flat_sweeps": sweeps, "tile_visits": visits,
             "acc_rounds": rounds, "converged": bool(converged and flat_converged), "filled": fill}
+    if return_surface:
+        return direction, acc, info, w
     return direction, acc, info
 
 
@@ -199,7 +211,15 @@ def basin_doubling(d, pour, ws, check_every=CHECK_EVERY):
     from tg_hip import ops as O
     H, W = d.shape
     pc = O.flow_basin_init(d, pour, ws)
-    state = torch.empty(2, dtype=torch.int32, device=d.device)
+    rounds = basin_rounds(H, W, ws, check_every)
+    used, ignored = pc.cpu().tolist()
+    return rounds, used, ignored
+
+
+def basin_rounds(H, W, ws, check_every=CHECK_EVERY, who="watersheds"):
+    """The rounds of the doubling on the start records in ws (ops.flow_basin_init's or ops.stream_class's) -> rounds that ran."""
+    from tg_hip import ops as O
+    state = torch.empty(2, dtype=torch.int32, device=ws.device)
     k, left, rounds = 0, 1, 0
     while left and k < ACC_MAX_ROUNDS:
         n = min(check_every, ACC_MAX_ROUNDS - k)
@@ -207,9 +227,8 @@ def basin_doubling(d, pour, ws, check_every=CHECK_EVERY):
         k += n
         left, rounds = state.cpu().tolist()
     if left:
-        raise RuntimeError("watersheds: the direction grid has a cycle")
-    used, ignored = pc.cpu().tolist()
-    return rounds, used, ignored
+        raise RuntimeError(f"{who}: the direction grid has a cycle")
+    return rounds
 
 
 def compact_labels(basin):
@@ -250,6 +269,155 @@ def watersheds(direction, pour_points=None, *, cellsize=1.0, compact=False, chec
     return basin, length, info
 
 
+# ---- stream network: classes, links, Strahler order ------------------------------------------------------------------
+ORDER_MAX_ROUNDS = 65536
+
+
+def _min_cells(n, who):
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n < 2 ** 31:
+        raise ValueError(f"{who}: min_cells {n!r} must be an integer in [1, 2^31)")
+    return n
+
+
+def check_stream_args(direction, accumulation, min_cells, cellsize, max_rounds, check_every, who="stream_network"):
+    """Host-side rejection before any launch; -> (H, W, cellsize)."""
+    from .fill_depressions import _count, _shape
+    H, W, c = check_watershed_args(direction, None, cellsize, False, check_every, who)
+    if _shape(accumulation) != (H, W):
+        raise ValueError(f"{who}: accumulation {_shape(accumulation)} differs from the direction grid {(H, W)}")
+    dt = accumulation.dtype if isinstance(accumulation, (torch.Tensor, np.ndarray)) else None
+    if dt not in (torch.int32, np.dtype(np.int32)):
+        raise ValueError(f"{who}: accumulation must be an int32 grid of flow_routing's counts, got {dt}")
+    _min_cells(min_cells, who)
+    _count(max_rounds, 1, "max_rounds", who)
+    return H, W, c
+
+
+def _device_i32(a, device, what, who):
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda:
+            raise ValueError(f"{who}: {what} is on {a.device}; pass a numpy array or a HIP tensor")
+        return a.to(device=device).contiguous()
+    return torch.from_numpy(np.array(a, dtype=np.int32, order="C")).to(device)
+
+
+def order_rounds(d, cls, top, order, max_rounds=ORDER_MAX_ROUNDS, check_every=CHECK_EVERY):
+    """The Strahler iteration on device tensors (order as ops.stream_class leaves it, in place) -> (rounds enqueued, converged).
+    One host sync per check_every rounds; the junction list is torch.nonzero on the class plane."""
+    from tg_hip import ops as O
+    junctions = torch.nonzero(cls.reshape(-1) == O.STREAM_JUNCTION).reshape(-1).to(torch.int32)
+    if junctions.numel() == 0:
+        return 0, True
+    changed = torch.zeros(1, dtype=torch.int32, device=d.device)
+    rounds, converged = 0, False
+    while rounds < max_rounds and not converged:
+        n = min(check_every, max_rounds - rounds)
+        O.stream_order(d, cls, top, junctions, n, order, changed)
+        rounds += n
+        converged = int(changed.item()) == 0
+    return rounds, converged
+
+
+def network_known(d, acc, min_cells, cellsize, max_rounds=ORDER_MAX_ROUNDS, check_every=CHECK_EVERY):
+    """stream_network's body on device tensors (d uint8 [H][W] without the code 254, acc int32 [H][W]) -> (order, link, info)."""
+    from tg_hip import ops as O
+    H, W = d.shape
+    ws = O.flow_basin_ws(H, W, d.device)
+    cls, node, c0 = O.stream_class(d, acc, min_cells, ws)
+    link_rounds = basin_rounds(H, W, ws, check_every, "stream_network")
+    top, _, _, _, c1 = O.flow_basin_finish(H, W, link_rounds, ws, cellsize)
+    rounds, converged = order_rounds(d, cls, top, node, max_rounds, check_every)
+    order, c2 = O.stream_order_finish(cls, top, node)
+    cells, heads, junctions, outlets = c0.cpu().tolist()
+    oc = c2.cpu().tolist()
+    nb = O.STREAM_ORDER_BINS
+    info = {"stream_cells": cells, "heads": heads, "junctions": junctions, "outlets": outlets, "links": heads + junctions,
+            "max_order": oc[0], "cells_by_order": oc[1:1 + nb], "links_by_order": oc[1 + nb:1 + 2 * nb],
+            "link_rounds": link_rounds, "order_rounds": rounds, "converged": converged,
+            "longest_link_m": _bits_f32(c1.cpu().tolist()[2])}
+    return order, top, info
+
+
+@torch.no_grad()
+def stream_network(direction, accumulation, min_cells, *, cellsize=1.0, max_rounds=ORDER_MAX_ROUNDS, check_every=CHECK_EVERY):
+    """direction: uint8 [H][W] of flow_routing's codes; accumulation: int32 [H][W] (both numpy or HIP tensors); a stream pixel
+    has direction != 0 and accumulation >= min_cells.  Returns (order uint8 HIP tensor [H][W]: the Strahler order, 0 off the
+    streams; link int32 HIP tensor [H][W]: the linear index y * W + x of the head or junction at the upstream end of the pixel's
+    link, -1 off the streams; info: stream_cells, heads, junctions, outlets (stream pixels whose receiver is no stream pixel),
+    links, max_order, cells_by_order and links_by_order (orders 1..15, higher ones in the last), link_rounds, order_rounds (may
+    differ between runs; the rasters do not), converged, longest_link_m).  If max_rounds stops the order iteration, converged
+    is False and every order is a lower bound.  Exact and bitwise reproducible (csrc/drainage.hip)."""
+    who = "stream_network"
+    H, W, c = check_stream_args(direction, accumulation, min_cells, cellsize, max_rounds, check_every, who)
+    if not torch.cuda.is_available():
+        raise RuntimeError("stream_network: no HIP device visible; this build has no CPU path")
+    device = torch.device("cuda", torch.cuda.current_device())
+    d = _device_u8(direction, device, "direction", who)
+    if bool(torch.any(d == 254)):
+        raise ValueError(f"{who}: the direction grid holds the code 254 (undecided): route it to the end first")
+    acc = _device_i32(accumulation, device, "accumulation", who)
+    return network_known(d, acc, min_cells, c, max_rounds, check_every)
+
+
+# ---- height above the nearest drainage -------------------------------------------------------------------------------
+def hand_from_routing(w, direction, stream, cellsize, check_every=CHECK_EVERY):
+    """HAND on device tensors: w float32 [H][W] the routed surface, direction uint8 [H][W], stream uint8 [H][W] the drainage
+    mask.  Every path is followed to its first drainage pixel (watersheds with the mask as pour points) -> (hand float32 [H][W] =
+    w(p) - w(T(p)) where T(p) is a drainage pixel, NaN elsewhere; distance_m float32 [H][W]: the flow length to T(p), NaN where
+    not drained; info: drained, undrained, stream_cells, max_hand_m, rounds)."""
+    from tg_hip import ops as O
+    H, W = direction.shape
+    ws = O.flow_basin_ws(H, W, direction.device)
+    rounds, _, _ = basin_doubling(direction, stream, ws, check_every)
+    basin, _, _, length, _ = O.flow_basin_finish(H, W, rounds, ws, cellsize)
+    h, dist, counts = O.hand(w, basin, stream, length)
+    drained, undrained, cells, bits = counts.cpu().tolist()
+    return h, dist, {"drained": drained, "undrained": undrained, "stream_cells": cells, "max_hand_m": _bits_f32(bits),
+                     "rounds": rounds}
+
+
+@torch.no_grad()
+def hand(dem, mask=None, *, nodata=None, cellsize=1.0, min_cells=1000, min_order=1, fill=True, max_sweeps=MAX_SWEEPS,
+         check_every=CHECK_EVERY):
+    """Height above the nearest drainage of a DEM (inputs as flow_routing).  The raster is routed; the drainage is the stream
+    pixels (accumulation >= min_cells) of Strahler order >= min_order (stream_network runs only for min_order > 1); every pixel
+    is followed down to its first drainage pixel T.  Returns (hand float32 HIP tensor [H][W] = w(p) - w(T(p)) on the routed
+    surface w (the filled one with fill=True), one float32 subtract, >= 0, 0 on the drainage, NaN where the path ends off the
+    drainage or the pixel is unknown; distance_m float32 HIP tensor [H][W]: the flow length to T(p), NaN likewise; info:
+    flow_routing's numbers plus drained, undrained, stream_cells, max_hand_m, rounds, and "network" with min_order > 1; orders
+    that have not converged raise a RuntimeError, since lower bounds would leave links out of the drainage).  The
+    flood extent at stage h is hand <= h."""
+    from .fill_depressions import _cellsize
+    who = "hand"
+    _min_cells(min_cells, who)
+    _min_order(min_order, who)
+    direction, acc, info, w = route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who)
+    return hand_routed(w, direction, acc, info, _cellsize(cellsize, who), min_cells, min_order, check_every)[:3]
+
+
+def _min_order(k, who):
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 255:
+        raise ValueError(f"{who}: min_order {k!r} must be an integer in [1, 255]")
+    return k
+
+
+def hand_routed(w, direction, acc, info, c, min_cells, min_order=1, check_every=CHECK_EVERY, max_rounds=ORDER_MAX_ROUNDS):
+    """hand's second half on a routing -> (hand, distance_m, info updated, the drainage mask).  Orders that max_rounds stopped
+    short are lower bounds and would leave links out of the drainage, so that is an error here and not a flag."""
+    if min_order > 1:
+        order, _, ninfo = network_known(direction, acc, min_cells, c, max_rounds, check_every)
+        if not ninfo["converged"]:
+            raise RuntimeError(f"hand: the Strahler orders have not converged after {ninfo['order_rounds']} rounds, so the "
+                               f"drainage of order >= {min_order} is not known")
+        stream = (order >= min_order).to(torch.uint8)
+        info["network"] = ninfo
+    else:
+        stream = ((acc >= min_cells) & (direction != 0)).to(torch.uint8)
+    h, dist, hinfo = hand_from_routing(w, direction, stream, c, check_every)
+    info.update(hinfo)
+    return h, dist, info, stream
+
+
 # ---- CLI ------------------------------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(description="D8 flow directions and flow accumulation of an ESRI ASCII grid DEM: depressions "
@@ -263,7 +431,16 @@ def build_parser():
     ap.add_argument("--max-sweeps", type=int, default=MAX_SWEEPS, help="stop the fill and the flat resolution after this many "
                                                                        "sweeps each even if not converged")
     ap.add_argument("--streams-out", help="also write the stream mask (.asc): 1 where the accumulation >= --min-cells")
-    ap.add_argument("--min-cells", type=int, help="stream threshold in cells (required with --streams-out)")
+    ap.add_argument("--min-cells", type=int, help="stream threshold in cells (required with --streams-out, --order-out, "
+                                                  "--links-out and --hand-out)")
+    ap.add_argument("--order-out", help="also write the Strahler order of the streams (.asc): 0 off the streams")
+    ap.add_argument("--links-out", help="also write the stream links (.asc): the linear index y * ncols + x of the head or "
+                                        "junction at the upstream end of a stream cell's link, -1 off the streams")
+    ap.add_argument("--hand-out", help="also write the height above the nearest drainage in metres (.asc, full float32 precision; "
+                                       "NODATA_value where a cell's path ends off the drainage)")
+    ap.add_argument("--hand-distance-out", help="with --hand-out: also write the flow length to that drainage cell in metres (.asc)")
+    ap.add_argument("--min-order", type=int, default=1, help="with --hand-out: the drainage is the streams of at least this "
+                                                             "Strahler order (default 1: every stream)")
     ap.add_argument("--basins-out", help="also write the watershed labels (.asc): the linear index y * ncols + x of the pixel each "
                                          "cell drains to, -1 = void")
     ap.add_argument("--pour", help="pour points for --basins-out (.png or .asc of the raster's size): nonzero = a cell where "
@@ -279,10 +456,18 @@ def build_parser():
 def parse_args(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
-    if (a.streams_out is None) != (a.min_cells is None):
-        ap.error("--streams-out and --min-cells go together")
+    wants = [f for f, v in (("--streams-out", a.streams_out), ("--order-out", a.order_out), ("--links-out", a.links_out),
+                            ("--hand-out", a.hand_out)) if v is not None]
+    if bool(wants) != (a.min_cells is not None):
+        ap.error("--min-cells goes together with --streams-out, --order-out, --links-out or --hand-out")
     if a.min_cells is not None and a.min_cells < 1:
         ap.error("--min-cells must be >= 1")
+    if a.hand_distance_out and not a.hand_out:
+        ap.error("--hand-distance-out needs --hand-out")
+    if a.min_order != 1 and not a.hand_out:
+        ap.error("--min-order needs --hand-out")
+    if not 1 <= a.min_order <= 255:
+        ap.error("--min-order must lie in [1, 255]")
     if a.compact and not a.basins_out:
         ap.error("--compact needs --basins-out")
     if a.pour and not (a.basins_out or a.length_out):
@@ -310,12 +495,31 @@ def main(argv=None):
     dem, header = read_asc(a.dem)
     mask = _read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
-    direction, acc, info = flow_routing(dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")),
-                                        fill=not a.no_fill, max_sweeps=a.max_sweeps)
+    cs = float(asc_value(header, "cellsize"))
+    direction, acc, info, w = route_raster(dem, mask, nodata, cs, not a.no_fill, a.max_sweeps, CHECK_EVERY, "flow_routing")
     write_int_asc(a.dir_out, (to_esri(direction) if a.esri else direction).cpu().numpy(), header)
     write_int_asc(a.acc_out, acc.cpu().numpy(), header)
     if a.streams_out:
         write_int_asc(a.streams_out, streams(acc, a.min_cells).cpu().numpy(), header)
+    if a.order_out or a.links_out:
+        order, link, ninfo = network_known(direction, acc, a.min_cells, cs)
+        if a.order_out:
+            write_int_asc(a.order_out, order.cpu().numpy(), header)
+        if a.links_out:
+            write_int_asc(a.links_out, link.cpu().numpy(), header)
+        info["network"] = ninfo
+        print(f"{a.order_out or a.links_out}: {ninfo['stream_cells']} stream cells in {ninfo['links']} links ({ninfo['heads']} "
+              f"heads, {ninfo['junctions']} junctions, {ninfo['outlets']} outlets), largest Strahler order {ninfo['max_order']}, "
+              f"longest link {ninfo['longest_link_m']:.9g} m, {ninfo['link_rounds']} link rounds, {ninfo['order_rounds']} order "
+              f"rounds" + ("" if ninfo["converged"] else " (NOT converged: the orders are lower bounds)"))
+    if a.hand_out:
+        h, dist, _, _ = hand_routed(w, direction, acc, info, cs, a.min_cells, a.min_order)
+        fh = list(header) if asc_value(header, "NODATA_value") is not None else list(header) + [("NODATA_value", "-9999")]
+        write_asc(a.hand_out, h.cpu().numpy(), fh)
+        if a.hand_distance_out:
+            write_asc(a.hand_distance_out, dist.cpu().numpy(), fh)
+        print(f"{a.hand_out}: {info['drained']} cells drain to {info['stream_cells']} drainage cells (order >= {a.min_order}), "
+              f"{info['undrained']} do not; largest height above drainage {info['max_hand_m']:.9g} m, {info['rounds']} rounds")
     if a.basins_out or a.length_out:
         pour = _read_mask(a.pour, dem.shape) if a.pour else None
         basin, length, winfo = watersheds(direction, pour, cellsize=float(asc_value(header, "cellsize")), compact=a.compact)

@@ -56,6 +56,14 @@ class TgDepthClasses(C.Structure):
 
 TG_FLOW_OUT, TG_FLOW_UNDECIDED, TG_FLOW_PIT, TG_FLOW_FAR, TG_FLOW_MAX_ROUNDS = 9, 254, 255, 0x7fffffff, 32
 TG_FLOW_BASIN_COUNTS, TG_FLOW_COMPARE_COUNTS = 3, 19
+TG_STREAM_HEAD, TG_STREAM_INTERIOR, TG_STREAM_JUNCTION, TG_STREAM_ORDER_BINS = 1, 2, 3, 15
+TG_STREAM_ORDER_COUNTS = 1 + 2 * TG_STREAM_ORDER_BINS
+TG_FLOOD_MAX_STAGES = 8
+TG_FLOOD_COUNTS = 6 + 3 * TG_FLOOD_MAX_STAGES
+
+
+class TgFloodStages(C.Structure):
+    _fields_ = [("s", C.c_float * TG_FLOOD_MAX_STAGES)]
 
 
 class TgError(RuntimeError):
@@ -206,6 +214,11 @@ SIGNATURES = {
     "tg_flow_basin": (I, [I, I, I, I, P, P, SZ, P]),
     "tg_flow_basin_finish": (I, [I, I, I, D, P, P, P, P, P, P, SZ, P]),
     "tg_flow_compare": (I, [P, P, P, P, P, P, P, P, P, I, I, C.c_int32, C.c_int32, P, P]),
+    "tg_stream_class": (I, [P, P, I, I, C.c_int32, P, P, P, P, SZ, P]),
+    "tg_stream_order": (I, [P, P, P, P, I, I, I, I, P, P, P]),
+    "tg_stream_order_finish": (I, [P, P, P, I, I, P, P, P]),
+    "tg_hand": (I, [P, P, P, P, I, I, P, P, P, P]),
+    "tg_flood_compare": (I, [P, P, P, I, I, TgFloodStages, I, P, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -1582,6 +1582,114 @@ def flow_compare(sel, dir_t, dir_p, basin_t, basin_p, acc_t, acc_p, d2_t, d2_p, 
     return counts
 
 
+STREAM_HEAD, STREAM_INTERIOR, STREAM_JUNCTION = L.TG_STREAM_HEAD, L.TG_STREAM_INTERIOR, L.TG_STREAM_JUNCTION
+STREAM_ORDER_BINS, STREAM_ORDER_COUNTS = L.TG_STREAM_ORDER_BINS, L.TG_STREAM_ORDER_COUNTS
+FLOOD_MAX_STAGES, FLOOD_COUNTS = L.TG_FLOOD_MAX_STAGES, L.TG_FLOOD_COUNTS
+# tg_flood_compare's first six counters; then wet_t, wet_p, wet_both for each of the FLOOD_MAX_STAGES stages
+FLOOD_NAMES = ("cells", "undrained_t", "undrained_p", "abs_q10", "bias_q10", "abs_max_bits")
+
+
+def stream_class(d, acc, min_cells, ws):
+    """-> (cls uint8 [H][W]: 0, STREAM_HEAD, STREAM_INTERIOR, STREAM_JUNCTION; order int32 [H][W]: 1 on the stream pixels (dir != 0
+    and acc >= min_cells), the start of stream_order; counts int64 [4]: stream pixels, heads, junctions, stream terminals); the
+    start records of the upstream doubling go into ws (flow_basin_ws) for flow_basin and flow_basin_finish (tg_stream_class)."""
+    H, W = _raster_hw(d, "dir")
+    _hip(d, torch.uint8, (H, W), "dir")
+    _hip(acc, torch.int32, (H, W), "acc")
+    _flow_count(min_cells, 1, 2 ** 31 - 1, "min_cells", "stream_class")
+    _flow_basin_ws_chk(ws, H, W)
+    cls = torch.empty(H, W, dtype=torch.uint8, device=d.device)
+    order = torch.empty(H, W, dtype=torch.int32, device=d.device)
+    counts = torch.empty(4, dtype=torch.int64, device=d.device)
+    L.check(_lib().tg_stream_class(_p(d), _p(acc), H, W, min_cells, _p(cls), _p(order), _p(counts), _p(ws), ws.numel(), _stream()),
+            "tg_stream_class")
+    return cls, order, counts
+
+
+def stream_order(d, cls, top, junctions, n, order, changed):
+    """n >= 1 rounds of the Strahler iteration over the junctions (int32 [nj]: the linear indices of the STREAM_JUNCTION pixels),
+    order int32 [H][W] in place; changed int32 [1] = raises of the last round (0: a fixed point) (tg_stream_order)."""
+    H, W = _raster_hw(d, "dir")
+    _hip(d, torch.uint8, (H, W), "dir")
+    _hip(cls, torch.uint8, (H, W), "cls")
+    _hip(top, torch.int32, (H, W), "top")
+    _hip(order, torch.int32, (H, W), "order")
+    _hip(changed, torch.int32, (1,), "changed")
+    if not (isinstance(junctions, torch.Tensor) and junctions.is_cuda and junctions.dtype == torch.int32 and junctions.dim() == 1
+            and junctions.is_contiguous() and junctions.numel() <= H * W):
+        raise L.TgError(f"stream_order: junctions must be a contiguous int32 HIP tensor [nj] with nj <= {H * W}")
+    _flow_count(n, 1, 1 << 20, "n", "stream_order")
+    nj = junctions.numel()
+    L.check(_lib().tg_stream_order(_p(d), _p(cls), _p(top), _p(junctions) if nj else None, nj, H, W, n, _p(order), _p(changed),
+                                   _stream()), "tg_stream_order")
+
+
+def stream_order_finish(cls, top, order):
+    """-> (out uint8 [H][W]: order[top] on the stream pixels, 0 elsewhere; counts int64 [STREAM_ORDER_COUNTS]: the largest order,
+    cells of order 1 .. STREAM_ORDER_BINS, links of order 1 .. STREAM_ORDER_BINS) (tg_stream_order_finish)."""
+    H, W = _raster_hw(cls, "cls")
+    _hip(cls, torch.uint8, (H, W), "cls")
+    _hip(top, torch.int32, (H, W), "top")
+    _hip(order, torch.int32, (H, W), "order")
+    out = torch.empty(H, W, dtype=torch.uint8, device=cls.device)
+    counts = torch.empty(STREAM_ORDER_COUNTS, dtype=torch.int64, device=cls.device)
+    L.check(_lib().tg_stream_order_finish(_p(cls), _p(top), _p(order), H, W, _p(out), _p(counts), _stream()),
+            "tg_stream_order_finish")
+    return out, counts
+
+
+def hand(w, basin, smask, length_m=None):
+    """-> (hand float32 [H][W]: w(p) - w(basin(p)) where the terminal basin(p) is a pixel of smask (uint8 [H][W]), NaN elsewhere;
+    distance float32 [H][W] or None: length_m where drained, NaN elsewhere; counts int64 [4]: drained, undrained, drainage
+    pixels, the bits of the largest hand) (tg_hand)."""
+    H, W = _raster_hw(w, "w")
+    _hip(w, torch.float32, (H, W), "w")
+    _hip(basin, torch.int32, (H, W), "basin")
+    _hip(smask, torch.uint8, (H, W), "stream")
+    if length_m is not None:
+        _hip(length_m, torch.float32, (H, W), "length_m")
+    out = torch.empty(H, W, dtype=torch.float32, device=w.device)
+    dist = torch.empty(H, W, dtype=torch.float32, device=w.device) if length_m is not None else None
+    counts = torch.empty(4, dtype=torch.int64, device=w.device)
+    L.check(_lib().tg_hand(_p(w), _p(basin), _p(smask), _p(length_m), H, W, _p(out), _p(dist), _p(counts), _stream()), "tg_hand")
+    return out, dist, counts
+
+
+def flood_stages(stages):
+    """The stages of flood_compare checked on the host: 1 .. FLOOD_MAX_STAGES numbers, each finite and > 0 as float32, strictly
+    increasing as float32 -> (L.TgFloodStages, k)."""
+    import numpy as np
+    try:
+        vals = [float(v) for v in stages]
+    except (TypeError, ValueError):
+        raise L.TgError(f"flood_compare: stages {stages!r} must be a sequence of numbers") from None
+    if any(isinstance(v, bool) for v in stages) or not 1 <= len(vals) <= FLOOD_MAX_STAGES:
+        raise L.TgError(f"flood_compare: stages {stages!r} must be 1 to {FLOOD_MAX_STAGES} numbers")
+    with np.errstate(over="ignore"):
+        f = np.array(vals, np.float64).astype(np.float32)
+    if not (np.isfinite(f).all() and (f > 0).all()):
+        raise L.TgError(f"flood_compare: stages {stages!r} must be finite and > 0 in float32")
+    if not (np.diff(f) > 0).all():
+        raise L.TgError(f"flood_compare: stages {stages!r} must be strictly increasing in float32")
+    st = L.TgFloodStages()
+    for i, v in enumerate(f.tolist()):
+        st.s[i] = v
+    return st, len(vals)
+
+
+def flood_compare(sel, hand_t, hand_p, stages):
+    """-> counts int64 [FLOOD_COUNTS] of two HAND planes (float32 [H][W]) over the pixels with sel != 0 (uint8 [H][W]):
+    FLOOD_NAMES, then wet_t, wet_p, wet_both per stage (tg_flood_compare)."""
+    H, W = _raster_hw(sel, "sel")
+    _hip(sel, torch.uint8, (H, W), "sel")
+    _hip(hand_t, torch.float32, (H, W), "hand_t")
+    _hip(hand_p, torch.float32, (H, W), "hand_p")
+    st, k = flood_stages(stages)
+    counts = torch.empty(FLOOD_COUNTS, dtype=torch.int64, device=sel.device)
+    L.check(_lib().tg_flood_compare(_p(sel), _p(hand_t), _p(hand_p), H, W, st, k, _p(counts), _stream()), "tg_flood_compare")
+    return counts
+
+
 VFILL_NSTATS = 4                                # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
