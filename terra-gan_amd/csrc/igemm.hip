@@ -1009,7 +1009,7 @@ static int launch_pgemm_cfg(const IGemmParams& p, const PatchGeom& q, double flo
     if (int rc = lds_opt_in(opt, reinterpret_cast<const void*>(kern), LDS_MAX, "pgemm")) return rc;
     dim3 grid(q.total_work, 1, p.splits);
     {
-        ProfScope ps(s, BF16 ? 3 : 0, flops, bytes, Mtot, p.N, p.Ktot, p.C, p.splits, (BF16 ? 3000 : 1000) + BN);
+        ProfScope ps(s, BF16 ? 3 : 0, flops, bytes, Mtot, p.N, p.Ktot, p.C, p.splits, (BF16 ? 3200 : 1000) + BN);
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, p, q);
     }
     TG_CHECK_LAUNCH("pgemm_kernel");
@@ -2461,7 +2461,7 @@ static int launch_wgrad_bf16_cfg(const WgradParams& p, hipStream_t s) {
     {
         const double by = 4.0 * ((double)p.B * p.H * p.W * p.C + (double)p.Mpix * p.Cout + (double)p.Cout * p.Ktot +
                                  (double)p.Mpix + (p.amask ? (double)p.B * p.H * p.W : 0.0));
-        ProfScope ps(s, 3, 2.0 * p.Mpix * (double)p.Cout * p.Ktot, by, p.Cout, p.Ktot, p.Mpix, p.C, p.splits, 3500 + BM);
+        ProfScope ps(s, 3, 2.0 * p.Mpix * (double)p.Cout * p.Ktot, by, p.Cout, p.Ktot, p.Mpix, p.C, p.splits, 3700 + BM);
         hipLaunchKernelGGL((wgrad_bf16_kernel<WAVES_M, WAVES_N, WM, WN>), grid, dim3(256), lds, s, pp);
     }
     TG_CHECK_LAUNCH("wgrad_bf16_kernel");

@@ -2,6 +2,7 @@
 passes; csrc/smallconv.hip), shared by tests/test_hip_direct_conv.py (GPU: the launch records must show exactly the expected
 kernel, then the exact-integer and the a-priori-bound checks of tests/conv_oracle.py) and tests/test_conv_oracle_cpu.py (CPU: the
 oracle against float64 autograd, the exactness condition, fp32 PyTorch inside the bound, and `predict` = the expectation).
+B16_CASES: the same for the bf16-operand instantiations of these kernels and wgrad_bf16_kernel (tests/test_hip_bf16_direct.py).
 
 `predict` restates the host-side planners of the two files (pick_bn, choose_splits, plan_splits, try_pgemm, try_igemm_multi,
 wgrad_plan, the smallconv_* and Winograd admission predicates) in Python, for the default environment (no TG_* switch) and a
@@ -184,19 +185,29 @@ def try_igemm_multi(cls):
     return 500 + bn, tuple(cdiv(p.T, cdiv(p.T, s)) for p, s in zip(cls, sp))
 
 
-def launch_igemm(p, bnin=False, env=None, sparse=False):
+# The record of an MFMA launch: in bf16 mode (tg_hip.ops.set_precision("bf16")) the gathered-row kernel at BN 64 / 128 with the
+# vector gather, the patch kernel and the merged gathered-row launch run their BF16 = true instantiations, kind 3 with a cfg of
+# their own each; BN 32 and the scalar gather (Cin % 4 != 0) have no bf16 twin and keep the fp32 record.
+B16_CFG = {64: 3064, 128: 3128, 1064: 3264, 1128: 3328, 564: 3564, 628: 3628}
+
+
+def mfma_record(cfg, bf16=False):
+    return (3, B16_CFG[cfg], 0) if bf16 and cfg in B16_CFG else (0, cfg, 0)
+
+
+def launch_igemm(p, bnin=False, env=None, sparse=False, bf16=False):
     """(kind, cfg, route), splits of launch_igemm after plan_splits."""
     if smallconv_fwd_applies(p):
         return (2, SMALL_FWD, smallconv_fwd_route(p, bnin, env, sparse)), 1
     assert not bnin
     pg = try_pgemm([p])
     if pg:
-        return (0, pg[0], 0), pg[1]
-    return (0, pick_bn(p.N) + (1 if p.C % 4 else 0), 0), plan_splits(p)
+        return mfma_record(pg[0], bf16), pg[1]
+    return mfma_record(pick_bn(p.N) + (1 if p.C % 4 else 0), bf16), plan_splits(p)
 
 
-def wino_geom_ok(p):
-    return p.TH == 3 and p.TW == 3 and p.ss == 1 and p.C % 8 == 0 and p.N % 64 == 0 and p.OH >= 16 and p.OW >= 16
+def wino_geom_ok(p, bf16=False):
+    return p.TH == 3 and p.TW == 3 and p.ss == 1 and p.C % (16 if bf16 else 8) == 0 and p.N % 64 == 0 and p.OH >= 16 and p.OW >= 16
 
 
 def _halved(g):
@@ -215,7 +226,7 @@ def wino22_ok(g, c8, c64):
 
 
 def wgrad_plan(g):
-    """(bm, splits) of wgrad_kernel."""
+    """(bm, splits) of wgrad_kernel and of wgrad_bf16_kernel."""
     B, H, W, Cin, Cout, k, s, pad = g
     Ho, Wo = CO.out_size(H, k, s, pad), CO.out_size(W, k, s, pad)
     bm = 32 if Cout % 4 or Cout < 32 else (128 if Cout >= 128 and Cin % 4 == 0 else 64)
@@ -258,20 +269,26 @@ def wgrad_slabs(g, route):
     return cdiv(quads, qpb) if qpb > 0 else 1
 
 
+def wgrad_bf16_ok(g, bm, setenv=None):
+    """bf16 mode: wgrad_bf16_kernel takes the launch wgrad_kernel would get (conv_wgrad_impl; the switch is read per call)."""
+    B, H, W, Cin, Cout, k, s, pad = g
+    return Cin % 4 == 0 and Cout % 4 == 0 and CO.out_size(W, k, s, pad) % 32 == 0 and bm >= 64 and setenv != "TG_NO_BF16_WGRAD"
+
+
 def predict(case):
     """[(kind, cfg, route), ...] in launch order, and the recorded split counts [splits, ...] (igemm_multi: per class, as one tuple)."""
     g, op, mods = case.geom, case.op, case.mods
     B, H, W, Cin, Cout, k, s, pad = g
-    masked, bnin, env = "mask" in mods, "bnin" in mods, case.env
+    masked, bnin, env, bf16 = "mask" in mods, "bnin" in mods, case.env, case.prec == "bf16"
     if op == "fwd":
         p = fwd_params(g)
-        assert not s2d_ok(g) and not wino22_ok(g, Cin, Cout) and not wino_geom_ok(p), "a Winograd route takes this forward"
-        r, sp = launch_igemm(p, bnin, env)
+        assert not s2d_ok(g) and (bf16 or not wino22_ok(g, Cin, Cout)) and not wino_geom_ok(p, bf16), "a Winograd route takes this forward"
+        r, sp = launch_igemm(p, bnin, env, bf16=bf16)
         return [r], [sp]
     if op == "dgrad":
-        assert not (s2d_ok(g) and "gate" not in mods) and not wino22_ok(g, Cout, Cin), "a Winograd route takes this dgrad"
+        assert not (s2d_ok(g) and "gate" not in mods) and (bf16 or not wino22_ok(g, Cout, Cin)), "a Winograd route takes this dgrad"
         p1 = NS(TH=k, TW=k, ss=s, C=Cout, N=Cin, OH=H, OW=W)
-        assert not wino_geom_ok(p1), "a Winograd route takes this dgrad"
+        assert not wino_geom_ok(p1, bf16), "a Winograd route takes this dgrad"
         cls = dgrad_classes(g)
         if s * s <= 4:
             if to1_multi_applies(cls):
@@ -279,11 +296,11 @@ def predict(case):
             if len(cls) > 1 and not smallconv_fwd_applies(cls[0]):
                 pg = try_pgemm(cls)
                 if pg:
-                    return [(0, pg[0], 0)], [pg[1]]
+                    return [mfma_record(pg[0], bf16)], [pg[1]]
                 mu = try_igemm_multi(cls)
                 if mu:
-                    return [(0, mu[0], 0)], [mu[1]]
-        rs = [launch_igemm(p, False, env, "map" in mods) for p in cls]
+                    return [mfma_record(mu[0], bf16)], [mu[1]]
+        rs = [launch_igemm(p, False, env, "map" in mods, bf16) for p in cls]
         return [r for r, _ in rs], [sp for _, sp in rs]
     assert op == "wgrad"
     route = smallconv_wgrad_route(g, "bias" in mods, bnin, env)
@@ -291,10 +308,14 @@ def predict(case):
         return [(2, SMALL_WGRAD, route)], [1]
     Ho, Wo = CO.out_size(H, k, s, pad), CO.out_size(W, k, s, pad)
     assert not s2d_ok(g), "a Winograd route takes this wgrad"
-    assert masked or not ((k, s) == (3, 1) and Cin % 64 == 0 and Cout % 64 == 0 and Ho >= 16 and Wo >= 16), "Winograd wgrad"
-    assert masked or not (wino22_ok(g, 64, 64) and Cin % 64 == 0 and Cout % 64 == 0), "Winograd F(2x2,2x2) wgrad"
+    s1_64 = (k, s) == (3, 1) and Cin % 64 == 0 and Cout % 64 == 0 and Ho >= 16
+    if bf16:        # wino16_wgrad_ok: Wo >= 32; the fp32 F(3x3,2x2) kernel up to 256 input channels; F(2x2,2x2) never
+        assert masked or not (s1_64 and (Wo >= 32 or (Wo >= 16 and Cin <= 256))), "Winograd wgrad"
+    else:
+        assert masked or not (s1_64 and Wo >= 16), "Winograd wgrad"
+        assert masked or not (wino22_ok(g, 64, 64) and Cin % 64 == 0 and Cout % 64 == 0), "Winograd F(2x2,2x2) wgrad"
     bm, sp = wgrad_plan(g)
-    return [(1, bm, 0)], [sp]
+    return [(3, 3700 + bm, 0) if bf16 and wgrad_bf16_ok(g, bm, case.setenv) else (1, bm, 0)], [sp]
 
 
 # ---- split-count classes ----------------------------------------------------------------------------------------------------------
@@ -323,8 +344,8 @@ def slab_cap(case, pred):
     gradients and min(ceil(T / 4), 512) for wgrad_plan; 1 (the accumulator itself) where the route has no second pass."""
     kind, cfg, route = pred[0]
     if case.op != "wgrad":
-        return 1 if kind == 2 else (32 if cfg > 1000 else 64)
-    if kind == 1:
+        return 1 if kind == 2 else (32 if cfg in (1064, 1128, B16_CFG[1064], B16_CFG[1128]) else 64)
+    if kind in (1, 3):
         return 512
     if route in (SR_TO1WGRADW + 3, SR_TO1WGRADW + 4):
         B, H, W, Cin, Cout, k, s, pad = case.geom
@@ -334,9 +355,18 @@ def slab_cap(case, pred):
 
 # ---- the table --------------------------------------------------------------------------------------------------------------------
 class Case:
-    def __init__(self, id, geom, op, mods, expect, splits="1", env=None):
+    """prec: 'f32' | 'bf16' (tg_hip.ops.set_precision around the launch under test);  env: a switch the library reads once per
+    process (the case runs in a child);  setenv: a switch it reads per call, set around the launch."""
+
+    def __init__(self, id, geom, op, mods, expect, splits="1", env=None, prec="f32", setenv=None):
         self.id, self.geom, self.op, self.mods, self.splits, self.env = id, geom, op, frozenset(mods.split()), splits, env
         self.expect = [expect] if isinstance(expect[0], int) else list(expect)
+        self.prec, self.setenv = prec, setenv
+
+    @property
+    def rounds(self):
+        """The case runs on a bf16 direct kernel: its reference is the convolution of the operands rounded to bf16."""
+        return self.prec == "bf16" and all(kind == 3 for kind, _, _ in self.expect)
 
     def __repr__(self):
         return self.id
@@ -492,6 +522,72 @@ BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES)
 HERE = [c for c in CASES if c.env is None]
 
+# ---- the same kernels' BF16 = true instantiations, and wgrad_bf16_kernel (tests/test_hip_bf16_direct.py) ------------------------------
+# Every case runs in bf16 mode.  The kernels round the two MFMA operands to bf16 (RNE) when they stage them into LDS and nothing
+# else, so a case on a bf16 kernel (Case.rounds) faces the oracle on the ROUNDED operands with the unchanged fp32 bound; the
+# integers of the exact run are bf16 numbers.  Records: gathered-row 3000 + BN, patch 3200 + BN, merged 3500 + BN, wgrad 3700 + BM.
+B16_CASES = []
+
+
+def Bf(cfg):
+    return (3, cfg, 0)
+
+
+def b16(id, src, expect, splits=None, **k):
+    """A bf16-mode case: `src` = (geometry, op, modifiers), or the id of the fp32 case whose geometry, op, modifiers (and split
+    class, unless given: the bf16 launchers share the fp32 planners) it takes."""
+    if isinstance(src, str):
+        c = BY_ID[src]
+        src, splits = (c.geom, c.op, " ".join(sorted(c.mods))), c.splits if splits is None else splits
+    B16_CASES.append(Case(id, src[0], src[1], src[2], expect, splits or "1", prec="bf16", **k))
+
+
+# gathered-row kernel (igemm_kernel<.., BF16>): 3000 + BN
+b16("b16_ig64_s2_split2", "ig64_s2_split2", Bf(3064))
+b16("b16_ig64_n34_ragged", ((2, 13, 15, 8, 34, 3, 2, 1), "fwd", "bias relu"), Bf(3064), "2-7")         # ragged N, scalar stores
+b16("b16_ig128_1x1_ragged_m", "ig128_1x1_ragged_m", Bf(3128))
+# Cin % 8 != 0: one 32-wide chunk is mostly zero padding, and half of an 8-wide bf16 LDS read is padding
+b16("b16_ig64_c12", ((2, 9, 11, 12, 64, 3, 2, 1), "fwd", "mask bias"), Bf(3064), "2-7")
+b16("b16_ig64_c20", ((2, 9, 11, 20, 64, 3, 1, 1), "fwd", "bias"), Bf(3064), "2-7")
+b16("b16_ig128_c36_tail", ((2, 9, 11, 36, 128, 3, 2, 1), "fwd", "mask"), Bf(3128), "2-7")               # a full chunk + a 4-channel tail
+b16("b16_ig64_d4x4s2", ((2, 32, 32, 64, 64, 4, 2, 1), "fwd", "bias leaky"), Bf(3064), "8")              # F(2x2,2x2) in fp32 mode
+b16("b16_splitk_9", "splitk_9", Bf(3128))
+b16("b16_splitk_11", "splitk_11", Bf(3128))
+b16("b16_splitk_18_n34_scalar", "splitk_18_n34_scalar", Bf(3064))
+b16("b16_splitk_36", "splitk_36", Bf(3128))
+b16("b16_splitk_dgrad_acc", "splitk_dgrad_acc", Bf(3128))
+b16("b16_classes_stride3", ((2, 10, 13, 64, 64, 3, 3, 1), "dgrad", "mask"), [Bf(3064)] * 9)
+# patch kernel (pgemm_kernel<.., BF16>): 3200 + BN
+for _id in ("pg64_whole_3x3", "pg64_over_4x4", "pg64_splitk2", "pg64_n50_scalar_store", "pg64_n50_splitk2_scalar", "pg64_dgrad_1x1_acc"):
+    b16("b16_" + _id, _id, Bf(3264))
+for _id in ("pg128_whole_1x1", "pg128_over_2x2", "pg128_over_4x4", "pg128_splitk4", "pg128_dgrad_2x2_gate", "pg128_merged4_dgrad"):
+    b16("b16_" + _id, _id, Bf(3328))
+# the four 2x2-tap classes of a discriminator layer, merged: 4 x 128 work items, the least the merged patch launch takes
+b16("b16_pg128_merged4_d4x4s2", ((16, 64, 64, 128, 64, 4, 2, 1), "dgrad", "mask"), Bf(3328))
+# merged gathered-row launch (igemm_multi_kernel<.., true>): 3500 + BN
+for _id in ("multi128_small_grid", "multi128_per_class", "multi128_per_class_8"):
+    b16("b16_" + _id, _id, Bf(3628))
+for _id in ("multi64_per_class", "multi64_per_class_8"):
+    b16("b16_" + _id, _id, Bf(3564))
+# weight gradient (wgrad_bf16_kernel): 3700 + BM
+b16("b16_wg128_rowseg_split2", "wg128_rowseg_split2", Bf(3828))
+b16("b16_wg64_rowseg_split2", "wg64_rowseg_split2", Bf(3764))
+b16("b16_wg64_masked_3x3_split8", "wg64_masked_3x3_split8", Bf(3764))
+b16("b16_wg128_rowseg_split1", "wg128_rowseg_split1", Bf(3828))
+b16("b16_wg64_rowseg_split1", "wg64_rowseg_split1", Bf(3764))
+b16("b16_wg64_36_rows_k72", ((1, 4, 32, 8, 36, 3, 1, 1), "wgrad", "mask bias"), Bf(3764))              # 36 of 64 rows, Ktot 72 < 128
+b16("b16_wg128_ragged_bm_k180", ((2, 4, 32, 20, 160, 3, 1, 1), "wgrad", "bias"), Bf(3828), ">=1")      # 160 = 128 + 32, Ktot 180 = 128 + 52
+b16("b16_wg64_5x5_s2", ((1, 9, 64, 16, 96, 5, 2, 2), "wgrad", "mask"), Bf(3764), ">=1")                # Wo = 32
+b16("b16_wg128_image_edges", ((3, 2, 32, 16, 128, 3, 1, 1), "wgrad", ""), Bf(3828), ">=1")             # image boundaries inside the K walk
+# precision must not leak: these stay on the fp32 kernels in bf16 mode -- the fp32 record, the UNROUNDED reference
+for _id in ("ig33_c3_s2", "ig65_c6_5x5", "ig32_dgrad_5x5_split5", "classes_n24", "wg32_c3", "wg64_c6", "c1mfma7", "to1_lds_ragged",
+            "to1convw_256_3", "multi22_lds", "c1wgrad_mfma3_bias", "to1wgrad_lds"):
+    b16("b16_keeps_" + _id, _id, BY_ID[_id].expect)
+b16("b16_keeps_wg64_wo8", ((2, 13, 16, 16, 96, 3, 2, 1), "wgrad", "mask bias"), Wg(64))                 # Wo = 8, no multiple of 32
+b16("b16_keeps_wg64_behind_switch", "wg64_rowseg_split2", Wg(64), setenv="TG_NO_BF16_WGRAD")
+B16_BY_ID = {c.id: c for c in B16_CASES}
+assert len(B16_BY_ID) == len(B16_CASES) and not set(B16_BY_ID) & set(BY_ID)
+
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------
 LEAKY_SLOPE = float(np.float32(0.2))           # the C ABI takes slopes as float: the fp32 value nearest 0.2, on every side
@@ -543,11 +639,28 @@ def make_inputs(case, mode):
     return d
 
 
+OPERANDS = {"fwd": ("x", "w"), "dgrad": ("dy", "w"), "wgrad": ("x", "dy")}
+
+
+def round_operands(case, d, rnd=CO.bf16_rne):
+    """The arrays with the two MFMA operands of the case's op passed through `rnd` and `dy_bias` = the dy as drawn: the bias
+    gradient is the fp32 column sum of the unrounded dy.  (The 0/1 mask multiply that precedes the rounding in the kernels
+    commutes with it.)"""
+    assert d["bn"] is None, "no bf16 kernel applies BatchNorm on load"
+    out = dict(d, dy_bias=d["dy"])
+    for name in OPERANDS[case.op]:
+        out[name] = rnd(d[name])
+    return out
+
+
 def reference(case, d, mode):
     """The oracle's results for the arrays of make_inputs (and, for a backward run behind an activation, the dy the test derived
-    from the kernel's own forward output): {'y' | 'dx' | 'dw', 'db'} -> conv_oracle.Res."""
+    from the kernel's own forward output): {'y' | 'dx' | 'dw', 'db'} -> conv_oracle.Res.  A case on a bf16 kernel (Case.rounds):
+    for those arrays with the MFMA operands rounded to bf16."""
     B, H, W, Cin, Cout, k, s, pad = case.geom
     a, sl = fwd_act(case, mode)
+    if case.rounds and "dy_bias" not in d:
+        d = round_operands(case, d)
     if case.op == "fwd":
         return {"y": CO.conv_fwd(d["x"], d["w"], k, s, pad, d["mask"], d["bias"], d["ratio"], a, sl, d["bn"])}
     if case.op == "dgrad":
@@ -557,7 +670,7 @@ def reference(case, d, mode):
             keep = d["needed"][..., None].astype(np.float64)
             r = r._replace(val=r.val * keep, S=r.S * keep)
         return {"dx": r}
-    rw, rb = CO.conv_wgrad(d["x"], d["dy"], k, s, pad, d["mask"], d["bn"])
+    rw, rb = CO.conv_wgrad(d["x"], d["dy"], k, s, pad, d["mask"], d["bn"], d.get("dy_bias"))
     return {"dw": rw, "db": rb} if "bias" in case.mods else {"dw": rw}
 
 

@@ -37,6 +37,22 @@ def f64(a):
     return None if a is None else np.asarray(a, dtype=np.float64)
 
 
+def bf16_rne(a):
+    """An fp32 array rounded to the nearest bf16, ties to even, as fp32 -- what the bf16 direct kernels do to the two MFMA operands
+    when they stage them into LDS (igemm.hip: __builtin_convertvector f32x4 -> bf16x4 = v_cvt_pk_bf16_f32), and to nothing else.
+    The bit form: add 0x7FFF plus the lowest kept bit, drop the low half.  A carry out of the mantissa moves the exponent, the
+    largest finite values go to inf, subnormals round on the same grid.  (No NaN handling: the tables draw none.)"""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    r = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
+    return r.astype(np.uint32).view(np.float32).reshape(np.shape(a))
+
+
+def bf16_trunc(a):
+    """The fp32 array with the low 16 bits dropped: the WRONG conversion, which the rounded-operand run must tell from bf16_rne."""
+    u = np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+    return (u & np.uint32(0xFFFF0000)).view(np.float32).reshape(np.shape(a))
+
+
 def act(v, kind, slope=0.0):
     if kind == ACT_RELU:
         return np.where(v > 0, v, 0.0)
@@ -140,9 +156,10 @@ def conv_dgrad(dy, w, x_shape, k, s, p, mask=None, gate=None, gate_act=ACT_RELU,
     return Res(dx, S, np.broadcast_to(K, S.shape), np.abs(scale), b0, False)
 
 
-def conv_wgrad(x, dy, k, s, p, mask=None, in_bn=None):
-    """(dW as [Cout][k][k][Cin], db)."""
-    dy = f64(dy)
+def conv_wgrad(x, dy, k, s, p, mask=None, in_bn=None, dy_bias=None):
+    """(dW as [Cout][k][k][Cin], db).  `dy_bias`: the dy that db sums, where it is not the dW operand (bf16 mode rounds the MFMA
+    operands; the bias gradient stays the fp32 column sum of the unrounded dy)."""
+    dy, dyb = f64(dy), f64(dy if dy_bias is None else dy_bias)
     B, H, W, Cin = np.shape(x)
     Ho, Wo = out_size(H, k, s, p), out_size(W, k, s, p)
     Cout = dy.shape[3]
@@ -160,8 +177,8 @@ def conv_wgrad(x, dy, k, s, p, mask=None, in_bn=None):
         K[0, ky, kx, 0] = B * inside[sl].sum()
     one = np.ones_like(S)
     rw = Res(dw, S, np.broadcast_to(K, S.shape), one, np.zeros_like(S), in_bn is not None)
-    Sb = np.abs(dy).sum(axis=(0, 1, 2))
-    rb = Res(dy.sum(axis=(0, 1, 2)), Sb, np.full(Cout, float(B * Ho * Wo)), np.ones(Cout), np.zeros(Cout), False)
+    Sb = np.abs(dyb).sum(axis=(0, 1, 2))
+    rb = Res(dyb.sum(axis=(0, 1, 2)), Sb, np.full(Cout, float(B * Ho * Wo)), np.ones(Cout), np.zeros(Cout), False)
     return rw, rb
 
 

@@ -1,6 +1,8 @@
 """tests/conv_oracle.py and tests/conv_cases.py on the CPU, for every case of the table: the fp64 oracle against float64 autograd
 (F.conv2d, torch.nn.grad.conv2d_weight), the exactness condition of the integer run, fp32 PyTorch-CPU inside the a-priori bound
-the kernels face, and the table's expected route against the Python restatement of the planners."""
+the kernels face, and the table's expected route against the Python restatement of the planners.  For the bf16-mode cases
+(conv_cases.B16_CASES) in addition: bf16_rne against torch's conversion, and that the rounded-operand reference tells a kernel
+that stayed fp32 and one that truncates from one that rounds to nearest even."""
 import numpy as np
 import pytest
 import torch
@@ -132,3 +134,106 @@ def test_table_is_complete():
     for r in wg:
         assert (2, CC.SMALL_WGRAD, r) in seen, r
     assert len({c.env for c in CC.CASES if c.env}) <= 4
+
+
+# ---- bf16 mode (conv_cases.B16_CASES) ------------------------------------------------------------------------------------------------
+def test_bf16_rne_is_torch_bfloat16():
+    """conv_oracle.bf16_rne against torch's fp32 -> bf16 conversion, bit for bit: normals, exact ties of both parities, +-0, values
+    just below a power of two (the carry moves the exponent), the largest finite fp32 (-> inf) and subnormals."""
+    rng = np.random.default_rng(16)
+    bits = lambda *u: np.array(u, np.uint32).view(np.float32)
+    ties = bits(0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F807FFF, 0x3F808001, 0x3F817FFF, 0x3F818001, 0x40FF8000, 0x40FE8000)
+    below = bits(0x3FFFFFFF, 0x3FFF8000, 0x3FFF7FFF, 0xBFFFFFFF, 0x407FFFFF, 0x7F7FFFFF, 0xFF7FFFFF, 0x7F7F8000, 0x7F7F7FFF)
+    sub = bits(0x00000001, 0x00007FFF, 0x00008000, 0x00008001, 0x00018000, 0x007FFFFF, 0x007F8000, 0x80008000, 0x80018000, 0x00800000)
+    a = np.concatenate([rng.standard_normal(4096, dtype=np.float32), rng.standard_normal(512, dtype=np.float32) * np.float32(1e-3),
+                        rng.integers(0, 0x7F800000, 4096, dtype=np.uint32).view(np.float32), ties, below, sub,
+                        np.array([0.0, -0.0, 1.0, -1.0, 3.0, -3.0], np.float32)])
+    got = CO.bf16_rne(a)
+    want = torch.from_numpy(a).bfloat16().float().numpy()
+    assert got.dtype == np.float32 and got.shape == a.shape
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    # the ties go to the even neighbour, in both directions; the largest finite value leaves the range
+    assert np.array_equal(CO.bf16_rne(ties[:4]).view(np.uint32), np.array([0x3F800000, 0x3F820000, 0xBF800000, 0xBF820000], np.uint32))
+    assert np.isinf(CO.bf16_rne(bits(0x7F7FFFFF))[0]) and np.signbit(CO.bf16_rne(np.float32(-0.0)))
+    assert CO.bf16_rne(np.ones((2, 3), np.float32)).shape == (2, 3)
+    # truncation is another function, and differs where the dropped half is above a half
+    assert np.array_equal(CO.bf16_trunc(ties[:2]).view(np.uint32), np.array([0x3F800000, 0x3F810000], np.uint32))
+
+
+@pytest.mark.parametrize("case", CC.B16_CASES, ids=[c.id for c in CC.B16_CASES])
+def test_bf16_expected_route_follows_from_the_geometry(case):
+    assert case.prec == "bf16"
+    routes, splits = CC.predict(case)
+    assert routes == case.expect
+    assert CC.splits_ok(case.splits, splits), (case.splits, splits)
+    if isinstance(case.splits, tuple):
+        assert splits == [case.splits]
+    assert CC.slab_cap(case, routes) >= max(max(s) if isinstance(s, tuple) else s for s in splits)
+    if case.op == "wgrad":
+        assert CC.slab_cap(case, routes) >= CC.wgrad_slabs(case.geom, routes[0][2])
+    # a case that keeps its fp32 kernel has that kernel's record; every other one a record of kind 3 that no other launcher writes
+    kinds = {kind for kind, _, _ in case.expect}
+    assert kinds == {3} if case.rounds else 3 not in kinds
+    assert case.id.startswith("b16_keeps_") != case.rounds
+    if case.id.startswith("b16_keeps_") and not case.setenv and case.id[len("b16_keeps_"):] in CC.BY_ID:
+        assert case.expect == CC.BY_ID[case.id[len("b16_keeps_"):]].expect
+
+
+def test_bf16_table_is_complete():
+    """Every record of the four bf16 direct launchers is expected by some case, each at both tile sizes; no two launchers share one,
+    and none is a cfg the benchmark's kernel report names."""
+    seen = {e for c in CC.B16_CASES for e in c.expect}
+    want = [3064, 3128, 3264, 3328, 3564, 3628, 3764, 3828]
+    for cfg in want:
+        assert (3, cfg, 0) in seen, cfg
+    assert sorted(CC.B16_CFG.values()) + [3764, 3828] == want
+    assert not set(want) & {4064, 4164, 4016, 4022, 4122, 4044, 1128, 1064}
+    assert {e for e in seen if e[0] == 3} == {(3, cfg, 0) for cfg in want}
+
+
+@pytest.mark.parametrize("case", CC.B16_CASES, ids=[c.id for c in CC.B16_CASES])
+def test_bf16_exact_run_is_exact(case):
+    """The integer run of a bf16 case: its operands are bf16 numbers (rounding leaves them alone), and every partial sum is an
+    integer below 2^24, so the bf16 kernels owe the same bits as the fp32 ones."""
+    d = _inputs(case, "exact")
+    for name in CC.OPERANDS[case.op]:
+        assert np.array_equal(CO.bf16_rne(d[name]), d[name]) and np.array_equal(CO.bf16_trunc(d[name]), d[name]), name
+    ref = CC.reference(case, d, "exact")
+    t64 = torch_run(case, d, "exact", torch.float64)
+    for name, r in ref.items():
+        assert CO.exact_ok(r), f"{name}: max S = {float(r.S.max()):.0f} is not below 2^24"
+        assert np.array_equal(t64[name].numpy(), r.val) and np.array_equal(np.rint(r.val), r.val), name
+
+
+@pytest.mark.parametrize("case", CC.B16_CASES, ids=[c.id for c in CC.B16_CASES])
+def test_bf16_real_run_can_tell(case):
+    """The real run of a bf16 case.  On a bf16 kernel: the reference on rounded operands agrees with float64 autograd on them;
+    fp32 PyTorch-CPU on the rounded operands lies inside the bound (it is not vacuous that way), while the reference of a kernel
+    that stayed fp32 (unrounded operands) and of one that truncates both lie OUTSIDE it (nor the other way): a condition on the
+    table's inputs, not a measurement of the kernels.  A case that keeps its fp32 kernel: the plain fp32 check."""
+    d = _inputs(case, "real")
+    slabs = CC.slab_cap(case, case.expect)
+    if not case.rounds:
+        ref = CC.reference(case, d, "real")
+        t32 = torch_run(case, d, "real", torch.float32)
+        for name, r in ref.items():
+            assert CO.worst(t32[name].numpy(), r, slabs)[0] <= 1.0, name
+        return
+    dr = CC.round_operands(case, d)
+    ref = CC.reference(case, dr, "real")
+    for name in CC.OPERANDS[case.op]:
+        assert not np.array_equal(dr[name], d[name]), name
+    t64, t32 = torch_run(case, dr, "real", torch.float64), torch_run(case, dr, "real", torch.float32)
+    main = {"fwd": "y", "dgrad": "dx", "wgrad": "dw"}[case.op]
+    r = ref[main]
+    assert bool((np.abs(t64[main].numpy() - r.val) <= 2 * CO.bound(r, slabs) * 2.0 ** -29).all())
+    q32 = CO.worst(t32[main].numpy(), r, slabs)[0]
+    assert q32 <= 1.0, f"fp32 PyTorch-CPU on the rounded operands at {q32:.3f} of the a-priori bound"
+    if "db" in ref:     # the bias gradient sums the dy as drawn
+        plain = CC.reference(case, dict(d, dy_bias=d["dy"]), "real")["db"]
+        assert np.array_equal(ref["db"].val, plain.val) and np.array_equal(ref["db"].S, plain.S)
+    for what, rnd in (("unrounded", lambda a: a), ("truncated", CO.bf16_trunc)):
+        other = CC.reference(case, CC.round_operands(case, d, rnd), "real")[main]
+        q = CO.worst(other.val, r, slabs)[0]
+        print(f"DISCRIMINATION {case.id} {main} {what} {q:.2f}")
+        assert q > 1.0, f"the {what} operands' result lies within the bound ({q:.3f}): the real run could not tell"

@@ -5,7 +5,9 @@ Every case asserts from the launch records that exactly the expected kernel ran 
 split count -- and then faces two references that need no measured tolerance (tests/conv_oracle.py):
   - exact: small-integer data, so that every fp32 summation order gives the same bits; torch.equal with the fp64 reference;
   - real: normals with ratio / LeakyReLU / gates / accumulate base; |hip - ref| <= n 2^-24 S |scale| per element.
-The routes behind an environment switch that the library reads once per process run in one fresh child process per switch."""
+The routes behind an environment switch that the library reads once per process run in one fresh child process per switch.
+The bf16-operand instantiations of the same kernels face the same two runs, through the same run_case, in
+tests/test_hip_bf16_direct.py."""
 import csv
 import os
 import subprocess
@@ -109,13 +111,30 @@ def launch(case, d, mode, dev):
     return out
 
 
+def launch_as_asked(case, d, mode, dev):
+    """`launch` under the precision and the per-call switch the case names, both restored afterwards."""
+    from tg_hip import ops as O
+    try:
+        O.set_precision(case.prec)
+        if case.setenv:
+            os.environ[case.setenv] = "1"
+        out = launch(case, d, mode, dev)
+        torch.cuda.synchronize()
+        return out
+    finally:
+        O.set_precision("f32")
+        if case.setenv:
+            os.environ.pop(case.setenv, None)
+
+
 def run_case(case, dev, csv_path, table=CC, launch_fn=None):
     """The runs of a case (both, unless the case names its own); returns [(output name, err / bound of the real run)].  Raises
     AssertionError on any miss.  `table`: the case module (conv_cases, or wino_cases with `launch_fn` its launcher, which sets
-    and restores whatever process-wide state the case asks for around the launch)."""
+    and restores whatever process-wide state the case asks for around the launch).  Only the launch under test runs at the
+    case's precision: the forward a backward case derives its dy from is an fp32 one, whatever the case asks for."""
     from tg_hip import ops as O
-    assert O.get_precision() == "f32", "fp32 outside the launch: the bf16 twins of the direct kernels have tests/test_hip_bf16.py"
-    launch_fn = launch_fn or launch
+    assert O.get_precision() == "f32", "fp32 outside the launch: a case names its precision, and only its launch runs under it"
+    launch_fn = launch_fn or launch_as_asked
     figures = []
     for mode in getattr(case, "runs", ("exact", "real")):
         d = table.make_inputs(case, mode)
