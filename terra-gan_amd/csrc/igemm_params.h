@@ -116,7 +116,7 @@ enum SmallRoute {
 //                                          8 + bit gate;  9-16 the same eight with a work-stealing queue;  17 tile map  18 tile map
 //                                          + pool;  19-21 the list-only tile map: plain, gate, bit gate
 //   4016 (launch_wino, bf16):              1-8 as 4064's first eight (wino16_kernel / wino16_pipe_kernel)
-//   4022 (launch_wino22):                  1 + (queue ? 4 : 0) + (fast ? 2 : 0) + gate
+//   4022 (launch_wino22):                  1 + (queue ? 4 : 0) + (fast ? 2 : 0) + gate;  + 8: the wide form, wino22w_kernel (fast only)
 //   4044 (launch_wino44):                  1 plain  2 gate  3 bit gate
 //   4164 / 4116 / 4122:                    1 (one kernel each)
 enum WinoRoute {
@@ -127,6 +127,7 @@ enum WinoRoute {
     WR_MAP = WR_FIRST + 16,         // 4064: + pool
     WR_MAP_LIST = WR_FIRST + 18,    // 4064: + gate; + 2 bit gate
     WR_W22_FAST = 2, WR_W22_QUEUED = 4,         // 4022: WR_FIRST + these + gate
+    WR_W22_WIDE = 8,                // 4022: + the narrow form's index (128-channel items)
     WR_WGRAD = WR_FIRST,
 };
 

@@ -381,9 +381,294 @@ __global__ __launch_bounds__(WINO_THREADS) void wino22_kernel(const IGemmParams 
     wk.done(q.qctr);
 }
 
+// The wide form: item = (image, 16x16 output patch, class, 128-channel N tile).  Wave (mw, nw = 0..3) owns 32 tiles x 32 channels
+// x ALL nine transform points (144 accumulator registers), so a K step stages the patch and the V image once for two of the
+// narrow kernel's N tiles and carries 72 MFMAs per SIMD instead of 36; only the U copy doubles.  The U image of a step is two
+// adjacent 64-channel blocks of the prepared layout (N tiles 2i, 2i+1 follow each other in U[k/8][n/64]), i.e. one contiguous
+// run of 2 x W22_V floats: the prepared weights are the narrow kernel's.  K order, the 8-channel steps and the MFMA chain of a
+// point are the narrow kernel's, and a wave holds all three point rows of its tiles, so the output transform needs no exchange
+// and gives the same bits: Y[0][j] = s0j + s1j, Y[1][j] = s1j + s2j with s[a][j] = M[a][j] + M[a][j+1].
+// Sources are read through buffer descriptors only (the narrow kernel's FAST form): masked sources stay on the narrow kernel,
+// and so does every split-K launch (launch_wino22 has the rule).  The kernel sits close to the 256 registers a 512-thread
+// workgroup has: DESIGN 8z lists what keeps it free of scratch (no values assigned under wave-role branches in the K loop,
+// thread-index arithmetic re-derived behind opaque copies instead of being held across the loop, epilogue operands a tile at a time).
+constexpr int W22W_U = 2 * W22_V;                                  // floats of one wide U image: 9216
+constexpr int W22W_LDS_FLOATS = 2 * W22_V + 2 * W22W_U + W22_P + 8;    // 29968 floats = 120 KB
+
+template <bool GATED, bool STEAL>
+__global__ __launch_bounds__(WINO_THREADS) void wino22w_kernel(const IGemmParams p, const W22Geom q, const float* __restrict__ U) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* Vs = smem;                            // [2][9][64][8]
+    float* Us = smem + 2 * W22_V;                // [2][2][9][64][8]
+    float* Ps = smem + 2 * W22_V + 2 * W22W_U;   // [17*17][8]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int mw = wave & 1, nw = wave >> 1;
+    __shared__ int wq_slot[2];
+    WinoWork<STEAL> wk;
+    wk.init(q.total_work, q.interleave, q.qctr, wq_slot);
+
+    int n0, oy0, ox0, b, cls;
+    int py0, px0;               // patch origin of the item (scalars); the slots' pixel offsets are re-derived per parity phase
+    int32_t poff[2];
+    int i_nt, i_tx, i_ty;
+    auto locate = [&]() {       // as wino22_kernel, q.nt = N / 128
+        const int item = wk.item;
+        i_nt = item % q.nt;
+        int tile = item / q.nt;
+        cls = tile % q.ncls;
+        tile /= q.ncls;
+        i_tx = tile % q.tiles_x;
+        tile /= q.tiles_x;
+        i_ty = tile % q.tiles_y;
+        b = tile / q.tiles_y;
+    };
+    const bool p1_ok = ((tid + WINO_THREADS) >> 1) < W22_PPIX;
+    auto set_phase = [&](int ph) {
+        // (an opaque thread index: the slot coordinates would otherwise be hoisted and held in registers across the K loop)
+        int st = tid;
+        asm volatile("" : "+v"(st));
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int pp = (st + WINO_THREADS * i) >> 1, spy = pp / 17, spx = pp - spy * 17;
+            int iy = py0 + spy, ix = px0 + spx, H = p.IH, W = p.IW, Cc = p.C;
+            if (q.s2d) {
+                iy = 2 * iy + (ph >> 1) - 1;
+                ix = 2 * ix + (ph & 1) - 1;
+                H = q.XH; W = q.XW; Cc = q.XC;
+            }
+            const bool ok = (i == 0 || p1_ok) && iy >= 0 && iy < H && ix >= 0 && ix < W;
+            const int32_t pix = ok ? (b * H + iy) * W + ix : 0;
+            poff[i] = ok ? (pix * Cc + 4 * (st & 1)) * 4 : (int32_t)0x80000000u;      // byte offset; out of range = beyond 2 GB
+        }
+    };
+    const auto srsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.src), 0, (int)(q.s2d ? (size_t)p.B * q.XH * q.XW * q.XC * 4 : (size_t)p.B * p.IH * p.IW * p.C * 4), 0x00020000);
+    const auto ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(U), 0, (int)((size_t)q.ncls * W22_PTS * p.N * p.C * 4), 0x00020000);
+    auto decode = [&]() {
+        n0 = i_nt * (2 * WINO_BN); oy0 = i_ty * 16; ox0 = i_tx * 16;
+        py0 = oy0 + (q.ncls > 1 ? -(cls >> 1) : q.sy_min);
+        px0 = ox0 + (q.ncls > 1 ? -(cls & 1) : q.sx_min);
+    };
+    const int c_begin = 0, c_end = p.C >> 3, c_last = c_end - 1;      // one split
+    const size_t ustep = (size_t)(p.N / WINO_BN) * W22_V;
+    const int cpp = q.s2d ? (q.XC >> 3) : (p.C >> 3);       // K steps per parity phase
+
+    f32x4 ru[5], rp[2];
+    int cur_ph, c_base, c_next;
+    auto start_phase = [&](int ph) { cur_ph = ph; c_base = ph * cpp; c_next = c_base + cpp; set_phase(ph); };
+    auto pload1 = [&](int c, int i) {
+        rp[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srsrc, poff[i], (c - c_base) * 32, 0));
+    };
+    // the U image is 4.5 float4 per thread: in the fifth round the upper half of the threads re-reads its first one
+    const size_t u_base = (size_t)W22_PTS * p.N * p.C;       // floats of one class's U
+    const int u_last = tid < 256 ? tid + 4 * WINO_THREADS : tid;
+    auto uload1 = [&](int c, int j) {
+        ru[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+            ursrc, 16 * (j < 4 ? tid + WINO_THREADS * j : u_last), (int)(((size_t)cls * u_base + (size_t)i_nt * W22W_U + (size_t)c * ustep) * 4), 0));
+    };
+    auto pstore1 = [&](int i) {
+        if (i == 0 || p1_ok) *reinterpret_cast<f32x4*>(Ps + 4 * (tid + WINO_THREADS * i)) = rp[i];
+    };
+    auto ustore1 = [&](int buf, int j) {
+        if (j < 4 || tid < 256) *reinterpret_cast<f32x4*>(Us + buf * W22W_U + 4 * (tid + WINO_THREADS * j)) = ru[j];
+    };
+
+    // input transform: the roles of wino22_kernel (waves 0..5), one patch column at a time -- column 1 first, it is in every
+    // output: V[a][1] = r1, V[a][0] = r0 - r1, V[a][2] = r2 - r1 with r = row a of Bt d.  Every wave reads and computes (waves 6, 7
+    // repeat row 2) and only the store is conditional: values assigned under `if (t_on)` would stay live around the whole K loop.
+    const int t_quad = lane & 1, t_tile = (lane >> 1) + 32 * (wave & 1), t_a = min(wave >> 1, 2);
+    const bool t_on = wave < 6;
+    const int t_src0 = ((2 * (t_tile >> 3) + t_a) * 17 + 2 * (t_tile & 7)) * 8 + 4 * t_quad;
+    const int t_src1 = ((2 * (t_tile >> 3) + 1) * 17 + 2 * (t_tile & 7)) * 8 + 4 * t_quad;
+    const int t_dst = (t_a * 3) * 512 + t_tile * 8 + (((t_quad ^ (t_tile >> 4)) & 1) << 2);
+    f32x4 tp[2], tm;
+    auto t_read1 = [&](int j) {
+        tp[0] = *reinterpret_cast<const f32x4*>(Ps + t_src0 + j * 8);
+        tp[1] = *reinterpret_cast<const f32x4*>(Ps + t_src1 + j * 8);
+    };
+    auto t_row1 = [&]() -> f32x4 { return t_a == 1 ? tp[0] : tp[0] - tp[1]; };
+    auto t_col1 = [&](int buf, int k, f32x4 v) {
+        if (t_on) *reinterpret_cast<f32x4*>(Vs + buf * W22_V + t_dst + k * 512) = v;
+    };
+
+    const int arow = 32 * mw + (lane & 31), brow = 32 * (nw & 1) + (lane & 31);
+    const int a_off = arow * 8 + ((((lane >> 5) ^ (arow >> 4)) & 1) << 2);
+    const int b_off = (nw >> 1) * W22_V + brow * 8 + ((((lane >> 5) ^ (brow >> 4)) & 1) << 2);
+
+    if (wk.item < 0 || c_begin >= c_end) { wk.done(q.qctr); return; }
+    locate();
+    decode();
+    start_phase(0);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) pload1(c_begin, i);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) uload1(c_begin, j);
+
+    for (;;) {
+        f32x16 acc[W22_PTS];
+#pragma unroll
+        for (int i = 0; i < W22_PTS; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+        {
+            // prologue: as wino22_kernel
+#pragma unroll
+            for (int i = 0; i < 2; ++i) pstore1(i);
+#pragma unroll
+            for (int j = 0; j < 5; ++j) ustore1(0, j);
+            {
+                const int c1 = min(c_begin + 1, c_last);
+                if (c1 >= c_next) start_phase(cur_ph + 1);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) pload1(c1, i);
+#pragma unroll
+                for (int j = 0; j < 5; ++j) uload1(c1, j);
+            }
+            wino_barrier();
+            t_read1(1);
+            tm = t_row1();
+            t_col1(0, 1, tm);
+            t_read1(0);
+            t_col1(0, 0, t_row1() - tm);
+            t_read1(2);
+            t_col1(0, 2, t_row1() - tm);
+            wino_barrier();
+            f32x4 fa[2], fb[2];
+            fa[0] = *reinterpret_cast<const f32x4*>(Vs + a_off);
+            fb[0] = *reinterpret_cast<const f32x4*>(Us + b_off);
+            int cur = 0;
+            for (int c = c_begin; c < c_end; ++c) {
+                const int nxt = cur ^ 1;
+                const int c2 = min(c + 2, c_last);               // tail steps: redundant staging instead of branches
+                const float* Vc = Vs + cur * W22_V + a_off;
+                const float* Uc = Us + cur * W22W_U + b_off;
+                const float* Vn = Vs + nxt * W22_V + a_off;
+                const float* Un = Us + nxt * W22W_U + b_off;
+                // 36 ticks: t = 4*xi + e, an MFMA of every wave in each; point xi takes the fragment registers xi & 1
+                wino_static_for(std::make_integer_sequence<int, 36>{}, [&](auto tc) {
+                    constexpr int t = decltype(tc)::value;
+                    constexpr int xi = t >> 2, e = t & 3;
+                    if constexpr (t < 2) pstore1(t);                           // patch c+1 -> LDS (readers of patch c are done)
+                    if constexpr (t == 2) {                                    // patch c+2 -> rp; new slot offsets on a phase change
+                        if (c2 >= c_next) start_phase(cur_ph + 1);
+                        pload1(c2, 0);
+                    }
+                    if constexpr (t == 3) pload1(c2, 1);
+                    if constexpr (t == 4) wino_barrier();                      // patch c+1 visible
+                    if constexpr (t == 5) t_read1(1);
+                    if constexpr (t == 8) { tm = t_row1(); t_col1(nxt, 1, tm); t_read1(0); }
+                    if constexpr (t == 11) { t_col1(nxt, 0, t_row1() - tm); t_read1(2); }
+                    if constexpr (t == 14) t_col1(nxt, 2, t_row1() - tm);
+                    if constexpr (t >= 17 && t < 22) ustore1(nxt, t - 17);
+                    if constexpr (t >= 23 && t < 28) uload1(c2, t - 23);       // U c+2 -> ru
+                    if constexpr (t == 32) wino_barrier();                     // V / U images of step c+1 complete
+                    if constexpr (e == 0 && xi < 8) {
+                        fa[(xi + 1) & 1] = *reinterpret_cast<const f32x4*>(Vc + (xi + 1) * 512);
+                        fb[(xi + 1) & 1] = *reinterpret_cast<const f32x4*>(Uc + (xi + 1) * 512);
+                    }
+                    if constexpr (t == 33) {                                   // point 0 of step c+1 (point 7 is done with its registers)
+                        fa[1] = *reinterpret_cast<const f32x4*>(Vn);
+                        fb[1] = *reinterpret_cast<const f32x4*>(Un);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[xi] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[xi & 1][e], fb[xi & 1][e], acc[xi], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                // nine points on two fragment registers: the next step starts in the other one -- moved, not renamed
+                fa[0] = fa[1];
+                fb[0] = fb[1];
+                cur = nxt;
+            }
+        }
+        const int e_n0 = n0, e_oy0 = oy0, e_ox0 = ox0, e_b = b, e_cls = cls;      // output coordinates of the finished item
+        const int wq_next = wk.next(wq_slot);
+        const bool more_items = wq_next >= 0;
+        const int wq_pulled = wk.request(wq_next);
+        wino_barrier();        // the epilogue scratch overlays U
+
+        // row sums s[a][j] = M[a][j] + M[a][j+1] of the 3x3 points: the accumulators die here
+        // the lane index of the epilogue is opaque to the compiler: the row / column offsets derived from it are otherwise hoisted
+        // out of the item loop and held in registers across the K loop, where there are none to spare
+        int el = lane;
+        asm volatile("" : "+v"(el));
+        float* scratch = smem + 2 * W22_V + wave * (32 * 36);
+        f32x16 rs[3][2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) rs[a][j][r] = acc[3 * a + j][r] + acc[3 * a + j + 1][r];
+        const int e_dy0 = q.ncls > 1 ? 1 - (e_cls >> 1) : p.dy0, e_dx0 = q.ncls > 1 ? 1 - (e_cls & 1) : p.dx0;
+        f32x4 bq = {0.f, 0.f, 0.f, 0.f};
+        if (p.bias) bq = *reinterpret_cast<const f32x4*>(p.bias + e_n0 + 32 * nw + 4 * (el & 7));
+#pragma unroll
+        for (int xh = 0; xh < 2; ++xh) {
+            // the staging state switches to the next item and its first operands are requested between the two output rows: ahead of
+            // the second row's stores, once the first row's sums are dead (all of it does not fit beside three rows of sums)
+            if (xh == 1 && more_items) {
+                wk.item = wq_next;
+                locate();
+                decode();
+                start_phase(0);
+#pragma unroll
+                for (int i = 0; i < 2; ++i) pload1(c_begin, i);
+#pragma unroll
+                for (int j = 0; j < 5; ++j) uload1(c_begin, j);
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                // row scales and gate quads of this tile are fetched ahead of its stores (a load behind a store waits for the store's
+                // acknowledgement) -- a tile at a time, as wino_kernel does: the quads of two tiles do not fit beside the row sums
+                float rsq[4] = {1.f, 1.f, 1.f, 1.f};
+                if (p.rowscale) {
+#pragma unroll
+                    for (int t4 = 0; t4 < 4; ++t4) {
+                        const int t = 32 * mw + (el >> 3) + 8 * t4;
+                        const int oy = min(e_oy0 + 2 * (t >> 3) + xh, p.OH - 1), ox = min(e_ox0 + 2 * (t & 7) + j, p.OW - 1);
+                        rsq[t4] = p.rowscale[((size_t)e_b * p.DH + (oy * p.ds + e_dy0)) * p.DW + (ox * p.ds + e_dx0)];
+                    }
+                }
+                f32x4 gq[GATED ? 4 : 1];
+                if constexpr (GATED) {
+#pragma unroll
+                    for (int t4 = 0; t4 < 4; ++t4) {
+                        const int t = 32 * mw + (el >> 3) + 8 * t4;
+                        const int oy = min(e_oy0 + 2 * (t >> 3) + xh, p.OH - 1), ox = min(e_ox0 + 2 * (t & 7) + j, p.OW - 1);
+                        const size_t pix = ((size_t)e_b * p.DH + (oy * p.ds + e_dy0)) * p.DW + (ox * p.ds + e_dx0);
+                        gq[t4] = *reinterpret_cast<const f32x4*>(p.gate + pix * p.N + e_n0 + 32 * nw + 4 * (el & 7));
+                    }
+                }
+                f32x16 y;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) y[r] = rs[xh][j][r] + rs[xh + 1][j][r];
+                tile_rows4i(scratch, y, el, [&](int t4, int rr, int cc, f32x4 v4) {
+                    const int t = 32 * mw + rr;
+                    const int oy = e_oy0 + 2 * (t >> 3) + xh, ox = e_ox0 + 2 * (t & 7) + j;
+                    const int nb = e_n0 + 32 * nw + cc;
+                    if (oy >= p.OH || ox >= p.OW) return;
+                    const size_t pix = ((size_t)e_b * p.DH + (oy * p.ds + e_dy0)) * p.DW + (ox * p.ds + e_dx0);
+                    *reinterpret_cast<f32x4*>(p.dst + pix * p.N + nb) = epilogue4(p, v4, pix, nb, GATED ? &gq[GATED ? t4 : 0] : nullptr, &rsq[t4], &bq);
+                });
+            }
+        }
+        wk.publish(wq_pulled, wq_slot);
+        if (!more_items) break;
+        wino_barrier();        // every wave is done with the scratch before the next prologue stages into it
+        wk.advance(wq_next);
+    }
+    wk.done(q.qctr);
+}
+
 static bool wino22_enabled() {
     static const bool off = getenv("TG_NO_WINO") != nullptr || getenv("TG_NO_WINO22") != nullptr;
     return !off;
+}
+// TG_WINO22_WIDE=0 keeps every launch on the 64-channel items.  Read at each launch: both forms can run in one process.
+static bool wino22_wide_enabled() {
+    const char* e = getenv("TG_WINO22_WIDE");
+    return e == nullptr || atoi(e) != 0;
 }
 // 4x4 / stride 2 / pad 1, fp32, even input: forward needs Cout % 64 == 0 and Cin % 8 == 0, dgrad the mirror image
 static bool wino22_fwd_geom_ok(const TgConv* g) {
@@ -427,6 +712,12 @@ static int launch_wino22(const TgConv* g, IGemmParams& p, int dgrad, size_t ws_f
     q.tiles_y = cdiv(p.OH, 16);
     q.nt = p.N / WINO_BN;
     q.total_work = q.tiles_x * q.tiles_y * p.B * q.nt * q.ncls;
+    // Sized by ONE class's U although the ~32 consecutive items an XCD works on in the interleaved walk cover all four classes of a
+    // dgrad (N tile fastest, then class), i.e. 4x these bytes are in use at a time.  By wino_distribute's rule (the whole U in the
+    // 4 MB L2) that would move the 256 <- 512 dgrad (4.7 MB per class, 18.9 MB in all) to contiguous ranges; measured on that layer,
+    // both walks in fresh processes, twice: 115.7 / 116.5 against 115.6 / 114.6 us at 16 images, 171.7 / 172.1 against 167.9 / 170.3 us
+    // at 32 -- inside the spread of the timings (profiles/r07_wino22_wide.txt), so the rule stays as it was.  The smaller dgrads
+    // are below the limit either way (128 <- 256: 4.7 MB in all).
     q.interleave = wino_interleave_ok((size_t)W22_PTS * p.N * p.C * sizeof(float));
     const int nchunks = p.C / 8;
     int splits = 1;
@@ -457,12 +748,24 @@ static int launch_wino22(const TgConv* g, IGemmParams& p, int dgrad, size_t ws_f
                                      wino22_kernel<true, true, false>, wino22_kernel<false, false, true>, wino22_kernel<false, true, true>,
                                      wino22_kernel<true, false, true>, wino22_kernel<true, true, true>};
     static LdsOptIn opts[8];
+    // the wide form (wino22w_kernel): 128-channel items, where they still fill the chip -- one split (the split plan above is made
+    // for the 64-channel items and is not touched), an unmasked source, and at least one item per planned CU.  Both forms read the
+    // same prepared weights and give the same bits.
+    const bool wide = wino22_wide_enabled() && fast && (p.N % (2 * WINO_BN)) == 0 && p.splits == 1 && q.total_work / 2 >= WINO_PLAN_CUS;
+    if (wide) { q.nt /= 2; q.total_work /= 2; }
+    static const W22Kern kernsw[4] = {wino22w_kernel<false, false>, wino22w_kernel<true, false>, wino22w_kernel<false, true>,
+                                      wino22w_kernel<true, true>};
+    static LdsOptIn optsw[4];
     q.qctr = wino_queue_block(s, p.splits, q.total_work);
     const int ki = (q.qctr ? 4 : 0) + (fast ? 2 : 0) + (gated ? 1 : 0);
     const double mtot = (double)p.M * q.ncls;
     const WinoProf pf = {0, 4022, (int)mtot, 2.0 * mtot * (double)p.N * p.Ktot,              // (direct form: 16 taps)
                          4.0 * ((double)g->B * (dgrad ? g->Ho * g->Wo * g->Cout : g->H * g->W * g->Cin) + 16.0 * g->Cin * g->Cout +
-                                mtot * p.N + (p.rowscale ? mtot : 0.0)), WR_FIRST + ki};
+                                mtot * p.N + (p.rowscale ? mtot : 0.0)), WR_FIRST + (wide ? WR_W22_WIDE : 0) + ki};
+    if (wide) {
+        const int kw = (q.qctr ? 2 : 0) + (gated ? 1 : 0);
+        return wino_launch(kernsw[kw], optsw[kw], (size_t)W22W_LDS_FLOATS * sizeof(float), "wino22w_kernel", p, q, pf, false, s);
+    }
     // the split-K slabs of the ncls classes are reduced by one launch of the multi-class epilogue
     if ((rc = wino_launch(kerns[ki], opts[ki], (size_t)W22_LDS_FLOATS * sizeof(float), "wino22_kernel", p, q, pf, false, s))) return rc;
     if (p.splits > 1) {
