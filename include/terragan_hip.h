@@ -931,6 +931,54 @@ int tg_hand(const float* w, const int32_t* basin, const uint8_t* smask, const fl
 int tg_flood_compare(const uint8_t* sel, const float* hand_t, const float* hand_p, int H, int W, tg_flood_stages stages, int k,
                      int64_t* counts, tg_stream_t stream);
 
+/* ---- Multiple-flow-direction accumulation, slope, topographic wetness index (csrc/mfd.hip) ---------------------
+ * w, known and dir [H][W] are a routed surface, its known map and its direction grid as the sections above leave them (dir
+ * without TG_FLOW_UNDECIDED).  Neighbour k = 0..7 is code k + 1.  For a known pixel q and a known neighbour n_j inside the raster:
+ * d_j = w(q) - w(n_j), one fp32 subtract, valid iff d_j > 0 (a NaN never is); t_j = (double)d_j raised to the integer exponent
+ * e (1 .. TG_MFD_MAX_EXPONENT) by e - 1 fp64 multiplies t = t * d, times cdiag for odd j (a diagonal); S = the fp64 sum of the
+ * valid t_j in the order j = 0..7.  S > 0 ("dispersive"): q gives the fraction f_j = t_j / S, one fp64 divide, to n_j; otherwise
+ * with dir(q) in 1..8 ("single") it gives 1.0 to its D8 receiver; otherwise (a "sink": TG_FLOW_OUT, TG_FLOW_PIT) nothing.  cdiag
+ * in (0, 1] is the caller's 2^(-(e + 1) / 2).  A(p) = 1.0 for a known p, then for k = 0..7 in order, where neighbour k gives a
+ * fraction f > 0 to p, A(p) = A(p) + f * A(n_k): one fp64 multiply, one fp64 add, nothing fused; 0 at unknown pixels.  Every A(p) is
+ * computed once, from final values, so the plane does not depend on the order of the visits.  Sides as tg_objmask_known.
+ * One workspace ws >= tg_mfd_ws_bytes(H, W) serves all calls: 256 control bytes, three planes of one byte per 64x64 tile (open,
+ * and the wake marks of two sweeps), one donor byte per pixel, one fp64 S per pixel (each rounded up to 256 bytes) and 64 KiB of
+ * partial sums.  0 for sides out of range. */
+#define TG_MFD_MAX_EXPONENT 8
+#define TG_MFD_COUNTS 5
+size_t tg_mfd_ws_bytes(int H, int W);
+/* S and the donor bytes into ws, every tile on the work list; A [H][W] fp64 = -1.0 ("not final") at known pixels, 0.0 at unknown
+ * ones.  counts [TG_MFD_COUNTS] int64 (zeroed here) = dispersive, single, sink pixels, pixels that are not final (their sum), tile
+ * visits (0). */
+int tg_mfd_setup(const float* w, const uint8_t* known, const uint8_t* dir, int H, int W, int exponent, double cdiag, double* A,
+                 int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream);
+/* Enqueues n sweeps, 1 <= n <= 2^20 (after tg_mfd_setup with the same w, exponent, cdiag, A, counts and ws): every marked tile
+ * that holds a pixel that is not final is visited; in it a pixel that is not final and whose donors are all final gets its value,
+ * until nothing more can (or a cap on the inner rounds).  A tile is marked for a sweep when the sweep before stopped it at the cap
+ * or made a pixel on a neighbour tile's rim final; for the first sweep every tile is.  The marks decide which visits happen, never
+ * what a visit computes.  counts[3] goes down by the pixels made final, counts[4] up by the tiles visited.  A block of sweeps in
+ * which counts[3] stays above 0 and unchanged would mean a cycle; the graph has none. */
+int tg_mfd_sweep(const float* w, int H, int W, int exponent, double cdiag, int n, double* A, int64_t* counts, void* ws,
+                 size_t ws_bytes, tg_stream_t stream);
+/* acc [H][W] fp32 = A rounded once; out [2] double (zeroed here) = the largest A, and the sum of A over the sinks in a fixed order
+ * (per-workgroup partials, then one ordered pass: two calls agree bitwise).  With every pixel final that sum is the number of
+ * known pixels up to rounding. */
+int tg_mfd_finish(const double* A, const uint8_t* dir, int H, int W, float* acc, double* out, void* ws, size_t ws_bytes,
+                  tg_stream_t stream);
+/* Horn's slope tan(beta) in fp32, nothing fused: with the 3x3 neighbourhood a b c / d . f / g h i (rows top to bottom), a neighbour
+ * outside the raster or unknown replaced by the centre, gx = ((c - a) + 2 (f - d)) + (i - g), gy = ((g - a) + 2 (h - b)) + (i - c),
+ * slope = sqrtf(gx gx + gy gy) / den with den = (float)(8 * cellsize) from the caller; NaN (0x7fc00000) at unknown pixels. */
+int tg_terrain_slope(const float* w, const uint8_t* known, int H, int W, float den, float* slope, tg_stream_t stream);
+/* twi = logf((acc * cellsize) / fmaxf(slope, min_slope)) at known pixels, NaN (0x7fc00000) at unknown ones; cellsize and min_slope
+ * finite and > 0. */
+int tg_wetness(const float* acc, const float* slope, const uint8_t* known, int H, int W, float cellsize, float min_slope,
+               float* twi, tg_stream_t stream);
+/* Two wetness planes over the pixels with sel != 0 where both are finite (t = truth, p = the fill), d = twi_p - twi_t in fp32:
+ * counts [2] int64 (zeroed here) = cells, the bits of the largest |d|; sums [3] double = the sums of d, |d| and d * d in fp64 in a
+ * fixed order (as tg_mfd_finish's).  ws >= tg_mfd_ws_bytes(H, W); only its partial sums are used. */
+int tg_wetness_compare(const uint8_t* sel, const float* twi_t, const float* twi_p, int H, int W, int64_t* counts, double* sums,
+                       void* ws, size_t ws_bytes, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

@@ -56,12 +56,18 @@ streams of stream_cells cells) is taken, and report["flood"] compares the two HA
 flood_stages_m inside the holes, in integers; report["baseline"] and every report["compare"][name] gain the same key.  Without it
 the report has no "flood" key and nothing more runs.
 
+With wetness=True the report also says whether a fill keeps the hillslopes (wetness_errors): both surfaces
+are routed as above, each side's topographic wetness index ln(a / tan(beta)) is taken from a multiple-flow-direction accumulation
+and Horn's slope, and report["wetness"] holds the bias, MAE, RMSE and largest difference of the two inside the holes;
+report["baseline"] and every report["compare"][name] gain the same key.  Without it the report has no "wetness" key and nothing
+more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
-         [--flood [--flood-stages s ...]]
+         [--flood [--flood-stages s ...]] [--wetness [--exponent e] [--min-slope s]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -460,10 +466,11 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 @torch.no_grad()
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
-                    stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M):
+                    stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
+                    wetness_min_slope=1e-3):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
     fill info under "fill"; with sinks also sink_errors' dict under "sinks", with drainage drainage_errors' under "drainage",
-    with flood flood_errors' under "flood"."""
+    with flood flood_errors' under "flood", with wetness wetness_errors' under "wetness"."""
     from .fill_voids import fill_voids
     device = _device()
     z = _f32(dem, device, "dem")
@@ -481,6 +488,9 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     if flood:
         rep["flood"] = flood_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
                                     stages_m=flood_stages_m)
+    if wetness:
+        rep["wetness"] = wetness_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=wetness_exponent,
+                                        min_slope=wetness_min_slope)
     return rep
 
 
@@ -502,10 +512,10 @@ def _check_compare(compare, who="evaluate_raster"):
     return names
 
 
-def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None):
+def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None, wetness=None):
     """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name; with sinks
     ({name: sink_errors' dict}) also "sinks", with drainage ({name: drainage_errors' dict}) also "drainage", with flood ({name:
-    flood_errors' dict}) also "flood"."""
+    flood_errors' dict}) also "flood", with wetness ({name: wetness_errors' dict}) also "wetness"."""
     out = {}
     for name, rep in reports.items():
         out[name] = dict(rep)
@@ -517,19 +527,22 @@ def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None):
             out[name]["drainage"] = drainage[name]
         if flood is not None:
             out[name]["flood"] = flood[name]
+        if wetness is not None:
+            out[name]["wetness"] = wetness[name]
     return out
 
 
 @torch.no_grad()
 def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
                    quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
-                   stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M):
+                   stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
+                   wetness_min_slope=1e-3):
     """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
     from .interpolate import interpolate_voids
     device = _device()
     z = _f32(dem, device, "dem")
     k = _f32(keep, device, "keep", binary=True)
-    reports, infos, snk, drn, fld = {}, {}, {}, {}, {}
+    reports, infos, snk, drn, fld, wet = {}, {}, {}, {}, {}, {}
     for name in _check_compare(names):
         pred, infos[name] = interpolate_voids(z, k, nodata=_nodata(nodata), method=name, cellsize=cellsize)
         reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
@@ -542,7 +555,11 @@ def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None,
         if flood:
             fld[name] = flood_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
                                      stages_m=flood_stages_m)
-    return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None, fld if flood else None)
+        if wetness:
+            wet[name] = wetness_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=wetness_exponent,
+                                       min_slope=wetness_min_slope)
+    return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None, fld if flood else None,
+                            wet if wetness else None)
 
 
 # ---- sinks: does a fill drain ---------------------------------------------------------------------------------------------
@@ -806,12 +823,70 @@ def flood_summary(d):
             f"{d['undrained_truth']} truth / {d['undrained_pred']} fill); CSI by stage: {st}")
 
 
+# ---- wetness: does a fill keep the hillslopes' contributing area and slope ----------------------------------------------------
+def assemble_wetness(counts, sums):
+    """The wetness dict from tg_wetness_compare's numbers (counts: cells, the bits of the largest |d|; sums: of d, |d|, d * d)
+    (pure: no GPU): cells, and bias, mae, rmse and max of the TWI difference fill minus truth; None without cells."""
+    cells, bits = (int(v) for v in counts)
+    sd, sa, s2 = (float(v) for v in sums)
+    if not cells:
+        return {"cells": 0, "bias": None, "mae": None, "rmse": None, "max": None}
+    return {"cells": cells, "bias": sd / cells, "mae": sa / cells, "rmse": math.sqrt(s2 / cells), "max": _f32bits(bits)}
+
+
+@torch.no_grad()
+def wetness_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, exponent=1, min_slope=1e-3):
+    """wetness_errors' measurement -> (counts, sums as lists, [truth side, pred side]: each wetness_known's info)."""
+    from tg_hip import ops as O
+    from .flow_routing import check_exponent, check_min_slope, wetness_known
+    who = "wetness_errors"
+    c = _cellsize(cellsize, who)
+    _inputs(dem, mask, who)
+    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
+        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    check_exponent(exponent, who)
+    check_min_slope(min_slope, who)
+    device = _device()
+    z = _f32(dem, device, "dem")
+    p = _f32(pred, device, "pred")
+    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    sel = _u8(holes, device)
+    kz, _ = O.objmask_known(z, m, _nodata(nodata), transposed=False)
+    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
+    known = kz & kp
+    twis, sides = [], []
+    for surf in (z, p):
+        twi, _, _, info = wetness_known(surf, known, c, fill=True, exponent=exponent, min_slope=min_slope)
+        twis.append(twi)
+        sides.append(info)
+    counts, sums = O.wetness_compare(sel, twis[0], twis[1])
+    return counts.cpu().tolist(), sums.cpu().tolist(), sides
+
+
+def wetness_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, exponent=1, min_slope=1e-3):
+    """Does a fill keep the hillslopes' wetness.  dem and pred are routed (flow_routing's chain with fill=True) over one known
+    mask, the pixels known in both, exactly as drainage_errors routes them; each side's topographic wetness index
+    (flow_routing.wetness_known: the multiple-flow-direction accumulation at `exponent`, Horn's slope not below min_slope) is
+    taken, and inside holes (nonzero = hole), where both are finite, d = twi_pred - twi_truth in float32 is summed in float64 in a
+    fixed order.  -> {"cells", "bias", "mae", "rmse", "max"} (assemble_wetness)."""
+    counts, sums, _ = wetness_raw(dem, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=exponent,
+                                  min_slope=min_slope)
+    return assemble_wetness(counts, sums)
+
+
+def wetness_summary(d):
+    """One line for a wetness dict."""
+    f = lambda v, spec: "n/a" if v is None else format(v, spec)
+    return (f"wetness: TWI bias {f(d['bias'], '.4g')}, MAE {f(d['mae'], '.4g')}, RMSE {f(d['rmse'], '.4g')}, max "
+            f"{f(d['max'], '.4g')} over {d['cells']} px")
+
+
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
                     solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
-                    flood=False, flood_stages_m=FLOOD_STAGES_M):
+                    flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -822,20 +897,24 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     sinks=True adds sink_errors' dict under "sinks" to the report, to report["baseline"] and to every report["compare"][name];
     drainage=True adds drainage_errors' dict (streams of stream_cells cells, matched within stream_tol_m) under "drainage" to the
     same three places; flood=True adds flood_errors' dict (HAND against streams of stream_cells cells, flood extents at
-    flood_stages_m) under "flood" to the same three places."""
+    flood_stages_m) under "flood" to the same three places; wetness=True adds wetness_errors' dict (the TWI from the
+    multiple-flow-direction accumulation at wetness_exponent, slopes not below wetness_min_slope) under "wetness" to the same
+    three places."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
                              seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
                              depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
-                             stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m)
+                             stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m,
+                             wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope)
     return rep, pred
 
 
 def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, block, tile, holes, seed, window, overlap, batch,
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
-              stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M):
+              stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
+              wetness_min_slope=1e-3):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
@@ -856,6 +935,10 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     if flood:
         _check_stream_cells(stream_cells, "evaluate_raster")
         check_flood_stages(flood_stages_m, "evaluate_raster")
+    if wetness:
+        from .flow_routing import check_exponent, check_min_slope
+        check_exponent(wetness_exponent, "evaluate_raster")
+        check_min_slope(wetness_min_slope, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
@@ -879,13 +962,17 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     if sinks:
         rep["sinks"] = sink_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata)
     drn = {"drainage": bool(drainage), "stream_cells": stream_cells, "stream_tol_m": stream_tol_m, "flood": bool(flood),
-           "flood_stages_m": flood_stages_m}
+           "flood_stages_m": flood_stages_m, "wetness": bool(wetness), "wetness_exponent": wetness_exponent,
+           "wetness_min_slope": wetness_min_slope}
     if drainage:
         rep["drainage"] = drainage_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, stream_cells=stream_cells,
                                           stream_tol_m=stream_tol_m)
     if flood:
         rep["flood"] = flood_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, stream_cells=stream_cells,
                                     stages_m=flood_stages_m)
+    if wetness:
+        rep["wetness"] = wetness_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, exponent=wetness_exponent,
+                                        min_slope=wetness_min_slope)
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
@@ -975,6 +1062,12 @@ def build_parser():
     ap.add_argument("--flood-stages", type=float, nargs="+", metavar="S", default=list(FLOOD_STAGES_M),
                     help="with --flood: 1 to 8 water stages above the drainage in metres, increasing (default: "
                          + " ".join(f"{s:g}" for s in FLOOD_STAGES_M) + ")")
+    ap.add_argument("--wetness", action="store_true",
+                    help="also compare the topographic wetness index ln(a / tan(beta)) of the truth and of every scored fill "
+                         "inside the holes (a from a multiple-flow-direction accumulation): one more summary line per fill")
+    ap.add_argument("--exponent", type=int, default=1,
+                    help="with --wetness: the exponent of the multiple-flow-direction rule, an integer in 1..8")
+    ap.add_argument("--min-slope", type=float, default=1e-3, help="with --wetness: slopes below this count as this (> 0)")
     return ap
 
 
@@ -991,6 +1084,10 @@ def main(argv=None):
         check_flood_stages(a.flood_stages, "--flood-stages")
     except ValueError as e:
         ap.error(str(e))
+    if not 1 <= a.exponent <= 8:
+        ap.error("--exponent must lie in [1, 8]")
+    if not (a.min_slope > 0 and a.min_slope < math.inf):
+        ap.error("--min-slope must be finite and > 0")
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
@@ -1015,7 +1112,8 @@ def main(argv=None):
                                   baseline=a.baseline, fallback=a.fallback, seam=a.seam, model_cellsize=a.model_cellsize,
                                   min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges,
                                   compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
-                                  stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages))
+                                  stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages),
+                                  wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -1029,13 +1127,17 @@ def main(argv=None):
         if a.sinks:
             rep["sinks"] = sink_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata)
         drn = {"drainage": a.drainage, "stream_cells": a.stream_cells, "stream_tol_m": a.stream_tol, "flood": a.flood,
-               "flood_stages_m": tuple(a.flood_stages)}
+               "flood_stages_m": tuple(a.flood_stages), "wetness": a.wetness, "wetness_exponent": a.exponent,
+               "wetness_min_slope": a.min_slope}
         if a.drainage:
             rep["drainage"] = drainage_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, stream_cells=a.stream_cells,
                                               stream_tol_m=a.stream_tol)
         if a.flood:
             rep["flood"] = flood_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, stream_cells=a.stream_cells,
                                         stages_m=tuple(a.flood_stages))
+        if a.wetness:
+            rep["wetness"] = wetness_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, exponent=a.exponent,
+                                            min_slope=a.min_slope)
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
                                               solver=a.solver, depth_edges_m=depth_edges, sinks=a.sinks, **drn)
@@ -1060,6 +1162,8 @@ def main(argv=None):
         print(drainage_summary(rep["drainage"]))
     if "flood" in rep:
         print(flood_summary(rep["flood"]))
+    if "wetness" in rep:
+        print(wetness_summary(rep["wetness"]))
     if "seam" in rep:
         sm = rep["seam"]
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
@@ -1073,6 +1177,8 @@ def main(argv=None):
             print(f"baseline {rep['baseline']['method']} {drainage_summary(rep['baseline']['drainage'])}")
         if "flood" in rep["baseline"]:
             print(f"baseline {rep['baseline']['method']} {flood_summary(rep['baseline']['flood'])}")
+        if "wetness" in rep["baseline"]:
+            print(f"baseline {rep['baseline']['method']} {wetness_summary(rep['baseline']['wetness'])}")
     for name, r in rep.get("compare", {}).items():
         print(f"compare {name}: {summary(r)}")
         if "sinks" in r:
@@ -1081,6 +1187,8 @@ def main(argv=None):
             print(f"compare {name} {drainage_summary(r['drainage'])}")
         if "flood" in r:
             print(f"compare {name} {flood_summary(r['flood'])}")
+        if "wetness" in r:
+            print(f"compare {name} {wetness_summary(r['wetness'])}")
     return rep
 
 

@@ -36,13 +36,20 @@ stream_network(direction, accumulation, min_cells) gives the streams their struc
 stream pixel (head, interior, junction), the link it belongs to and its Strahler order; hand(dem, ...) the height of every pixel
 above the drainage pixel its water reaches first and the flow length to it.  Exact and bitwise reproducible as well.
 
+mfd_accumulation(dem, ...) is the contributing area by a multiple-flow-direction rule (csrc/mfd.hip): on
+hillslopes, where D8 draws parallel stripes, every pixel spreads over all its lower neighbours; terrain_slope(dem, ...) is Horn's
+slope and wetness_index(dem, ...) the topographic wetness index ln(a / tan(beta)) built on the two.  The accumulation is float64
+in a fixed order, bitwise equal to tests/mfd_oracle.py and bitwise reproducible.
+
 CLI: python -m mvp_gan.src.flow_routing --dem in.asc --dir-out d.asc --acc-out a.asc [--mask m.png|m.asc] [--nodata v]
          [--no-fill] [--esri] [--streams-out s.asc --min-cells n] [--max-sweeps n]       (cellsize from the header)
          [--basins-out b.asc [--pour p.png|p.asc] [--compact]] [--length-out l.asc]
          [--order-out o.asc] [--links-out l.asc] [--hand-out h.asc [--hand-distance-out d.asc] [--min-order k]]   (with --min-cells)
+         [--mfd-acc-out m.asc] [--slope-out s.asc] [--twi-out t.asc [--min-slope s]] [--exponent e]
 """
 import argparse
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -122,9 +129,15 @@ def flow_routing(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, max_sw
 
 def route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who):
     """flow_routing's checks, upload and known mask -> (direction, accumulation, info, w: the surface that was routed)."""
+    z, known, c = _upload(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who)
+    return route_known(z, known, c, fill=fill, max_sweeps=max_sweeps, check_every=check_every, return_surface=True)
+
+
+def _upload(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who):
+    """flow_routing's checks, upload and known mask -> (z float32 [H][W], known uint8 [H][W], cellsize)."""
     from tg_hip import ops as O
     from .fill_voids import _device_f32
-    H, W, c = check_args(dem, mask, cellsize, 8, max_sweeps, check_every, who=who)
+    _, _, c = check_args(dem, mask, cellsize, 8, max_sweeps, check_every, who=who)
     if not isinstance(fill, bool):
         raise ValueError(f"{who}: fill {fill!r} must be True or False")
     if not torch.cuda.is_available():
@@ -135,7 +148,7 @@ def route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who
     if nodata is not None and math.isnan(nodata):
         nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
     known, _ = O.objmask_known(z, m, nodata, transposed=False)
-    return route_known(z, known, c, fill=fill, max_sweeps=max_sweeps, check_every=check_every, return_surface=True)
+    return z, known, c
 
 
 def route_known(z, known, cellsize, *, fill=True, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY, return_surface=False):
@@ -418,6 +431,129 @@ def hand_routed(w, direction, acc, info, c, min_cells, min_order=1, check_every=
     return h, dist, info, stream
 
 
+# ---- multiple flow directions, slope, wetness --------------------------------------------------------------------------
+MIN_SLOPE = 1e-3
+
+
+def check_exponent(exponent, who="mfd_accumulation"):
+    """An integer (Python's or numpy's, not a bool) in 1..8 -> int."""
+    if isinstance(exponent, (bool, np.bool_)) or not isinstance(exponent, numbers.Integral) or not 1 <= exponent <= 8:
+        raise ValueError(f"{who}: exponent {exponent!r} must be an integer in [1, 8]")
+    return int(exponent)
+
+
+def check_min_slope(min_slope, who="wetness_index"):
+    """A finite real number (Python's or numpy's, not a bool) > 0, also as float32 -> float."""
+    ok = not isinstance(min_slope, (bool, np.bool_)) and isinstance(min_slope, numbers.Real)
+    if ok:
+        with np.errstate(over="ignore"):
+            f = float(np.float32(min_slope))
+        ok = 0 < f < math.inf
+    if not ok:
+        raise ValueError(f"{who}: min_slope {min_slope!r} must be a finite number > 0 (in float32 as well)")
+    return float(min_slope)
+
+
+def mfd_sweeps(w, exponent, A, counts, ws, check_every=CHECK_EVERY):
+    """The sweeps of the MFD accumulation on device tensors (A, counts and ws as ops.mfd_setup leaves them) to the end ->
+    (sweeps enqueued, tile_visits).  One host sync per check_every sweeps.  Every block of sweeps makes at least one pixel final
+    (a pixel that is lowest in (w, D) among those not final has only final donors), so there is no limit to set."""
+    from tg_hip import ops as O
+    left, visits = counts.cpu().tolist()[3:5]
+    sweeps = 0
+    while left:
+        O.mfd_sweep(w, exponent, check_every, A, counts, ws)
+        sweeps += check_every
+        now, visits = counts.cpu().tolist()[3:5]
+        if now == left:
+            raise RuntimeError("mfd_accumulation: the flow graph has a cycle")     # cannot happen: every edge goes down in (w, D)
+        left = now
+    return sweeps, visits
+
+
+def mfd_known(w, known, direction, *, exponent=1, check_every=CHECK_EVERY, ws=None):
+    """mfd_accumulation's second half on a routing (w float32, known uint8, direction uint8, all [H][W] on the device) ->
+    (accumulation float32 [H][W], A float64 [H][W], info: dispersive, single, sinks, mfd_sweeps, mfd_tile_visits,
+    max_accumulation_mfd, mass_out, exponent)."""
+    from tg_hip import ops as O
+    exponent = check_exponent(exponent)
+    H, W = w.shape
+    if ws is None:
+        ws = O.mfd_ws(H, W, w.device)
+    A, counts = O.mfd_setup(w, known, direction, exponent, ws)
+    dispersive, single, sinks = counts.cpu().tolist()[:3]
+    sweeps, visits = mfd_sweeps(w, exponent, A, counts, ws, check_every)
+    acc, out = O.mfd_finish(A, direction, ws)
+    amax, mass = out.cpu().tolist()
+    info = {"dispersive": dispersive, "single": single, "sinks": sinks, "mfd_sweeps": sweeps, "mfd_tile_visits": visits,
+            "max_accumulation_mfd": amax, "mass_out": mass, "exponent": exponent}
+    return acc, A, info
+
+
+@torch.no_grad()
+def mfd_accumulation(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, exponent=1, max_sweeps=MAX_SWEEPS,
+                     check_every=CHECK_EVERY):
+    """Contributing area by a multiple-flow-direction rule (csrc/mfd.hip; inputs as flow_routing).  The
+    raster is routed as flow_routing routes it; on the routed surface w a known pixel q gives each lower known neighbour n_j the
+    fraction t_j / S of what it holds, t_j = (w(q) - w(n_j)) ** exponent times 2 ** (-(exponent + 1) / 2) for a diagonal n_j
+    (Quinn et al. 1991 at exponent 1, Holmgren 1994 above), S their sum; a pixel without a lower neighbour (a flat pixel) gives
+    all to its D8 receiver; OUT and PIT pixels give nothing.  A(p) = 1 + the sum of fraction * A(q) over the donors q, in
+    float64 in a fixed order.  exponent: an integer in 1..8; 1 spreads widest, large ones approach D8.  max_sweeps limits the
+    fill and the flats as in flow_routing; the MFD sweeps run to the end.  Returns (accumulation float32 HIP tensor [H][W] in
+    cells, 0 at unknown pixels; info: flow_routing's plus dispersive, single, sinks (pixels by what they give), mfd_sweeps,
+    mfd_tile_visits (both may differ between runs; the raster does not), max_accumulation_mfd, mass_out (the sum of A over the
+    sinks: the number of known pixels up to rounding) and exponent).  Bitwise equal to tests/mfd_oracle.py and bitwise
+    reproducible."""
+    who = "mfd_accumulation"
+    exponent = check_exponent(exponent, who)
+    z, known, c = _upload(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who)
+    direction, _, info, w = route_known(z, known, c, fill=fill, max_sweeps=max_sweeps, check_every=check_every,
+                                        return_surface=True)
+    acc, _, minfo = mfd_known(w, known, direction, exponent=exponent, check_every=check_every)
+    info.update(minfo)
+    return acc, info
+
+
+@torch.no_grad()
+def terrain_slope(dem, mask=None, *, nodata=None, cellsize=1.0):
+    """Horn's slope tan(beta) of a DEM as given (no fill): float32 HIP tensor [H][W], NaN at unknown pixels; a neighbour off
+    the raster or unknown counts as the centre height.  In float32, in the operation order of tests/mfd_oracle.py."""
+    from tg_hip import ops as O
+    z, known, c = _upload(dem, mask, nodata, cellsize, True, 1, 1, "terrain_slope")
+    return O.terrain_slope(z, known, c)
+
+
+def wetness_known(z, known, cellsize, *, fill=True, exponent=1, min_slope=MIN_SLOPE, max_sweeps=MAX_SWEEPS,
+                  check_every=CHECK_EVERY):
+    """wetness_index's body on device tensors with a ready known mask (as route_known) -> (twi, accumulation, slope, info)."""
+    from tg_hip import ops as O
+    exponent = check_exponent(exponent, "wetness_index")
+    min_slope = check_min_slope(min_slope)
+    direction, _, info, w = route_known(z, known, cellsize, fill=fill, max_sweeps=max_sweeps, check_every=check_every,
+                                        return_surface=True)
+    acc, _, minfo = mfd_known(w, known, direction, exponent=exponent, check_every=check_every)
+    info.update(minfo)
+    slope = O.terrain_slope(w, known, cellsize)
+    twi = O.wetness(acc, slope, known, cellsize, min_slope)
+    info["min_slope"] = min_slope
+    return twi, acc, slope, info
+
+
+@torch.no_grad()
+def wetness_index(dem, mask=None, *, nodata=None, cellsize=1.0, fill=True, exponent=1, min_slope=MIN_SLOPE,
+                  max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY):
+    """The topographic wetness index ln(a / tan(beta)) of a DEM (inputs as flow_routing): a = float32(A) * float32(cellsize),
+    the specific catchment area in metres from mfd_accumulation; tan(beta) Horn's slope of the routed surface (the filled one
+    with fill=True), not below min_slope (> 0); twi = logf(a / fmaxf(slope, min_slope)) in float32.  Returns (twi, accumulation,
+    slope: float32 HIP tensors [H][W], twi and slope NaN at unknown pixels; info: mfd_accumulation's plus min_slope)."""
+    who = "wetness_index"
+    check_exponent(exponent, who)
+    check_min_slope(min_slope, who)
+    z, known, c = _upload(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who)
+    return wetness_known(z, known, c, fill=fill, exponent=exponent, min_slope=min_slope, max_sweeps=max_sweeps,
+                         check_every=check_every)
+
+
 # ---- CLI ------------------------------------------------------------------------------------------------------------
 def build_parser():
     ap = argparse.ArgumentParser(description="D8 flow directions and flow accumulation of an ESRI ASCII grid DEM: depressions "
@@ -448,6 +584,15 @@ def build_parser():
     ap.add_argument("--compact", action="store_true", help="with --basins-out: number the basins 1..n in raster order of their "
                                                            "outlets, 0 = void")
     ap.add_argument("--length-out", help="also write the flow length to the outlet in metres (.asc, full float32 precision)")
+    ap.add_argument("--mfd-acc-out", help="also write the multiple-flow-direction contributing area in cells (.asc, full float32 "
+                                          "precision): every cell spreads over all its lower neighbours (--exponent)")
+    ap.add_argument("--exponent", type=int, default=1, help="with --mfd-acc-out or --twi-out: a lower neighbour gets a share "
+                                                            "proportional to its drop to this power, an integer in 1..8 "
+                                                            "(default 1: widest spreading; large values approach D8)")
+    ap.add_argument("--slope-out", help="also write Horn's slope tan(beta) of the routed surface (.asc)")
+    ap.add_argument("--twi-out", help="also write the topographic wetness index ln(a / tan(beta)) (.asc), a the specific catchment "
+                                      "area in metres from the multiple-flow-direction accumulation")
+    ap.add_argument("--min-slope", type=float, default=MIN_SLOPE, help="with --twi-out: slopes below this count as this (> 0)")
     ap.add_argument("--dir-out", required=True, help="output .asc raster of direction codes")
     ap.add_argument("--acc-out", required=True, help="output .asc raster of the flow accumulation in cells")
     return ap
@@ -472,6 +617,14 @@ def parse_args(argv=None):
         ap.error("--compact needs --basins-out")
     if a.pour and not (a.basins_out or a.length_out):
         ap.error("--pour needs --basins-out or --length-out")
+    if not 1 <= a.exponent <= 8:
+        ap.error("--exponent must lie in [1, 8]")
+    if a.exponent != 1 and not (a.mfd_acc_out or a.twi_out):
+        ap.error("--exponent needs --mfd-acc-out or --twi-out")
+    if not (a.min_slope > 0 and a.min_slope < math.inf):
+        ap.error("--min-slope must be finite and > 0")
+    if a.min_slope != MIN_SLOPE and not a.twi_out:
+        ap.error("--min-slope needs --twi-out")
     return a
 
 
@@ -520,6 +673,24 @@ def main(argv=None):
             write_asc(a.hand_distance_out, dist.cpu().numpy(), fh)
         print(f"{a.hand_out}: {info['drained']} cells drain to {info['stream_cells']} drainage cells (order >= {a.min_order}), "
               f"{info['undrained']} do not; largest height above drainage {info['max_hand_m']:.9g} m, {info['rounds']} rounds")
+    if a.mfd_acc_out or a.slope_out or a.twi_out:
+        from tg_hip import ops as O
+        known = (direction != 0).to(torch.uint8)                    # every known pixel has a code
+        fh = list(header) if asc_value(header, "NODATA_value") is not None else list(header) + [("NODATA_value", "-9999")]
+        if a.slope_out or a.twi_out:
+            slope = O.terrain_slope(w, known, cs)
+            if a.slope_out:
+                write_asc(a.slope_out, slope.cpu().numpy(), fh)
+        if a.mfd_acc_out or a.twi_out:
+            macc, _, minfo = mfd_known(w, known, direction, exponent=a.exponent)
+            info.update(minfo)
+            if a.mfd_acc_out:
+                write_asc(a.mfd_acc_out, macc.cpu().numpy(), [(k, v) for k, v in header if k.lower() != "nodata_value"])
+            if a.twi_out:
+                write_asc(a.twi_out, O.wetness(macc, slope, known, cs, check_min_slope(a.min_slope, "--min-slope")).cpu().numpy(), fh)
+            print(f"{a.mfd_acc_out or a.twi_out}: exponent {minfo['exponent']}, {minfo['dispersive']} cells spread, "
+                  f"{minfo['single']} give to one neighbour, {minfo['sinks']} sinks; largest contributing area "
+                  f"{minfo['max_accumulation_mfd']:.9g} cells, {minfo['mass_out']:.9g} cells leave, {minfo['mfd_sweeps']} sweeps")
     if a.basins_out or a.length_out:
         pour = _read_mask(a.pour, dem.shape) if a.pour else None
         basin, length, winfo = watersheds(direction, pour, cellsize=float(asc_value(header, "cellsize")), compact=a.compact)

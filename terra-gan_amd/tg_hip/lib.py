@@ -60,6 +60,7 @@ TG_STREAM_HEAD, TG_STREAM_INTERIOR, TG_STREAM_JUNCTION, TG_STREAM_ORDER_BINS = 1
 TG_STREAM_ORDER_COUNTS = 1 + 2 * TG_STREAM_ORDER_BINS
 TG_FLOOD_MAX_STAGES = 8
 TG_FLOOD_COUNTS = 6 + 3 * TG_FLOOD_MAX_STAGES
+TG_MFD_MAX_EXPONENT, TG_MFD_COUNTS = 8, 5
 
 
 class TgFloodStages(C.Structure):
@@ -219,6 +220,13 @@ SIGNATURES = {
     "tg_stream_order_finish": (I, [P, P, P, I, I, P, P, P]),
     "tg_hand": (I, [P, P, P, P, I, I, P, P, P, P]),
     "tg_flood_compare": (I, [P, P, P, I, I, TgFloodStages, I, P, P]),
+    "tg_mfd_ws_bytes": (SZ, [I, I]),
+    "tg_mfd_setup": (I, [P, P, P, I, I, I, D, P, P, P, SZ, P]),
+    "tg_mfd_sweep": (I, [P, I, I, I, D, I, P, P, P, SZ, P]),
+    "tg_mfd_finish": (I, [P, P, I, I, P, P, P, SZ, P]),
+    "tg_terrain_slope": (I, [P, P, I, I, F, P, P]),
+    "tg_wetness": (I, [P, P, P, I, I, F, F, P, P]),
+    "tg_wetness_compare": (I, [P, P, P, I, I, P, P, P, SZ, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -1690,6 +1690,153 @@ def flood_compare(sel, hand_t, hand_p, stages):
     return counts
 
 
+MFD_MAX_EXPONENT, MFD_COUNTS = L.TG_MFD_MAX_EXPONENT, L.TG_MFD_COUNTS
+# tg_mfd_setup's counters in order
+MFD_COUNT_NAMES = ("dispersive", "single", "sinks", "not_final", "tile_visits")
+
+
+def mfd_cdiag(exponent):
+    """The weight of a diagonal drop against a cardinal one, 2 ** (-(e + 1) / 2) as a double: Quinn's contour lengths 0.5 and
+    sqrt(2) / 4 over the step lengths 1 and sqrt(2).  The kernels and the oracle of the tests get these bits."""
+    import numbers
+    if isinstance(exponent, bool) or not isinstance(exponent, numbers.Integral) or not 1 <= exponent <= MFD_MAX_EXPONENT:
+        raise ValueError(f"mfd: exponent {exponent!r} must be an integer in [1, {MFD_MAX_EXPONENT}]")
+    return 2.0 ** (-(int(exponent) + 1) / 2)
+
+
+def _mfd_plane(t, dtype, shape, name, who):
+    """The mfd entries refuse with ValueError, before any launch."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and (shape is None or tuple(t.shape) == shape)):
+        got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{who}: {name} must be a contiguous {dtype} HIP tensor {list(shape) if shape else '[H][W]'}, got {got}")
+
+
+def _mfd_hw(t, name, who):
+    _mfd_plane(t, torch.float32, None, name, who)
+    if t.dim() != 2 or min(t.shape) < 1 or t.shape[0] * t.shape[1] >= 2 ** 31:
+        raise ValueError(f"{who}: {name} must be [H][W], non-empty with H*W < 2^31, got {tuple(t.shape)}")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def mfd_ws(H, W, device):
+    """The workspace of one MFD accumulation: uint8 [tg_mfd_ws_bytes]; it carries S, the donor bytes and the tile list from
+    mfd_setup through the mfd_sweep calls to mfd_finish, so it is the caller's and not the shared one."""
+    n = _lib().tg_mfd_ws_bytes(int(H), int(W))
+    if n == 0:
+        raise ValueError(f"mfd: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _mfd_ws_chk(ws, H, W, who):
+    need = _lib().tg_mfd_ws_bytes(H, W)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+            and ws.data_ptr() % 8 == 0):
+        raise ValueError(f"{who}: ws must be a contiguous uint8 HIP tensor of at least {need} bytes, aligned to 8 (mfd_ws)")
+
+
+def mfd_setup(w, known, d, exponent, ws):
+    """-> (A float64 [H][W]: -1.0 at known pixels (not final), 0.0 at unknown ones; counts int64 [MFD_COUNTS]: MFD_COUNT_NAMES); S,
+    the donor bytes and the tile list go into ws (tg_mfd_setup)."""
+    who = "mfd_setup"
+    cdiag = mfd_cdiag(exponent)
+    H, W = _mfd_hw(w, "w", who)
+    _mfd_plane(known, torch.uint8, (H, W), "known", who)
+    _mfd_plane(d, torch.uint8, (H, W), "dir", who)
+    _mfd_ws_chk(ws, H, W, who)
+    A = torch.empty(H, W, dtype=torch.float64, device=w.device)
+    counts = torch.empty(MFD_COUNTS, dtype=torch.int64, device=w.device)
+    L.check(_lib().tg_mfd_setup(_p(w), _p(known), _p(d), H, W, int(exponent), cdiag, _p(A), _p(counts), _p(ws), ws.numel(), _stream()),
+            "tg_mfd_setup")
+    return A, counts
+
+
+def mfd_sweep(w, exponent, n, A, counts, ws):
+    """n >= 1 sweeps of A in place; counts[3] goes down by the pixels made final, counts[4] up by the tiles visited
+    (tg_mfd_sweep)."""
+    who = "mfd_sweep"
+    cdiag = mfd_cdiag(exponent)
+    H, W = _mfd_hw(w, "w", who)
+    _mfd_plane(A, torch.float64, (H, W), "A", who)
+    _mfd_plane(counts, torch.int64, (MFD_COUNTS,), "counts", who)
+    _mfd_ws_chk(ws, H, W, who)
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
+        raise ValueError(f"{who}: n {n!r} must be an integer in [1, 2^20]")
+    L.check(_lib().tg_mfd_sweep(_p(w), H, W, int(exponent), cdiag, n, _p(A), _p(counts), _p(ws), ws.numel(), _stream()), "tg_mfd_sweep")
+
+
+def mfd_finish(A, d, ws):
+    """-> (acc float32 [H][W]: A rounded once; out float64 [2]: the largest A, the sum of A over the sinks in a fixed order)
+    (tg_mfd_finish)."""
+    who = "mfd_finish"
+    _mfd_plane(A, torch.float64, None, "A", who)
+    if A.dim() != 2:
+        raise ValueError(f"{who}: A must be [H][W], got {tuple(A.shape)}")
+    H, W = int(A.shape[0]), int(A.shape[1])
+    _mfd_plane(d, torch.uint8, (H, W), "dir", who)
+    _mfd_ws_chk(ws, H, W, who)
+    acc = torch.empty(H, W, dtype=torch.float32, device=A.device)
+    out = torch.empty(2, dtype=torch.float64, device=A.device)
+    L.check(_lib().tg_mfd_finish(_p(A), _p(d), H, W, _p(acc), _p(out), _p(ws), ws.numel(), _stream()), "tg_mfd_finish")
+    return acc, out
+
+
+def _pos_f32(v, name, who):
+    """A finite number > 0 that stays so as float32 -> that float32 as a Python float."""
+    import numbers
+    import numpy as np
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, numbers.Real):
+        raise ValueError(f"{who}: {name} {v!r} must be a number")
+    with np.errstate(over="ignore"):
+        f = float(np.float32(v))
+    if not (f > 0 and f < float("inf")):
+        raise ValueError(f"{who}: {name} {v!r} must be finite and > 0 in float32")
+    return f
+
+
+def terrain_slope(w, known, cellsize=1.0):
+    """-> slope float32 [H][W]: Horn's tan(beta) of w over the known pixels, NaN at unknown ones (tg_terrain_slope)."""
+    who = "terrain_slope"
+    H, W = _mfd_hw(w, "w", who)
+    _mfd_plane(known, torch.uint8, (H, W), "known", who)
+    _pos_f32(cellsize, "cellsize", who)
+    den = _pos_f32(8.0 * float(cellsize), "8 * cellsize", who)
+    out = torch.empty(H, W, dtype=torch.float32, device=w.device)
+    L.check(_lib().tg_terrain_slope(_p(w), _p(known), H, W, den, _p(out), _stream()), "tg_terrain_slope")
+    return out
+
+
+def wetness(acc, slope, known, cellsize=1.0, min_slope=1e-3):
+    """-> twi float32 [H][W] = logf(acc * float32(cellsize) / fmaxf(slope, float32(min_slope))), NaN at unknown pixels
+    (tg_wetness)."""
+    who = "wetness"
+    H, W = _mfd_hw(acc, "acc", who)
+    _mfd_plane(slope, torch.float32, (H, W), "slope", who)
+    _mfd_plane(known, torch.uint8, (H, W), "known", who)
+    c = _pos_f32(cellsize, "cellsize", who)
+    ms = _pos_f32(min_slope, "min_slope", who)
+    out = torch.empty(H, W, dtype=torch.float32, device=acc.device)
+    L.check(_lib().tg_wetness(_p(acc), _p(slope), _p(known), H, W, c, ms, _p(out), _stream()), "tg_wetness")
+    return out
+
+
+def wetness_compare(sel, twi_t, twi_p, ws=None):
+    """-> (counts int64 [2]: cells, the bits of the largest |d|; sums float64 [3]: of d, |d|, d * d in a fixed order) of
+    d = twi_p - twi_t over the pixels with sel != 0 where both are finite (tg_wetness_compare).  ws: an mfd_ws, made here if None."""
+    who = "wetness_compare"
+    H, W = _mfd_hw(twi_t, "twi_t", who)
+    _mfd_plane(twi_p, torch.float32, (H, W), "twi_p", who)
+    _mfd_plane(sel, torch.uint8, (H, W), "sel", who)
+    if ws is None:
+        ws = mfd_ws(H, W, sel.device)
+    _mfd_ws_chk(ws, H, W, who)
+    counts = torch.empty(2, dtype=torch.int64, device=sel.device)
+    sums = torch.empty(3, dtype=torch.float64, device=sel.device)
+    L.check(_lib().tg_wetness_compare(_p(sel), _p(twi_t), _p(twi_p), H, W, _p(counts), _p(sums), _p(ws), ws.numel(), _stream()),
+            "tg_wetness_compare")
+    return counts, sums
+
+
 VFILL_NSTATS = 4                                # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
