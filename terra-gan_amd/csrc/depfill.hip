@@ -7,60 +7,42 @@
 // is exact, independent of the order of the updates and bitwise equal to a priority-flood.
 //
 //   depfill_init_kernel    W = z at outlets, +inf at the other known pixels, NaN at unknown ones
-//   depfill_begin_kernel   one thread: zero `changed`, advance the sweep counter by n
+//   sweep_begin_kernel     (raster_sweep.h) one thread: zero `changed`, advance the sweep counter by n
 //   depfill_sweep_kernel   one workgroup per 64x64 tile: z and W with a one-pixel halo in LDS, relaxed to a local fixed point
 //                          by directional line scans (down, up, right, left), written back if anything was lowered
 //   depfill_stats_kernel   counts, the fp64 depth sum and the largest depth: per-workgroup partials in a fixed order
 //   depfill_stats_finish_kernel  the partials in one ordered pass
 //   depfill_finish_kernel  out, depth, flags
 //
-// In place, one W plane: a tile's halo belongs to neighbours that may be writing it in the same launch.  Halo loads and the
-// write-back are relaxed atomic 32-bit accesses; a halo value is an old or a new W of that pixel, both upper bounds of the
-// answer, and a neighbour that lowers its rim marks this tile for the next sweep, so no lowered value is ever missed.
-//
-// Dirty tiles: two byte planes; plane (s & 1) is read in sweep s ("visit me"), the other one is written ("visit next").  A
-// visiting workgroup clears its own byte of the plane it read.
+// The tile-sweep protocol (one W plane in place, stale halos, the dirty planes, the line scans) is raster_sweep.h's; here an old and
+// a new W of a pixel are both upper bounds of the answer.
 //
 // Determinism: the raster is the unique fixed point.  Integer atomics only (`changed`, `visits`); the fp64 sum is taken in a
 // fixed order.  The number of sweeps and visits may differ between runs.
 #include <math.h>
 
-#include "common.h"
-
-static inline hipStream_t S(tg_stream_t s) { return (hipStream_t)s; }
-
-typedef unsigned long long ull;
+#include "raster_sweep.h"
 
 // The fp64 depth sums are compared with a reference that does not fuse: no multiply-add contraction in this file.
 #pragma clang fp contract(off)
 
-constexpr int DF_T = 64;                 // tile side
-constexpr int DF_R = DF_T + 2;           // rows and columns with the halo
-constexpr int DF_S = DF_T + 3;           // LDS row stride in floats: odd, so a wave is conflict-free along rows and along columns
+constexpr int DF_T = SW_T, DF_R = SW_R, DF_S = SW_S;
 constexpr int DF_ROUNDS = 64;            // cap on the inner rounds of one visit; a tile that hits it stays dirty
-constexpr int DF_CTL_BYTES = 256;        // int32 [0]: sweeps enqueued since init
 constexpr int DF_STAT_PIX = 4096;        // pixels per workgroup of the statistics
 constexpr int DF_STAT_MAX_BLOCKS = 1024;
 constexpr int DF_STAT_WORDS = 5;         // per workgroup: sum, max (double); raised, unreached, counted (int64)
 
-static size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct DfLayout {
-    size_t ctl, plane[2], stats, total;
-    int ty, tx, nstat;
+struct DfLayout : SweepLayout {
+    size_t stats, total;
+    int nstat;
 };
 
 static DfLayout df_layout(int H, int W) {
     DfLayout L;
-    L.ty = cdiv(H, DF_T);
-    L.tx = cdiv(W, DF_T);
+    size_t o;
+    static_cast<SweepLayout&>(L) = sweep_layout(H, W, o);
     int64_t nb = cdiv64((int64_t)H * W, DF_STAT_PIX);
     L.nstat = (int)(nb > DF_STAT_MAX_BLOCKS ? DF_STAT_MAX_BLOCKS : nb);
-    const size_t tiles = (size_t)L.ty * L.tx;
-    size_t o = 0;
-    L.ctl = o; o += DF_CTL_BYTES;
-    L.plane[0] = o; o += al256(tiles);
-    L.plane[1] = o; o += al256(tiles);
     L.stats = o; o += al256((size_t)L.nstat * DF_STAT_WORDS * 8);
     L.total = o;
     return L;
@@ -89,13 +71,6 @@ __global__ __launch_bounds__(256) void depfill_init_kernel(const float* __restri
     }
 }
 
-__global__ void depfill_begin_kernel(int32_t* __restrict__ ctl, int n, int32_t* __restrict__ changed) {
-    if (threadIdx.x == 0) {
-        ctl[0] = (ctl[0] + n) & 0x3fffffff;                         // only its parity is used
-        changed[0] = 0;
-    }
-}
-
 // ---- the sweep ----------------------------------------------------------------------------------------------------------
 template <int CONN>
 __global__ __launch_bounds__(256) void depfill_sweep_kernel(const float* __restrict__ z, const uint8_t* __restrict__ known, int H,
@@ -104,40 +79,35 @@ __global__ __launch_bounds__(256) void depfill_sweep_kernel(const float* __restr
                                                             uint8_t* plane1, int32_t* changed, ull* visits) {
     __shared__ float zs[DF_R * DF_S];
     __shared__ float ws[DF_R * DF_S];
-    const int tile = blockIdx.x;
-    const int sweep = ctl[0] - n + j;                               // begin_kernel has added n already
-    uint8_t* cur = (sweep & 1) ? plane1 : plane0;
-    uint8_t* nxt = (sweep & 1) ? plane0 : plane1;
-    if (!cur[tile]) return;                                         // uniform: a clean tile
+    SweepVisit v = sweep_visit_begin(ctl, n, j, plane0, plane1);
+    if (!v.marked) return;                                          // uniform: a clean tile
+    sweep_visit_place(v, tiles_x);
     const int t = threadIdx.x;
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * DF_T, x0 = tx * DF_T;
+    const int y0 = v.y0, x0 = v.x0;
     const float inf = df_inf();
 
     // stage: unknown and out-of-raster positions hold +inf in both images, so the loop below has no bounds or mask tests
     for (int i = t; i < DF_R * DF_R; i += 256) {
-        const int ly = i / DF_R, lx = i - ly * DF_R;
-        const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
-        float v = inf, zz = inf;
-        if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
-            const int64_t p = (int64_t)gy * W + gx;
-            const bool interior = ly >= 1 && ly <= DF_T && lx >= 1 && lx <= DF_T;
-            if (interior) {
-                v = w[p];
+        const SweepStage g = sweep_stage(i, y0, x0, H, W);
+        float wv = inf, zz = inf;
+        if (g.in_raster) {
+            const int64_t p = (int64_t)g.gy * W + g.gx;
+            if (g.interior()) {
+                wv = w[p];
                 if (known[p]) zz = z[p];
             } else {
-                v = __hip_atomic_load(w + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                wv = __hip_atomic_load(w + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
-            if (!(v == v)) v = inf;                                 // NaN: an unknown pixel
+            if (!(wv == wv)) wv = inf;                              // NaN: an unknown pixel
         }
-        ws[ly * DF_S + lx] = v;
-        zs[ly * DF_S + lx] = zz;
+        ws[g.ly * DF_S + g.lx] = wv;
+        zs[g.ly * DF_S + g.lx] = zz;
     }
     __syncthreads();
 
-    // relax: thread = one line (a column in rounds 0, 1; a row in rounds 2, 3) and one band of 16 pixels along it; the three
-    // values across the line are carried from pixel to pixel, so a pixel costs three new W reads and one z read.  A value read
-    // may be a neighbour's old or new one: both are upper bounds, and the last round, in which nobody writes, sees final values.
+    // relax by the line scans of raster_sweep.h: thread = one line and one band of 16 pixels along it; the three values across
+    // the line are carried from pixel to pixel, so a pixel costs three new W reads and one z read.  A value read may be a
+    // neighbour's old or new one: both are upper bounds, and the last round, in which nobody writes, sees final values.
     const int line = t & 63, band = t >> 6;
     const bool line_rim = line == 0 || line == DF_T - 1;
     int any = 0, rim = 0, round = 0, live = 1;
@@ -174,10 +144,7 @@ __global__ __launch_bounds__(256) void depfill_sweep_kernel(const float* __restr
     }
     any = __syncthreads_or(any);
     if (!any) {                                                     // nothing to write, nobody to wake
-        if (t == 0) {
-            cur[tile] = 0;
-            atomicAdd(visits, 1ull);
-        }
+        sweep_visit_end(v, tiles_y, tiles_x, visits, false, false);
         return;
     }
     rim = __syncthreads_or(rim);
@@ -187,21 +154,12 @@ __global__ __launch_bounds__(256) void depfill_sweep_kernel(const float* __restr
         const int ly = i >> 6, lx = i & 63;
         const int gy = y0 + ly, gx = x0 + lx;
         if (gy < H && gx < W) {
-            const float v = ws[(ly + 1) * DF_S + lx + 1];
-            if (v < inf) __hip_atomic_store(w + (int64_t)gy * W + gx, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const float wv = ws[(ly + 1) * DF_S + lx + 1];
+            if (wv < inf) __hip_atomic_store(w + (int64_t)gy * W + gx, wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
-    if (t == 0) {
-        cur[tile] = 0;
-        atomicAdd(visits, 1ull);
-        if (j == n - 1) atomicAdd(changed, 1);
-    }
-    // marks: itself, and after a lowered rim value the eight neighbour tiles (the same byte value from every writer)
-    if (t < 9) {
-        const int ny = ty + t / 3 - 1, nx = tx + t % 3 - 1;
-        if ((t == 4 || rim) && ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x)
-            __hip_atomic_store(nxt + (int64_t)ny * tiles_x + nx, (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (t == 0 && j == n - 1) atomicAdd(changed, 1);
+    sweep_visit_end(v, tiles_y, tiles_x, visits, true, rim != 0);   // marks: itself, and after a lowered rim value its neighbours
 }
 
 // ---- statistics ---------------------------------------------------------------------------------------------------------
@@ -300,31 +258,21 @@ __global__ __launch_bounds__(256) void depfill_finish_kernel(const float* __rest
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static int df_size_check(const char* who, int H, int W) {
-    TG_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "%s: raster %dx%d must be non-empty with H*W < 2^31", who,
-               H, W);
-    return TG_OK;
-}
-
 extern "C" size_t tg_depfill_ws_bytes(int H, int W) {
-    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    if (!raster_size_ok(H, W)) return 0;
     return df_layout(H, W).total;
 }
 
 extern "C" int tg_depfill_init(const float* z, const uint8_t* known, int H, int W, int conn, float* w, void* ws, size_t ws_bytes,
                                tg_stream_t stream) {
-    if (int rc = df_size_check("tg_depfill_init", H, W)) return rc;
+    if (int rc = raster_size_check("tg_depfill_init", H, W)) return rc;
     TG_REQUIRE(z && known && w && ws, "tg_depfill_init: null pointer");
     TG_REQUIRE(conn == 8 || conn == 4, "tg_depfill_init: connectivity %d must be 8 or 4", conn);
     TG_REQUIRE(w != z, "tg_depfill_init: w must not alias z");
     const DfLayout L = df_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_depfill_init: workspace %zu bytes < %zu", ws_bytes, L.total);
     const hipStream_t s = S(stream);
-    char* base = (char*)ws;
-    const size_t tiles = (size_t)L.ty * L.tx;
-    if (hipMemsetAsync(base + L.ctl, 0, DF_CTL_BYTES, s) != hipSuccess ||
-        hipMemsetAsync(base + L.plane[0], 1, tiles, s) != hipSuccess ||
-        hipMemsetAsync(base + L.plane[1], 0, tiles, s) != hipSuccess) {
+    if (!sweep_reset(L, ws, s)) {
         tg_set_error("tg_depfill_init: hipMemsetAsync failed");
         return TG_ERR_LAUNCH;
     }
@@ -337,7 +285,7 @@ extern "C" int tg_depfill_init(const float* z, const uint8_t* known, int H, int 
 
 extern "C" int tg_depfill_sweep(const float* z, const uint8_t* known, int H, int W, int conn, int n, float* w, int32_t* changed,
                                 int64_t* visits, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = df_size_check("tg_depfill_sweep", H, W)) return rc;
+    if (int rc = raster_size_check("tg_depfill_sweep", H, W)) return rc;
     TG_REQUIRE(z && known && w && changed && visits && ws, "tg_depfill_sweep: null pointer");
     TG_REQUIRE(conn == 8 || conn == 4, "tg_depfill_sweep: connectivity %d must be 8 or 4", conn);
     TG_REQUIRE(n >= 1 && n <= (1 << 20), "tg_depfill_sweep: n = %d sweeps must lie in [1, 2^20]", n);
@@ -345,28 +293,17 @@ extern "C" int tg_depfill_sweep(const float* z, const uint8_t* known, int H, int
     const DfLayout L = df_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_depfill_sweep: workspace %zu bytes < %zu", ws_bytes, L.total);
     const hipStream_t s = S(stream);
-    char* base = (char*)ws;
-    int32_t* ctl = (int32_t*)(base + L.ctl);
-    uint8_t* p0 = (uint8_t*)(base + L.plane[0]);
-    uint8_t* p1 = (uint8_t*)(base + L.plane[1]);
-    hipLaunchKernelGGL(depfill_begin_kernel, dim3(1), dim3(64), 0, s, ctl, n, changed);
-    TG_CHECK_LAUNCH("depfill_begin_kernel");
-    const dim3 grid(L.ty * L.tx);                                   // < 2^31 / 4096
-    for (int j = 0; j < n; ++j) {
-        if (conn == 8)
-            hipLaunchKernelGGL(depfill_sweep_kernel<8>, grid, dim3(256), 0, s, z, known, H, W, L.ty, L.tx, w, ctl, n, j, p0, p1,
-                               changed, reinterpret_cast<ull*>(visits));
-        else
-            hipLaunchKernelGGL(depfill_sweep_kernel<4>, grid, dim3(256), 0, s, z, known, H, W, L.ty, L.tx, w, ctl, n, j, p0, p1,
-                               changed, reinterpret_cast<ull*>(visits));
-        TG_CHECK_LAUNCH("depfill_sweep_kernel");
-    }
-    return TG_OK;
+    const auto sweep = conn == 8 ? depfill_sweep_kernel<8> : depfill_sweep_kernel<4>;
+    return sweep_run(L, ws, n, changed, s, "depfill_begin_kernel", "depfill_sweep_kernel",
+                     [&](dim3 grid, const int32_t* ctl, int j, uint8_t* p0, uint8_t* p1) {
+                         hipLaunchKernelGGL(sweep, grid, dim3(256), 0, s, z, known, H, W, L.ty, L.tx, w, ctl, n, j, p0, p1, changed,
+                                            reinterpret_cast<ull*>(visits));
+                     });
 }
 
 extern "C" int tg_depfill_stats(const float* z, const float* w, const uint8_t* known, const uint8_t* sel, int H, int W,
                                 int64_t* counts, double* sums, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = df_size_check("tg_depfill_stats", H, W)) return rc;
+    if (int rc = raster_size_check("tg_depfill_stats", H, W)) return rc;
     TG_REQUIRE(z && w && known && counts && sums && ws, "tg_depfill_stats: null pointer");
     const DfLayout L = df_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_depfill_stats: workspace %zu bytes < %zu", ws_bytes, L.total);
@@ -383,7 +320,7 @@ extern "C" int tg_depfill_stats(const float* z, const float* w, const uint8_t* k
 
 extern "C" int tg_depfill_finish(const float* z, const float* w, const uint8_t* known, int H, int W, float* out, float* depth,
                                  uint8_t* flags, tg_stream_t stream) {
-    if (int rc = df_size_check("tg_depfill_finish", H, W)) return rc;
+    if (int rc = raster_size_check("tg_depfill_finish", H, W)) return rc;
     TG_REQUIRE(z && w && known && out, "tg_depfill_finish: null pointer");
     TG_REQUIRE(out != z && out != w && depth != z && depth != w, "tg_depfill_finish: out and depth must not alias z or w");
     const int64_t n = (int64_t)H * W;

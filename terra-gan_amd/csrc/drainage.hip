@@ -11,29 +11,21 @@
 //   basin_init_kernel     the start state (next0, p, c0, d0) into plane 0; (-1, -1, 0, 0) at unknown pixels; live[0]; pour counts
 //   basin_round_kernel    a live pixel takes (next(q), last(q), nc + nc(q), nd + nd(q)); any other pixel copies its record, so the
 //                         plane of every later round holds its final record; live[k + 1]
-//   basin_state_kernel    one thread: the live count after the rounds enqueued and the number of rounds that ran
-//   basin_finish_kernel   last -> basin, nc, nd, the length in metres; terminals, the largest nc + nd and length
+//   doubling_state_kernel (raster_sweep.h) one thread: the live count after the rounds enqueued and the number of rounds that ran
+//   basin_finish_kernel  last -> basin, nc, nd, the length in metres; terminals, the largest nc + nd and length
 //   flow_compare_kernel   the 19 integer counters of two routings over the selected pixels
 //
+// live[], the rounds and the state follow the pointer-doubling protocol of raster_sweep.h, whose D8 tables these kernels use too.
 // A round moves 32 bytes per pixel (its record read and written) and 16 more per pixel whose pointer is live (the gather).
 //
 // Determinism: gathers and plain stores only on the rasters; the counters are sums and maxima of integers by integer atomics,
 // exact in any order.
-#include "common.h"
-
-static inline hipStream_t S(tg_stream_t s) { return (hipStream_t)s; }
-
-typedef unsigned long long ull;
+#include "raster_sweep.h"
 
 // length_m is one fp64 multiply, one add, one multiply, one rounding to fp32: nothing is fused in this file.
 #pragma clang fp contract(off)
 
-constexpr int DR_CTL_BYTES = 256;        // int32 [8 .. 40]: live[k] of the doubling
-constexpr int DR_LIVE = 8;               // first word of live[0 .. 32]
-constexpr int DR_MAX_ROUNDS = TG_FLOW_MAX_ROUNDS;
 constexpr int DR_NCMP = TG_FLOW_COMPARE_COUNTS;
-
-static size_t dr_al256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 struct DrLayout {
     size_t ctl, rec[2], total;
@@ -41,27 +33,13 @@ struct DrLayout {
 
 static DrLayout dr_layout(int H, int W) {
     DrLayout L;
-    const size_t px = dr_al256((size_t)H * W * 16);
+    const size_t px = al256((size_t)H * W * 16);
     size_t o = 0;
-    L.ctl = o; o += DR_CTL_BYTES;
+    L.ctl = o; o += SW_CTL_BYTES;
     L.rec[0] = o; o += px;
     L.rec[1] = o; o += px;
     L.total = o;
     return L;
-}
-
-// code - 1 -> (dy, dx): E, SE, S, SW, W, NW, N, NE (flow.hip's tables)
-__host__ __device__ constexpr int dr_dy(int k) { return ((0x01a9 >> (2 * k)) & 3) - 1; }     // 0, 1, 1, 1, 0, -1, -1, -1
-__host__ __device__ constexpr int dr_dx(int k) { return ((0x901a >> (2 * k)) & 3) - 1; }     // 1, 1, 0, -1, -1, -1, 0, 1
-static_assert(dr_dy(0) == 0 && dr_dy(1) == 1 && dr_dy(2) == 1 && dr_dy(3) == 1 && dr_dy(4) == 0 && dr_dy(5) == -1 &&
-              dr_dy(6) == -1 && dr_dy(7) == -1, "dy");
-static_assert(dr_dx(0) == 1 && dr_dx(1) == 1 && dr_dx(2) == 0 && dr_dx(3) == -1 && dr_dx(4) == -1 && dr_dx(5) == -1 &&
-              dr_dx(6) == 0 && dr_dx(7) == 1, "dx");
-
-__device__ __forceinline__ void dr_count_live(int alive, int32_t* dst) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) alive += __shfl_xor(alive, o, 64);
-    if ((threadIdx.x & 63) == 0 && alive) atomicAdd(dst, alive);
 }
 
 // ---- the doubling -------------------------------------------------------------------------------------------------------
@@ -79,7 +57,7 @@ __global__ __launch_bounds__(256) void basin_init_kernel(const uint8_t* __restri
             else ++ignored;
         } else if (code >= 1 && code <= 8) {
             const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
-            const int yy = y + dr_dy(code - 1), xx = x + dr_dx(code - 1);
+            const int yy = y + d8_dy(code - 1), xx = x + d8_dx(code - 1);
             if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
                 r.x = (int32_t)((int64_t)yy * W + xx);
                 r.z = (code & 1) ? 1 : 0;                           // codes 1, 3, 5, 7 are E, S, W, N
@@ -89,7 +67,7 @@ __global__ __launch_bounds__(256) void basin_init_kernel(const uint8_t* __restri
         rec[p] = r;
         alive += r.x >= 0;
     }
-    dr_count_live(alive, live);
+    count_live(alive, live);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         used += __shfl_xor(used, o, 64);
@@ -118,15 +96,7 @@ __global__ __launch_bounds__(256) void basin_round_kernel(int64_t n, const int4*
         out[p] = r;
         alive += r.x >= 0;
     }
-    dr_count_live(alive, live + 1);
-}
-
-__global__ void basin_state_kernel(const int32_t* __restrict__ live, int k_end, int32_t* __restrict__ state) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    int k = 0;
-    while (k < k_end && live[k] != 0) ++k;                          // round k ran iff live[k] != 0
-    state[0] = live[k];
-    state[1] = k;
+    count_live(alive, live + 1);
 }
 
 __global__ __launch_bounds__(256) void basin_finish_kernel(const int4* __restrict__ rec, int64_t n, double cellsize,
@@ -242,28 +212,22 @@ __global__ __launch_bounds__(256) void flow_compare_kernel(const uint8_t* __rest
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static int dr_size_check(const char* who, int H, int W) {
-    TG_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "%s: raster %dx%d must be non-empty with H*W < 2^31", who,
-               H, W);
-    return TG_OK;
-}
-
 extern "C" size_t tg_flow_basin_ws_bytes(int H, int W) {
-    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    if (!raster_size_ok(H, W)) return 0;
     return dr_layout(H, W).total;
 }
 
 extern "C" int tg_flow_basin_init(const uint8_t* dir, const uint8_t* pour, int H, int W, int64_t* counts, void* ws,
                                   size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_flow_basin_init", H, W)) return rc;
+    if (int rc = raster_size_check("tg_flow_basin_init", H, W)) return rc;
     TG_REQUIRE(dir && counts && ws, "tg_flow_basin_init: null pointer");
     const DrLayout L = dr_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_flow_basin_init: workspace %zu bytes < %zu", ws_bytes, L.total);
     TG_REQUIRE(((uintptr_t)ws & 15) == 0, "tg_flow_basin_init: workspace must be aligned to 16 bytes");
     const hipStream_t s = S(stream);
     char* base = (char*)ws;
-    int32_t* live = (int32_t*)(base + L.ctl) + DR_LIVE;
-    if (hipMemsetAsync(base + L.ctl, 0, DR_CTL_BYTES, s) != hipSuccess ||
+    int32_t* live = (int32_t*)(base + L.ctl) + DBL_LIVE;
+    if (hipMemsetAsync(base + L.ctl, 0, SW_CTL_BYTES, s) != hipSuccess ||
         hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s) != hipSuccess) {
         tg_set_error("tg_flow_basin_init: hipMemsetAsync failed");
         return TG_ERR_LAUNCH;
@@ -275,35 +239,30 @@ extern "C" int tg_flow_basin_init(const uint8_t* dir, const uint8_t* pour, int H
 }
 
 extern "C" int tg_flow_basin(int H, int W, int k0, int n, int32_t* state, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_flow_basin", H, W)) return rc;
+    if (int rc = raster_size_check("tg_flow_basin", H, W)) return rc;
     TG_REQUIRE(state && ws, "tg_flow_basin: null pointer");
-    TG_REQUIRE(k0 >= 0 && n >= 1 && k0 <= DR_MAX_ROUNDS && n <= DR_MAX_ROUNDS - k0,
-               "tg_flow_basin: rounds k0 = %d, n = %d must satisfy k0 >= 0, n >= 1, k0 + n <= %d", k0, n, DR_MAX_ROUNDS);
+    if (int rc = doubling_rounds_check("tg_flow_basin", k0, n)) return rc;
     const DrLayout L = dr_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_flow_basin: workspace %zu bytes < %zu", ws_bytes, L.total);
     TG_REQUIRE(((uintptr_t)ws & 15) == 0, "tg_flow_basin: workspace must be aligned to 16 bytes");
     const hipStream_t s = S(stream);
     char* base = (char*)ws;
-    int32_t* live = (int32_t*)(base + L.ctl) + DR_LIVE;
     const int64_t px = (int64_t)H * W;
     const dim3 grid(ew_grid(px, 256));
-    for (int k = k0; k < k0 + n; ++k) {
-        const int a = k & 1, b = a ^ 1;
-        hipLaunchKernelGGL(basin_round_kernel, grid, dim3(256), 0, s, px, (const int4*)(base + L.rec[a]), (int4*)(base + L.rec[b]),
-                           live + k);
-        TG_CHECK_LAUNCH("basin_round_kernel");
-    }
-    hipLaunchKernelGGL(basin_state_kernel, dim3(1), dim3(64), 0, s, live, k0 + n, state);
-    TG_CHECK_LAUNCH("basin_state_kernel");
-    return TG_OK;
+    return doubling_run(k0, n, (int32_t*)(base + L.ctl) + DBL_LIVE, state, s, "basin_round_kernel", "basin_state_kernel",
+                        [&](int k, int32_t* live) {
+                            const int a = k & 1, b = a ^ 1;
+                            hipLaunchKernelGGL(basin_round_kernel, grid, dim3(256), 0, s, px, (const int4*)(base + L.rec[a]),
+                                               (int4*)(base + L.rec[b]), live);
+                        });
 }
 
 extern "C" int tg_flow_basin_finish(int H, int W, int rounds, double cellsize, int32_t* basin, int32_t* nc, int32_t* nd,
                                     float* length_m, int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_flow_basin_finish", H, W)) return rc;
+    if (int rc = raster_size_check("tg_flow_basin_finish", H, W)) return rc;
     TG_REQUIRE(basin && counts && ws, "tg_flow_basin_finish: null pointer");
-    TG_REQUIRE(rounds >= 0 && rounds <= DR_MAX_ROUNDS, "tg_flow_basin_finish: rounds = %d must lie in [0, %d]", rounds,
-               DR_MAX_ROUNDS);
+    TG_REQUIRE(rounds >= 0 && rounds <= DBL_MAX_ROUNDS, "tg_flow_basin_finish: rounds = %d must lie in [0, %d]", rounds,
+               DBL_MAX_ROUNDS);
     TG_REQUIRE(cellsize > 0 && cellsize * 0.0 == 0.0, "tg_flow_basin_finish: cellsize %g must be finite and > 0", cellsize);
     const DrLayout L = dr_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_flow_basin_finish: workspace %zu bytes < %zu", ws_bytes, L.total);
@@ -374,7 +333,7 @@ __global__ __launch_bounds__(256) void stream_class_kernel(const uint8_t* __rest
             int sd = 0, up = -1, upcode = 0;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {                           // the neighbour at offset k flows here with the opposite code
-                const int yy = y + dr_dy(k), xx = x + dr_dx(k);
+                const int yy = y + d8_dy(k), xx = x + d8_dx(k);
                 if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
                     const int64_t q = (int64_t)yy * W + xx;
                     const int back = ((k + 4) & 7) + 1;
@@ -394,7 +353,7 @@ __global__ __launch_bounds__(256) void stream_class_kernel(const uint8_t* __rest
             }
             bool terminal = true;                                   // the receiver is no stream pixel
             if (code >= 1 && code <= 8) {
-                const int yy = y + dr_dy(code - 1), xx = x + dr_dx(code - 1);
+                const int yy = y + d8_dy(code - 1), xx = x + d8_dx(code - 1);
                 if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W)
                     terminal = !dr_is_stream(dir, acc, (int64_t)yy * W + xx, min_cells);
             }
@@ -408,7 +367,7 @@ __global__ __launch_bounds__(256) void stream_class_kernel(const uint8_t* __rest
         rec[p] = r;
         alive += r.x >= 0;
     }
-    dr_count_live(alive, live);
+    count_live(alive, live);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         ns += __shfl_xor(ns, o, 64);
@@ -438,7 +397,7 @@ __global__ __launch_bounds__(256) void stream_order_kernel(const uint8_t* __rest
         int m1 = 0, m2 = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const int yy = y + dr_dy(k), xx = x + dr_dx(k);
+            const int yy = y + d8_dy(k), xx = x + d8_dx(k);
             if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) {
                 const int64_t q = (int64_t)yy * W + xx;
                 if (cls[q] != 0 && dir[q] == ((k + 4) & 7) + 1) {
@@ -463,7 +422,7 @@ __global__ __launch_bounds__(256) void stream_order_kernel(const uint8_t* __rest
             ++raised;
         }
     }
-    if (last) dr_count_live(raised, changed);
+    if (last) count_live(raised, changed);
 }
 
 __global__ __launch_bounds__(256) void stream_order_finish_kernel(const uint8_t* __restrict__ cls, const int32_t* __restrict__ top,
@@ -601,7 +560,7 @@ __global__ __launch_bounds__(256) void flood_compare_kernel(const uint8_t* __res
 
 extern "C" int tg_stream_class(const uint8_t* dir, const int32_t* acc, int H, int W, int32_t min_cells, uint8_t* cls,
                                int32_t* order, int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_stream_class", H, W)) return rc;
+    if (int rc = raster_size_check("tg_stream_class", H, W)) return rc;
     TG_REQUIRE(dir && acc && cls && order && counts && ws, "tg_stream_class: null pointer");
     TG_REQUIRE(min_cells >= 1, "tg_stream_class: min_cells = %d must be >= 1", min_cells);
     const DrLayout L = dr_layout(H, W);
@@ -609,8 +568,8 @@ extern "C" int tg_stream_class(const uint8_t* dir, const int32_t* acc, int H, in
     TG_REQUIRE(((uintptr_t)ws & 15) == 0, "tg_stream_class: workspace must be aligned to 16 bytes");
     const hipStream_t s = S(stream);
     char* base = (char*)ws;
-    int32_t* live = (int32_t*)(base + L.ctl) + DR_LIVE;
-    if (hipMemsetAsync(base + L.ctl, 0, DR_CTL_BYTES, s) != hipSuccess ||
+    int32_t* live = (int32_t*)(base + L.ctl) + DBL_LIVE;
+    if (hipMemsetAsync(base + L.ctl, 0, SW_CTL_BYTES, s) != hipSuccess ||
         hipMemsetAsync(counts, 0, 4 * sizeof(int64_t), s) != hipSuccess) {
         tg_set_error("tg_stream_class: hipMemsetAsync failed");
         return TG_ERR_LAUNCH;
@@ -623,7 +582,7 @@ extern "C" int tg_stream_class(const uint8_t* dir, const int32_t* acc, int H, in
 
 extern "C" int tg_stream_order(const uint8_t* dir, const uint8_t* cls, const int32_t* top, const int32_t* junctions, int nj, int H,
                                int W, int n, int32_t* order, int32_t* changed, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_stream_order", H, W)) return rc;
+    if (int rc = raster_size_check("tg_stream_order", H, W)) return rc;
     TG_REQUIRE(dir && cls && top && order && changed, "tg_stream_order: null pointer");
     TG_REQUIRE(nj >= 0 && (int64_t)nj <= (int64_t)H * W, "tg_stream_order: nj = %d must lie in [0, H * W]", nj);
     TG_REQUIRE(junctions || nj == 0, "tg_stream_order: null junction list with nj = %d", nj);
@@ -645,7 +604,7 @@ extern "C" int tg_stream_order(const uint8_t* dir, const uint8_t* cls, const int
 
 extern "C" int tg_stream_order_finish(const uint8_t* cls, const int32_t* top, const int32_t* order, int H, int W, uint8_t* out,
                                       int64_t* counts, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_stream_order_finish", H, W)) return rc;
+    if (int rc = raster_size_check("tg_stream_order_finish", H, W)) return rc;
     TG_REQUIRE(cls && top && order && out && counts, "tg_stream_order_finish: null pointer");
     const hipStream_t s = S(stream);
     if (hipMemsetAsync(counts, 0, TG_STREAM_ORDER_COUNTS * sizeof(int64_t), s) != hipSuccess) {
@@ -661,7 +620,7 @@ extern "C" int tg_stream_order_finish(const uint8_t* cls, const int32_t* top, co
 
 extern "C" int tg_hand(const float* w, const int32_t* basin, const uint8_t* smask, const float* length_m, int H, int W, float* hand,
                        float* distance_m, int64_t* counts, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_hand", H, W)) return rc;
+    if (int rc = raster_size_check("tg_hand", H, W)) return rc;
     TG_REQUIRE(w && basin && smask && hand && counts, "tg_hand: null pointer");
     TG_REQUIRE((length_m == nullptr) == (distance_m == nullptr), "tg_hand: length_m and distance_m go together");
     const hipStream_t s = S(stream);
@@ -678,7 +637,7 @@ extern "C" int tg_hand(const float* w, const int32_t* basin, const uint8_t* smas
 
 extern "C" int tg_flood_compare(const uint8_t* sel, const float* hand_t, const float* hand_p, int H, int W, tg_flood_stages stages,
                                 int k, int64_t* counts, tg_stream_t stream) {
-    if (int rc = dr_size_check("tg_flood_compare", H, W)) return rc;
+    if (int rc = raster_size_check("tg_flood_compare", H, W)) return rc;
     TG_REQUIRE(sel && hand_t && hand_p && counts, "tg_flood_compare: null pointer");
     TG_REQUIRE(k >= 1 && k <= TG_FLOOD_MAX_STAGES, "tg_flood_compare: k = %d stages must lie in [1, %d]", k, TG_FLOOD_MAX_STAGES);
     for (int i = 0; i < k; ++i) {

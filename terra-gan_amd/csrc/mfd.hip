@@ -12,10 +12,10 @@
 //                       counts of dispersive (S > 0), single and sink pixels
 //   mfd_mask_kernel     the donor byte of every pixel: bit k set iff neighbour k gives to it
 //   mfd_left_kernel     one thread: the pixels that are not final = the three counts together
-//   mfd_begin_kernel    one thread: advance the sweep counter by n (its parity picks the plane of wake marks)
+//   sweep_begin_kernel  (raster_sweep.h) one thread: advance the sweep counter by n (its parity picks the plane of wake marks)
 //   mfd_sweep_kernel    one workgroup per marked 64x64 tile that still holds a pixel that is not final: A, S and w with a one-pixel halo
 //                       and the donor bytes in LDS; a pixel that is not final and whose donors are all final computes its value,
-//                       by the directional line scans of flow_flat_sweep_kernel, until a round finalises nothing or a cap
+//                       by the directional line scans of raster_sweep.h, until a round finalises nothing or a cap
 //   mfd_finish_kernel   A -> fp32, the largest A, the fp64 sum of A over the sinks as per-workgroup partials
 //   mfd_psum_kernel     the partials summed in their order
 //   slope_kernel        Horn's 3x3 slope in fp32
@@ -23,51 +23,34 @@
 //   wetness_cmp_kernel  the differences of two wetness planes inside a selection
 //
 // Every value of A is written exactly once, from final donor values, in a fixed neighbour order, so the plane does not depend on
-// the order of the visits; a value that is not final is only ever waited for.  Halo loads and the write-back of A are relaxed
-// 64-bit atomic accesses at agent scope: a tile may read a neighbour tile's pixel as not final or as final, and either is right.
-#include "common.h"
-
-static inline hipStream_t S(tg_stream_t s) { return (hipStream_t)s; }
-
-typedef unsigned long long ull;
+// the order of the visits; a value that is not final is only ever waited for.  The sweep follows the tile-sweep protocol of
+// raster_sweep.h with 64-bit halo loads and write-backs of A: a tile may read a neighbour tile's pixel as not final or as final, and
+// either is right.
+#include "raster_sweep.h"
 
 #pragma clang fp contract(off)
 
-constexpr int MF_T = 64;                 // tile side
-constexpr int MF_R = MF_T + 2;           // rows and columns with the halo
-constexpr int MF_S = MF_T + 3;           // LDS row stride in elements: odd
+constexpr int MF_T = SW_T, MF_R = SW_R, MF_S = SW_S;
 constexpr int MF_ROUNDS = 128;           // cap on the inner rounds of one visit; the tile stays on the list anyway while open
-constexpr int MF_CTL_BYTES = 256;        // int32 [0]: sweeps enqueued since tg_mfd_setup (only its parity is used)
 constexpr int MF_PARTS = 2048;           // ew_grid's cap: workgroups of the reductions
 constexpr int MF_PART_W = 4;             // doubles per workgroup
 
-static size_t mf_al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
-struct MfLayout {
-    size_t ctl, open, plane[2], mask, s, part, total;
-    int ty, tx;
+struct MfLayout : SweepLayout {
+    size_t open, mask, s, part, total;
 };
 
 static MfLayout mf_layout(int H, int W) {
     MfLayout L;
-    L.ty = cdiv(H, MF_T);
-    L.tx = cdiv(W, MF_T);
-    const size_t tiles = (size_t)L.ty * L.tx, px = (size_t)H * W;
-    size_t o = 0;
-    L.ctl = o; o += MF_CTL_BYTES;
-    L.open = o; o += mf_al256(tiles);
-    L.plane[0] = o; o += mf_al256(tiles);
-    L.plane[1] = o; o += mf_al256(tiles);
-    L.mask = o; o += mf_al256(px);
-    L.s = o; o += mf_al256(px * 8);
+    size_t o;
+    static_cast<SweepLayout&>(L) = sweep_layout(H, W, o, 1);        // the open plane keeps its place before the marks
+    L.open = SW_CTL_BYTES;
+    const size_t px = (size_t)H * W;
+    L.mask = o; o += al256(px);
+    L.s = o; o += al256(px * 8);
     L.part = o; o += (size_t)MF_PARTS * MF_PART_W * 8;
     L.total = o;
     return L;
 }
-
-__host__ __device__ constexpr int mf_dy(int k) { return ((0x01a9 >> (2 * k)) & 3) - 1; }     // 0, 1, 1, 1, 0, -1, -1, -1
-__host__ __device__ constexpr int mf_dx(int k) { return ((0x901a >> (2 * k)) & 3) - 1; }     // 1, 1, 0, -1, -1, -1, 0, 1
-static_assert(mf_dy(1) == 1 && mf_dy(5) == -1 && mf_dx(0) == 1 && mf_dx(3) == -1 && mf_dx(7) == 1 && mf_dy(7) == -1, "offsets");
 
 // t_j of a valid drop d towards neighbour j
 __device__ __forceinline__ double mf_term(float d32, int j, int e, double cdiag) {
@@ -109,7 +92,7 @@ __global__ __launch_bounds__(256) void mfd_s_kernel(const float* __restrict__ w,
         double s = 0.0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const int yy = y + mf_dy(j), xx = x + mf_dx(j);
+            const int yy = y + d8_dy(j), xx = x + d8_dx(j);
             if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
             const int64_t q = (int64_t)yy * W + xx;
             if (!known[q]) continue;
@@ -137,7 +120,7 @@ __global__ __launch_bounds__(256) void mfd_mask_kernel(const float* __restrict__
             const float wp = w[p];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
-                const int yy = y + mf_dy(k), xx = x + mf_dx(k);
+                const int yy = y + d8_dy(k), xx = x + d8_dx(k);
                 if ((unsigned)yy >= (unsigned)H || (unsigned)xx >= (unsigned)W) continue;
                 const int64_t q = (int64_t)yy * W + xx;
                 if (!known[q]) continue;
@@ -164,14 +147,8 @@ __device__ __forceinline__ void mf_store(double* p, double v) {
     __hip_atomic_store(reinterpret_cast<ull*>(p), (ull)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ void mfd_begin_kernel(int32_t* __restrict__ ctl, int n) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) ctl[0] = (ctl[0] + n) & 0x3fffffff;
-}
-
-// Wake marks, as the dirty planes of flow.hip: a tile is visited in a sweep when it is marked for it.  A visit marks the tile
-// itself for the next sweep when it stopped at the cap on the rounds, and its eight neighbours when it made a pixel on its rim
-// final (their halo has changed).  An open tile without a mark can make no pixel final, so the marks change which visits
-// happen and never what a visit computes.
+// Wake marks (raster_sweep.h): a visit marks the tile itself for the next sweep when it stopped at the cap on the rounds, and its
+// eight neighbours when it made a pixel on its rim final.  An open tile without a mark can make no pixel final.
 __global__ __launch_bounds__(256) void mfd_sweep_kernel(const float* __restrict__ w, const double* __restrict__ Sp,
                                                         const uint8_t* __restrict__ mask, int H, int W, int tiles_y, int tiles_x,
                                                         int e, double cdiag, double* A, uint8_t* open, const int32_t* __restrict__ ctl,
@@ -181,36 +158,31 @@ __global__ __launch_bounds__(256) void mfd_sweep_kernel(const float* __restrict_
     __shared__ float hs[MF_R * MF_S];
     __shared__ uint8_t ms[MF_T * MF_T];
     __shared__ int tot[3];
-    const int tile = blockIdx.x;
-    const int sweep = ctl[0] - n + j;                               // mfd_begin_kernel has added n already
-    uint8_t* cur = (sweep & 1) ? plane1 : plane0;
-    uint8_t* nxt = (sweep & 1) ? plane0 : plane1;
-    if (!cur[tile]) return;                                         // uniform: nothing has changed for this tile
-    const int t = threadIdx.x;
-    if (!open[tile]) {                                              // uniform: every pixel of the tile is final
-        if (t == 0) cur[tile] = 0;
+    SweepVisit v = sweep_visit_begin(ctl, n, j, plane0, plane1);
+    if (!v.marked) return;                                          // uniform: nothing has changed for this tile
+    const int t = threadIdx.x, tile = v.tile;
+    if (!open[tile]) {                                              // uniform: every pixel of the tile is final; not a visit
+        if (t == 0) v.cur[tile] = 0;
         return;
     }
-    const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    const int y0 = ty * MF_T, x0 = tx * MF_T;
+    sweep_visit_place(v, tiles_x);
+    const int y0 = v.y0, x0 = v.x0;
     if (t < 3) tot[t] = 0;
 
     // stage: positions outside the raster are final at 0, as unknown pixels are; no donor bit ever points at either
     for (int i = t; i < MF_R * MF_R; i += 256) {
-        const int ly = i / MF_R, lx = i - ly * MF_R;
-        const int gy = y0 - 1 + ly, gx = x0 - 1 + lx;
+        const SweepStage g = sweep_stage(i, y0, x0, H, W);
         double a = 0.0, s = 0.0;
         float h = 0.f;
-        if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) {
-            const int64_t p = (int64_t)gy * W + gx;
-            const bool interior = ly >= 1 && ly <= MF_T && lx >= 1 && lx <= MF_T;
-            a = interior ? A[p] : mf_load(A + p);
+        if (g.in_raster) {
+            const int64_t p = (int64_t)g.gy * W + g.gx;
+            a = g.on_tile ? A[p] : mf_load(A + p);         // the field: see SweepStage
             s = Sp[p];
             h = w[p];
         }
-        as[ly * MF_S + lx] = a;
-        ss[ly * MF_S + lx] = s;
-        hs[ly * MF_S + lx] = h;
+        as[g.ly * MF_S + g.lx] = a;
+        ss[g.ly * MF_S + g.lx] = s;
+        hs[g.ly * MF_S + g.lx] = h;
     }
     __syncthreads();
     uint32_t was = 0;                                               // bit q: pixel t + 256 q was not final at the start
@@ -227,19 +199,15 @@ __global__ __launch_bounds__(256) void mfd_sweep_kernel(const float* __restrict_
         ms[i] = (uint8_t)m;
     }
     if (!__syncthreads_or((int)was)) {
-        if (t == 0) {
-            open[tile] = 0;
-            cur[tile] = 0;
-            atomicAdd(counts + 4, 1ull);
-        }
+        if (t == 0) open[tile] = 0;
+        sweep_visit_end(v, tiles_y, tiles_x, counts + 4, false, false);
         return;
     }
 
-    // thread = one line (a column in rounds 0, 1; a row in rounds 2, 3) and one band of 16 pixels along it, scanned forwards or
-    // backwards, so a value travels a whole band within the round.  A value read may be a neighbour thread's old one (not final:
-    // wait) or its new one (final for good).  This needs 64-bit LDS accesses that do not tear: as[] holds 8-byte aligned doubles
-    // read and written by single ds_read_b64 / ds_write_b64 operations, so the step from -1.0 to a value is never seen half
-    // written.  A layout that splits them (packing, two 32-bit accesses) would break the rounds silently.
+    // the line scans of raster_sweep.h.  A value read may be a neighbour thread's old one (not final: wait) or its new one (final
+    // for good).  This needs 64-bit LDS accesses that do not tear: as[] holds 8-byte aligned doubles read and written by single
+    // ds_read_b64 / ds_write_b64 operations, so the step from -1.0 to a value is never seen half written.  A layout that splits
+    // them (packing, two 32-bit accesses) would break the rounds silently.
     const int line = t & 63, band = t >> 6;
     int live = 1;
     for (int round = 0; round < MF_ROUNDS && live; ++round) {
@@ -257,14 +225,14 @@ __global__ __launch_bounds__(256) void mfd_sweep_kernel(const float* __restrict_
                 bool ready = true;
 #pragma unroll
                 for (int b = 0; b < 8; ++b)
-                    if ((m >> b & 1) && as[idx + mf_dy(b) * MF_S + mf_dx(b)] < 0.0) ready = false;
+                    if ((m >> b & 1) && as[idx + d8_dy(b) * MF_S + d8_dx(b)] < 0.0) ready = false;
                 if (ready) {
                     const float hp = hs[idx];
                     double a = 1.0;
 #pragma unroll
                     for (int b = 0; b < 8; ++b) {
                         if (m >> b & 1) {
-                            const int nb = idx + mf_dy(b) * MF_S + mf_dx(b);
+                            const int nb = idx + d8_dy(b) * MF_S + d8_dx(b);
                             const double sn = ss[nb];
                             double f = 1.0;
                             if (sn > 0.0) f = mf_term(hs[nb] - hp, (b + 4) & 7, e, cdiag) / sn;
@@ -288,9 +256,9 @@ __global__ __launch_bounds__(256) void mfd_sweep_kernel(const float* __restrict_
         if (was >> q & 1) {
             const int i = t + 256 * q;
             const int ly = i >> 6, lx = i & 63;
-            const double v = as[(ly + 1) * MF_S + lx + 1];
-            if (v >= 0.0) {
-                mf_store(A + (int64_t)(y0 + ly) * W + x0 + lx, v);
+            const double av = as[(ly + 1) * MF_S + lx + 1];
+            if (av >= 0.0) {
+                mf_store(A + (int64_t)(y0 + ly) * W + x0 + lx, av);
                 ++nf;
                 if (ly == 0 || ly == MF_T - 1 || lx == 0 || lx == MF_T - 1) rim = 1;
             } else {
@@ -312,18 +280,10 @@ __global__ __launch_bounds__(256) void mfd_sweep_kernel(const float* __restrict_
     __syncthreads();
     if (t == 0) {
         if (tot[1] == 0) open[tile] = 0;
-        cur[tile] = 0;
-        atomicAdd(counts + 4, 1ull);
         if (tot[0]) atomicAdd(counts + 3, (ull)(-(long long)tot[0]));   // pixels that are not final yet
     }
-    // marks: itself if the cap stopped it with pixels left, and after a final rim value the eight neighbour tiles (the same byte
-    // value from every writer)
-    if (t < 9) {
-        const int ny = ty + t / 3 - 1, nx = tx + t % 3 - 1;
-        const bool want = t == 4 ? (live && tot[1] != 0) : tot[2] != 0;
-        if (want && ny >= 0 && ny < tiles_y && nx >= 0 && nx < tiles_x)
-            __hip_atomic_store(nxt + (int64_t)ny * tiles_x + nx, (uint8_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    // marks: itself if the cap stopped it with pixels left, and after a final rim value its neighbours
+    sweep_visit_end(v, tiles_y, tiles_x, counts + 4, live && tot[1] != 0, tot[2] != 0);
 }
 
 // ---- finish and reductions ----------------------------------------------------------------------------------------------
@@ -448,12 +408,6 @@ __global__ __launch_bounds__(256) void wetness_cmp_kernel(const uint8_t* __restr
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-static int mf_size_check(const char* who, int H, int W) {
-    TG_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 31), "%s: raster %dx%d must be non-empty with H*W < 2^31", who,
-               H, W);
-    return TG_OK;
-}
-
 static int mf_exp_check(const char* who, int e, double cdiag) {
     TG_REQUIRE(e >= 1 && e <= TG_MFD_MAX_EXPONENT, "%s: exponent %d must lie in [1, %d]", who, e, TG_MFD_MAX_EXPONENT);
     TG_REQUIRE(cdiag > 0.0 && cdiag <= 1.0, "%s: cdiag %g must lie in (0, 1]", who, cdiag);
@@ -466,13 +420,13 @@ __global__ void mfd_left_kernel(ull* __restrict__ counts) {
 }
 
 extern "C" size_t tg_mfd_ws_bytes(int H, int W) {
-    if (H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31)) return 0;
+    if (!raster_size_ok(H, W)) return 0;
     return mf_layout(H, W).total;
 }
 
 extern "C" int tg_mfd_setup(const float* w, const uint8_t* known, const uint8_t* dir, int H, int W, int exponent, double cdiag,
                             double* A, int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = mf_size_check("tg_mfd_setup", H, W)) return rc;
+    if (int rc = raster_size_check("tg_mfd_setup", H, W)) return rc;
     if (int rc = mf_exp_check("tg_mfd_setup", exponent, cdiag)) return rc;
     TG_REQUIRE(w && known && dir && A && counts && ws, "tg_mfd_setup: null pointer");
     TG_REQUIRE((const void*)A != (const void*)w, "tg_mfd_setup: A must not alias w");
@@ -480,10 +434,7 @@ extern "C" int tg_mfd_setup(const float* w, const uint8_t* known, const uint8_t*
     TG_REQUIRE(ws_bytes >= L.total, "tg_mfd_setup: workspace %zu bytes < %zu", ws_bytes, L.total);
     const hipStream_t s = S(stream);
     char* base = (char*)ws;
-    if (hipMemsetAsync(base + L.ctl, 0, MF_CTL_BYTES, s) != hipSuccess ||
-        hipMemsetAsync(base + L.open, 1, (size_t)L.ty * L.tx, s) != hipSuccess ||
-        hipMemsetAsync(base + L.plane[0], 1, (size_t)L.ty * L.tx, s) != hipSuccess ||
-        hipMemsetAsync(base + L.plane[1], 0, (size_t)L.ty * L.tx, s) != hipSuccess ||
+    if (!sweep_reset(L, ws, s) || hipMemsetAsync(base + L.open, 1, L.tiles(), s) != hipSuccess ||
         hipMemsetAsync(counts, 0, TG_MFD_COUNTS * sizeof(int64_t), s) != hipSuccess) {
         tg_set_error("tg_mfd_setup: hipMemsetAsync failed");
         return TG_ERR_LAUNCH;
@@ -503,7 +454,7 @@ extern "C" int tg_mfd_setup(const float* w, const uint8_t* known, const uint8_t*
 
 extern "C" int tg_mfd_sweep(const float* w, int H, int W, int exponent, double cdiag, int n, double* A, int64_t* counts, void* ws,
                             size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = mf_size_check("tg_mfd_sweep", H, W)) return rc;
+    if (int rc = raster_size_check("tg_mfd_sweep", H, W)) return rc;
     if (int rc = mf_exp_check("tg_mfd_sweep", exponent, cdiag)) return rc;
     TG_REQUIRE(w && A && counts && ws, "tg_mfd_sweep: null pointer");
     TG_REQUIRE(n >= 1 && n <= (1 << 20), "tg_mfd_sweep: n = %d sweeps must lie in [1, 2^20]", n);
@@ -512,23 +463,17 @@ extern "C" int tg_mfd_sweep(const float* w, int H, int W, int exponent, double c
     TG_REQUIRE(ws_bytes >= L.total, "tg_mfd_sweep: workspace %zu bytes < %zu", ws_bytes, L.total);
     const hipStream_t s = S(stream);
     char* base = (char*)ws;
-    int32_t* ctl = (int32_t*)(base + L.ctl);
-    hipLaunchKernelGGL(mfd_begin_kernel, dim3(1), dim3(64), 0, s, ctl, n);
-    TG_CHECK_LAUNCH("mfd_begin_kernel");
-    const dim3 grid(L.ty * L.tx);                                   // < 2^31 / 4096
-    for (int j = 0; j < n; ++j) {
-        hipLaunchKernelGGL(mfd_sweep_kernel, grid, dim3(256), 0, s, w, (const double*)(base + L.s),
-                           (const uint8_t*)(base + L.mask), H, W, L.ty, L.tx, exponent, cdiag, A, (uint8_t*)(base + L.open),
-                           (const int32_t*)ctl, n, j, (uint8_t*)(base + L.plane[0]), (uint8_t*)(base + L.plane[1]),
-                           reinterpret_cast<ull*>(counts));
-        TG_CHECK_LAUNCH("mfd_sweep_kernel");
-    }
-    return TG_OK;
+    return sweep_run(L, ws, n, nullptr, s, "mfd_begin_kernel", "mfd_sweep_kernel",
+                     [&](dim3 grid, const int32_t* ctl, int j, uint8_t* p0, uint8_t* p1) {
+                         hipLaunchKernelGGL(mfd_sweep_kernel, grid, dim3(256), 0, s, w, (const double*)(base + L.s),
+                                            (const uint8_t*)(base + L.mask), H, W, L.ty, L.tx, exponent, cdiag, A,
+                                            (uint8_t*)(base + L.open), ctl, n, j, p0, p1, reinterpret_cast<ull*>(counts));
+                     });
 }
 
 extern "C" int tg_mfd_finish(const double* A, const uint8_t* dir, int H, int W, float* acc, double* out, void* ws, size_t ws_bytes,
                              tg_stream_t stream) {
-    if (int rc = mf_size_check("tg_mfd_finish", H, W)) return rc;
+    if (int rc = raster_size_check("tg_mfd_finish", H, W)) return rc;
     TG_REQUIRE(A && dir && acc && out && ws, "tg_mfd_finish: null pointer");
     const MfLayout L = mf_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_mfd_finish: workspace %zu bytes < %zu", ws_bytes, L.total);
@@ -550,7 +495,7 @@ extern "C" int tg_mfd_finish(const double* A, const uint8_t* dir, int H, int W, 
 }
 
 extern "C" int tg_terrain_slope(const float* w, const uint8_t* known, int H, int W, float den, float* slope, tg_stream_t stream) {
-    if (int rc = mf_size_check("tg_terrain_slope", H, W)) return rc;
+    if (int rc = raster_size_check("tg_terrain_slope", H, W)) return rc;
     TG_REQUIRE(w && known && slope, "tg_terrain_slope: null pointer");
     TG_REQUIRE(den > 0.f && den < __builtin_inff(), "tg_terrain_slope: the divisor 8 * cellsize = %g must be finite and > 0",
                (double)den);
@@ -562,7 +507,7 @@ extern "C" int tg_terrain_slope(const float* w, const uint8_t* known, int H, int
 
 extern "C" int tg_wetness(const float* acc, const float* slope, const uint8_t* known, int H, int W, float cellsize, float min_slope,
                           float* twi, tg_stream_t stream) {
-    if (int rc = mf_size_check("tg_wetness", H, W)) return rc;
+    if (int rc = raster_size_check("tg_wetness", H, W)) return rc;
     TG_REQUIRE(acc && slope && known && twi, "tg_wetness: null pointer");
     TG_REQUIRE(cellsize > 0.f && cellsize < __builtin_inff(), "tg_wetness: cellsize %g must be finite and > 0", (double)cellsize);
     TG_REQUIRE(min_slope > 0.f && min_slope < __builtin_inff(), "tg_wetness: min_slope %g must be finite and > 0",
@@ -575,7 +520,7 @@ extern "C" int tg_wetness(const float* acc, const float* slope, const uint8_t* k
 
 extern "C" int tg_wetness_compare(const uint8_t* sel, const float* twi_t, const float* twi_p, int H, int W, int64_t* counts,
                                   double* sums, void* ws, size_t ws_bytes, tg_stream_t stream) {
-    if (int rc = mf_size_check("tg_wetness_compare", H, W)) return rc;
+    if (int rc = raster_size_check("tg_wetness_compare", H, W)) return rc;
     TG_REQUIRE(sel && twi_t && twi_p && counts && sums && ws, "tg_wetness_compare: null pointer");
     const MfLayout L = mf_layout(H, W);
     TG_REQUIRE(ws_bytes >= L.total, "tg_wetness_compare: workspace %zu bytes < %zu", ws_bytes, L.total);

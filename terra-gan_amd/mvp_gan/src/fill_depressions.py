@@ -57,6 +57,32 @@ def check_args(dem, mask, cellsize, connectivity, max_sweeps, check_every, who="
     return shape[0], shape[1], _cellsize(cellsize, who)
 
 
+def run_until_unchanged(enqueue, changed, cap, check_every):
+    """enqueue(n) queues n steps, the last of which counts what it changed into `changed` (int32 [1] on the device); at most
+    `cap` steps, one host sync per check_every -> (steps enqueued, converged)."""
+    steps, converged = 0, False
+    while steps < cap and not converged:
+        n = min(check_every, cap - steps)
+        enqueue(n)
+        steps += n
+        converged = int(changed.item()) == 0
+    return steps, converged
+
+
+def run_doubling(enqueue, state, max_rounds, check_every, who):
+    """enqueue(k, n) queues rounds k .. k + n - 1 of a pointer doubling and its (live pointers, rounds that ran) into `state`
+    (int32 [2] on the device); one host sync per check_every rounds -> rounds that ran."""
+    k, left, rounds = 0, 1, 0
+    while left and k < max_rounds:
+        n = min(check_every, max_rounds - k)
+        enqueue(k, n)
+        k += n
+        left, rounds = state.cpu().tolist()
+    if left:
+        raise RuntimeError(f"{who}: the direction grid has a cycle")
+    return rounds
+
+
 def relax(z, known, connectivity=8, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY):
     """The iteration on device tensors: z float32 [H][W], known uint8 [H][W] -> (w float32 [H][W] as tg_depfill_sweep leaves
     it, outlets, sweeps, tile_visits, converged).  One host sync per check_every sweeps."""
@@ -67,12 +93,8 @@ def relax(z, known, connectivity=8, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVE
     outlets = int((w == z).count_nonzero().item())              # after init W == z exactly at the outlets (NaN != NaN)
     changed = torch.zeros(1, dtype=torch.int32, device=z.device)
     visits = torch.zeros(1, dtype=torch.int64, device=z.device)
-    sweeps, converged = 0, False
-    while sweeps < max_sweeps and not converged:
-        n = min(check_every, max_sweeps - sweeps)
-        O.depfill_sweep(z, known, connectivity, n, w, changed, visits, ws)
-        sweeps += n
-        converged = int(changed.item()) == 0
+    sweeps, converged = run_until_unchanged(lambda n: O.depfill_sweep(z, known, connectivity, n, w, changed, visits, ws), changed,
+                                            max_sweeps, check_every)
     return w, outlets, sweeps, int(visits.item()), converged
 
 

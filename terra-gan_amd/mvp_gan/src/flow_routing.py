@@ -54,7 +54,7 @@ import numbers
 import numpy as np
 import torch
 
-from .fill_depressions import CHECK_EVERY, MAX_SWEEPS, check_args
+from .fill_depressions import CHECK_EVERY, MAX_SWEEPS, check_args, run_doubling, run_until_unchanged
 
 OUT, PIT, UNKNOWN = 9, 255, 0
 FAR = 0x7fffffff
@@ -92,12 +92,8 @@ def resolve_flats(w, D, ws, max_sweeps=MAX_SWEEPS, check_every=CHECK_EVERY):
     from tg_hip import ops as O
     changed = torch.zeros(1, dtype=torch.int32, device=w.device)
     visits = torch.zeros(1, dtype=torch.int64, device=w.device)
-    sweeps, converged = 0, False
-    while sweeps < max_sweeps and not converged:
-        n = min(check_every, max_sweeps - sweeps)
-        O.flow_flat_sweep(w, n, D, changed, visits, ws)
-        sweeps += n
-        converged = int(changed.item()) == 0
+    sweeps, converged = run_until_unchanged(lambda n: O.flow_flat_sweep(w, n, D, changed, visits, ws), changed, max_sweeps,
+                                            check_every)
     return sweeps, int(visits.item()), converged
 
 
@@ -108,14 +104,8 @@ def accumulate(direction, ws, check_every=CHECK_EVERY):
     H, W = direction.shape
     O.flow_accum_init(direction, ws)
     state = torch.empty(2, dtype=torch.int32, device=direction.device)
-    k, left, rounds = 0, 1, 0
-    while left and k < ACC_MAX_ROUNDS:
-        n = min(check_every, ACC_MAX_ROUNDS - k)
-        O.flow_accum(H, W, k, n, state, ws)
-        k += n
-        left, rounds = state.cpu().tolist()
-    if left:
-        raise RuntimeError("flow_routing: the direction grid has a cycle")      # cannot happen: (w, D) decreases along every edge
+    # a cycle cannot happen in flow_routing's own grids: (w, D) decreases along every edge
+    rounds = run_doubling(lambda k, n: O.flow_accum(H, W, k, n, state, ws), state, ACC_MAX_ROUNDS, check_every, "flow_routing")
     acc, amax = O.flow_accum_finish(H, W, rounds, ws)
     return acc, int(amax.item()), rounds
 
@@ -233,15 +223,7 @@ def basin_rounds(H, W, ws, check_every=CHECK_EVERY, who="watersheds"):
     """The rounds of the doubling on the start records in ws (ops.flow_basin_init's or ops.stream_class's) -> rounds that ran."""
     from tg_hip import ops as O
     state = torch.empty(2, dtype=torch.int32, device=ws.device)
-    k, left, rounds = 0, 1, 0
-    while left and k < ACC_MAX_ROUNDS:
-        n = min(check_every, ACC_MAX_ROUNDS - k)
-        O.flow_basin(H, W, k, n, state, ws)
-        k += n
-        left, rounds = state.cpu().tolist()
-    if left:
-        raise RuntimeError(f"{who}: the direction grid has a cycle")
-    return rounds
+    return run_doubling(lambda k, n: O.flow_basin(H, W, k, n, state, ws), state, ACC_MAX_ROUNDS, check_every, who)
 
 
 def compact_labels(basin):
@@ -322,13 +304,8 @@ def order_rounds(d, cls, top, order, max_rounds=ORDER_MAX_ROUNDS, check_every=CH
     if junctions.numel() == 0:
         return 0, True
     changed = torch.zeros(1, dtype=torch.int32, device=d.device)
-    rounds, converged = 0, False
-    while rounds < max_rounds and not converged:
-        n = min(check_every, max_rounds - rounds)
-        O.stream_order(d, cls, top, junctions, n, order, changed)
-        rounds += n
-        converged = int(changed.item()) == 0
-    return rounds, converged
+    return run_until_unchanged(lambda n: O.stream_order(d, cls, top, junctions, n, order, changed), changed, max_rounds,
+                               check_every)
 
 
 def network_known(d, acc, min_cells, cellsize, max_rounds=ORDER_MAX_ROUNDS, check_every=CHECK_EVERY):

@@ -1326,6 +1326,23 @@ def void_smooth(x, known, steps=1):
     return a
 
 
+def _ws_make(ws_bytes, name, H, W, device, err=L.TgError):
+    """A caller-owned workspace of ws_bytes(H, W) bytes (a tg_*_ws_bytes function); `name` stands in the message."""
+    n = ws_bytes(int(H), int(W))
+    if n == 0:
+        raise err(f"{name}: raster {H}x{W} must be non-empty with H*W < 2^31")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def _ws_chk(ws, H, W, ws_bytes, name, who=None, align=1, err=L.TgError):
+    """ws is what {name}_ws makes for an H x W raster, or larger; `who` (default: name) stands in the message."""
+    need = ws_bytes(H, W)
+    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+            and ws.data_ptr() % align == 0):
+        aligned = f", aligned to {align}" if align > 1 else ""
+        raise err(f"{who or name}: ws must be a contiguous uint8 HIP tensor of at least {need} bytes{aligned} ({name}_ws)")
+
+
 DEPFILL_CONNS = (8, 4)
 
 
@@ -1345,23 +1362,14 @@ def _depfill_in(z, known, w, conn, who):
 def depfill_ws(H, W, device):
     """The workspace of one depression fill: uint8 [tg_depfill_ws_bytes]; it carries the dirty tiles from depfill_init through
     the depfill_sweep calls, so it is the caller's and not the shared one."""
-    n = _lib().tg_depfill_ws_bytes(int(H), int(W))
-    if n == 0:
-        raise L.TgError(f"depfill: raster {H}x{W} must be non-empty with H*W < 2^31")
-    return torch.empty(n, dtype=torch.uint8, device=device)
-
-
-def _depfill_ws_chk(ws, H, W):
-    need = _lib().tg_depfill_ws_bytes(H, W)
-    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need):
-        raise L.TgError(f"depfill: ws must be a contiguous uint8 HIP tensor of at least {need} bytes (depfill_ws)")
+    return _ws_make(_lib().tg_depfill_ws_bytes, "depfill", H, W, device)
 
 
 def depfill_init(z, known, conn, ws):
     """-> w float32 [H][W]: z at the outlets (known pixels on the edge or with an unknown conn-neighbour), +inf at the other
     known pixels, NaN at unknown ones; every tile of ws dirty (tg_depfill_init)."""
     H, W = _depfill_in(z, known, None, conn, "depfill_init")
-    _depfill_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_depfill_ws_bytes, "depfill")
     w = torch.empty(H, W, dtype=torch.float32, device=z.device)
     L.check(_lib().tg_depfill_init(_p(z), _p(known), H, W, int(conn), _p(w), _p(ws), ws.numel(), _stream()), "tg_depfill_init")
     return w
@@ -1371,7 +1379,7 @@ def depfill_sweep(z, known, conn, n, w, changed, visits, ws):
     """n >= 1 sweeps of w in place; changed int32 [1] = visits of the last sweep that lowered a value (0: a fixed point);
     visits int64 [1] is added to (tg_depfill_sweep)."""
     H, W = _depfill_in(z, known, w, conn, "depfill_sweep")
-    _depfill_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_depfill_ws_bytes, "depfill")
     _hip(changed, torch.int32, (1,), "changed")
     _hip(visits, torch.int64, (1,), "visits")
     if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
@@ -1411,16 +1419,7 @@ def depfill_finish(z, w, known, want_depth=False, want_flags=False):
 def flow_ws(H, W, device):
     """The workspace of one flow routing: uint8 [tg_flow_ws_bytes]; it carries the dirty tiles of the flat sweeps and the planes
     of the accumulation from call to call, so it is the caller's and not the shared one."""
-    n = _lib().tg_flow_ws_bytes(int(H), int(W))
-    if n == 0:
-        raise L.TgError(f"flow: raster {H}x{W} must be non-empty with H*W < 2^31")
-    return torch.empty(n, dtype=torch.uint8, device=device)
-
-
-def _flow_ws_chk(ws, H, W):
-    need = _lib().tg_flow_ws_bytes(H, W)
-    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need):
-        raise L.TgError(f"flow: ws must be a contiguous uint8 HIP tensor of at least {need} bytes (flow_ws)")
+    return _ws_make(_lib().tg_flow_ws_bytes, "flow", H, W, device)
 
 
 def _flow_count(v, lo, hi, name, who):
@@ -1436,7 +1435,7 @@ def flow_slope(w, known, ws):
     H, W = _raster_hw(w, "w")
     _hip(w, torch.float32, (H, W), "w")
     _hip(known, torch.uint8, (H, W), "known")
-    _flow_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_flow_ws_bytes, "flow")
     d = torch.empty(H, W, dtype=torch.uint8, device=w.device)
     D = torch.empty(H, W, dtype=torch.int32, device=w.device)
     counts = torch.empty(2, dtype=torch.int64, device=w.device)
@@ -1450,7 +1449,7 @@ def flow_flat_sweep(w, n, D, changed, visits, ws):
     H, W = _raster_hw(w, "w")
     _hip(w, torch.float32, (H, W), "w")
     _hip(D, torch.int32, (H, W), "D")
-    _flow_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_flow_ws_bytes, "flow")
     _hip(changed, torch.int32, (1,), "changed")
     _hip(visits, torch.int64, (1,), "visits")
     _flow_count(n, 1, 1 << 20, "n", "flow_flat_sweep")
@@ -1474,13 +1473,13 @@ def flow_accum_init(d, ws):
     """The pointers and unit sums of the accumulation from the codes d (uint8 [H][W]) into ws (tg_flow_accum_init)."""
     H, W = _raster_hw(d, "dir")
     _hip(d, torch.uint8, (H, W), "dir")
-    _flow_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_flow_ws_bytes, "flow")
     L.check(_lib().tg_flow_accum_init(_p(d), H, W, _p(ws), ws.numel(), _stream()), "tg_flow_accum_init")
 
 
 def flow_accum(H, W, k0, n, state, ws):
     """Rounds k0 .. k0 + n - 1 of the pointer doubling; state int32 [2] = pointers left, rounds that ran (tg_flow_accum)."""
-    _flow_ws_chk(ws, int(H), int(W))
+    _ws_chk(ws, int(H), int(W), _lib().tg_flow_ws_bytes, "flow")
     _hip(state, torch.int32, (2,), "state")
     _flow_count(k0, 0, L.TG_FLOW_MAX_ROUNDS, "k0", "flow_accum")
     _flow_count(n, 1, L.TG_FLOW_MAX_ROUNDS - k0, "n", "flow_accum")
@@ -1489,7 +1488,7 @@ def flow_accum(H, W, k0, n, state, ws):
 
 def flow_accum_finish(H, W, rounds, ws):
     """-> (acc int32 [H][W], amax int32 [1]) after `rounds` rounds (tg_flow_accum_finish)."""
-    _flow_ws_chk(ws, int(H), int(W))
+    _ws_chk(ws, int(H), int(W), _lib().tg_flow_ws_bytes, "flow")
     _flow_count(rounds, 0, L.TG_FLOW_MAX_ROUNDS, "rounds", "flow_accum_finish")
     acc = torch.empty(int(H), int(W), dtype=torch.int32, device=ws.device)
     amax = torch.empty(1, dtype=torch.int32, device=ws.device)
@@ -1508,18 +1507,7 @@ FLOW_COMPARE_NAMES = ("cells", "dir_equal", "dir_routed", "dir_within_45", "same
 def flow_basin_ws(H, W, device):
     """The workspace of one watershed labelling: uint8 [tg_flow_basin_ws_bytes]; it carries the two planes of records from
     flow_basin_init through the flow_basin calls to flow_basin_finish, so it is the caller's and not the shared one."""
-    n = _lib().tg_flow_basin_ws_bytes(int(H), int(W))
-    if n == 0:
-        raise L.TgError(f"flow_basin: raster {H}x{W} must be non-empty with H*W < 2^31")
-    return torch.empty(n, dtype=torch.uint8, device=device)
-
-
-def _flow_basin_ws_chk(ws, H, W):
-    need = _lib().tg_flow_basin_ws_bytes(H, W)
-    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
-            and ws.data_ptr() % 16 == 0):
-        raise L.TgError(f"flow_basin: ws must be a contiguous uint8 HIP tensor of at least {need} bytes, aligned to 16 "
-                        "(flow_basin_ws)")
+    return _ws_make(_lib().tg_flow_basin_ws_bytes, "flow_basin", H, W, device)
 
 
 def flow_basin_init(d, pour, ws):
@@ -1530,7 +1518,7 @@ def flow_basin_init(d, pour, ws):
     _hip(d, torch.uint8, (H, W), "dir")
     if pour is not None:
         _hip(pour, torch.uint8, (H, W), "pour")
-    _flow_basin_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_flow_basin_ws_bytes, "flow_basin", align=16)
     counts = torch.empty(2, dtype=torch.int64, device=d.device)
     L.check(_lib().tg_flow_basin_init(_p(d), _p(pour), H, W, _p(counts), _p(ws), ws.numel(), _stream()), "tg_flow_basin_init")
     return counts
@@ -1538,7 +1526,7 @@ def flow_basin_init(d, pour, ws):
 
 def flow_basin(H, W, k0, n, state, ws):
     """Rounds k0 .. k0 + n - 1 of the watershed doubling; state int32 [2] = pointers left, rounds that ran (tg_flow_basin)."""
-    _flow_basin_ws_chk(ws, int(H), int(W))
+    _ws_chk(ws, int(H), int(W), _lib().tg_flow_basin_ws_bytes, "flow_basin", align=16)
     _hip(state, torch.int32, (2,), "state")
     _flow_count(k0, 0, L.TG_FLOW_MAX_ROUNDS, "k0", "flow_basin")
     _flow_count(n, 1, L.TG_FLOW_MAX_ROUNDS - k0, "n", "flow_basin")
@@ -1550,7 +1538,7 @@ def flow_basin_finish(H, W, rounds, ws, cellsize=1.0, want_steps=False, want_len
     steps; length_m float32 [H][W] or None; counts int64 [FLOW_BASIN_COUNTS]: terminals, the largest nc + nd, the bits of the
     largest length) after `rounds` rounds (tg_flow_basin_finish)."""
     H, W = int(H), int(W)
-    _flow_basin_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_flow_basin_ws_bytes, "flow_basin", align=16)
     _flow_count(rounds, 0, L.TG_FLOW_MAX_ROUNDS, "rounds", "flow_basin_finish")
     c = float(cellsize)
     if not (c > 0 and c < float("inf")):
@@ -1597,7 +1585,7 @@ def stream_class(d, acc, min_cells, ws):
     _hip(d, torch.uint8, (H, W), "dir")
     _hip(acc, torch.int32, (H, W), "acc")
     _flow_count(min_cells, 1, 2 ** 31 - 1, "min_cells", "stream_class")
-    _flow_basin_ws_chk(ws, H, W)
+    _ws_chk(ws, H, W, _lib().tg_flow_basin_ws_bytes, "flow_basin", align=16)
     cls = torch.empty(H, W, dtype=torch.uint8, device=d.device)
     order = torch.empty(H, W, dtype=torch.int32, device=d.device)
     counts = torch.empty(4, dtype=torch.int64, device=d.device)
@@ -1722,17 +1710,7 @@ def _mfd_hw(t, name, who):
 def mfd_ws(H, W, device):
     """The workspace of one MFD accumulation: uint8 [tg_mfd_ws_bytes]; it carries S, the donor bytes and the tile list from
     mfd_setup through the mfd_sweep calls to mfd_finish, so it is the caller's and not the shared one."""
-    n = _lib().tg_mfd_ws_bytes(int(H), int(W))
-    if n == 0:
-        raise ValueError(f"mfd: raster {H}x{W} must be non-empty with H*W < 2^31")
-    return torch.empty(n, dtype=torch.uint8, device=device)
-
-
-def _mfd_ws_chk(ws, H, W, who):
-    need = _lib().tg_mfd_ws_bytes(H, W)
-    if not (isinstance(ws, torch.Tensor) and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
-            and ws.data_ptr() % 8 == 0):
-        raise ValueError(f"{who}: ws must be a contiguous uint8 HIP tensor of at least {need} bytes, aligned to 8 (mfd_ws)")
+    return _ws_make(_lib().tg_mfd_ws_bytes, "mfd", H, W, device, err=ValueError)
 
 
 def mfd_setup(w, known, d, exponent, ws):
@@ -1743,7 +1721,7 @@ def mfd_setup(w, known, d, exponent, ws):
     H, W = _mfd_hw(w, "w", who)
     _mfd_plane(known, torch.uint8, (H, W), "known", who)
     _mfd_plane(d, torch.uint8, (H, W), "dir", who)
-    _mfd_ws_chk(ws, H, W, who)
+    _ws_chk(ws, H, W, _lib().tg_mfd_ws_bytes, "mfd", who=who, align=8, err=ValueError)
     A = torch.empty(H, W, dtype=torch.float64, device=w.device)
     counts = torch.empty(MFD_COUNTS, dtype=torch.int64, device=w.device)
     L.check(_lib().tg_mfd_setup(_p(w), _p(known), _p(d), H, W, int(exponent), cdiag, _p(A), _p(counts), _p(ws), ws.numel(), _stream()),
@@ -1759,7 +1737,7 @@ def mfd_sweep(w, exponent, n, A, counts, ws):
     H, W = _mfd_hw(w, "w", who)
     _mfd_plane(A, torch.float64, (H, W), "A", who)
     _mfd_plane(counts, torch.int64, (MFD_COUNTS,), "counts", who)
-    _mfd_ws_chk(ws, H, W, who)
+    _ws_chk(ws, H, W, _lib().tg_mfd_ws_bytes, "mfd", who=who, align=8, err=ValueError)
     if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 1 << 20:
         raise ValueError(f"{who}: n {n!r} must be an integer in [1, 2^20]")
     L.check(_lib().tg_mfd_sweep(_p(w), H, W, int(exponent), cdiag, n, _p(A), _p(counts), _p(ws), ws.numel(), _stream()), "tg_mfd_sweep")
@@ -1774,7 +1752,7 @@ def mfd_finish(A, d, ws):
         raise ValueError(f"{who}: A must be [H][W], got {tuple(A.shape)}")
     H, W = int(A.shape[0]), int(A.shape[1])
     _mfd_plane(d, torch.uint8, (H, W), "dir", who)
-    _mfd_ws_chk(ws, H, W, who)
+    _ws_chk(ws, H, W, _lib().tg_mfd_ws_bytes, "mfd", who=who, align=8, err=ValueError)
     acc = torch.empty(H, W, dtype=torch.float32, device=A.device)
     out = torch.empty(2, dtype=torch.float64, device=A.device)
     L.check(_lib().tg_mfd_finish(_p(A), _p(d), H, W, _p(acc), _p(out), _p(ws), ws.numel(), _stream()), "tg_mfd_finish")
@@ -1829,7 +1807,7 @@ def wetness_compare(sel, twi_t, twi_p, ws=None):
     _mfd_plane(sel, torch.uint8, (H, W), "sel", who)
     if ws is None:
         ws = mfd_ws(H, W, sel.device)
-    _mfd_ws_chk(ws, H, W, who)
+    _ws_chk(ws, H, W, _lib().tg_mfd_ws_bytes, "mfd", who=who, align=8, err=ValueError)
     counts = torch.empty(2, dtype=torch.int64, device=sel.device)
     sums = torch.empty(3, dtype=torch.float64, device=sel.device)
     L.check(_lib().tg_wetness_compare(_p(sel), _p(twi_t), _p(twi_p), H, W, _p(counts), _p(sums), _p(ws), ws.numel(), _stream()),

@@ -75,7 +75,7 @@ def test_scenes(dev, name, e):
         assert info2["mfd_sweeps"] > 8                              # 8256 steps: the inner-round cap is hit, the tiles stay listed
 
 
-@pytest.mark.parametrize("shape", ((1, 1), (1, 77), (77, 1), (63, 65), (64, 64)))
+@pytest.mark.parametrize("shape", ((1, 1), (1, 77), (77, 1), (63, 65), (64, 64), (65, 193), (193, 65)))
 def test_shapes(dev, shape):
     from mvp_gan.src.flow_routing import mfd_accumulation
     H, W = shape

@@ -178,6 +178,13 @@ def test_c_entry_points_reject_without_gpu():
     assert lib.tg_mfd_ws_bytes(0, 5) == 0 and lib.tg_mfd_ws_bytes(1 << 16, 1 << 15) == 0
     n = lib.tg_mfd_ws_bytes(130, 70)
     assert n >= 256 + 130 * 70 * 9 + 6 and lib.tg_mfd_ws_bytes(131, 70) > n
+    # the layout exactly: 256 control bytes, the open plane and two mark planes of a byte per 64x64 tile, the donor bytes, S, and
+    # 2048 partials of 4 doubles; each of the first five rounded up to 256 bytes
+    up = lambda v: -(-v // 256) * 256
+    for H, W in [(1, 1), (1, 2049), (2049, 1), (63, 65), (64, 64), (65, 63), (130, 70), (257, 1101), (1501, 2099), (4097, 513),
+                 (8191, 8193), (32767, 3), (3, 32767), (32767, 32767), (46340, 46340), (1, (1 << 31) - 1)]:
+        tiles = -(-H // 64) * -(-W // 64)
+        assert lib.tg_mfd_ws_bytes(H, W) == 256 + 3 * up(tiles) + up(H * W) + up(8 * H * W) + 65536, (H, W)
     one, two = C.c_void_p(8), C.c_void_p(16)                             # non-null, never dereferenced: every call is refused
     for e in (0, 9):
         assert lib.tg_mfd_setup(one, one, one, 4, 4, e, 0.5, two, one, one, n, None) == -1
