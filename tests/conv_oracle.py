@@ -259,16 +259,62 @@ def _tiles(xp, step, size, ty, tx):
     return v[:, ::step, ::step][:, :ty, :tx]
 
 
-def wino_corr(xp, w, alg, OH, OW, absolute=False):
-    """y[b][i][j][n] = sum_{u,v,c} xp[b][i + u][j + v][c] w[n][u][v][c] for i < OH, j < OW, evaluated in the Winograd domain of
-    `alg` with tiles that start at (0, 0) -- or, `absolute`, S_w of that evaluation (the arguments are then magnitudes).
-    Returns (y, max |Bt d B|, max |G g Gt|)."""
+def wino_operands(xp, w, alg, OH, OW, absolute=False):
+    """The transformed operands of wino_corr: Bt d B as [B][ty][tx][C][a][a] and G g Gt as [a][a][N][C]."""
     Bt, G, At = (np.abs(M) for M in WINO[alg]) if absolute else WINO[alg]
     m, a = At.shape[0], Bt.shape[0]
     assert w.shape[1] == w.shape[2] == G.shape[1] and w.shape[3] == xp.shape[3], (w.shape, xp.shape, alg)
     ty, tx = _cdiv(OH, m), _cdiv(OW, m)
-    V = Bt @ _tiles(f64(xp), m, a, ty, tx) @ Bt.T                           # [B][ty][tx][C][a][a]
-    Uw = np.einsum("au,nuvc,bv->abnc", G, f64(w), G)                         # [a][a][N][C]
+    return Bt @ _tiles(f64(xp), m, a, ty, tx) @ Bt.T, np.einsum("au,nuvc,bv->abnc", G, f64(w), G)
+
+
+def wino_woperands(xp, dy, alg, absolute=False):
+    """The transformed operands of wino_wcorr: Bt X B as [B][ty][tx][C][a][a] and A dY At as [B][ty][tx][N][a][a]."""
+    Bt, G, At = (np.abs(M) for M in WINO[alg]) if absolute else WINO[alg]
+    m, a = At.shape[0], Bt.shape[0]
+    ty, tx = _cdiv(dy.shape[1], m), _cdiv(dy.shape[2], m)
+    return Bt @ _tiles(f64(xp), m, a, ty, tx) @ Bt.T, At.T @ _tiles(f64(dy), m, m, ty, tx) @ At
+
+
+def wino_grid_ok(alg, mats, raw, transformed):
+    """The condition of the rounded-operand reference.  `raw` = the arrays that enter the transforms `mats` (one matrix per
+    array, applied from both sides), `transformed` = what comes out.  Every transformed operand is an integer multiple of the
+    algorithm's quantum q, and max |raw| (largest absolute row sum of the matrix)^2, which bounds every partial sum of every
+    evaluation order of the two passes, stays below 2^24 q: with coefficients +-1 and 1/2 any fp32 evaluation of the transform is
+    then exact, and the bf16 operand is the rounding of an exact number."""
+    q = WINO_QUANTUM[alg]
+    for M, r, t in zip(mats, raw, transformed):
+        n = t / q
+        if not (np.array_equal(n, np.rint(n)) and float(np.abs(n).max(initial=0.0)) < EXACT_LIMIT):
+            return False
+        if float(np.abs(f64(r)).max(initial=0.0)) * float(np.abs(M).sum(axis=1).max()) ** 2 / q >= EXACT_LIMIT:
+            return False
+    return True
+
+
+def _rounded(t, rnd):
+    """A float64 array of fp32 numbers through `rnd` (fp32 -> fp32), as float64."""
+    t32 = t.astype(np.float32)
+    assert np.array_equal(t32.astype(np.float64), t), "the transformed operand is not an fp32 number"
+    return rnd(t32).astype(np.float64)
+
+
+def wino_corr(xp, w, alg, OH, OW, absolute=False, rnd=None):
+    """y[b][i][j][n] = sum_{u,v,c} xp[b][i + u][j + v][c] w[n][u][v][c] for i < OH, j < OW, evaluated in the Winograd domain of
+    `alg` with tiles that start at (0, 0) -- or, `absolute`, S_w of that evaluation (the arguments are then magnitudes).
+    `rnd`: the transformed operands pass through it (bf16_rne: what wino16.inc stores as V / U) before they are multiplied; the
+    arguments are then the SIGNED data also where `absolute` -- the transforms do not round on the grid wino_grid_ok asserts, so
+    S_w starts at the magnitudes of the rounded operands.
+    Returns (y, max |Bt d B|, max |G g Gt|)."""
+    Bt, G, At = WINO[alg]
+    m, a = At.shape[0], Bt.shape[0]
+    ty, tx = _cdiv(OH, m), _cdiv(OW, m)
+    V, Uw = wino_operands(xp, w, alg, OH, OW, absolute and rnd is None)     # [B][ty][tx][C][a][a], [a][a][N][C]
+    if rnd is not None:
+        assert wino_grid_ok(alg, (Bt, G), (xp, w), (V, Uw)), "rounded-operand reference off its grid"
+        V, Uw = _rounded(V, rnd), _rounded(Uw, rnd)
+    if absolute:
+        V, Uw, At = np.abs(V), np.abs(Uw), np.abs(At)
     B, N = xp.shape[0], w.shape[0]
     M = np.empty((B, ty, tx, N, a, a))
     for i in range(a):
@@ -279,15 +325,20 @@ def wino_corr(xp, w, alg, OH, OW, absolute=False):
     return y, float(np.abs(V).max()), float(np.abs(Uw).max())
 
 
-def wino_wcorr(xp, dy, alg, absolute=False):
+def wino_wcorr(xp, dy, alg, absolute=False, rnd=None):
     """dw[n][u][v][c] = sum_{b,i,j} dy[b][i][j][n] xp[b][i + u][j + v][c] in the Winograd domain of `alg` contracted over the tiles
-    of dy (they start at (0, 0)) -- or S_w of it.  Returns (dw, max |Bt X B|, max |A dY At|, number of tiles)."""
-    Bt, G, At = (np.abs(M) for M in WINO[alg]) if absolute else WINO[alg]
+    of dy (they start at (0, 0)) -- or S_w of it.  `rnd`: as in wino_corr, applied to Bt X B and A dY At.
+    Returns (dw, max |Bt X B|, max |A dY At|, number of tiles)."""
+    Bt, G, At = WINO[alg]
     m, a = At.shape[0], Bt.shape[0]
     B, OH, OW, N = dy.shape
     ty, tx = _cdiv(OH, m), _cdiv(OW, m)
-    V = Bt @ _tiles(f64(xp), m, a, ty, tx) @ Bt.T                           # [B][ty][tx][C][a][a]
-    Yt = At.T @ _tiles(f64(dy), m, m, ty, tx) @ At                          # [B][ty][tx][N][a][a]
+    V, Yt = wino_woperands(xp, dy, alg, absolute and rnd is None)           # [B][ty][tx][C][a][a], [B][ty][tx][N][a][a]
+    if rnd is not None:
+        assert wino_grid_ok(alg, (Bt, At.T), (xp, dy), (V, Yt)), "rounded-operand reference off its grid"
+        V, Yt = _rounded(V, rnd), _rounded(Yt, rnd)
+    if absolute:
+        V, Yt, G = np.abs(V), np.abs(Yt), np.abs(G)
     C = xp.shape[3]
     M = np.empty((a, a, N, C))
     for i in range(a):
@@ -410,6 +461,54 @@ def wino_wgrad(x, dy, k, s, p, alg):
     S, vm, ym, ntiles = _wino_wgrad_corr(np.abs(f64(x)), np.abs(f64(dy)), k, s, p, alg, True)
     K = np.full(S.shape, float(ntiles + wino_T(alg, wgrad=True)))
     return WRes(rw.val, S, K, rw.scale, rw.base, False, alg, vm, ym), rb
+
+
+# ---- the bf16 Winograd kernels (wino16.inc): the reference that rounds where the kernel rounds ------------------------------------------
+# Both transforms are fp32, the transformed operands are rounded to bf16 once (at the V / U store; A dY At and Bt X B in the weight
+# gradient), the products run on a bf16 MFMA with fp32 accumulation, the output transform is fp32.  On data for which the
+# transforms are exact in fp32 (wino_grid_ok, asserted by wino_corr / wino_wcorr) the bf16 operands are fully determined -- RNE of
+# exact numbers -- and what is left to round is the contraction and the output transform:
+#     value = At [ sum_c rnd(G g Gt) (.) rnd(Bt d B) ] A         S = |At| [ sum_c |rnd(G g Gt)| (.) |rnd(Bt d B)| ] |A|
+# with n = K + slabs + T + 4 as for the fp32 kernels (T keeps the roundings of the operand transforms, which cannot happen here: a
+# safe over-count).  Bias, ratio, mask, gate, activation and base follow as in conv_fwd / conv_dgrad; db stays the fp32 column
+# sum of the unrounded dy.
+def wino_fwd_rounded(x, w, k, s, p, alg, mask=None, bias=None, ratio=None, act_kind=ACT_NONE, slope=0.0, rnd=bf16_rne):
+    xin = _source(x, mask, None)[0]
+    w = f64(w)
+    (z, vm, um), K = _wino_fwd_corr(xin, w, k, s, p, alg, False, lambda *a: wino_corr(*a, rnd=rnd))
+    S = _wino_fwd_corr(xin, w, k, s, p, alg, True, lambda *a: wino_corr(*a, absolute=True, rnd=rnd))[0][0]
+    if bias is not None:
+        z, S = z + f64(bias), S + np.abs(f64(bias))
+    scale = np.ones(z.shape[:3] + (1,))
+    if ratio is not None:
+        z, scale = z * f64(ratio)[..., None], np.abs(f64(ratio))[..., None]
+    return WRes(act(z, act_kind, slope), S, np.full(S.shape, float(K + wino_T(alg))), np.broadcast_to(scale, S.shape),
+                np.zeros_like(S), False, alg, vm, um)
+
+
+def wino_dgrad_rounded(dy, w, x_shape, k, s, p, alg, mask=None, gate=None, gate_act=ACT_RELU, gate_slope=0.0, base=None,
+                       rnd=bf16_rne):
+    dy, w = f64(dy), f64(w)
+    dx, vm, um = _wino_dgrad_corr(dy, w, x_shape, k, s, p, alg, False, lambda *a: wino_corr(*a, rnd=rnd))
+    S = _wino_dgrad_corr(dy, w, x_shape, k, s, p, alg, True, lambda *a: wino_corr(*a, absolute=True, rnd=rnd))[0]
+    scale = np.ones(dx.shape)
+    if mask is not None:
+        scale = scale * f64(mask)[..., None]
+    if gate is not None:
+        scale = scale * act_grad(f64(gate), gate_act, gate_slope)
+    dx, b0 = dx * scale, np.zeros_like(dx)
+    if base is not None:
+        dx, b0 = dx + f64(base), np.abs(f64(base))
+    return WRes(dx, S, np.full(S.shape, float(w.shape[0] + wino_T(alg))), np.abs(scale), b0, False, alg, vm, um)
+
+
+def wino_wgrad_rounded(x, dy, k, s, p, alg, rnd=bf16_rne):
+    """(dW, db): dW from the rounded A dY At and Bt X B, db the direct column sum of the dy as given."""
+    x, dy = f64(x), f64(dy)
+    dw, vm, ym, ntiles = _wino_wgrad_corr(x, dy, k, s, p, alg, False, lambda *a: wino_wcorr(*a, rnd=rnd))
+    S = _wino_wgrad_corr(x, dy, k, s, p, alg, True, lambda *a: wino_wcorr(*a, absolute=True, rnd=rnd))[0]
+    K = np.full(S.shape, float(ntiles + wino_T(alg, wgrad=True)))
+    return WRes(dw, S, K, np.ones_like(S), np.zeros_like(S), False, alg, vm, ym), conv_wgrad(x, dy, k, s, p)[1]
 
 
 def wino_exact_ok(r, bf16=False):

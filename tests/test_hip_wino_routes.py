@@ -6,9 +6,14 @@ WinoRoute (csrc/igemm_params.h), and the split count -- and then faces the refer
 measured number:
   - exact: small-integer data.  The transforms of F(2x2,3x3), F(3x3,2x2) and F(2x2,2x2) have coefficients +-1 and 1/2 only, so
     every intermediate of every summation order, split-K plan and work distribution is an fp32 (and, transformed, a bf16) number:
-    torch.equal with the fp64 reference.  The bf16 kernels face this run only;
+    torch.equal with the fp64 reference;
   - real: normals with ratio / LeakyReLU / gates / accumulate base; |hip - ref| <= n 2^-24 (S_w |scale| + |base|) per element,
-    S_w the sum of absolute values of the Winograd-domain expression.  F(4x4,3x3), whose 1/6 and 1/24 round, faces this run only.
+    S_w the sum of absolute values of the Winograd-domain expression.  F(4x4,3x3), whose 1/6 and 1/24 round, faces this run only;
+  - rounded, the bf16 kernels (wino16.inc) in place of the real run: integers of eleven bits and more, on which the fp32
+    transforms are exact and the bf16 rounding of the transformed operands is not the identity, against the reference that rounds
+    V / U (wgrad: A dY At / Bt X B) to nearest-even and nothing else: the same per-element bound, with S_w from the rounded
+    operands.  tests/test_wino_oracle_cpu.py shows per case that truncation, round-half-away and a rounding of x / w / dy ahead of
+    the transforms lie outside it.
 The switches the library reads once per process (TG_WINO_NO_PIPE, TG_WINO_NO_FAST, TG_WINO_INTERLEAVE) run in one fresh child
 process each."""
 import time

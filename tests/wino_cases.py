@@ -5,6 +5,11 @@ the exact-integer run and, where the case has one, the a-priori-bound run of tes
 tests/test_wino_oracle_cpu.py (CPU: the oracle against float64 autograd, the exactness and sensitivity conditions, an fp32
 emulation of each algorithm inside the bound, and `predict` = the expectation).
 
+Runs: 'exact' (integers of {-3 ... 3}: bit equality), 'real' (normals: the a-priori bound of any fp32 evaluation) and, for the
+cases on a kernel of wino16.inc, 'rounded': integers of eleven bits (twelve: GRID_WIDE), on which the fp32 transforms are exact and the bf16 rounding of
+the transformed operands is NOT the identity, against the reference that rounds them to nearest-even as the kernel must -- the
+same fp32 bound then holds per element, and truncation, round-half-away or a rounding ahead of the transforms miss it by far.
+
 `predict` restates the host-side planners (wino_geom_ok, wino_plan, launch_wino22, wino44_ok, wino_wgrad_plan and its twins,
 s2d_ok, choose_splits, choose_splits_k) in Python on top of tests/conv_cases.py, for a workspace of the size the queries report.
 The table's expectations are literals; the restatement only has to agree with them, and the GPU has the last word.
@@ -192,21 +197,32 @@ def splits_ok(expected, recorded):
 class Case(CC.Case):
     """prec: 'f32' | 'bf16' (tg_hip.ops.set_precision for the launch);  runs: the references the case faces;  ctx: 'reserve' =
     tg_set_cu_reserve(128), 'steal' = tg_set_work_stealing(2) around the launch;  env: 'NAME' or 'NAME=value', a switch the library
-    reads once per process."""
+    reads once per process;  grid: (sigma, largest magnitude) of the rounded run's integers, where GRID is too narrow for the case."""
 
-    def __init__(self, id, geom, op, mods, expect, splits=1, env=None, prec="f32", runs=None, ctx=None):
+    def __init__(self, id, geom, op, mods, expect, splits=1, env=None, prec="f32", runs=None, ctx=None, grid=None):
         CC.Case.__init__(self, id, geom, op, mods, expect, splits, env)
+        self.grid = grid or GRID
         if "twice" in self.mods:
             self.expect = self.expect * 2
         self.prec, self.ctx = prec, ctx
         self.envname = env.split("=")[0] if env else None
         self.alg = algorithm(self)
-        # F(4x4,3x3) rounds its coefficients (1/6, 1/24): no exact run.  bf16 operands: no usable a-priori bound (2^-8 S_w is a
-        # third of the result's rms): the exact run only.
-        self.runs = runs or (("real",) if self.alg == "F43" else ("exact",) if prec == "bf16" else ("exact", "real"))
+        # F(4x4,3x3) rounds its coefficients (1/6, 1/24): no exact run.  bf16 operands: no usable a-priori bound against the
+        # unrounded convolution (2^-8 S_w is a third of the result's rms); a case on a bf16 Winograd kernel (Case.rounds) faces the
+        # reference that rounds the transformed operands as the kernel does instead, on data for which that rounding is determined.
+        self.runs = runs or (("real",) if self.alg == "F43" else ("exact", "rounded") if self.rounds else
+                             ("exact",) if prec == "bf16" else ("exact", "real"))
+
+    @property
+    def rounds(self):
+        """The case runs on a kernel of wino16.inc: V / U (wgrad: A dY At / Bt X B) are rounded to bf16."""
+        return self.prec == "bf16" and all(r[:2] in ((3, 4016), (3, 4116)) for r in self.expect)
 
 
 CASES = []
+# The rounded run's integers: clip(rint(sigma N(0,1)), +-max).  GRID_WIDE: where structural zeros (the taps a 5x5 filter lacks of the
+# 6x6 it is regrouped into; the padding tiles of a ragged strip) thin out the share of operand elements that bf16 rounding changes.
+GRID, GRID_WIDE = (400.0, 2047.0), (800.0, 4095.0)
 
 
 def case(*a, **k):
@@ -280,7 +296,7 @@ case("q_wp_split2", (1, 17, 19, 128, 64, 3, 1, 1), "fwd", "bias", W(Q + R_PIPE),
 case("s2d_fwd", (1, 64, 64, 16, 64, 5, 2, 2), "fwd", "mask bias leaky", W(R_PIPE))
 case("s2d_dgrad", (1, 64, 64, 16, 64, 5, 2, 2), "dgrad", "mask acc", W(R_PIPE))
 case("s2d_wgrad", (1, 64, 64, 16, 64, 5, 2, 2), "wgrad", "bias", WG, 4)
-# ---- bf16 operands (wino16_kernel / wino16_pipe_kernel: K steps of 16 channels), exact run -----------------------------------------------
+# ---- bf16 operands (wino16_kernel / wino16_pipe_kernel: K steps of 16 channels), exact and rounded run -----------------------------------
 case("w16_masked", (2, 17, 19, 16, 64, 3, 1, 1), "fwd", "mask bias relu", W16(R_PLAIN), prec="bf16")
 case("w16_fast_1k", (2, 17, 19, 16, 128, 3, 1, 1), "fwd", "bias relu", W16(R_FAST), prec="bf16")
 case("w16_fast_gate", (2, 17, 19, 64, 16, 3, 1, 1), "dgrad", "mask gate", W16(R_FAST_GATE), prec="bf16")
@@ -292,10 +308,16 @@ case("w16_pool", (2, 24, 40, 32, 64, 3, 1, 1), "fwd", "bias relu pool", W16(R_PO
 case("w16_gbits", (2, 17, 19, 64, 32, 3, 1, 1), "dgrad", "gbits", W16(R_GBITS), prec="bf16")
 case("w16_split2", (1, 17, 19, 256, 64, 3, 1, 1), "fwd", "bias relu", W16(R_PIPE), 2, prec="bf16")
 case("w16_split2_masked", (1, 16, 16, 256, 64, 3, 1, 1), "fwd", "mask bias", W16(R_PLAIN), 2, prec="bf16")
-case("w16_s2d_fwd", (1, 64, 64, 16, 64, 5, 2, 2), "fwd", "mask bias relu", W16(R_PIPE), prec="bf16")
+case("w16_s2d_fwd", (1, 64, 64, 16, 64, 5, 2, 2), "fwd", "mask bias relu", W16(R_PIPE), prec="bf16", grid=GRID_WIDE)
 case("w16_wgrad", (1, 16, 32, 64, 64, 3, 1, 1), "wgrad", "bias", WG16, 2, prec="bf16")
-case("w16_wgrad_ragged_split", (2, 17, 35, 64, 128, 3, 1, 1), "wgrad", "twice", WG16, 9, prec="bf16")
+case("w16_wgrad_ragged_split", (2, 17, 35, 64, 128, 3, 1, 1), "wgrad", "twice", WG16, 9, prec="bf16", grid=GRID_WIDE)
 case("w16_keeps_fp32_wgrad", (1, 16, 16, 64, 64, 3, 1, 1), "wgrad", "bias", WG, prec="bf16")
+# wino16_wgrad_kernel without padding, above the 256 input channels where the fp32 kernel stops, and behind the space-to-depth
+# regrouping; the bf16 dgrad behind it
+case("w16_wgrad_pad0", (2, 20, 36, 64, 64, 3, 1, 0), "wgrad", "", WG16, 9, prec="bf16")
+case("w16_wgrad_c320", (1, 16, 32, 320, 64, 3, 1, 1), "wgrad", "", WG16, 2, prec="bf16")
+case("w16_s2d_wgrad", (1, 64, 64, 16, 64, 5, 2, 2), "wgrad", "bias", WG16, 4, prec="bf16")
+case("w16_s2d_dgrad", (1, 64, 64, 16, 64, 5, 2, 2), "dgrad", "mask acc", W16(R_PIPE), prec="bf16", grid=GRID_WIDE)
 # ---- wino22_kernel: 4x4 stride 2, forward over the shifted space-to-depth view, dgrad = four classes in one launch --------------------------
 case("w22_masked_fwd", (1, 32, 32, 8, 64, 4, 2, 1), "fwd", "mask bias leaky", W22(1))
 case("w22_fast_fwd", (2, 36, 44, 8, 128, 4, 2, 1), "fwd", "bias leaky", W22(1 + W22_FAST))
@@ -368,8 +390,29 @@ def gate_act(case, mode):
     return CO.ACT_LEAKY, CC.LEAKY_SLOPE
 
 
+def grid_draw(rng, grid, *shape):
+    """Integers clip(rint(sigma N(0,1)), +-max) as fp32 (GRID: eleven bits), so that the transformed operands (sums of up to four
+    of them, quarters of sums of up to nine) are exact in fp32 and mostly NOT bf16 numbers."""
+    sigma, top = grid
+    return np.clip(np.rint(sigma * rng.standard_normal(size=shape)), -top, top).astype(np.float32)
+
+
 def make_inputs(case, mode):
-    d = CC.make_inputs(case, mode)
+    """conv_cases.make_inputs, and the mode 'rounded' of the cases on a bf16 Winograd kernel: x, w and dy on the grid of
+    grid_draw; mask, ratio, gate and activation as in the real run; bias and base as in the real run times the power of two
+    nearest the rms of the result (sigma^2 sqrt(products per element))."""
+    if mode == "rounded":
+        B, H, W, Cin, Cout, k, s, pad = case.geom
+        d = CC.make_inputs(case, "real")
+        rng = np.random.default_rng(sum(case.geom) * 11 + len(case.id) + 2)
+        for name in ("x", "w", "dy"):
+            d[name] = grid_draw(rng, case.grid, *d[name].shape)
+        mag = np.float32(2.0 ** round(math.log2(case.grid[0] ** 2 * math.sqrt(k * k * (Cout if case.op == "dgrad" else Cin)))))
+        for name in ("bias", "base"):
+            if d[name] is not None:
+                d[name] = d[name] * mag
+    else:
+        d = CC.make_inputs(case, mode)
     if "gbits" in case.mods:
         B, H, W, Cin = case.geom[:4]
         rng = np.random.default_rng(len(case.id) + sum(case.geom))
@@ -384,9 +427,20 @@ def needs_forward(case, mode):
 
 def reference(case, d, mode):
     """{'y' (, 'yp') | 'dx' | 'dw' (, 'db')} -> conv_oracle.WRes / Res.  'yp' = the 2x2 max-pool of y: judged against the pooled
-    reference in the exact run, against the pool of the kernel's own y in the real run (a maximum does not round)."""
+    reference in the exact run, against the pool of the kernel's own y in the real and the rounded run (a maximum does not round).
+    The rounded run: conv_oracle's evaluation with the transformed operands rounded to bf16."""
     B, H, W, Cin, Cout, k, s, pad = case.geom
     a, sl = fwd_act(case, mode)
+    if mode == "rounded":
+        assert case.rounds and case.alg == "F23", case.id
+        if case.op == "fwd":
+            return {"y": CO.wino_fwd_rounded(d["x"], d["w"], k, s, pad, case.alg, d["mask"], d["bias"], d["ratio"], a, sl)}
+        if case.op == "dgrad":
+            ga, gs = gate_act(case, mode)
+            return {"dx": CO.wino_dgrad_rounded(d["dy"], d["w"], (B, H, W, Cin), k, s, pad, case.alg, d["mask"], d["gate"], ga, gs,
+                                                d["base"])}
+        rw, rb = CO.wino_wgrad_rounded(d["x"], d["dy"], k, s, pad, case.alg)
+        return {"dw": rw, "db": rb} if "bias" in case.mods else {"dw": rw}
     if case.op == "fwd":
         return {"y": CO.wino_fwd(d["x"], d["w"], k, s, pad, case.alg, d["mask"], d["bias"], d["ratio"], a, sl)}
     if case.op == "dgrad":
