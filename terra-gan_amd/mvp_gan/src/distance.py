@@ -21,25 +21,17 @@ import math
 import numpy as np
 import torch
 
+from . import raster_args as R
+
 MAX_SIDE = 32767                      # TG_EDT_MAX_SIDE: 2 * 32767^2 < 2^31
 FAR = 0x7fffffff                      # TG_EDT_FAR
-
-
-def _cellsize(c, who):
-    try:
-        v = float(c)
-    except (TypeError, ValueError):
-        v = math.nan
-    if not math.isfinite(v) or v <= 0:
-        raise ValueError(f"{who}: cellsize {c!r} must be finite and > 0")
-    return v
 
 
 def depth_px2(edges_m, cellsize, who="depth_px2"):
     """Distances in metres -> squared pixel distances: per edge the smallest integer t with sqrt(t) * cellsize >= edge in
     fp64, the arithmetic of the distance itself, so d2 >= t exactly when the distance in metres is >= edge.  ValueError for an
     edge that is not finite and > 0, or beyond every int32 squared distance."""
-    c = _cellsize(cellsize, who)
+    c = R.cellsize(cellsize, who)
     out = []
     for e in edges_m:
         try:
@@ -64,18 +56,10 @@ def px2_m(d2, cellsize):
     return math.inf if d2 >= FAR else float(np.float32(cellsize * math.sqrt(float(d2))))
 
 
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
 def check_args(dem, mask, cellsize, max_distance, who="distance_to_known"):
     """Host-side rejection before any launch; -> (H, W, cellsize, cap2)."""
-    shape = _shape(dem)
-    if len(shape) != 2 or min(shape) < 1 or max(shape) > MAX_SIDE:
-        raise ValueError(f"{who}: dem must be [H, W] with sides in [1, {MAX_SIDE}], got {shape}")
-    if mask is not None and _shape(mask) != shape:
-        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
-    c = _cellsize(cellsize, who)
+    shape = R.raster_shape(dem, mask, who, max_side=MAX_SIDE)
+    c = R.cellsize(cellsize, who)
     cap2 = 0
     if max_distance is not None:
         try:
@@ -91,16 +75,8 @@ def distance_to_known(dem, mask=None, *, nodata=None, cellsize=1.0, max_distance
     tensor [H][W] in metres, info dict: known, unknown, max_m (inf without a known pixel), cap_m (None without max_distance,
     else the metres of the cap: the smallest pixel distance >= max_distance), capped (pixels at the cap; 0 without one))."""
     from tg_hip import ops as O
-    from .fill_voids import _device_f32
     H, W, c, cap2 = check_args(dem, mask, cellsize, max_distance)
-    if not torch.cuda.is_available():
-        raise RuntimeError("distance_to_known: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem", who="distance_to_known")
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who="distance_to_known")
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
-    seed, _ = O.objmask_known(z, m, nodata, transposed=False)
+    _, seed = R.upload_known(dem, mask, nodata, "distance_to_known")
     d2, dist = O.edt(seed, cap2, c)
     known = int(seed.count_nonzero().item())
     info = {"known": known, "unknown": H * W - known, "max_m": px2_m(int(d2.max().item()), c) if known else math.inf,
@@ -115,16 +91,8 @@ def nearest_known(dem, mask=None, *, nodata=None, cellsize=1.0, max_distance=Non
     the smallest row and then the smallest column among those at the smallest distance, -1 where no known pixel is in reach:
     none at all, or none nearer than the cap of max_distance; info as distance_to_known's)."""
     from tg_hip import ops as O
-    from .fill_voids import _device_f32
     H, W, c, cap2 = check_args(dem, mask, cellsize, max_distance, who="nearest_known")
-    if not torch.cuda.is_available():
-        raise RuntimeError("nearest_known: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem", who="nearest_known")
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who="nearest_known")
-    if nodata is not None and math.isnan(nodata):
-        nodata = None
-    seed, _ = O.objmask_known(z, m, nodata, transposed=False)
+    _, seed = R.upload_known(dem, mask, nodata, "nearest_known")
     d2, index = O.edt_nearest(seed, cap2)
     dist = torch.where(d2 == FAR, math.inf, c * d2.double().sqrt()).float()      # fp64 sqrt and multiply, rounded once
     known = int(seed.count_nonzero().item())
@@ -145,18 +113,14 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import asc_nodata, read_inputs, with_nodata, write_asc
     a = build_parser().parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
-    dist, info = distance_to_known(dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")),
-                                   max_distance=a.max_distance)
+    dem, header, mask, nodata, cellsize = read_inputs(a)
+    dist, info = distance_to_known(dem, mask, nodata=nodata, cellsize=cellsize, max_distance=a.max_distance)
     out = dist.cpu().numpy()
     far = np.isinf(out)
     if far.any():
-        if asc_value(header, "NODATA_value") is None:
-            header = header + [("NODATA_value", "-9999")]
+        header = with_nodata(header)
         out = np.where(far, np.float32(asc_nodata(header)), out)
     write_asc(a.out, out, header)
     cap = "" if info["cap_m"] is None else f", {info['capped']} at the cap of {info['cap_m']:.6g} m"

@@ -78,6 +78,7 @@ from dataclasses import asdict
 import numpy as np
 import torch
 
+from . import raster_args as R
 from .utils.raster_dataset import SPLITS, HoleSpec, fit_primitives, primitive_draws
 
 MIN_TILE, MAX_TILE = 40, 1024
@@ -88,22 +89,13 @@ FIX = 2.0 ** 16                       # fixed-point scale of the per-hole sums
 CLAMP = 2.0 ** 15                     # metres: larger per-pixel errors are clamped in the per-hole sums
 MAX_CLASSES = 8
 BATCH_BYTES = 256 << 20               # cell masks rasterised per batch
+WHO = "evaluate_raster"               # the name at the head of every device and upload message of this module
 HOLE_COLS = ("label", "area", "scored", "sum", "max", "y0", "x0", "y1", "x1")
 SUMS = ("s_e", "s_a", "s_a2", "t_ds", "t_ds2", "t_dg2", "t_dl2", "r_a", "r_a2", "rt_dg2")     # then per class: a, a^2
 COUNTS = ("valid", "holes", "objects", "scored", "unfilled", "ring", "slope_scored", "ring_slope", "clamped", "max_bits")
 
 
 # ---- host-side plan -------------------------------------------------------------------------------------------------
-def _cellsize(c, who):
-    try:
-        v = float(c)
-    except (TypeError, ValueError):
-        v = math.nan
-    if not math.isfinite(v) or v <= 0:
-        raise ValueError(f"{who}: cellsize {c!r} must be finite and > 0")
-    return v
-
-
 def check_plan(H, W, split, block, tile, holes, who="eval_holes"):
     if split is not None and split not in SPLITS:
         raise ValueError(f"{who}: split {split!r} must be None or one of {tuple(SPLITS)}")
@@ -202,51 +194,6 @@ def rank(q, n):
     return min(max(math.ceil(q * n) - 1, 0), n - 1)
 
 
-# ---- device helpers -------------------------------------------------------------------------------------------------
-def _device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("evaluate_raster: no HIP device visible; this build has no CPU path")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _f32(a, device, what, binary=False):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"evaluate_raster: {what} is on {a.device}; pass a numpy array or a HIP tensor")
-        if binary and a.dtype != torch.float32:
-            a = a != 0
-        return a.to(device=device, dtype=torch.float32).contiguous()
-    a = np.asarray(a)
-    if binary:
-        a = a != 0
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-
-
-def _u8(a, device):
-    if isinstance(a, torch.Tensor) and a.dtype == torch.uint8 and a.device == device and a.is_contiguous():
-        return a                                                # the kernels read nonzero as a hole already
-    if isinstance(a, torch.Tensor):
-        return (a != 0).to(device=device, dtype=torch.uint8).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a) != 0, dtype=np.uint8)).to(device)
-
-
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
-def _nodata(nodata):
-    return None if nodata is None or math.isnan(nodata) else float(nodata)
-
-
-def _inputs(dem, mask, who):
-    shape = _shape(dem)
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
-        raise ValueError(f"{who}: dem must be [H, W] with H*W < 2^31, got {shape}")
-    if mask is not None and _shape(mask) != shape:
-        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
-    return shape
-
-
 # ---- evaluation holes -----------------------------------------------------------------------------------------------
 @torch.no_grad()
 def eval_holes(dem, mask=None, *, nodata=None, split="test", block=1024, tile=256, holes=HoleSpec(), seed=0, objects=None,
@@ -254,14 +201,11 @@ def eval_holes(dem, mask=None, *, nodata=None, split="test", block=1024, tile=25
     """-> (holes uint8 [H][W] = Hol, keep float32 [H][W] = K, info) as HIP tensors; info: cells, valid, holes, objects,
     and with `objects` the object_mask info under "object_mask"."""
     from tg_hip import ops as O
-    H, W = _inputs(dem, mask, "eval_holes")
+    H, W = R.raster_shape(dem, mask, "eval_holes")
     tile, block = check_plan(H, W, split, block, tile, holes)
     if objects is not None:
-        cellsize = _cellsize(cellsize, "eval_holes")
-    device = _device()
-    z = _f32(dem, device, "dem")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    nodata = _nodata(nodata)
+        cellsize = R.cellsize(cellsize, "eval_holes")
+    z, m, nodata, device = R.upload(dem, mask, nodata, WHO)
     obj, oinfo = None, None
     if objects is not None:
         from .object_mask import object_mask
@@ -303,15 +247,12 @@ def holes_from_map(dem, hole_map, mask=None, *, nodata=None, objects=None, cells
     """Holes given as a map (nonzero = hole, e.g. the --holes-out of an earlier run) -> (holes uint8, keep float32, info) with
     the rules of eval_holes: Hol = V and hole and not Obj, K = V and not hole and not Obj."""
     from tg_hip import ops as O
-    H, W = _inputs(dem, mask, "holes_from_map")
-    if _shape(hole_map) != (H, W):
-        raise ValueError(f"holes_from_map: hole map {_shape(hole_map)} differs from the dem {(H, W)}")
+    H, W = R.raster_shape(dem, mask, "holes_from_map")
+    if R.shape(hole_map) != (H, W):
+        raise ValueError(f"holes_from_map: hole map {R.shape(hole_map)} differs from the dem {(H, W)}")
     if objects is not None:
-        cellsize = _cellsize(cellsize, "holes_from_map")
-    device = _device()
-    z = _f32(dem, device, "dem")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    nodata = _nodata(nodata)
+        cellsize = R.cellsize(cellsize, "holes_from_map")
+    z, m, nodata, device = R.upload(dem, mask, nodata, WHO)
     obj, oinfo = None, None
     if objects is not None:
         from .object_mask import object_mask
@@ -319,7 +260,8 @@ def holes_from_map(dem, hole_map, mask=None, *, nodata=None, objects=None, cells
     hmap = torch.empty(H, W, dtype=torch.uint8, device=device)
     keep = torch.empty(H, W, dtype=torch.float32, device=device)
     counts = torch.zeros(3, dtype=torch.int64, device=device)
-    O.eval_holes(z, m, nodata, obj, None, None, MAX_TILE, 0, H, hmap, keep, counts, hole_in=_u8(hole_map, device))
+    O.eval_holes(z, m, nodata, obj, None, None, MAX_TILE, 0, H, hmap, keep, counts,
+                 hole_in=R.to_u8(hole_map, device, "hole map", WHO, nonzero=True, reuse=True))
     c = counts.cpu().tolist()
     info = {"cells": 0, "valid": c[0], "holes": c[1], "objects": c[2]}
     if oinfo is not None:
@@ -336,10 +278,6 @@ def _rms(s, n):
     return math.sqrt(float(s) / n) if n else math.nan
 
 
-def _f32bits(b):
-    return float(np.array([b], np.uint32).view(np.float32)[0])
-
-
 def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantiles, top, depth=None):
     """The report from the raw results: counts {COUNTS}, sums {SUMS + class_a / class_a2 lists}, table int64 [n][9] sorted by
     label, qa: the height quantile values, qs: the slope error p90.  depth (optional): {"edges_m", "cap_d2", "counts",
@@ -350,7 +288,7 @@ def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantile
     rep = {"pixels": {k: int(n[k]) for k in ("valid", "holes", "scored", "unfilled", "ring", "slope_scored", "objects",
                                               "clamped")}}
     h = {"bias": _mean(sums["s_e"], ns), "mae": _mean(sums["s_a"], ns), "rmse": _rms(sums["s_a2"], ns),
-         "max": _f32bits(n["max_bits"]) if ns else math.nan,
+         "max": R.bits_f32(n["max_bits"]) if ns else math.nan,
          "quantiles": {repr(q): float(v) for q, v in zip(quantiles, qa)}}
     h["le90"] = h["quantiles"].get(repr(0.9), math.nan)
     rep["height"] = h
@@ -374,14 +312,14 @@ def assemble_report(counts, sums, table, qa, qs, *, cellsize, edges_m2, quantile
     order = [i for i in np.lexsort((table[:, 0], -mae)) if sc[i] > 0][:int(top)]
     rep["holes"] = {"count": int(len(table)), "worst": [
         {"label": int(table[i, 0]), "bbox": [int(v) for v in table[i, 5:9]], "area_m2": float(table[i, 1]) * c2,
-         "scored": int(sc[i]), "mae": float(mae[i]), "max": _f32bits(table[i, 4])} for i in order]}
+         "scored": int(sc[i]), "mae": float(mae[i]), "max": R.bits_f32(table[i, 4])} for i in order]}
     if depth is not None:
         from .distance import px2_m
         db = [0.0] + list(depth["edges_m"]) + [math.inf]
         rep["by_depth"] = {"cap_m": px2_m(depth["cap_d2"], cellsize), "classes": [
             {"lo_m": db[k], "hi_m": db[k + 1], "pixels": int(depth["counts"][k]),
              "mae": _mean(depth["sum_a"][k], int(depth["counts"][k])), "rmse": _rms(depth["sum_a2"][k], int(depth["counts"][k])),
-             "max": _f32bits(depth["max_bits"][k]) if depth["counts"][k] else math.nan} for k in range(len(db) - 1)]}
+             "max": R.bits_f32(depth["max_bits"][k]) if depth["counts"][k] else math.nan} for k in range(len(db) - 1)]}
         for h, i in zip(rep["holes"]["worst"], order):
             h["depth_m"] = px2_m(int(depth["hole_d2"][i]), cellsize)
     return rep
@@ -394,11 +332,11 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
     scored on the same holes.  holes: nonzero = evaluation hole; keep: nonzero = known to the model.  depth_edges_m: class
     bounds in metres of the distance to the nearest pixel of K (valid and keep) for "by_depth"; None: no such section."""
     from tg_hip import ops as O
-    c = _cellsize(cellsize, "terrain_errors")
-    H, W = _inputs(dem, mask, "terrain_errors")
+    c = R.cellsize(cellsize, "terrain_errors")
+    H, W = R.raster_shape(dem, mask, "terrain_errors")
     for t, nm in ((pred, "pred"), (holes, "holes"), (keep, "keep")):
-        if _shape(t) != (H, W):
-            raise ValueError(f"terrain_errors: {nm} {_shape(t)} differs from the dem {(H, W)}")
+        if R.shape(t) != (H, W):
+            raise ValueError(f"terrain_errors: {nm} {R.shape(t)} differs from the dem {(H, W)}")
     edges = _check_edges(area_edges_m2)
     qs = _check_quantiles(quantiles)
     dedges = _check_depth_edges(depth_edges_m)
@@ -409,12 +347,12 @@ def terrain_errors(dem, pred, holes, keep, *, cellsize, mask=None, nodata=None, 
         dpx2 = depth_px2(dedges, c, "terrain_errors: depth_edges_m")
     if int(top) < 0:
         raise ValueError(f"terrain_errors: top {top} < 0")
-    device = _device()
-    z, p = _f32(dem, device, "dem"), _f32(pred, device, "pred")
-    hm = _u8(holes, device)
-    k = _f32(keep, device, "keep", binary=True)
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    nodata = _nodata(nodata)
+    device = R.device(WHO)
+    z, p = R.to_f32(dem, device, "dem", WHO), R.to_f32(pred, device, "pred", WHO)
+    hm = R.to_u8(holes, device, "holes", WHO, nonzero=True, reuse=True)
+    k = R.to_f32(keep, device, "keep", WHO, binary=True)
+    m = None if mask is None else R.to_f32(mask, device, "mask", WHO, binary=True)
+    nodata = R.nodata_value(nodata)
 
     labels, area = O.objmask_components(hm)
     cap = 4096
@@ -472,10 +410,10 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     fill info under "fill"; with sinks also sink_errors' dict under "sinks", with drainage drainage_errors' under "drainage",
     with flood flood_errors' under "flood", with wetness wetness_errors' under "wetness"."""
     from .fill_voids import fill_voids
-    device = _device()
-    z = _f32(dem, device, "dem")
-    k = _f32(keep, device, "keep", binary=True)
-    bpred, finfo = fill_voids(z, k, nodata=_nodata(nodata), method=method, solver=solver)
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO)
+    k = R.to_f32(keep, device, "keep", WHO, binary=True)
+    bpred, finfo = fill_voids(z, k, nodata=R.nodata_value(nodata), method=method, solver=solver)
     rep = terrain_errors(z, bpred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
     rep["method"] = method
@@ -539,12 +477,12 @@ def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None,
                    wetness_min_slope=1e-3):
     """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
     from .interpolate import interpolate_voids
-    device = _device()
-    z = _f32(dem, device, "dem")
-    k = _f32(keep, device, "keep", binary=True)
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO)
+    k = R.to_f32(keep, device, "keep", WHO, binary=True)
     reports, infos, snk, drn, fld, wet = {}, {}, {}, {}, {}, {}
     for name in _check_compare(names):
-        pred, infos[name] = interpolate_voids(z, k, nodata=_nodata(nodata), method=name, cellsize=cellsize)
+        pred, infos[name] = interpolate_voids(z, k, nodata=R.nodata_value(nodata), method=name, cellsize=cellsize)
         reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
                                        area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
         if sinks:
@@ -560,6 +498,29 @@ def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None,
                                        min_slope=wetness_min_slope)
     return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None, fld if flood else None,
                             wet if wetness else None)
+
+
+# ---- a fill against the truth: what sink_errors, drainage_raw, flood_raw and wetness_raw open with ----------------------------
+def _fill_shapes(dem, pred, holes, mask, cellsize, who):
+    """Host-side rejection before any launch; -> (cellsize, (H, W))."""
+    c = R.cellsize(cellsize, who)
+    shape = R.raster_shape(dem, mask, who)
+    if R.shape(pred) != shape or R.shape(holes) != shape:
+        raise ValueError(f"{who}: pred {R.shape(pred)} and holes {R.shape(holes)} must have the dem's shape {shape}")
+    return c, shape
+
+
+def _fill_upload(dem, pred, holes, mask, nodata):
+    """-> (z, p float32 [H][W], sel uint8 [H][W]: nonzero = hole, known uint8 [H][W]: the pixels known in both surfaces)."""
+    from tg_hip import ops as O
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO)
+    p = R.to_f32(pred, device, "pred", WHO)
+    m = None if mask is None else R.to_f32(mask, device, "mask", WHO, binary=True)
+    sel = R.to_u8(holes, device, "holes", WHO, nonzero=True, reuse=True)
+    kz, _ = O.objmask_known(z, m, R.nodata_value(nodata), transposed=False)
+    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
+    return z, p, sel, kz & kp
 
 
 # ---- sinks: does a fill drain ---------------------------------------------------------------------------------------------
@@ -586,21 +547,10 @@ def sink_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, connectiv
     from tg_hip import ops as O
     from .fill_depressions import CONNECTIVITIES, count_depressions, relax
     who = "sink_errors"
-    c = _cellsize(cellsize, who)
-    _inputs(dem, mask, who)
-    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
-        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    c, _ = _fill_shapes(dem, pred, holes, mask, cellsize, who)
     if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES:
         raise ValueError(f"{who}: connectivity {connectivity!r} must be 8 or 4")
-    device = _device()
-    z = _f32(dem, device, "dem")
-    p = _f32(pred, device, "pred")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    sel = _u8(holes, device)
-    nd = _nodata(nodata)
-    kz, _ = O.objmask_known(z, m, nd, transposed=False)
-    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
-    known = kz & kp
+    z, p, sel, known = _fill_upload(dem, pred, holes, mask, nodata)
     raw = []
     for surf in (z, p):
         w, _, _, _, converged = relax(surf, known, connectivity)
@@ -624,7 +574,7 @@ def stream_tolerance(cellsize, stream_tol_m=None, who="drainage_errors"):
     tol2 = 9 exactly.  Otherwise tol2 is computed in exact rational arithmetic on the two doubles as given (fractions.Fraction),
     so no rounding can move it across an integer; it must be below 2^31 - 1."""
     from fractions import Fraction
-    c = _cellsize(cellsize, who)
+    c = R.cellsize(cellsize, who)
     if stream_tol_m is None:
         return 3.0 * c, 9
     try:
@@ -677,22 +627,12 @@ def drainage_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, stream_c
     from tg_hip import ops as O
     from .flow_routing import route_known, streams, watersheds
     who = "drainage_errors"
-    c = _cellsize(cellsize, who)
-    H, W = _inputs(dem, mask, who)
-    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
-        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    c, (H, W) = _fill_shapes(dem, pred, holes, mask, cellsize, who)
     if max(H, W) > 32767:
         raise ValueError(f"{who}: needs sides of at most 32767 px (exact int32 squared distances), got {H}x{W}")
     _check_stream_cells(stream_cells, who)
     tol_m, tol2 = stream_tolerance(c, stream_tol_m, who)
-    device = _device()
-    z = _f32(dem, device, "dem")
-    p = _f32(pred, device, "pred")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    sel = _u8(holes, device)
-    kz, _ = O.objmask_known(z, m, _nodata(nodata), transposed=False)
-    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
-    known = kz & kp
+    z, p, sel, known = _fill_upload(dem, pred, holes, mask, nodata)
     sides, grids = [], []
     for surf in (z, p):
         direction, acc, info = route_known(surf, known, c, fill=True)
@@ -715,7 +655,7 @@ def drainage_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, strea
     each side within stream_tol_m (None: 3 cells; stream_tolerance) of the other's.  -> assemble_drainage's dict."""
     counts, sides, tol_m, _ = drainage_raw(dem, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata,
                                            stream_cells=stream_cells, stream_tol_m=stream_tol_m)
-    return assemble_drainage(counts, sides[0], sides[1], cellsize=_cellsize(cellsize, "drainage_errors"),
+    return assemble_drainage(counts, sides[0], sides[1], cellsize=R.cellsize(cellsize, "drainage_errors"),
                              stream_cells=stream_cells, stream_tol_m=tol_m)
 
 
@@ -761,7 +701,7 @@ def assemble_flood(counts, stages_m, *, stream_cells):
     ratio = lambda a, b: a / b if b else None
     out = {"cells": cells, "stream_cells": int(stream_cells), "undrained_truth": und_t, "undrained_pred": und_p,
            "hand": {"mae_m": ratio(abs_q / 1024, cells), "bias_m": ratio(bias_q / 1024, cells),
-                    "max_m": _f32bits(max_bits) if cells else None},
+                    "max_m": R.bits_f32(max_bits) if cells else None},
            "stages": []}
     for i, s in enumerate(stages):
         t, p, b = c[6 + 3 * i:9 + 3 * i]
@@ -777,20 +717,10 @@ def flood_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, stream_cell
     from tg_hip import ops as O
     from .flow_routing import hand_from_routing, route_known
     who = "flood_errors"
-    c = _cellsize(cellsize, who)
-    _inputs(dem, mask, who)
-    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
-        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    c, _ = _fill_shapes(dem, pred, holes, mask, cellsize, who)
     _check_stream_cells(stream_cells, who)
     stages = check_flood_stages(stages_m, who)
-    device = _device()
-    z = _f32(dem, device, "dem")
-    p = _f32(pred, device, "pred")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    sel = _u8(holes, device)
-    kz, _ = O.objmask_known(z, m, _nodata(nodata), transposed=False)
-    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
-    known = kz & kp
+    z, p, sel, known = _fill_upload(dem, pred, holes, mask, nodata)
     hands, sides = [], []
     for surf in (z, p):
         direction, acc, _, w = route_known(surf, known, c, fill=True, return_surface=True)
@@ -831,7 +761,7 @@ def assemble_wetness(counts, sums):
     sd, sa, s2 = (float(v) for v in sums)
     if not cells:
         return {"cells": 0, "bias": None, "mae": None, "rmse": None, "max": None}
-    return {"cells": cells, "bias": sd / cells, "mae": sa / cells, "rmse": math.sqrt(s2 / cells), "max": _f32bits(bits)}
+    return {"cells": cells, "bias": sd / cells, "mae": sa / cells, "rmse": math.sqrt(s2 / cells), "max": R.bits_f32(bits)}
 
 
 @torch.no_grad()
@@ -840,20 +770,10 @@ def wetness_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, exponent=
     from tg_hip import ops as O
     from .flow_routing import check_exponent, check_min_slope, wetness_known
     who = "wetness_errors"
-    c = _cellsize(cellsize, who)
-    _inputs(dem, mask, who)
-    if _shape(pred) != _shape(dem) or _shape(holes) != _shape(dem):
-        raise ValueError(f"{who}: pred {_shape(pred)} and holes {_shape(holes)} must have the dem's shape {_shape(dem)}")
+    c, _ = _fill_shapes(dem, pred, holes, mask, cellsize, who)
     check_exponent(exponent, who)
     check_min_slope(min_slope, who)
-    device = _device()
-    z = _f32(dem, device, "dem")
-    p = _f32(pred, device, "pred")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
-    sel = _u8(holes, device)
-    kz, _ = O.objmask_known(z, m, _nodata(nodata), transposed=False)
-    kp, _ = O.objmask_known(p, None, None, transposed=False)           # a fill may leave NaN
-    known = kz & kp
+    z, p, sel, known = _fill_upload(dem, pred, holes, mask, nodata)
     twis, sides = [], []
     for surf in (z, p):
         twi, _, _, info = wetness_known(surf, known, c, fill=True, exponent=exponent, min_slope=min_slope)
@@ -922,9 +842,9 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     compare = _check_compare(compare)
     check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
-    c = _cellsize(cellsize, "evaluate_raster")
+    c = R.cellsize(cellsize, "evaluate_raster")
     check_resample_options(c, model_cellsize, min_coverage, who="evaluate_raster")
-    H, W = _inputs(dem, mask, "evaluate_raster")
+    H, W = R.raster_shape(dem, mask, "evaluate_raster")
     if compare and max(H, W) > 32767:
         raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
     if drainage:
@@ -943,9 +863,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
     _check_depth_edges(depth_edges_m)
-    device = _device()
-    z = _f32(dem, device, "dem")
-    m = None if mask is None else _f32(mask, device, "mask", binary=True)
+    z, m, _, _ = R.upload(dem, mask, None, WHO)
     hm, keep, hinfo = eval_holes(z, m, nodata=nodata, split=split, block=block, tile=tile, holes=holes, seed=seed,
                                  objects=objects, cellsize=c)
     pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
@@ -1072,8 +990,8 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
-    from .object_mask import spec_from_args, write_mask
+    from .asc import asc_nodata, read_asc, read_inputs, read_mask, with_nodata, write_asc, write_mask
+    from .object_mask import spec_from_args
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.stream_cells < 1:
@@ -1098,10 +1016,7 @@ def main(argv=None):
         ap.error("--seam needs --checkpoint")
     if a.model_cellsize is not None and a.pred:
         ap.error("--model-cellsize needs --checkpoint")
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
-    c = float(asc_value(header, "cellsize"))
+    dem, header, mask, nodata, c = read_inputs(a)
     objects = spec_from_args(a) if a.remove_objects else None
     split = None if a.split == "all" else a.split
     depth_edges = None if a.by_depth is None else (tuple(a.by_depth) or DEPTH_EDGES_M)
@@ -1121,7 +1036,7 @@ def main(argv=None):
         pnd = asc_nodata(ph)
         if pnd is not None:
             p = np.where(p == np.float32(pnd), np.float32(np.nan), p)     # unfilled cells stay unfilled
-        hm, keep, _ = holes_from_map(dem, _read_mask(a.holes, dem.shape), mask, nodata=nodata, objects=objects, cellsize=c)
+        hm, keep, _ = holes_from_map(dem, read_mask(a.holes, dem.shape), mask, nodata=nodata, objects=objects, cellsize=c)
         rep = terrain_errors(dem, p, hm, keep, cellsize=c, mask=mask, nodata=nodata, depth_edges_m=depth_edges)
         rep.update(params(c, split, a.block, a.tile, a.seed, HoleSpec()))
         if a.sinks:
@@ -1150,9 +1065,7 @@ def main(argv=None):
             json.dump(rep, f, indent=1)
     if a.pred_out and pred is not None:
         out = pred.cpu().numpy()
-        if np.isnan(out).any() and asc_value(header, "NODATA_value") is None:
-            header = header + [("NODATA_value", "-9999")]
-        write_asc(a.pred_out, out, header)
+        write_asc(a.pred_out, out, with_nodata(header) if np.isnan(out).any() else header)
     if a.holes_out and hm is not None:
         write_mask(a.holes_out, hm.cpu().numpy(), header)
     print(summary(rep))

@@ -26,35 +26,24 @@ CLI: python -m mvp_gan.src.fill_depressions --dem in.asc --out filled.asc [--mas
          [--connectivity 4|8] [--depth-out depth.asc] [--max-sweeps n]       (cellsize from the header; NaN -> NODATA_value)
 """
 import argparse
-import math
 
 import torch
 
-from .distance import _cellsize, _shape
+from . import raster_args as R
 
 CONNECTIVITIES = (8, 4)
 MAX_SWEEPS = 4096
 CHECK_EVERY = 8
 
 
-def _count(v, lo, name, who):
-    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= 1 << 20:
-        raise ValueError(f"{who}: {name} {v!r} must be an integer in [{lo}, 2^20]")
-    return v
-
-
 def check_args(dem, mask, cellsize, connectivity, max_sweeps, check_every, who="fill_depressions"):
     """Host-side rejection before any launch; -> (H, W, cellsize)."""
-    shape = _shape(dem)
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
-        raise ValueError(f"{who}: dem must be [H, W], non-empty with H*W < 2^31, got {shape}")
-    if mask is not None and _shape(mask) != shape:
-        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
+    shape = R.raster_shape(dem, mask, who, what="dem must be [H, W], non-empty")
     if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES:
         raise ValueError(f"{who}: connectivity {connectivity!r} must be 8 or 4")
-    _count(max_sweeps, 1, "max_sweeps", who)
-    _count(check_every, 1, "check_every", who)
-    return shape[0], shape[1], _cellsize(cellsize, who)
+    R.count(max_sweeps, 1, "max_sweeps", who)
+    R.count(check_every, 1, "check_every", who)
+    return shape[0], shape[1], R.cellsize(cellsize, who)
 
 
 def run_until_unchanged(enqueue, changed, cap, check_every):
@@ -122,17 +111,8 @@ def fill_depressions(dem, mask=None, *, nodata=None, cellsize=1.0, connectivity=
     tensor [H][W], info) or, with want_depth, (raster, depth float32 [H][W] = raster - dem: 0 where not raised, NaN where the
     raster is, info)."""
     from tg_hip import ops as O
-    from .fill_voids import _device_f32
-    who = "fill_depressions"
     H, W, c = check_args(dem, mask, cellsize, connectivity, max_sweeps, check_every)
-    if not torch.cuda.is_available():
-        raise RuntimeError("fill_depressions: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem", who=who)
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who=who)
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
-    known, _ = O.objmask_known(z, m, nodata, transposed=False)
+    z, known = R.upload_known(dem, mask, nodata, "fill_depressions")
     w, outlets, sweeps, visits, converged = relax(z, known, connectivity, max_sweeps, check_every)
     counts, sums = O.depfill_stats(z, w, known)
     out, depth, flags = O.depfill_finish(z, w, known, want_depth=want_depth, want_flags=True)
@@ -159,15 +139,13 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import read_inputs, with_nodata, write_asc
     a = build_parser().parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
-    out, depth, info = fill_depressions(dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")),
-                                        connectivity=a.connectivity, max_sweeps=a.max_sweeps, want_depth=True)
-    if (info["unknown"] or info["unreached"]) and asc_value(header, "NODATA_value") is None:
-        header = header + [("NODATA_value", "-9999")]
+    dem, header, mask, nodata, cellsize = read_inputs(a)
+    out, depth, info = fill_depressions(dem, mask, nodata=nodata, cellsize=cellsize, connectivity=a.connectivity,
+                                        max_sweeps=a.max_sweeps, want_depth=True)
+    if info["unknown"] or info["unreached"]:
+        header = with_nodata(header)
     write_asc(a.out, out.cpu().numpy(), header)
     if a.depth_out:
         write_asc(a.depth_out, depth.cpu().numpy(), header)

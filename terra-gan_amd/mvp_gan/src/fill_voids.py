@@ -33,6 +33,8 @@ import math
 import numpy as np
 import torch
 
+from . import raster_args as R
+
 METHODS = ("laplace", "biharmonic")
 MAX_CYCLES = {"laplace": 50, "biharmonic": 200}    # what max_cycles=None resolves to
 INNER = 3                      # V-cycles of one approximate Laplace solve of the biharmonic preconditioner
@@ -139,17 +141,9 @@ def resolve_max_cycles(max_cycles, method):
 
 
 # ---- validation -----------------------------------------------------------------------------------------------------
-def _shape(a):
-    return tuple(a.shape) if hasattr(a, "shape") else np.shape(a)
-
-
 def check_args(dem, mask, method, tol, max_cycles, objects, cellsize, who="fill_voids"):
     """Host-side rejection before any launch; -> (H, W, cellsize or None)."""
-    shape = _shape(dem)
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
-        raise ValueError(f"{who}: dem must be [H, W] with H*W < 2^31, got {shape}")
-    if mask is not None and _shape(mask) != shape:
-        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
+    shape = R.raster_shape(dem, mask, who)
     if not isinstance(method, str) or method not in METHODS:
         raise ValueError(f"{who}: method {method!r} must be one of {METHODS}")
     max_cycles = resolve_max_cycles(max_cycles, method)
@@ -164,30 +158,12 @@ def check_args(dem, mask, method, tol, max_cycles, objects, cellsize, who="fill_
         raise ValueError(f"{who}: max_cycles {max_cycles!r} must be an integer >= 1")
     c = None
     if objects is not None:
-        from .object_mask import _check_cellsize
         try:
-            c = _check_cellsize(cellsize)
+            c = R.cellsize(cellsize, who)
         except ValueError:
             raise ValueError(f"{who}: objects need a cellsize, finite and > 0, got {cellsize!r}") from None
         objects.check()
     return shape[0], shape[1], c
-
-
-def _device_f32(a, device, what, binary=False, who="fill_voids"):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{who}: {what} is on {a.device}; pass a numpy array or a HIP tensor")
-        if binary and a.dtype != torch.float32:
-            a = a != 0
-        return a.to(device=device, dtype=torch.float32).contiguous()
-    a = np.asarray(a)
-    if binary:
-        a = a != 0
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-
-
-def _bits_f32(b):
-    return float(np.array([int(b) & 0xffffffff], np.uint32).view(np.float32)[0])
 
 
 # ---- the fill -------------------------------------------------------------------------------------------------------
@@ -207,13 +183,7 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
     inner = check_inner(inner)
     max_cycles = resolve_max_cycles(max_cycles, method)
     bih = method == "biharmonic"
-    if not torch.cuda.is_available():
-        raise RuntimeError("fill_voids: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem")
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True)
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
+    z, m, nodata, device = R.upload(dem, mask, nodata, "fill_voids")
     oinfo = None
     if objects is not None:
         from .object_mask import object_mask
@@ -221,7 +191,7 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
     ws = O.vfill_ws(H, W, device)
     st = O.vfill_setup(z, m, nodata, ws).cpu().tolist()        # the one sync before the cycles
     known, unknown = int(st[0]), int(st[1])
-    rng = _bits_f32(st[3]) - _bits_f32(st[2]) if known else 0.0
+    rng = R.bits_f32(st[3]) - R.bits_f32(st[2]) if known else 0.0
     t = 1e-6 * rng if tol is None else float(tol)
     cycles, change, converged, restarts, vcycles = 0, 0.0, known > 0, 0, 0
     if known and unknown and bih:
@@ -234,7 +204,7 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
             O.vfill_bih_iter(H, W, ws, bws, inner, st)
             cycles += 1
             vcycles += 2 * inner
-            change = _bits_f32(st[0].item())                    # one read per outer iteration
+            change = R.bits_f32(st[0].item())                    # one read per outer iteration
             if change <= t:
                 converged = True
                 break
@@ -247,7 +217,7 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
         while cycles < max_cycles:
             O.vfill_pcg_iter(H, W, ws, pws, st)
             cycles += 1
-            change = _bits_f32(st[0].item())                    # one read per iteration
+            change = R.bits_f32(st[0].item())                    # one read per iteration
             if change <= t:
                 converged = True
                 break
@@ -258,7 +228,7 @@ def fill_voids(dem, mask=None, *, nodata=None, method="laplace", tol=None, max_c
         while cycles < max_cycles:
             O.vfill_cycle(H, W, ws, ch)
             cycles += 1
-            change = _bits_f32(ch.item())                       # one read per cycle
+            change = R.bits_f32(ch.item())                       # one read per cycle
             if change <= t:
                 converged = True
                 break
@@ -303,20 +273,16 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import read_inputs, with_nodata, write_asc
     from .object_mask import spec_from_args
     ap = build_parser()
     a = ap.parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
+    dem, header, mask, nodata, cellsize = read_inputs(a)
     objects = spec_from_args(a) if a.remove_objects else None
     max_cycles = None if isinstance(a.max_cycles, _Unset) else a.max_cycles
     out, info = fill_voids(dem, mask, nodata=nodata, tol=a.tol, max_cycles=max_cycles, objects=objects,
-                           cellsize=float(asc_value(header, "cellsize")), solver=a.solver, method=a.method, inner=a.inner)
-    if info["unfilled"] and asc_value(header, "NODATA_value") is None:
-        header = header + [("NODATA_value", "-9999")]
-    write_asc(a.out, out.cpu().numpy(), header)
+                           cellsize=cellsize, solver=a.solver, method=a.method, inner=a.inner)
+    write_asc(a.out, out.cpu().numpy(), with_nodata(header) if info["unfilled"] else header)
     print(f"{a.out}: {info['unknown']} void pixels, {info['cycles']} cycles, converged {info['converged']}, "
           + (f"method {a.method}, {info['vcycles']} V-cycles" if a.method == "biharmonic" else f"solver {a.solver}"))
     if not info["converged"]:

@@ -54,6 +54,7 @@ import numbers
 import numpy as np
 import torch
 
+from . import raster_args as R
 from .fill_depressions import CHECK_EVERY, MAX_SWEEPS, check_args, run_doubling, run_until_unchanged
 
 OUT, PIT, UNKNOWN = 9, 255, 0
@@ -125,19 +126,10 @@ def route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who
 
 def _upload(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who):
     """flow_routing's checks, upload and known mask -> (z float32 [H][W], known uint8 [H][W], cellsize)."""
-    from tg_hip import ops as O
-    from .fill_voids import _device_f32
     _, _, c = check_args(dem, mask, cellsize, 8, max_sweeps, check_every, who=who)
     if not isinstance(fill, bool):
         raise ValueError(f"{who}: fill {fill!r} must be True or False")
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{who}: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem", who=who)
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who=who)
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
-    known, _ = O.objmask_known(z, m, nodata, transposed=False)
+    z, known = R.upload_known(dem, mask, nodata, who)
     return z, known, c
 
 
@@ -175,37 +167,18 @@ def route_known(z, known, cellsize, *, fill=True, max_sweeps=MAX_SWEEPS, check_e
 SQRT2 = 1.4142135623730951
 
 
-def _bits_f32(b):
-    return float(np.array([int(b) & 0xffffffff], np.uint32).view(np.float32)[0])
-
-
-def _device_u8(a, device, what, who, nonzero=False):
-    """A direction grid (uint8 as given) or a pour raster (any numeric type, nonzero -> 1) as a uint8 HIP tensor."""
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{who}: {what} is on {a.device}; pass a numpy array or a HIP tensor")
-        a = (a != 0) if nonzero else a
-        return a.to(device=device, dtype=torch.uint8).contiguous()
-    a = np.asarray(a)
-    a = (a != 0) if nonzero else a
-    return torch.from_numpy(np.array(a, dtype=np.uint8, order="C")).to(device)      # a copy: the input may be read-only
-
-
 def check_watershed_args(direction, pour_points, cellsize, compact, check_every, who="watersheds"):
     """Host-side rejection before any launch; -> (H, W, cellsize)."""
-    from .fill_depressions import _cellsize, _count, _shape
-    shape = _shape(direction)
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
-        raise ValueError(f"{who}: direction must be [H, W], non-empty with H*W < 2^31, got {shape}")
+    shape = R.raster_shape(direction, None, who, what="direction must be [H, W], non-empty")
     dt = direction.dtype if isinstance(direction, (torch.Tensor, np.ndarray)) else None
     if dt not in (torch.uint8, np.dtype(np.uint8)):
         raise ValueError(f"{who}: direction must be a uint8 grid of flow_routing's codes, got {dt}")
-    if pour_points is not None and _shape(pour_points) != shape:
-        raise ValueError(f"{who}: pour_points {_shape(pour_points)} differs from the direction grid {shape}")
+    if pour_points is not None and R.shape(pour_points) != shape:
+        raise ValueError(f"{who}: pour_points {R.shape(pour_points)} differs from the direction grid {shape}")
     if not isinstance(compact, bool):
         raise ValueError(f"{who}: compact {compact!r} must be True or False")
-    _count(check_every, 1, "check_every", who)
-    return shape[0], shape[1], _cellsize(cellsize, who)
+    R.count(check_every, 1, "check_every", who)
+    return shape[0], shape[1], R.cellsize(cellsize, who)
 
 
 def basin_doubling(d, pour, ws, check_every=CHECK_EVERY):
@@ -246,20 +219,18 @@ def watersheds(direction, pour_points=None, *, cellsize=1.0, compact=False, chec
     from tg_hip import ops as O
     who = "watersheds"
     H, W, c = check_watershed_args(direction, pour_points, cellsize, compact, check_every, who)
-    if not torch.cuda.is_available():
-        raise RuntimeError("watersheds: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    d = _device_u8(direction, device, "direction", who)
+    device = R.device(who)
+    d = R.to_u8(direction, device, "direction", who)
     if bool(torch.any(d == 254)):
         raise ValueError(f"{who}: the direction grid holds the code 254 (undecided): route it to the end first")
-    pour = None if pour_points is None else _device_u8(pour_points, device, "pour_points", who, nonzero=True)
+    pour = None if pour_points is None else R.to_u8(pour_points, device, "pour_points", who, nonzero=True)
     ws = O.flow_basin_ws(H, W, device)
     rounds, used, ignored = basin_doubling(d, pour, ws, check_every)
     basin, _, _, length, counts = O.flow_basin_finish(H, W, rounds, ws, c)
     terminals, longest, bits = counts.cpu().tolist()
     if compact:
         basin = compact_labels(basin)
-    info = {"basins": terminals, "rounds": rounds, "longest_steps": longest, "max_length_m": _bits_f32(bits),
+    info = {"basins": terminals, "rounds": rounds, "longest_steps": longest, "max_length_m": R.bits_f32(bits),
             "pour_points": used, "pour_ignored": ignored}
     return basin, length, info
 
@@ -276,24 +247,15 @@ def _min_cells(n, who):
 
 def check_stream_args(direction, accumulation, min_cells, cellsize, max_rounds, check_every, who="stream_network"):
     """Host-side rejection before any launch; -> (H, W, cellsize)."""
-    from .fill_depressions import _count, _shape
     H, W, c = check_watershed_args(direction, None, cellsize, False, check_every, who)
-    if _shape(accumulation) != (H, W):
-        raise ValueError(f"{who}: accumulation {_shape(accumulation)} differs from the direction grid {(H, W)}")
+    if R.shape(accumulation) != (H, W):
+        raise ValueError(f"{who}: accumulation {R.shape(accumulation)} differs from the direction grid {(H, W)}")
     dt = accumulation.dtype if isinstance(accumulation, (torch.Tensor, np.ndarray)) else None
     if dt not in (torch.int32, np.dtype(np.int32)):
         raise ValueError(f"{who}: accumulation must be an int32 grid of flow_routing's counts, got {dt}")
     _min_cells(min_cells, who)
-    _count(max_rounds, 1, "max_rounds", who)
+    R.count(max_rounds, 1, "max_rounds", who)
     return H, W, c
-
-
-def _device_i32(a, device, what, who):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"{who}: {what} is on {a.device}; pass a numpy array or a HIP tensor")
-        return a.to(device=device).contiguous()
-    return torch.from_numpy(np.array(a, dtype=np.int32, order="C")).to(device)
 
 
 def order_rounds(d, cls, top, order, max_rounds=ORDER_MAX_ROUNDS, check_every=CHECK_EVERY):
@@ -324,7 +286,7 @@ def network_known(d, acc, min_cells, cellsize, max_rounds=ORDER_MAX_ROUNDS, chec
     info = {"stream_cells": cells, "heads": heads, "junctions": junctions, "outlets": outlets, "links": heads + junctions,
             "max_order": oc[0], "cells_by_order": oc[1:1 + nb], "links_by_order": oc[1 + nb:1 + 2 * nb],
             "link_rounds": link_rounds, "order_rounds": rounds, "converged": converged,
-            "longest_link_m": _bits_f32(c1.cpu().tolist()[2])}
+            "longest_link_m": R.bits_f32(c1.cpu().tolist()[2])}
     return order, top, info
 
 
@@ -339,13 +301,11 @@ def stream_network(direction, accumulation, min_cells, *, cellsize=1.0, max_roun
     is False and every order is a lower bound.  Exact and bitwise reproducible (csrc/drainage.hip)."""
     who = "stream_network"
     H, W, c = check_stream_args(direction, accumulation, min_cells, cellsize, max_rounds, check_every, who)
-    if not torch.cuda.is_available():
-        raise RuntimeError("stream_network: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    d = _device_u8(direction, device, "direction", who)
+    device = R.device(who)
+    d = R.to_u8(direction, device, "direction", who)
     if bool(torch.any(d == 254)):
         raise ValueError(f"{who}: the direction grid holds the code 254 (undecided): route it to the end first")
-    acc = _device_i32(accumulation, device, "accumulation", who)
+    acc = R.to_i32(accumulation, device, "accumulation", who)
     return network_known(d, acc, min_cells, c, max_rounds, check_every)
 
 
@@ -362,7 +322,7 @@ def hand_from_routing(w, direction, stream, cellsize, check_every=CHECK_EVERY):
     basin, _, _, length, _ = O.flow_basin_finish(H, W, rounds, ws, cellsize)
     h, dist, counts = O.hand(w, basin, stream, length)
     drained, undrained, cells, bits = counts.cpu().tolist()
-    return h, dist, {"drained": drained, "undrained": undrained, "stream_cells": cells, "max_hand_m": _bits_f32(bits),
+    return h, dist, {"drained": drained, "undrained": undrained, "stream_cells": cells, "max_hand_m": R.bits_f32(bits),
                      "rounds": rounds}
 
 
@@ -377,12 +337,11 @@ def hand(dem, mask=None, *, nodata=None, cellsize=1.0, min_cells=1000, min_order
     flow_routing's numbers plus drained, undrained, stream_cells, max_hand_m, rounds, and "network" with min_order > 1; orders
     that have not converged raise a RuntimeError, since lower bounds would leave links out of the drainage).  The
     flood extent at stage h is hand <= h."""
-    from .fill_depressions import _cellsize
     who = "hand"
     _min_cells(min_cells, who)
     _min_order(min_order, who)
     direction, acc, info, w = route_raster(dem, mask, nodata, cellsize, fill, max_sweeps, check_every, who)
-    return hand_routed(w, direction, acc, info, _cellsize(cellsize, who), min_cells, min_order, check_every)[:3]
+    return hand_routed(w, direction, acc, info, R.cellsize(cellsize, who), min_cells, min_order, check_every)[:3]
 
 
 def _min_order(k, who):
@@ -605,27 +564,10 @@ def parse_args(argv=None):
     return a
 
 
-def write_int_asc(path, arr, header):
-    """An integer grid under read_asc's header, without its NODATA_value (every code is a value); exact for any int32."""
-    from .inpaint_raster import asc_value
-    arr = np.asarray(arr)
-    if arr.shape != (int(asc_value(header, "nrows")), int(asc_value(header, "ncols"))):
-        raise ValueError(f"write_int_asc: array {arr.shape} does not match the header")
-    with open(path, "w") as f:
-        for k, v in header:
-            if k.lower() != "nodata_value":
-                f.write(f"{k} {v}\n")
-        for row in arr.astype(np.int64):
-            f.write(" ".join(map(str, row.tolist())) + "\n")
-
-
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import read_inputs, read_mask, with_nodata, write_asc, write_int_asc
     a = parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
-    cs = float(asc_value(header, "cellsize"))
+    dem, header, mask, nodata, cs = read_inputs(a)
     direction, acc, info, w = route_raster(dem, mask, nodata, cs, not a.no_fill, a.max_sweeps, CHECK_EVERY, "flow_routing")
     write_int_asc(a.dir_out, (to_esri(direction) if a.esri else direction).cpu().numpy(), header)
     write_int_asc(a.acc_out, acc.cpu().numpy(), header)
@@ -644,7 +586,7 @@ def main(argv=None):
               f"rounds" + ("" if ninfo["converged"] else " (NOT converged: the orders are lower bounds)"))
     if a.hand_out:
         h, dist, _, _ = hand_routed(w, direction, acc, info, cs, a.min_cells, a.min_order)
-        fh = list(header) if asc_value(header, "NODATA_value") is not None else list(header) + [("NODATA_value", "-9999")]
+        fh = with_nodata(header)
         write_asc(a.hand_out, h.cpu().numpy(), fh)
         if a.hand_distance_out:
             write_asc(a.hand_distance_out, dist.cpu().numpy(), fh)
@@ -653,7 +595,7 @@ def main(argv=None):
     if a.mfd_acc_out or a.slope_out or a.twi_out:
         from tg_hip import ops as O
         known = (direction != 0).to(torch.uint8)                    # every known pixel has a code
-        fh = list(header) if asc_value(header, "NODATA_value") is not None else list(header) + [("NODATA_value", "-9999")]
+        fh = with_nodata(header)
         if a.slope_out or a.twi_out:
             slope = O.terrain_slope(w, known, cs)
             if a.slope_out:
@@ -669,8 +611,8 @@ def main(argv=None):
                   f"{minfo['single']} give to one neighbour, {minfo['sinks']} sinks; largest contributing area "
                   f"{minfo['max_accumulation_mfd']:.9g} cells, {minfo['mass_out']:.9g} cells leave, {minfo['mfd_sweeps']} sweeps")
     if a.basins_out or a.length_out:
-        pour = _read_mask(a.pour, dem.shape) if a.pour else None
-        basin, length, winfo = watersheds(direction, pour, cellsize=float(asc_value(header, "cellsize")), compact=a.compact)
+        pour = read_mask(a.pour, dem.shape) if a.pour else None
+        basin, length, winfo = watersheds(direction, pour, cellsize=cs, compact=a.compact)
         if a.basins_out:
             write_int_asc(a.basins_out, basin.cpu().numpy(), header)
         if a.length_out:

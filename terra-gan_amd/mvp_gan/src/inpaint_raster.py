@@ -36,11 +36,12 @@ CLI: python -m mvp_gan.src.inpaint_raster --dem in.asc [--mask m.png|m.asc] --ch
          [--seam harmonic [--seam-order 0|1]] [--model-cellsize 1.0 [--min-coverage 0.5]]
 """
 import argparse
-import math
 from collections import namedtuple
 
 import numpy as np
 import torch
+
+from . import raster_args as R
 
 MIN_SIDE = 40          # smallest window side the generator is tested at (fixture g72x40b3)
 FALLBACK_MAX_CYCLES = 200
@@ -81,65 +82,6 @@ def window_ramp(w, overlap, first=False, last=False):
     return r
 
 
-# ---- ESRI ASCII grid ------------------------------------------------------------------------------------------------
-_ASC_KEYS = ("ncols", "nrows", "xllcorner", "xllcenter", "yllcorner", "yllcenter", "cellsize", "nodata_value")
-
-
-def read_asc(path):
-    """-> (float32 array [nrows][ncols], header): header is a list of (key, value string) in file order, kept verbatim
-    so that write_asc reproduces it."""
-    header = []
-    with open(path) as f:
-        lines = f.readlines()
-    i = 0
-    while i < len(lines):
-        tok = lines[i].split()
-        if len(tok) == 2 and tok[0].lower() in _ASC_KEYS:
-            header.append((tok[0], tok[1]))
-            i += 1
-        else:
-            break
-    keys = {k.lower() for k, _ in header}
-    if not {"ncols", "nrows", "cellsize"} <= keys or not (keys & {"xllcorner", "xllcenter"}) or \
-            not (keys & {"yllcorner", "yllcenter"}):
-        raise ValueError(f"{path}: not an ESRI ASCII grid (header {header})")
-    nrows, ncols = int(asc_value(header, "nrows")), int(asc_value(header, "ncols"))
-    vals = np.array(" ".join(lines[i:]).split(), dtype=np.float32)
-    if vals.size != nrows * ncols:
-        raise ValueError(f"{path}: {vals.size} values for a {nrows}x{ncols} grid")
-    return vals.reshape(nrows, ncols), header
-
-
-def asc_value(header, key, default=None):
-    for k, v in header:
-        if k.lower() == key.lower():
-            return v
-    return default
-
-
-def asc_nodata(header):
-    v = asc_value(header, "NODATA_value")
-    return None if v is None else float(v)
-
-
-def write_asc(path, arr, header):
-    """Write [nrows][ncols] values under `header` (as read_asc returns it).  float32 values are written with 9
-    significant digits (they read back bit for bit); NaN is written as the header's NODATA_value when it has one."""
-    arr = np.asarray(arr, dtype=np.float32)
-    nrows, ncols = int(asc_value(header, "nrows")), int(asc_value(header, "ncols"))
-    if arr.shape != (nrows, ncols):
-        raise ValueError(f"write_asc: array {arr.shape} does not match the header's {nrows}x{ncols}")
-    nd = asc_value(header, "NODATA_value")
-    with open(path, "w") as f:
-        for k, v in header:
-            f.write(f"{k} {v}\n")
-        for row in arr:
-            txt = ["%.9g" % v for v in row.tolist()]
-            if nd is not None:
-                txt = [nd if t == "nan" else t for t in txt]
-            f.write(" ".join(txt) + "\n")
-
-
 # ---- GPU path -------------------------------------------------------------------------------------------------------
 def _load_generator(generator_or_checkpoint, device):
     from .models.generator import PConvUNet
@@ -149,19 +91,6 @@ def _load_generator(generator_or_checkpoint, device):
     ckpt = torch.load(generator_or_checkpoint, map_location=device)
     generator.load_state_dict(ckpt["generator_state_dict"] if isinstance(ckpt, dict) and "generator_state_dict" in ckpt else ckpt)
     return generator
-
-
-def _to_device_f32(a, device, what, binary=False):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"inpaint_raster: {what} is on {a.device}; pass a numpy array or a HIP tensor")
-        if binary and a.dtype != torch.float32:
-            a = a != 0
-        return a.to(device=device, dtype=torch.float32).contiguous()
-    a = np.asarray(a)
-    if binary:
-        a = a != 0
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
 
 
 def check_seam_options(seam, seam_order, who="inpaint_raster"):
@@ -231,26 +160,23 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
     from .fill_voids import check_solver
     scale = check_resample_options(cellsize, model_cellsize, min_coverage)
     check_solver(solver, who="inpaint_raster")
-    if not torch.cuda.is_available():
-        raise RuntimeError("inpaint_raster: no HIP device visible; this build has no CPU path")
+    device = R.device("inpaint_raster")
     if batch < 1:
         raise ValueError(f"inpaint_raster: batch {batch} < 1")
     if fallback not in (None, "laplace"):
         raise ValueError(f"inpaint_raster: fallback {fallback!r} must be None or 'laplace'")
     check_seam_options(seam, seam_order)
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _to_device_f32(dem, device, "dem")
+    z = R.to_f32(dem, device, "dem", "inpaint_raster")
     if z.dim() != 2:
         raise ValueError(f"inpaint_raster: dem must be [H, W], got {tuple(z.shape)}")
-    m = None if mask is None else _to_device_f32(mask, device, "mask", binary=True)
+    m = None if mask is None else R.to_f32(mask, device, "mask", "inpaint_raster", binary=True)
     if m is not None and m.shape != z.shape:
         raise ValueError(f"inpaint_raster: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
     oinfo = None
     if objects is not None:
         from .object_mask import object_mask
         _, m, oinfo = object_mask(z, m, nodata=nodata, cellsize=cellsize, spec=objects)
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are holes already
+    nodata = R.nodata_value(nodata)
     rinfo = None
     if scale is None:
         out, nwin, nrun, unfilled = _inpaint_windows(generator_or_checkpoint, z, m, nodata, window, overlap, batch, device)
@@ -294,17 +220,6 @@ def inpaint_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, wind
 
 
 # ---- CLI ------------------------------------------------------------------------------------------------------------
-def _read_mask(path, shape):
-    if path.lower().endswith(".asc"):
-        mk, _ = read_asc(path)
-    else:
-        from PIL import Image
-        mk = np.asarray(Image.open(path).convert("L"))
-    if mk.shape != shape:
-        raise ValueError(f"mask {path} is {mk.shape[0]}x{mk.shape[1]}, the raster {shape[0]}x{shape[1]} (no resizing)")
-    return mk != 0
-
-
 def build_parser():
     from .object_mask import add_spec_args
     ap = argparse.ArgumentParser(description="Inpaint the holes of an ESRI ASCII grid DSM with a TERRA-GAN generator.")
@@ -336,27 +251,22 @@ def build_parser():
 
 
 def main(argv=None):
-    from .object_mask import object_mask, spec_from_args, write_mask
+    from .asc import read_inputs, with_nodata, write_asc, write_mask
+    from .object_mask import object_mask, spec_from_args
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.objects_out and not a.remove_objects:
         ap.error("--objects-out needs --remove-objects")
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = asc_nodata(header)
+    dem, header, mask, nodata, cellsize = read_inputs(a)
     if a.remove_objects:                      # what inpaint_raster(objects=...) does, keeping the object map for --objects-out
-        objects, mask, oinfo = object_mask(dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")),
-                                           spec=spec_from_args(a))
+        objects, mask, oinfo = object_mask(dem, mask, nodata=nodata, cellsize=cellsize, spec=spec_from_args(a))
         if a.objects_out:
             write_mask(a.objects_out, objects.cpu().numpy(), header)
         print(f"{oinfo['objects']} objects, {oinfo['object_pixels']} px removed")
     out, info = inpaint_raster(a.checkpoint, dem, mask, nodata=nodata, window=a.window, overlap=a.overlap, batch=a.batch,
-                               fallback=a.fallback, seam=a.seam, seam_order=a.seam_order,
-                               cellsize=float(asc_value(header, "cellsize")), model_cellsize=a.model_cellsize,
-                               min_coverage=a.min_coverage, solver=a.solver)
-    if info["unfilled"] and asc_value(header, "NODATA_value") is None:
-        header = header + [("NODATA_value", "-9999")]
-    write_asc(a.out, out.cpu().numpy(), header)
+                               fallback=a.fallback, seam=a.seam, seam_order=a.seam_order, cellsize=cellsize,
+                               model_cellsize=a.model_cellsize, min_coverage=a.min_coverage, solver=a.solver)
+    write_asc(a.out, out.cpu().numpy(), with_nodata(header) if info["unfilled"] else header)
     print(f"{a.out}: {info['windows']} windows, {info['run']} run, {info['unfilled']} holes left unfilled")
     if "resample" in info:
         rs = info["resample"]

@@ -25,7 +25,8 @@ import math
 
 import torch
 
-from .distance import FAR, MAX_SIDE, _cellsize, _shape
+from . import raster_args as R
+from .distance import FAR, MAX_SIDE
 
 METHODS = ("idw", "nearest")
 MAX_SMOOTH = 64
@@ -36,7 +37,7 @@ def ray_px2(max_distance, cellsize, who="ray_px2"):
     """Metres -> squared pixels: the largest integer n with cellsize * sqrt(n) <= max_distance in fp64, the arithmetic of the
     distance itself, so d2 <= n exactly when the distance in metres is <= max_distance.  ValueError for a distance that is not
     finite and > 0, is shorter than one cell (no pixel would be in reach), or is beyond every int32 squared distance."""
-    c = _cellsize(cellsize, who)
+    c = R.cellsize(cellsize, who)
     try:
         e = float(max_distance)
     except (TypeError, ValueError):
@@ -59,11 +60,7 @@ def ray_px2(max_distance, cellsize, who="ray_px2"):
 
 def check_args(dem, mask, method, power, max_distance, cellsize, smooth, fallback, who="interpolate_voids"):
     """Host-side rejection before any launch; -> (H, W, cellsize, power, lim2 (0: no limit), smooth)."""
-    shape = _shape(dem)
-    if len(shape) != 2 or min(shape) < 1 or max(shape) > MAX_SIDE:
-        raise ValueError(f"{who}: dem must be [H, W] with sides in [1, {MAX_SIDE}], got {shape}")
-    if mask is not None and _shape(mask) != shape:
-        raise ValueError(f"{who}: mask {_shape(mask)} differs from the dem {shape}")
+    shape = R.raster_shape(dem, mask, who, max_side=MAX_SIDE)
     if method not in METHODS:
         raise ValueError(f"{who}: method {method!r} must be one of {METHODS}")
     if fallback not in (None, "nearest"):
@@ -76,7 +73,7 @@ def check_args(dem, mask, method, power, max_distance, cellsize, smooth, fallbac
         raise ValueError(f"{who}: power {power!r} must lie in (0, {MAX_POWER:g}]")
     if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= MAX_SMOOTH:
         raise ValueError(f"{who}: smooth {smooth!r} must be an integer in [0, {MAX_SMOOTH}]")
-    c = _cellsize(cellsize, who)
+    c = R.cellsize(cellsize, who)
     lim2 = 0 if max_distance is None else ray_px2(max_distance, c, who)
     return shape[0], shape[1], c, p, lim2, smooth
 
@@ -89,17 +86,8 @@ def interpolate_voids(dem, mask=None, *, nodata=None, method="idw", power=2.0, m
     by_nearest (filled from the nearest known pixel), unfilled, method, power, smooth, max_distance, lim2 (None without
     max_distance))."""
     from tg_hip import ops as O
-    from .fill_voids import _device_f32
-    who = "interpolate_voids"
     H, W, c, p, lim2, smooth = check_args(dem, mask, method, power, max_distance, cellsize, smooth, fallback)
-    if not torch.cuda.is_available():
-        raise RuntimeError("interpolate_voids: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem", who=who)
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who=who)
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are unknown already
-    known, _ = O.objmask_known(z, m, nodata, transposed=False)
+    z, known = R.upload_known(dem, mask, nodata, "interpolate_voids")
     cap2 = lim2 + 1 if lim2 else 0                              # idx >= 0 exactly where d2 <= lim2
     if method == "nearest":
         _, idx = O.edt_nearest(known, cap2)
@@ -139,17 +127,12 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import read_inputs, with_nodata, write_asc
     a = build_parser().parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
+    dem, header, mask, nodata, cellsize = read_inputs(a)
     out, info = interpolate_voids(dem, mask, nodata=nodata, method=a.method, power=a.power, max_distance=a.max_distance,
-                                  cellsize=float(asc_value(header, "cellsize")), smooth=a.smooth,
-                                  fallback=None if a.no_fallback else "nearest")
-    if info["unfilled"] and asc_value(header, "NODATA_value") is None:
-        header = header + [("NODATA_value", "-9999")]
-    write_asc(a.out, out.cpu().numpy(), header)
+                                  cellsize=cellsize, smooth=a.smooth, fallback=None if a.no_fallback else "nearest")
+    write_asc(a.out, out.cpu().numpy(), with_nodata(header) if info["unfilled"] else header)
     print(f"{a.out}: {info['unknown']} void pixels, {info['filled']} filled by {a.method} ({info['by_nearest']} from the "
           f"nearest known cell), {info['unfilled']} left unfilled")
     return info

@@ -27,6 +27,8 @@ from dataclasses import dataclass, fields
 import numpy as np
 import torch
 
+from . import raster_args as R
+
 
 @dataclass(frozen=True)
 class ObjectSpec:
@@ -46,20 +48,10 @@ class ObjectSpec:
             raise ValueError(f"ObjectSpec: dh0 {self.dh0} > dhmax {self.dhmax}")
 
 
-def _check_cellsize(cellsize):
-    try:
-        c = float(cellsize)
-    except (TypeError, ValueError):
-        c = math.nan
-    if not math.isfinite(c) or c <= 0:
-        raise ValueError(f"object_mask: cellsize {cellsize!r} must be finite and > 0")
-    return c
-
-
 def schedule(spec, cellsize):
     """-> (radii [int], thresholds float32 array, min_area_px, buffer_px) of `spec` at `cellsize` metres per pixel."""
     spec.check()
-    c = _check_cellsize(cellsize)
+    c = R.cellsize(cellsize, "object_mask")
     r_max = math.ceil(spec.max_size_m / (2.0 * c))
     radii, k = [], 0
     while 2 ** k < r_max:
@@ -76,19 +68,6 @@ def schedule(spec, cellsize):
     min_area = math.ceil(spec.min_area_m2 / (c * c))
     buffer_px = math.floor(spec.buffer_m / c + 0.5)
     return radii, np.array(dh, dtype=np.float64).astype(np.float32), min_area, buffer_px
-
-
-def _device_f32(a, device, what, binary=False):
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError(f"object_mask: {what} is on {a.device}; pass a numpy array or a HIP tensor")
-        if binary and a.dtype != torch.float32:
-            a = a != 0
-        return a.to(device=device, dtype=torch.float32).contiguous()
-    a = np.asarray(a)
-    if binary:
-        a = a != 0
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(device)
 
 
 def pmf(z, known, known_t, radii, thresholds):
@@ -115,18 +94,10 @@ def object_mask(dem, mask=None, *, nodata=None, cellsize, spec=ObjectSpec()):
                          f"more than {O.OBJMASK_MAX_BUFFER}")
     if min_area >= 2 ** 31:
         raise ValueError(f"object_mask: min_area {spec.min_area_m2} m^2 is {min_area} px, more than any raster here")
-    shape = tuple(dem.shape) if hasattr(dem, "shape") else np.shape(dem)
-    if len(shape) != 2 or min(shape) < 1 or shape[0] * shape[1] >= 2 ** 31:
-        raise ValueError(f"object_mask: dem must be [H, W] with H*W < 2^31, got {shape}")
-    if not torch.cuda.is_available():
-        raise RuntimeError("object_mask: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem")
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True)
+    R.raster_shape(dem, None, "object_mask")
+    z, m, nodata, _ = R.upload(dem, mask, nodata, "object_mask")
     if m is not None and m.shape != z.shape:
         raise ValueError(f"object_mask: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
-    if nodata is not None and math.isnan(nodata):
-        nodata = None
     known, known_t = O.objmask_known(z, m, nodata)
     flags, _ = pmf(z, known, known_t, radii, dh)
     labels, area = O.objmask_components(flags)
@@ -153,19 +124,8 @@ def spec_from_args(a):
                       buffer_m=a.buffer)
 
 
-def write_mask(path, m, header):
-    """A 0 / 1 map as .asc (under the raster's header, without its NODATA_value) or as an 8-bit image (255 = 1)."""
-    m = np.asarray(m)
-    if str(path).lower().endswith(".asc"):
-        from .inpaint_raster import write_asc
-        write_asc(path, (m != 0).astype(np.float32), [(k, v) for k, v in header if k.lower() != "nodata_value"])
-    else:
-        from PIL import Image
-        Image.fromarray(((m != 0) * 255).astype(np.uint8)).save(path)
-
-
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc
+    from .asc import read_inputs, write_mask
     ap = argparse.ArgumentParser(description="Find above-ground objects in an ESRI ASCII grid DSM; write the keep mask.")
     ap.add_argument("--dem", required=True, help="input .asc raster (NODATA_value cells are unknown)")
     ap.add_argument("--out", required=True, help="keep mask (.png or .asc): nonzero = keep, 0 = object or unknown")
@@ -173,10 +133,8 @@ def main(argv=None):
     ap.add_argument("--objects-out", help="optional object map (.png or .asc): nonzero = object")
     add_spec_args(ap)
     a = ap.parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    objects, keep, info = object_mask(dem, mask, nodata=asc_nodata(header), cellsize=float(asc_value(header, "cellsize")),
-                                      spec=spec_from_args(a))
+    dem, header, mask, nodata, cellsize = read_inputs(a)
+    objects, keep, info = object_mask(dem, mask, nodata=nodata, cellsize=cellsize, spec=spec_from_args(a))
     write_mask(a.out, keep.cpu().numpy(), header)
     if a.objects_out:
         write_mask(a.objects_out, objects.cpu().numpy(), header)

@@ -25,6 +25,8 @@ from fractions import Fraction
 
 import torch
 
+from . import raster_args as R
+
 MAX_DENOMINATOR = 64
 MIN_SCALE, MAX_SCALE = Fraction(1, 4), Fraction(16)
 COVERAGE_DENOMINATOR = 1000
@@ -131,19 +133,14 @@ def resampled_header(header, shape, cellsize, target_cellsize, out_shape):
 
 # ---- GPU path -------------------------------------------------------------------------------------------------------
 def _inputs(dem, mask, nodata, who):
-    from .inpaint_raster import _to_device_f32
-    if not torch.cuda.is_available():
-        raise RuntimeError(f"{who}: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _to_device_f32(dem, device, "dem")
+    device = R.device(who)
+    z = R.to_f32(dem, device, "dem", who)
     if z.dim() != 2:
         raise ValueError(f"{who}: dem must be [H, W], got {tuple(z.shape)}")
-    m = None if mask is None else _to_device_f32(mask, device, "mask", binary=True)
+    m = None if mask is None else R.to_f32(mask, device, "mask", who, binary=True)
     if m is not None and m.shape != z.shape:
         raise ValueError(f"{who}: mask {tuple(m.shape)} differs from the dem {tuple(z.shape)}")
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are holes already
-    return z, m, nodata
+    return z, m, R.nodata_value(nodata)
 
 
 def resample_to(z, m, nodata, scale, min_coverage=0.5):
@@ -201,17 +198,12 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import read_inputs, with_nodata, write_asc
     a = build_parser().parse_args(argv)
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    c = float(asc_value(header, "cellsize"))
-    out, _, info = resample_raster(dem, mask, nodata=asc_nodata(header), cellsize=c, target_cellsize=a.cellsize_out,
+    dem, header, mask, nodata, c = read_inputs(a)
+    out, _, info = resample_raster(dem, mask, nodata=nodata, cellsize=c, target_cellsize=a.cellsize_out,
                                    min_coverage=a.min_coverage)
-    header = resampled_header(header, dem.shape, c, a.cellsize_out, out.shape)
-    if asc_value(header, "NODATA_value") is None:
-        header = header + [("NODATA_value", "-9999")]
-    write_asc(a.out, out.cpu().numpy(), header)
+    write_asc(a.out, out.cpu().numpy(), with_nodata(resampled_header(header, dem.shape, c, a.cellsize_out, out.shape)))
     print(f"{a.out}: scale {info['scale']}, {info['shape'][0]}x{info['shape'][1]} at cellsize {info['cellsize']:g}, "
           f"{info['known']} known / {info['unknown']} unknown")
     return info

@@ -23,12 +23,11 @@ CLI: python -m mvp_gan.src.seam_correct --dem in.asc --filled fill.asc [--mask k
          [--tol t] [--max-cycles n] [--solver mg|pcg] --out out.asc
 """
 import argparse
-import math
-
 import numpy as np
 import torch
 
-from .fill_voids import SOLVERS, _bits_f32, _device_f32, _shape, check_args, check_solver
+from . import raster_args as R
+from .fill_voids import SOLVERS, check_args, check_solver
 
 ORDERS = (0, 1)
 MAX_CYCLES = 200               # the budget of inpaint_raster's fallback: holes as wide as a window converge slowly
@@ -37,8 +36,8 @@ MAX_CYCLES = 200               # the budget of inpaint_raster's fallback: holes 
 def check_seam_args(dem, filled, mask, order, tol, max_cycles, who="correct_seams"):
     """Host-side rejection before any launch; -> (H, W)."""
     H, W, _ = check_args(dem, mask, "laplace", tol, max_cycles, None, None, who=who)
-    if _shape(filled) != (H, W):
-        raise ValueError(f"{who}: filled {_shape(filled)} differs from the dem {(H, W)}")
+    if R.shape(filled) != (H, W):
+        raise ValueError(f"{who}: filled {R.shape(filled)} differs from the dem {(H, W)}")
     if isinstance(order, bool) or order not in ORDERS:
         raise ValueError(f"{who}: order {order!r} must be one of {ORDERS}")
     return H, W
@@ -53,17 +52,14 @@ def correct_seams(dem, filled, mask=None, *, nodata=None, order=1, tol=None, max
     from .fill_voids import fill_voids
     check_seam_args(dem, filled, mask, order, tol, max_cycles)
     check_solver(solver, who="correct_seams")
-    if not torch.cuda.is_available():
-        raise RuntimeError("correct_seams: no HIP device visible; this build has no CPU path")
-    device = torch.device("cuda", torch.cuda.current_device())
-    z = _device_f32(dem, device, "dem", who="correct_seams")
-    g = _device_f32(filled, device, "filled", who="correct_seams")
-    m = None if mask is None else _device_f32(mask, device, "mask", binary=True, who="correct_seams")
-    if nodata is not None and math.isnan(nodata):
-        nodata = None                                           # NaN is never a value: non-finite pixels are holes already
+    device = R.device("correct_seams")
+    z = R.to_f32(dem, device, "dem", "correct_seams")
+    g = R.to_f32(filled, device, "filled", "correct_seams")
+    m = None if mask is None else R.to_f32(mask, device, "mask", "correct_seams", binary=True)
+    nodata = R.nodata_value(nodata)
     delta, counts = O.seam_delta(z, m, nodata, g, order)
     ring, interior, unfilled, bits = counts.cpu().tolist()      # the one sync before the solve
-    info = {"ring": ring, "interior": interior, "unfilled": unfilled, "order": int(order), "max_delta": _bits_f32(bits)}
+    info = {"ring": ring, "interior": interior, "unfilled": unfilled, "order": int(order), "max_delta": R.bits_f32(bits)}
     if ring:
         delta, f = fill_voids(delta, tol=tol, max_cycles=max_cycles, solver=solver)
         info.update(cycles=f["cycles"], change=f["change"], tol=f["tol"], converged=f["converged"])
@@ -96,22 +92,20 @@ def build_parser():
 
 
 def main(argv=None):
-    from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc, write_asc
+    from .asc import asc_nodata, read_asc, read_mask, with_nodata, write_asc
     a = build_parser().parse_args(argv)
-    dem, header = read_asc(a.dem)
+    dem, header = read_asc(a.dem)                  # not read_inputs: the filled raster is read and checked before the mask
     fill, fh = read_asc(a.filled)
     if fill.shape != dem.shape:
         raise ValueError(f"{a.filled} is {fill.shape[0]}x{fill.shape[1]}, the dem {dem.shape[0]}x{dem.shape[1]}")
     fnd = asc_nodata(fh)
     if fnd is not None:
         fill = np.where(fill == np.float32(fnd), np.float32(np.nan), fill)       # unfilled cells stay unfilled
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
+    mask = read_mask(a.mask, dem.shape) if a.mask else None
     nodata = a.nodata if a.nodata is not None else asc_nodata(header)
     out, info = correct_seams(dem, fill, mask, nodata=nodata, order=a.order, tol=a.tol, max_cycles=a.max_cycles,
                               solver=a.solver)
-    if info["unfilled"] and asc_value(header, "NODATA_value") is None:
-        header = header + [("NODATA_value", "-9999")]
-    write_asc(a.out, out.cpu().numpy(), header)
+    write_asc(a.out, out.cpu().numpy(), with_nodata(header) if info["unfilled"] else header)
     print(f"{a.out}: {info['ring']} ring / {info['interior']} interior pixels, max_delta {info['max_delta']:.4g} m, "
           f"{info['cycles']} cycles, converged {info['converged']}")
     if not info["converged"]:

@@ -27,7 +27,7 @@ import logging
 
 import torch
 
-from .inpaint_raster import _read_mask, asc_nodata, asc_value, read_asc
+from .asc import read_inputs
 from .models.discriminator import Discriminator
 from .models.generator import PConvUNet
 from .object_mask import add_spec_args, spec_from_args
@@ -90,15 +90,13 @@ def main(argv=None):
         raise RuntimeError("train_raster: no HIP device visible; this build has no CPU path")
     device = torch.device("cuda", torch.cuda.current_device())
 
-    dem, header = read_asc(a.dem)
-    mask = _read_mask(a.mask, dem.shape) if a.mask else None
-    nodata = a.nodata if a.nodata is not None else asc_nodata(header)
+    dem, _, mask, nodata, cellsize = read_inputs(a)
     common = dict(nodata=nodata, window=a.window, batch_size=a.batch, block=a.block, norm=a.norm, seed=a.seed, device=device)
     if a.remove_objects:
-        common.update(objects=spec_from_args(a), cellsize=float(asc_value(header, "cellsize")))
+        common.update(objects=spec_from_args(a), cellsize=cellsize)
     if a.model_cellsize is not None:
         common.update(model_cellsize=a.model_cellsize, min_coverage=a.min_coverage,
-                      cellsize=float(asc_value(header, "cellsize")))
+                      cellsize=cellsize)
     tr = RasterWindowLoader(dem, mask, split="train", steps_per_epoch=a.steps, **common)
     va = RasterWindowLoader(dem, mask, split="val", steps_per_epoch=a.val_steps or max(1, a.steps // 10), augment=False,
                             **common)
@@ -125,7 +123,7 @@ def main(argv=None):
         import json
 
         from .evaluate_raster import evaluate_raster, summary
-        rep, _ = evaluate_raster(a.out, dem, mask, nodata=nodata, cellsize=float(asc_value(header, "cellsize")), split="test",
+        rep, _ = evaluate_raster(a.out, dem, mask, nodata=nodata, cellsize=cellsize, split="test",
                                  block=eval_block, tile=eval_tile, seed=a.seed, objects=common.get("objects"),
                                  model_cellsize=a.model_cellsize, min_coverage=a.min_coverage)
         if a.eval_json:

@@ -293,7 +293,7 @@ def test_laplace_info_keys_are_unchanged(monkeypatch):
 
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
-    monkeypatch.setattr(FV, "_device_f32", lambda a, *args, **kw: a)
+    monkeypatch.setattr(FV.R, "to_f32", lambda a, *args, **kw: a)
     monkeypatch.setattr(torch, "zeros", lambda *a, **kw: [np.int32(0), np.int32(0)])
     monkeypatch.setattr(torch, "empty", lambda *a, **kw: np.zeros(1, np.int32))
     for name in ("vfill_ws", "vfill_pcg_ws", "vfill_bih_ws", "vfill_pcg_start", "vfill_bih_start", "vfill_cycle", "vfill_pcg_iter",
@@ -332,7 +332,7 @@ def test_cli_parses_method_and_inner():
 
 def test_cli_default_budget_follows_the_method(monkeypatch, tmp_path):
     from mvp_gan.src import fill_voids as FV
-    from mvp_gan.src.inpaint_raster import write_asc
+    from mvp_gan.src.asc import write_asc
     src = str(tmp_path / "in.asc")
     write_asc(src, np.zeros((4, 5), np.float32), [("ncols", "5"), ("nrows", "4"), ("xllcorner", "0"), ("yllcorner", "0"),
                                                   ("cellsize", "1"), ("NODATA_value", "-9999")])

@@ -321,8 +321,8 @@ def test_to_esri_and_streams():
 
 
 def test_cli_parser(tmp_path):
-    from mvp_gan.src.flow_routing import build_parser, parse_args, write_int_asc
-    from mvp_gan.src.inpaint_raster import read_asc
+    from mvp_gan.src.asc import read_asc, write_int_asc
+    from mvp_gan.src.flow_routing import build_parser, parse_args
     base = ["--dem", "in.asc", "--dir-out", "d.asc", "--acc-out", "a.asc"]
     a = parse_args(base)
     assert (a.dem, a.dir_out, a.acc_out, a.mask, a.nodata, a.no_fill, a.esri, a.streams_out, a.min_cells, a.max_sweeps) == \

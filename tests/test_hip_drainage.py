@@ -264,7 +264,7 @@ def test_inputs_numpy_and_tensor(dev):
 
 
 def test_cli(dev, tmp_path):
-    from mvp_gan.src.inpaint_raster import read_asc
+    from mvp_gan.src.asc import read_asc
     from tests.test_hip_terrain_eval import _write_asc
     z, _ = _voids()
     z[np.isnan(z)] = -9999.0

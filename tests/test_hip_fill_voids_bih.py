@@ -192,7 +192,7 @@ def test_evaluate_raster_passes_the_baseline_through(dev):
 
 def test_cli_round_trips_an_asc(dev, tmp_path):
     from mvp_gan.src import fill_voids as FV
-    from mvp_gan.src.inpaint_raster import read_asc, write_asc
+    from mvp_gan.src.asc import read_asc, write_asc
     z, known = BM.case("37x53 disc, cubic")
     holed = np.where(known, z, np.float32(-9999.0))
     header = [("ncols", "53"), ("nrows", "37"), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", "1"),

@@ -275,7 +275,7 @@ def test_evaluate_baseline_reports_the_solver(dev, G):
 
 # ---- CLIs -----------------------------------------------------------------------------------------------------------
 def _write_asc(path, a, c, nodata=None):
-    from mvp_gan.src.inpaint_raster import write_asc
+    from mvp_gan.src.asc import write_asc
     hdr = [("ncols", str(a.shape[1])), ("nrows", str(a.shape[0])), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", str(c))]
     if nodata is not None:
         hdr.append(("NODATA_value", str(nodata)))
@@ -284,7 +284,7 @@ def _write_asc(path, a, c, nodata=None):
 
 def test_clis(dev, G, tmp_path):
     from mvp_gan.src.fill_voids import fill_voids
-    from mvp_gan.src.inpaint_raster import read_asc
+    from mvp_gan.src.asc import read_asc
     H, W, c = 256, 320, 2.0
     z = _terrain(H, W, 11)
     z[64:192, 128:256] = -9999.0                       # an aligned void, wider than a 64-px window

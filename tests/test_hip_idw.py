@@ -390,7 +390,7 @@ def test_interpolate_voids(dev, c, md):
 
 
 def test_cli_round_trip(dev, tmp_path):
-    from mvp_gan.src.inpaint_raster import read_asc
+    from mvp_gan.src.asc import read_asc
     from tests.test_hip_terrain_eval import _write_asc
     H, W, c = 100, 150, 0.5
     z, mask = _dirty_raster(H, W, 33)

@@ -221,7 +221,7 @@ def test_loader_never_samples_objects(dev):
 
 def test_clis(dev, G, tmp_path):
     from mvp_gan.src.inpaint_raster import main as inpaint_main
-    from mvp_gan.src.inpaint_raster import read_asc, write_asc
+    from mvp_gan.src.asc import read_asc, write_asc
     from mvp_gan.src.object_mask import main as om_main
     z, _ = OR.scene(400, 360, 7, buildings=6, trees=10)
     z[5, 5] = -9999.0

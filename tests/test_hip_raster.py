@@ -1,6 +1,8 @@
 """GPU checks of whole-raster inpainting (csrc/raster.hip, mvp_gan/src/inpaint_raster.py) against the numpy oracle in
 tests/raster_oracle.py: stats and gather bit for bit, blend against float64, end to end against inpaint_batch, the
 known-pixel and unfilled-hole rules, shift invariance, determinism, batch size and the CLI."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -199,7 +201,8 @@ def test_determinism_and_batch_size(dev, G):
 
 
 def test_cli_asc_in_asc_out(dev, G, tmp_path):
-    from mvp_gan.src.inpaint_raster import main, read_asc, write_asc
+    from mvp_gan.src.asc import read_asc, write_asc
+    from mvp_gan.src.inpaint_raster import main
     H, W = 120, 100
     z = RO.terrain(H, W, 71)
     z[RO.disc_holes(H, W, 0.2, 72, 3, 8)] = -9999.0
@@ -222,3 +225,50 @@ def test_cli_asc_in_asc_out(dev, G, tmp_path):
     with pytest.raises(ValueError, match="no resizing"):
         main(["--dem", str(tmp_path / "in.asc"), "--mask", str(tmp_path / "m.png"), "--checkpoint", str(tmp_path / "g.pth"),
               "--out", str(tmp_path / "o2.asc")])
+
+
+def test_shared_upload(dev):
+    """mvp_gan/src/raster_args.py: the upload every raster tool opens with, on a 5x7 raster with one NaN pixel, one nodata
+    pixel and one masked pixel."""
+    from mvp_gan.src import raster_args as R
+    from tg_hip import ops as O
+    z = (np.arange(35, dtype=np.float32).reshape(5, 7) * np.float32(1.1) - 7).astype(np.float32)
+    z[0, 0] = -0.0
+    z[1, 2] = np.nan
+    z[3, 4] = -9999.0
+    mask = np.ones((5, 7), np.uint8)
+    mask[2, 5] = 0
+    mask[4, 1] = 7                                              # any nonzero value is 1
+    bits = lambda t: t.view(torch.int32)
+    za, ma, nd, d = R.upload(z, mask, -9999, "test")
+    assert d == torch.device("cuda", torch.cuda.current_device()) and nd == -9999.0 and type(nd) is float
+    assert za.dtype == ma.dtype == torch.float32 and za.is_contiguous() and ma.is_contiguous() and za.device == ma.device == d
+    np.testing.assert_array_equal(_bits(za.cpu().numpy()), _bits(z))
+    np.testing.assert_array_equal(ma.cpu().numpy(), (mask != 0).astype(np.float32))
+    wide = torch.zeros(5, 14, dtype=torch.float32, device=dev)
+    wide[:, ::2] = torch.from_numpy(z).to(dev)
+    view = wide[:, ::2]                                         # the same dem as a non-contiguous HIP tensor view
+    assert not view.is_contiguous()
+    zb, mb, ndb, _ = R.upload(view, torch.from_numpy(mask).to(dev), math.nan, "test")
+    assert ndb is None and zb.is_contiguous() and torch.equal(bits(zb), bits(za)) and torch.equal(bits(mb), bits(ma))
+    for other in (mask != 0, mask.astype(np.float32), torch.from_numpy(mask != 0).to(dev),
+                  torch.from_numpy((mask != 0).astype(np.float32)).to(dev)):
+        assert torch.equal(bits(R.upload(z, other, None, "test")[1]), bits(ma))        # uint8, bool and float32 masks agree
+    assert R.upload(z, None, None, "test")[1] is None
+    zk, known = R.upload_known(z, mask, -9999, "test")
+    want, _ = O.objmask_known(za, ma, -9999.0, transposed=False)
+    assert known.dtype == torch.uint8 and torch.equal(known, want) and torch.equal(bits(zk), bits(za))
+    k = np.ones((5, 7), np.uint8)
+    k[1, 2] = k[3, 4] = k[2, 5] = 0
+    np.testing.assert_array_equal(known.cpu().numpy(), k)
+    # a uint8 map on the device is read where it lies (evaluate_raster's holes); anything else is converted
+    h = torch.from_numpy(mask).to(dev)
+    assert R.to_u8(h, dev, "holes", "test", nonzero=True, reuse=True).data_ptr() == h.data_ptr()
+    fresh = R.to_u8(h, dev, "holes", "test", nonzero=True)
+    assert fresh.data_ptr() != h.data_ptr() and fresh.cpu().tolist() == (mask != 0).astype(np.uint8).tolist()
+    strided = torch.zeros(5, 14, dtype=torch.uint8, device=dev)[:, ::2]
+    assert R.to_u8(strided, dev, "holes", "test", nonzero=True, reuse=True).is_contiguous()
+    moved = R.to_u8(torch.from_numpy(mask), dev, "holes", "test", nonzero=True, reuse=True)     # a CPU tensor: moved, not refused
+    assert moved.device == d and torch.equal(moved, fresh)
+    with pytest.raises(ValueError, match="^test: dem is on cpu; pass a numpy array or a HIP tensor$"):
+        R.upload(torch.from_numpy(z), None, None, "test")

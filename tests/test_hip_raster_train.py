@@ -220,7 +220,7 @@ def test_train_end_to_end_from_raster(dev, tmp_path):
 
 
 def test_cli_end_to_end(dev, tmp_path):
-    from mvp_gan.src.inpaint_raster import write_asc
+    from mvp_gan.src.asc import write_asc
     z = RO.terrain(330, 330, 8)
     z[10, 10] = -9999
     hdr = [("ncols", "330"), ("nrows", "330"), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", "1"),

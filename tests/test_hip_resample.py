@@ -434,7 +434,7 @@ def test_evaluate_and_loader_pass_min_coverage_on(dev, G):
 
 # ---- CLIs -----------------------------------------------------------------------------------------------------------
 def _write_asc(path, a, c, nodata=None):
-    from mvp_gan.src.inpaint_raster import write_asc
+    from mvp_gan.src.asc import write_asc
     hdr = [("ncols", str(a.shape[1])), ("nrows", str(a.shape[0])), ("xllcorner", "1000"), ("yllcorner", "2000"),
            ("cellsize", str(c))]
     if nodata is not None:
@@ -443,7 +443,8 @@ def _write_asc(path, a, c, nodata=None):
 
 
 def test_clis(dev, G, tmp_path):
-    from mvp_gan.src.inpaint_raster import asc_value, inpaint_raster, read_asc
+    from mvp_gan.src.asc import asc_value, read_asc
+    from mvp_gan.src.inpaint_raster import inpaint_raster
     from mvp_gan.src.resample import resample_raster
     H, W, c = 203, 317, 0.3
     z = RO.terrain(H, W, 46)

@@ -385,7 +385,7 @@ def test_evaluate_seam(dev, G):
 
 # ---- CLIs -----------------------------------------------------------------------------------------------------------
 def _write_asc(path, a, c, nodata=None):
-    from mvp_gan.src.inpaint_raster import write_asc
+    from mvp_gan.src.asc import write_asc
     hdr = [("ncols", str(a.shape[1])), ("nrows", str(a.shape[0])), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", str(c))]
     if nodata is not None:
         hdr.append(("NODATA_value", str(nodata)))
@@ -393,7 +393,7 @@ def _write_asc(path, a, c, nodata=None):
 
 
 def test_clis(dev, G, tmp_path):
-    from mvp_gan.src.inpaint_raster import read_asc
+    from mvp_gan.src.asc import read_asc
     from mvp_gan.src.seam_correct import correct_seams
     H, W, c = 300, 420, 2.0
     z = RO.terrain(H, W, 23)

@@ -552,7 +552,7 @@ def test_evaluate_raster_flood(dev):
 
 # ---- CLI ---------------------------------------------------------------------------------------------------------------------
 def test_cli(dev, tmp_path):
-    from mvp_gan.src.inpaint_raster import read_asc
+    from mvp_gan.src.asc import read_asc
     from tests.test_hip_terrain_eval import _write_asc
     z, _ = _voids()
     z[np.isnan(z)] = -9999.0

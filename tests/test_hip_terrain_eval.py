@@ -241,7 +241,7 @@ def test_evaluate_raster_end_to_end(dev, G):
 
 
 def _write_asc(path, a, c, nodata=None):
-    from mvp_gan.src.inpaint_raster import write_asc
+    from mvp_gan.src.asc import write_asc
     hdr = [("ncols", str(a.shape[1])), ("nrows", str(a.shape[0])), ("xllcorner", "0"), ("yllcorner", "0"), ("cellsize", str(c))]
     if nodata is not None:
         hdr.append(("NODATA_value", str(nodata)))

@@ -71,7 +71,7 @@ def test_ramp_positive_and_border_rule(w, ov):
 
 @pytest.mark.parametrize("nodata", [None, "-9999"])
 def test_asc_round_trip(tmp_path, nodata):
-    from mvp_gan.src.inpaint_raster import asc_nodata, read_asc, write_asc
+    from mvp_gan.src.asc import asc_nodata, read_asc, write_asc
     rng = np.random.default_rng(0)
     z = (rng.normal(0, 1, (7, 11)) * 300 + 1234.5).astype(np.float32)
     z[3, 4] = np.float32(1e-30)
@@ -100,7 +100,7 @@ def test_asc_round_trip(tmp_path, nodata):
 
 
 def test_asc_corner_header_five_lines(tmp_path):
-    from mvp_gan.src.inpaint_raster import read_asc, write_asc
+    from mvp_gan.src.asc import read_asc, write_asc
     (tmp_path / "a.asc").write_text("NCOLS 3\nNROWS 2\nXLLCORNER 10\nYLLCORNER 20\nCELLSIZE 1\n1 2 3\n4 5 6.5\n")
     a, hdr = read_asc(tmp_path / "a.asc")
     np.testing.assert_array_equal(a, np.array([[1, 2, 3], [4, 5, 6.5]], np.float32))

@@ -371,7 +371,7 @@ def test_c_abi_validates_before_any_launch():
 
 # ---- .asc header ----------------------------------------------------------------------------------------------------
 def test_resampled_header():
-    from mvp_gan.src.inpaint_raster import asc_value
+    from mvp_gan.src.asc import asc_value
     from mvp_gan.src.resample import resample_plan, resampled_header
     hdr = [("ncols", "317"), ("nrows", "203"), ("xllcorner", "500000.5"), ("yllcorner", "4100000"), ("cellsize", "0.3"),
            ("NODATA_value", "-9999")]
