@@ -64,11 +64,12 @@ def hip_adam_step(optimizer, grad_scale=1.0, buckets=None):
         optimizer.step()
         return
     hyper = {}
-    for group in optimizer.param_groups:
+    for gi, group in enumerate(optimizer.param_groups):
         if group.get("weight_decay", 0) != 0 or group.get("amsgrad", False) or group.get("maximize", False):
             raise NotImplementedError("hip_adam_step supports torch.optim.Adam defaults (no weight decay / amsgrad / maximize)")
         for p in group["params"]:
-            hyper[p] = (float(group["lr"]), group["betas"][0], group["betas"][1], float(group["eps"]))
+            # (gi: one launch per param_group, so that a captured launch can read its group's live learning rate)
+            hyper[p] = (float(group["lr"]), group["betas"][0], group["betas"][1], float(group["eps"]), gi)
 
     layout_ok = optimizer.__dict__.setdefault("_tg_layout_ok", set())     # (p, m, v) triples already checked
 
@@ -100,9 +101,10 @@ def hip_adam_step(optimizer, grad_scale=1.0, buckets=None):
                 layout_ok.add((p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()))
             st["step"] += 1
             groups.setdefault(hyper[p] + (int(st["step"]),), []).append((p, st))
-        for (lr, b1, b2, eps, step), items in groups.items():
+        for (lr, b1, b2, eps, gi, step), items in groups.items():
             O.adam_multi_([p.data for p, _ in items], [p.grad for p, _ in items], [st["exp_avg"] for _, st in items],
-                          [st["exp_avg_sq"] for _, st in items], lr, b1, b2, eps, step, grad_scale)
+                          [st["exp_avg_sq"] for _, st in items], lr, b1, b2, eps, step, grad_scale,
+                          owner=(optimizer, gi, [p for p, _ in items]))
 
     if buckets is None:
         _update(list(hyper))

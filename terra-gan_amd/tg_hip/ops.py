@@ -118,14 +118,26 @@ _wprep = {}                   # (weight ptr, mode, geometry) -> [weakref(weight)
                               #                                   batch descriptor (bytes) or False, used since the last batch]
 _wstamp = {}                  # weight ptr -> number of out-of-band updates (kernels writing through raw pointers)
 _wprep_tables = {}            # (device, concatenated descriptor bytes) -> device array of those descriptors
-wprep_capture_log = None      # tg_hip.graph, while a step is captured: the keys whose batched preparation the graph replays
+WPREP_TABLES_MAX = 16         # ... of which the most recently used stay
+wprep_capture = None          # tg_hip.graph, while a step is captured: the WprepCapture of that graph
+
+
+class WprepCapture:
+    """What a captured step does with the prepared-weight cache.  `keys`: the entries whose batched preparation the graph
+    replays (after its Adam).  `hits`: the batchable entries its convolutions read WITHOUT preparing them first -- the graph
+    takes those buffers as the previous replay left them.  `refs`: the device tables the captured launches read."""
+
+    def __init__(self):
+        self.keys, self.hits, self.refs = [], [], []
 
 
 def weights_updated(params):
     """REQUIRED after any parameter write torch's version counter does not see -- kernels writing through raw pointers
     (hip_adam_step does it itself), `.data` writes, custom broadcasts, user-side EMA / clamping through `.data`: the
     prepared-weight cache keeps its own stamp per storage and would otherwise keep convolving with stale transforms.
-    TG_WPREP_VERIFY=1 (debug) re-prepares on every use and raises when a cached buffer was stale."""
+    TG_WPREP_VERIFY=1 (debug) re-prepares on every use and raises when a cached buffer was stale.
+    A GraphedTrainStep honours the same protocol: before each replay it compares the stamps of the prepared buffers its
+    graph reads with their weights' and re-prepares the stale ones (prepared_stale / prepare_keys)."""
     ptrs = set()
     for p in params:
         if p.dim() == 4:
@@ -143,25 +155,51 @@ def _prepare_batch(ptrs):
     for key, e in _wprep.items():
         if key[0] in ptrs and e[3] and e[4] and e[0]() is not None:
             ents.append((key, e))
+    _run_batch(ents)
+
+
+def prepared_stale(keys):
+    """Those of `keys` whose live entry does not carry its weight's current stamp: the weight was written (in place through
+    torch, or out of band + weights_updated) or the buffer was re-prepared for an earlier value since the entry was stamped.
+    Host-side comparisons only."""
+    stale = []
+    for key in keys:
+        e = _wprep.get(key)
+        w = e[0]() if e is not None else None
+        if w is not None and e[1] != (w._version, _wstamp.get(key[0], 0)):
+            stale.append(key)
+    return stale
+
+
+def prepare_keys(keys):
+    """Re-prepare the batchable entries `keys` into their existing buffers by one launch on the current stream, whether or
+    not they were used since the last batch (tg_hip.graph: a replay's forward reads them without going through _prepared)."""
+    _run_batch([(key, _wprep[key]) for key in keys])
+
+
+def _run_batch(ents):
     if not ents:
         return
     # keyed by the descriptors themselves (they hold the w / out pointers, mode and geometry): an id()-based key could be
     # recycled by CPython for a replaced entry and hit a stale table whose `out` points at a freed prepared buffer
     raw = b"".join(e[3] for _, e in ents)
     tkey = (ents[0][1][2].device, raw)
-    table = _wprep_tables.get(tkey)
+    table = _wprep_tables.pop(tkey, None)
     if table is None:
         import numpy as np
         table = torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(ents[0][1][2].device)
-        if len(_wprep_tables) > 16:
-            _wprep_tables.clear()
-        _wprep_tables[tkey] = table
+        # the least recently used ones go, one at a time: emptying the cache here dropped the table the generator's step had made
+        # a moment ago, and the capture that followed the warm-up step cannot build one (a host-to-device copy)
+        while len(_wprep_tables) >= WPREP_TABLES_MAX:
+            del _wprep_tables[next(iter(_wprep_tables))]
+    _wprep_tables[tkey] = table                   # (re-inserted on a hit: the dict's order is the order of last use)
     L.check(_lib().tg_conv_wprep_run(C.c_void_p(table.data_ptr()), len(ents), _stream()), "tg_conv_wprep_run")
     for key, e in ents:
         e[1] = (e[0]()._version, _wstamp.get(key[0], 0))
         e[4] = False
-    if wprep_capture_log is not None:
-        wprep_capture_log.extend(key for key, _e in ents)
+    if wprep_capture is not None:
+        wprep_capture.keys.extend(key for key, _e in ents)
+        wprep_capture.refs.append(table)          # (_wprep_tables may be cleared while the graph still reads this one)
 
 
 def graph_replayed(weight_ptrs, refreshed_keys):
@@ -190,8 +228,12 @@ def _prepared(w, wv, g, mode):
     ent = _wprep.get(key)
     if ent is not None and ent[0]() is w and ent[1] == stamp:
         ent[4] = True
+        if wprep_capture is not None and ent[3]:
+            wprep_capture.hits.append(key)
         if WPREP_VERIFY and ent[2] is not None:
-            fresh = torch.empty_like(ent[2])
+            # (a copy, not an empty buffer: a dgrad buffer has room for the larger of the transposed and the transformed weights
+            # and the preparation writes one of them -- the rest is never written and must not take part in the comparison)
+            fresh = ent[2].clone()
             L.check(_lib().tg_conv_wprep(C.byref(g), mode, _p(wv), _p(fresh), _stream()), "tg_conv_wprep")
             if not torch.equal(fresh.view(torch.int32), ent[2].view(torch.int32)):
                 raise L.TgError("prepared weights are stale: a parameter was rewritten without tg_hip.ops.weights_updated()")
@@ -2019,28 +2061,62 @@ _adam_tables = {}
 adam_scalar_arena = None      # set by tg_hip.graph while a train step is captured / replayed: see AdamScalarArena
 
 
+class AdamLaunch:
+    """What one captured adam_multi_ launch has baked in beside its slot's (lr, beta1, beta2, step): eps and grad_scale (kernel
+    arguments), the pointers in its device table (which it keeps alive: _adam_tables may be cleared) and its owner -- None, or
+    (torch optimiser, index of the param_group, its Parameters in the launch's order), through which the live values are read."""
+
+    def __init__(self, lr, eps, grad_scale, params, ms, vs, owner, refs):
+        self.lr, self.eps, self.grad_scale = lr, eps, grad_scale
+        self.ptrs = [t.data_ptr() for pmv in zip(params, ms, vs) for t in pmv]
+        self.owner, self.refs = owner, refs
+
+    def live_lr(self):
+        if self.owner is None:
+            return self.lr
+        return float(self.owner[0].param_groups[self.owner[1]]["lr"])
+
+    def live_ptrs(self):
+        """Parameter and moment pointers as hip_adam_step would find them now (None: a state entry is gone)."""
+        if self.owner is None:
+            return self.ptrs
+        state, out = self.owner[0].state, []
+        for p in self.owner[2]:
+            st = state.get(p)
+            if not st:
+                return None
+            out += (p.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr())
+        return out
+
+
 class AdamScalarArena:
     """Per-step Adam scalars in device memory (tg_adam_multi_s) for hipGraph replay.  While `active` (during capture),
-    every adam_multi_ call takes the next slot and remembers (lr, betas, step).  `refresh(k)` recomputes every slot for `k`
-    steps later on the host (tg_adam_scalars: the very two floats the eager launch would have been given) and writes them
-    to the device through kernel arguments (tg_write_floats, <= 8 slots per launch) on the current stream."""
+    every adam_multi_ call takes the next slot and remembers (lr, betas, step) and its AdamLaunch.  `refresh(k)` recomputes
+    every slot for `k` steps later on the host (tg_adam_scalars: the very two floats the eager launch would have been given)
+    and writes them to the device through kernel arguments (tg_write_floats, <= 8 slots per launch) on the current stream.
+    The learning rate is read from the slot's live param_group at every refresh; the betas, eps and grad_scale are kernel
+    arguments of the captured launch and the pointers sit in its device table: `launches` keeps them for the owner of the
+    graph to hold against the live optimiser (tg_hip.graph)."""
 
     def __init__(self, device, nslots=8):
         import numpy as np
         self.dev = torch.zeros(nslots, 2, dtype=torch.float32, device=device)
         self.host = np.zeros((nslots, 2), dtype=np.float32)
-        self.slots, self.active = [], False
+        self.slots, self.launches, self.active = [], [], False
 
-    def take(self, lr, beta1, beta2, step):
+    def take(self, lr, beta1, beta2, step, launch=None):
         i = len(self.slots)
         if i >= self.dev.shape[0]:
             raise L.TgError("AdamScalarArena: more optimiser launches per step than slots")
         self.slots.append((lr, beta1, beta2, int(step)))
+        self.launches.append(launch)
         return self.dev[i]
 
     def refresh(self, k):
         lib = _lib()
-        for i, (lr, b1, b2, step) in enumerate(self.slots):
+        for i, ((lr, b1, b2, step), launch) in enumerate(zip(self.slots, self.launches)):
+            if launch is not None:
+                lr = launch.live_lr()
             L.check(lib.tg_adam_scalars(lr, b1, b2, step + k, C.c_void_p(self.host[i].ctypes.data)), "tg_adam_scalars")
         n = 2 * len(self.slots)
         if n:
@@ -2054,9 +2130,10 @@ def adam_table_key(params, grads, ms, vs):
     return (tuple(t.data_ptr() for ts in (params, grads, ms, vs) for t in ts), tuple(p.numel() for p in params))
 
 
-def adam_multi_(params, grads, ms, vs, lr, beta1, beta2, eps, step, grad_scale=1.0):
+def adam_multi_(params, grads, ms, vs, lr, beta1, beta2, eps, step, grad_scale=1.0, owner=None):
     """One-launch Adam over many tensors.  The (p, g, m, v, n) table and the work list live on the device and are
-    rebuilt only when a pointer changes (persistent gradient buffers keep them stable step after step)."""
+    rebuilt only when a pointer changes (persistent gradient buffers keep them stable step after step).
+    owner: see AdamLaunch (used while a step is captured only)."""
     import numpy as np
     key = adam_table_key(params, grads, ms, vs)
     ent = _adam_tables.get(key)
@@ -2079,7 +2156,7 @@ def adam_multi_(params, grads, ms, vs, lr, beta1, beta2, eps, step, grad_scale=1
         _adam_tables[key] = ent
     segs, work, nwork = ent
     if adam_scalar_arena is not None and adam_scalar_arena.active:
-        scal = adam_scalar_arena.take(lr, beta1, beta2, step)
+        scal = adam_scalar_arena.take(lr, beta1, beta2, step, AdamLaunch(lr, eps, grad_scale, params, ms, vs, owner, (segs, work)))
         L.check(_lib().tg_adam_multi_s(C.c_void_p(segs.data_ptr()), C.c_void_p(work.data_ptr()), nwork, ADAM_CHUNK, beta1, beta2,
                                        eps, _p(scal), grad_scale, _stream()), "tg_adam_multi_s")
     else:
