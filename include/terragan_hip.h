@@ -979,6 +979,24 @@ int tg_wetness(const float* acc, const float* slope, const uint8_t* known, int H
 int tg_wetness_compare(const uint8_t* sel, const float* twi_t, const float* twi_p, int H, int W, int64_t* counts, double* sums,
                        void* ws, size_t ws_bytes, tg_stream_t stream);
 
+/* ---- Second-difference spectrum of a fill against the truth (csrc/texture.hip) ----------------------------------
+ * z (truth) and p (the fill) fp32 [H][W]; sel uint8 [H][W], nonzero = scored; known uint8 [H][W], nonzero = known in both surfaces.
+ * Octave j = 0 .. octaves - 1 (octaves in 1 .. TG_TEX_OCTAVES) has the lag h = 2^j px; class 0 (axial) has the unit steps
+ * u = (dy, dx) in {(0, 1), (1, 0)}, class 1 (diagonal) {(1, 1), (1, -1)}; scale s = 2 j + class.  A triple (centre x, step u of
+ * the class) counts when sel[x] and known[x] are nonzero and both arms x - h u and x + h u lie inside the raster and are known;
+ * the arms may lie outside sel.  Per triple, in fp64 from the fp32 values and nothing fused:
+ * d_s = (s(x - h u) + s(x + h u)) - 2 s(x) for s in {z, p}.  counts [TG_TEX_SCALES] int64 (zeroed here) = the triples per scale,
+ * exact (integer atomics); sums [TG_TEX_SCALES][TG_TEX_NSUM] double = the sums of d_z d_z, d_p d_p and d_z d_p per scale in a
+ * fixed order (per-workgroup rows of partials in ws, then one workgroup adds the rows in index order: two calls agree bitwise).
+ * The entries of octaves that were not requested come back zero.  p may alias z (the spectrum of one surface); neither is written.
+ * ws >= tg_texture_ws_bytes(H, W), 8-byte aligned, contents arbitrary; 0 for sides out of range. */
+#define TG_TEX_OCTAVES 5
+#define TG_TEX_SCALES 10
+#define TG_TEX_NSUM 3
+size_t tg_texture_ws_bytes(int H, int W);
+int tg_texture_compare(const float* z, const float* p, const uint8_t* sel, const uint8_t* known, int H, int W, int octaves,
+                       int64_t* counts, double* sums, void* ws, size_t ws_bytes, tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

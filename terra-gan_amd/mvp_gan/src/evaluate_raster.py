@@ -62,12 +62,19 @@ and Horn's slope, and report["wetness"] holds the bias, MAE, RMSE and largest di
 report["baseline"] and every report["compare"][name] gain the same key.  Without it the report has no "wetness" key and nothing
 more runs.
 
+With texture=True the report also says whether a fill has the relief of the terrain at each scale (texture_errors; DESIGN.md
+section 8ad): the second differences of the fill and of the truth over the same triples of pixels centred in the holes, at the lags
+1, 2, .. 2^(texture_octaves - 1) px along the axes and along the diagonals, and report["texture"] holds per scale the RMS of both,
+their ratio and their correlation; report["baseline"] and every report["compare"][name] gain the same key.  Without it the report
+has no "texture" key and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
          [--flood [--flood-stages s ...]] [--wetness [--exponent e] [--min-slope s]]
+         [--texture [--octaves n]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -405,10 +412,11 @@ def _check_fill_options(baseline, fallback, who="evaluate_raster"):
 def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, method="laplace", area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, solver="mg", depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
                     stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-                    wetness_min_slope=1e-3):
+                    wetness_min_slope=1e-3, texture=False, texture_octaves=5):
     """The baseline fill of the keep mask (fill_voids) scored on the holes: terrain_errors' report plus "method" and the
     fill info under "fill"; with sinks also sink_errors' dict under "sinks", with drainage drainage_errors' under "drainage",
-    with flood flood_errors' under "flood", with wetness wetness_errors' under "wetness"."""
+    with flood flood_errors' under "flood", with wetness wetness_errors' under "wetness", with texture texture_errors' under
+    "texture"."""
     from .fill_voids import fill_voids
     device = R.device(WHO)
     z = R.to_f32(dem, device, "dem", WHO)
@@ -429,6 +437,8 @@ def baseline_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, metho
     if wetness:
         rep["wetness"] = wetness_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=wetness_exponent,
                                         min_slope=wetness_min_slope)
+    if texture:
+        rep["texture"] = texture_errors(z, bpred, holes, cellsize=cellsize, mask=mask, nodata=nodata, octaves=texture_octaves)
     return rep
 
 
@@ -450,10 +460,11 @@ def _check_compare(compare, who="evaluate_raster"):
     return names
 
 
-def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None, wetness=None):
+def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None, wetness=None, texture=None):
     """{name: report + "method" + "fill"} from the terrain_errors reports and the interpolate_voids infos by name; with sinks
     ({name: sink_errors' dict}) also "sinks", with drainage ({name: drainage_errors' dict}) also "drainage", with flood ({name:
-    flood_errors' dict}) also "flood", with wetness ({name: wetness_errors' dict}) also "wetness"."""
+    flood_errors' dict}) also "flood", with wetness ({name: wetness_errors' dict}) also "wetness", with texture ({name: texture_errors'
+    dict}) also "texture"."""
     out = {}
     for name, rep in reports.items():
         out[name] = dict(rep)
@@ -467,6 +478,8 @@ def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None, wetn
             out[name]["flood"] = flood[name]
         if wetness is not None:
             out[name]["wetness"] = wetness[name]
+        if texture is not None:
+            out[name]["texture"] = texture[name]
     return out
 
 
@@ -474,13 +487,13 @@ def assemble_compare(reports, infos, sinks=None, drainage=None, flood=None, wetn
 def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None, area_edges_m2=AREA_EDGES_M2,
                    quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
                    stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-                   wetness_min_slope=1e-3):
+                   wetness_min_slope=1e-3, texture=False, texture_octaves=5):
     """The interpolate_voids fills `names` of the keep mask, each scored on the holes like baseline_report's fill."""
     from .interpolate import interpolate_voids
     device = R.device(WHO)
     z = R.to_f32(dem, device, "dem", WHO)
     k = R.to_f32(keep, device, "keep", WHO, binary=True)
-    reports, infos, snk, drn, fld, wet = {}, {}, {}, {}, {}, {}
+    reports, infos, snk, drn, fld, wet, tex = {}, {}, {}, {}, {}, {}, {}
     for name in _check_compare(names):
         pred, infos[name] = interpolate_voids(z, k, nodata=R.nodata_value(nodata), method=name, cellsize=cellsize)
         reports[name] = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata,
@@ -496,11 +509,13 @@ def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None,
         if wetness:
             wet[name] = wetness_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=wetness_exponent,
                                        min_slope=wetness_min_slope)
+        if texture:
+            tex[name] = texture_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, octaves=texture_octaves)
     return assemble_compare(reports, infos, snk if sinks else None, drn if drainage else None, fld if flood else None,
-                            wet if wetness else None)
+                            wet if wetness else None, tex if texture else None)
 
 
-# ---- a fill against the truth: what sink_errors, drainage_raw, flood_raw and wetness_raw open with ----------------------------
+# ---- a fill against the truth: what sink_errors, drainage_raw, flood_raw, wetness_raw and texture_raw open with -----------
 def _fill_shapes(dem, pred, holes, mask, cellsize, who):
     """Host-side rejection before any launch; -> (cellsize, (H, W))."""
     c = R.cellsize(cellsize, who)
@@ -801,12 +816,95 @@ def wetness_summary(d):
             f"{f(d['max'], '.4g')} over {d['cells']} px")
 
 
+# ---- texture: does a fill have the relief of the terrain at each scale ------------------------------------------------------
+TEX_OCTAVES = 5                       # TG_TEX_OCTAVES: lags 1, 2, 4, 8, 16 px
+TEX_CLASSES = ("axial", "diagonal")   # scale index = 2 * octave + class
+
+
+def check_octaves(octaves, who="texture_errors"):
+    """An integer in 1..TEX_OCTAVES (numpy's integers too, no bool, no float) -> a plain int."""
+    import numbers
+    if isinstance(octaves, (bool, np.bool_)) or not isinstance(octaves, numbers.Integral) or not 1 <= octaves <= TEX_OCTAVES:
+        raise ValueError(f"{who}: octaves {octaves!r} must be an integer in [1, {TEX_OCTAVES}]")
+    return int(octaves)
+
+
+def texture_scales(octaves, cellsize):
+    """[(lag_px, class name, lag_m)] in scale-index order: ascending lag."""
+    return [(1 << j, name, (1 << j) * cellsize * (math.sqrt(2.0) if k else 1.0))
+            for j in range(octaves) for k, name in enumerate(TEX_CLASSES)]
+
+
+def assemble_texture(counts, sums, *, cellsize, octaves):
+    """The texture dict from tg_texture_compare's numbers (counts [10]: triples per scale; sums [10][3]: of d_z d_z, d_p d_p,
+    d_z d_p) (pure: no GPU): per scale of the requested octaves the lag, the triples, the RMS second difference of the truth and
+    of the fill, their ratio fill / truth and their correlation; log_ratio_rms = sqrt(mean(ln(ratio)^2)) over the scales_scored
+    scales where both RMS are > 0.  None stands for a value that is not defined."""
+    octaves = check_octaves(octaves, "assemble_texture")
+    c = R.cellsize(cellsize, "assemble_texture")
+    scales, logs = [], []
+    for s, (h, name, lag_m) in enumerate(texture_scales(octaves, c)):
+        n = int(counts[s])
+        szz, spp, szp = (float(v) for v in sums[s])
+        t_rms = math.sqrt(szz / n) if n else None
+        f_rms = math.sqrt(spp / n) if n else None
+        ratio = f_rms / t_rms if n and szz != 0 and t_rms > 0 else None      # t_rms == 0 with szz != 0: szz / n underflowed
+        den = szz * spp
+        corr = szp / math.sqrt(den) if n and den != 0 else None
+        scales.append({"lag_px": h, "class": name, "lag_m": lag_m, "triples": n, "truth_rms": t_rms, "fill_rms": f_rms,
+                       "ratio": ratio, "corr": corr})
+        if n and t_rms > 0 and f_rms > 0:
+            logs.append(math.log(ratio))
+    return {"octaves": octaves, "scales": scales, "scales_scored": len(logs),
+            "log_ratio_rms": math.sqrt(sum(v * v for v in logs) / len(logs)) if logs else None}
+
+
+@torch.no_grad()
+def texture_raw(dem, pred, holes, *, cellsize, mask=None, nodata=None, octaves=5):
+    """texture_errors' measurement -> (counts [10], sums [10][3] as lists)."""
+    from tg_hip import ops as O
+    who = "texture_errors"
+    _fill_shapes(dem, pred, holes, mask, cellsize, who)
+    octaves = check_octaves(octaves, who)
+    z, p, sel, known = _fill_upload(dem, pred, holes, mask, nodata)
+    counts, sums = O.texture_compare(z, p, sel, known, octaves)
+    return counts.cpu().tolist(), sums.cpu().tolist()
+
+
+def texture_errors(dem, pred, holes, *, cellsize, mask=None, nodata=None, octaves=5):
+    """Does a fill have the relief of the terrain at each scale.  Over the triples (centre in holes (nonzero = hole), two arms
+    at the lag h = 1, 2, .. 2^(octaves - 1) px along the axes or along the diagonals, all three pixels known in both surfaces; the
+    arms may lie outside the holes, where pred is the dem, so the seam is measured too) the second differences
+    (s(x - hu) + s(x + hu)) - 2 s(x) of dem and pred are taken in float64 and their squares and product summed in a fixed order.
+    -> {"octaves", "scales": [{"lag_px", "class", "lag_m", "triples", "truth_rms", "fill_rms", "ratio", "corr"}], "scales_scored",
+    "log_ratio_rms"} (assemble_texture)."""
+    c = R.cellsize(cellsize, "texture_errors")
+    counts, sums = texture_raw(dem, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, octaves=octaves)
+    return assemble_texture(counts, sums, cellsize=c, octaves=octaves)
+
+
+def texture_summary(d):
+    """One line for a texture dict: ratio and correlation at the shortest and at the longest scored scale, and log_ratio_rms."""
+    f = lambda v, spec: "n/a" if v is None else format(v, spec)
+    scored = [s for s in d["scales"] if s["truth_rms"] and s["fill_rms"]]
+    ends = [scored[0], scored[-1]] if scored else [None, None]
+    parts = []
+    for s in ends:
+        if s is None:
+            parts.append("n/a")
+        else:
+            parts.append(f"{s['lag_px']} px {s['class']} ratio {f(s['ratio'], '.3f')} corr {f(s['corr'], '.3f')}")
+    return (f"texture: second differences fill / truth, {parts[0]}; {parts[1]}; log-ratio RMS {f(d['log_ratio_rms'], '.3f')} over "
+            f"{d['scales_scored']} of {len(d['scales'])} scales")
+
+
 @torch.no_grad()
 def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cellsize, split="test", block=1024, tile=256,
                     holes=HoleSpec(), seed=0, window=512, overlap=64, batch=16, objects=None, area_edges_m2=AREA_EDGES_M2,
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
                     solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
-                    flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3):
+                    flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3,
+                    texture=False, texture_octaves=5):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -819,14 +917,16 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     same three places; flood=True adds flood_errors' dict (HAND against streams of stream_cells cells, flood extents at
     flood_stages_m) under "flood" to the same three places; wetness=True adds wetness_errors' dict (the TWI from the
     multiple-flow-direction accumulation at wetness_exponent, slopes not below wetness_min_slope) under "wetness" to the same
-    three places."""
+    three places; texture=True adds texture_errors' dict (second differences at texture_octaves octaves of lags) under "texture" to
+    the same three places."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
                              seam=seam, model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver,
                              depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
                              stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m,
-                             wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope)
+                             wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope,
+                             texture=texture, texture_octaves=texture_octaves)
     return rep, pred
 
 
@@ -834,7 +934,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
               stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-              wetness_min_slope=1e-3):
+              wetness_min_slope=1e-3, texture=False, texture_octaves=5):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
@@ -859,6 +959,8 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         from .flow_routing import check_exponent, check_min_slope
         check_exponent(wetness_exponent, "evaluate_raster")
         check_min_slope(wetness_min_slope, "evaluate_raster")
+    if texture:
+        check_octaves(texture_octaves, "evaluate_raster")
     check_plan(H, W, split, block, tile, holes, who="evaluate_raster")
     _check_edges(area_edges_m2)
     _check_quantiles(quantiles)
@@ -881,7 +983,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["sinks"] = sink_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata)
     drn = {"drainage": bool(drainage), "stream_cells": stream_cells, "stream_tol_m": stream_tol_m, "flood": bool(flood),
            "flood_stages_m": flood_stages_m, "wetness": bool(wetness), "wetness_exponent": wetness_exponent,
-           "wetness_min_slope": wetness_min_slope}
+           "wetness_min_slope": wetness_min_slope, "texture": bool(texture), "texture_octaves": texture_octaves}
     if drainage:
         rep["drainage"] = drainage_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, stream_cells=stream_cells,
                                           stream_tol_m=stream_tol_m)
@@ -891,6 +993,8 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     if wetness:
         rep["wetness"] = wetness_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, exponent=wetness_exponent,
                                         min_slope=wetness_min_slope)
+    if texture:
+        rep["texture"] = texture_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata, octaves=texture_octaves)
     if baseline is not None:
         rep["baseline"] = baseline_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, method=baseline,
                                           area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, solver=solver,
@@ -986,6 +1090,12 @@ def build_parser():
     ap.add_argument("--exponent", type=int, default=1,
                     help="with --wetness: the exponent of the multiple-flow-direction rule, an integer in 1..8")
     ap.add_argument("--min-slope", type=float, default=1e-3, help="with --wetness: slopes below this count as this (> 0)")
+    ap.add_argument("--texture", action="store_true",
+                    help="also compare the relief of every scored fill with the truth's at each scale: RMS second differences at "
+                         "the lags 1, 2, 4, .. px over triples centred in the holes, their ratio and correlation: one more summary "
+                         "line per fill")
+    ap.add_argument("--octaves", type=int, default=TEX_OCTAVES,
+                    help=f"with --texture: the number of lags 1, 2, 4, .. px, an integer in 1..{TEX_OCTAVES}")
     return ap
 
 
@@ -1006,6 +1116,8 @@ def main(argv=None):
         ap.error("--exponent must lie in [1, 8]")
     if not (a.min_slope > 0 and a.min_slope < math.inf):
         ap.error("--min-slope must be finite and > 0")
+    if not 1 <= a.octaves <= TEX_OCTAVES:
+        ap.error(f"--octaves must lie in [1, {TEX_OCTAVES}]")
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
@@ -1028,7 +1140,8 @@ def main(argv=None):
                                   min_coverage=a.min_coverage, solver=a.solver, depth_edges_m=depth_edges,
                                   compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
                                   stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages),
-                                  wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope)
+                                  wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope,
+                                  texture=a.texture, texture_octaves=a.octaves)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -1043,7 +1156,7 @@ def main(argv=None):
             rep["sinks"] = sink_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata)
         drn = {"drainage": a.drainage, "stream_cells": a.stream_cells, "stream_tol_m": a.stream_tol, "flood": a.flood,
                "flood_stages_m": tuple(a.flood_stages), "wetness": a.wetness, "wetness_exponent": a.exponent,
-               "wetness_min_slope": a.min_slope}
+               "wetness_min_slope": a.min_slope, "texture": a.texture, "texture_octaves": a.octaves}
         if a.drainage:
             rep["drainage"] = drainage_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, stream_cells=a.stream_cells,
                                               stream_tol_m=a.stream_tol)
@@ -1053,6 +1166,8 @@ def main(argv=None):
         if a.wetness:
             rep["wetness"] = wetness_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, exponent=a.exponent,
                                             min_slope=a.min_slope)
+        if a.texture:
+            rep["texture"] = texture_errors(dem, p, hm, cellsize=c, mask=mask, nodata=nodata, octaves=a.octaves)
         if a.baseline:
             rep["baseline"] = baseline_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, method=a.baseline,
                                               solver=a.solver, depth_edges_m=depth_edges, sinks=a.sinks, **drn)
@@ -1077,6 +1192,8 @@ def main(argv=None):
         print(flood_summary(rep["flood"]))
     if "wetness" in rep:
         print(wetness_summary(rep["wetness"]))
+    if "texture" in rep:
+        print(texture_summary(rep["texture"]))
     if "seam" in rep:
         sm = rep["seam"]
         print(f"seam {a.seam}: {sm['ring']} ring / {sm['interior']} interior pixels, max_delta {sm['max_delta']:.4g} m, "
@@ -1092,6 +1209,8 @@ def main(argv=None):
             print(f"baseline {rep['baseline']['method']} {flood_summary(rep['baseline']['flood'])}")
         if "wetness" in rep["baseline"]:
             print(f"baseline {rep['baseline']['method']} {wetness_summary(rep['baseline']['wetness'])}")
+        if "texture" in rep["baseline"]:
+            print(f"baseline {rep['baseline']['method']} {texture_summary(rep['baseline']['texture'])}")
     for name, r in rep.get("compare", {}).items():
         print(f"compare {name}: {summary(r)}")
         if "sinks" in r:
@@ -1102,6 +1221,8 @@ def main(argv=None):
             print(f"compare {name} {flood_summary(r['flood'])}")
         if "wetness" in r:
             print(f"compare {name} {wetness_summary(r['wetness'])}")
+        if "texture" in r:
+            print(f"compare {name} {texture_summary(r['texture'])}")
     return rep
 
 

@@ -61,6 +61,7 @@ TG_STREAM_ORDER_COUNTS = 1 + 2 * TG_STREAM_ORDER_BINS
 TG_FLOOD_MAX_STAGES = 8
 TG_FLOOD_COUNTS = 6 + 3 * TG_FLOOD_MAX_STAGES
 TG_MFD_MAX_EXPONENT, TG_MFD_COUNTS = 8, 5
+TG_TEX_OCTAVES, TG_TEX_SCALES, TG_TEX_NSUM = 5, 10, 3
 
 
 class TgFloodStages(C.Structure):
@@ -227,6 +228,8 @@ SIGNATURES = {
     "tg_terrain_slope": (I, [P, P, I, I, F, P, P]),
     "tg_wetness": (I, [P, P, P, I, I, F, F, P, P]),
     "tg_wetness_compare": (I, [P, P, P, I, I, P, P, P, SZ, P]),
+    "tg_texture_ws_bytes": (SZ, [I, I]),
+    "tg_texture_compare": (I, [P, P, P, P, I, I, I, P, P, P, SZ, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

@@ -1857,6 +1857,43 @@ def wetness_compare(sel, twi_t, twi_p, ws=None):
     return counts, sums
 
 
+TEX_OCTAVES, TEX_SCALES, TEX_NSUM = L.TG_TEX_OCTAVES, L.TG_TEX_SCALES, L.TG_TEX_NSUM
+
+
+def texture_ws(H, W, device=None):
+    """The workspace of one texture_compare: uint8 [tg_texture_ws_bytes], one row of partial sums per workgroup; its contents
+    do not matter.  device: the current HIP device if None."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return _ws_make(_lib().tg_texture_ws_bytes, "texture", H, W, device, err=ValueError)
+
+
+def texture_compare(z, p, sel, known, octaves=TEX_OCTAVES, ws=None):
+    """-> (counts int64 [TEX_SCALES]: the triples per scale 2 * octave + class; sums float64 [TEX_SCALES][TEX_NSUM]: of d_z d_z,
+    d_p d_p and d_z d_p in a fixed order) of the second differences of z and p (float32 [H][W]) at the lags 1, 2, .. 2^(octaves - 1)
+    px over the triples centred where sel != 0 whose three pixels are known (both uint8 [H][W]) (tg_texture_compare).  p may be z.
+    ws: a texture_ws, made here if None."""
+    import numbers
+    who = "texture_compare"
+    H, W = _mfd_hw(z, "z", who)
+    _mfd_plane(p, torch.float32, (H, W), "p", who)
+    _mfd_plane(sel, torch.uint8, (H, W), "sel", who)
+    _mfd_plane(known, torch.uint8, (H, W), "known", who)
+    if isinstance(octaves, bool) or not isinstance(octaves, numbers.Integral) or not 1 <= octaves <= TEX_OCTAVES:
+        raise ValueError(f"{who}: octaves {octaves!r} must be an integer in [1, {TEX_OCTAVES}]")
+    for t, name in ((p, "p"), (sel, "sel"), (known, "known")):
+        if t.device != z.device:
+            raise ValueError(f"{who}: {name} is on {t.device}, z on {z.device}")
+    if ws is None:
+        ws = texture_ws(H, W, z.device)
+    _ws_chk(ws, H, W, _lib().tg_texture_ws_bytes, "texture", who=who, align=8, err=ValueError)
+    counts = torch.empty(TEX_SCALES, dtype=torch.int64, device=z.device)
+    sums = torch.empty(TEX_SCALES, TEX_NSUM, dtype=torch.float64, device=z.device)
+    L.check(_lib().tg_texture_compare(_p(z), _p(p), _p(sel), _p(known), H, W, int(octaves), _p(counts), _p(sums), _p(ws),
+                                      ws.numel(), _stream()), "tg_texture_compare")
+    return counts, sums
+
+
 VFILL_NSTATS = 4                                # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
