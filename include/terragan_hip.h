@@ -997,6 +997,40 @@ size_t tg_texture_ws_bytes(int H, int W);
 int tg_texture_compare(const float* z, const float* p, const uint8_t* sel, const uint8_t* known, int H, int W, int octaves,
                        int64_t* counts, double* sums, void* ws, size_t ws_bytes, tg_stream_t stream);
 
+/* ---- Empirical semivariogram; ordinary kriging over the eight ray hits (csrc/kriging.hip) -------------------------
+ * z fp32 [H][W]; known uint8 [H][W], nonzero = known.  Octave j = 0 .. octaves - 1 (octaves in 1 .. TG_VGM_OCTAVES) has the lag
+ * L = 2^j px; class 0 (axial) has the unit steps u = (dy, dx) in {(0, 1), (1, 0)}, class 1 (diagonal) {(1, 1), (1, -1)}; scale
+ * s = 2 j + class.  A pair is (x, x + L u) with both pixels inside the raster and known: every unordered pair of a scale counts
+ * once.  Per pair, in fp64 from the fp32 values and nothing fused: d = (double)z(x) - (double)z(x + L u).  counts
+ * [TG_VGM_SCALES] int64 (zeroed here) = the pairs per scale, exact (integer atomics); sums [TG_VGM_SCALES] double = the sums of
+ * d * d per scale in a fixed order (per-workgroup rows of partials in ws, then one workgroup adds the rows in index order: two
+ * calls agree bitwise); the semivariance of a scale is sums / (2 counts).  The entries of octaves that were not requested come
+ * back zero.  ws >= tg_variogram_ws_bytes(H, W), 8-byte aligned, contents arbitrary; 0 for sides out of range. */
+#define TG_VGM_OCTAVES 6
+#define TG_VGM_SCALES 12
+size_t tg_variogram_ws_bytes(int H, int W);
+int tg_variogram(const float* z, const uint8_t* known, int H, int W, int octaves, int64_t* counts, double* sums, void* ws,
+                 size_t ws_bytes, tg_stream_t stream);
+/* Variogram models gamma(h), h > 0 in metres; gamma(0) = 0.  power: nugget + scale * h^shape, 0 < shape < 2, with
+ * h^shape taken as exp2(shape * log2(h)); exponential:
+ * nugget + scale * (1 - exp(-h / shape)), shape > 0; spherical: nugget + scale * (1.5 r - 0.5 r^3), r = min(h / shape, 1),
+ * shape > 0.  nugget >= 0 and scale > 0, all finite. */
+enum { TG_VGM_POWER = 0, TG_VGM_EXPONENTIAL = 1, TG_VGM_SPHERICAL = 2 };
+/* Ordinary kriging of the unknown pixels (known[p] == 0) from at most eight samples each: hits uint16 [8][H][W] as tg_rayfill
+ * writes it (k_j steps along N, NE, E, SE, S, SW, W, NW to the first known pixel, 0 = no sample; a k_j that leaves the raster
+ * counts as 0), sample j at p + k_j d_j.  Distances are h = cellsize * sqrt((double)n) with n the exact squared pixel distance.
+ * With n >= 1 samples the weights solve sum_j w_j gamma(h_ij) + mu = gamma(h_i0), sum w = 1, in fp64.  r is the nearest sample,
+ * the first in ray order among equals; out = (float)(z_r + sum_{i != r} w_i (z_i - z_r)), so a constant field comes back exactly
+ * constant, and var = (float)max(0, sum w_i gamma(h_i0) + mu) in m^2; one sample gives out = z_r and var = 2 gamma(h_r0).  The
+ * system is reduced against r (M_ij = gamma_ir + gamma_jr - gamma_ij, b_i = gamma_ir + gamma_r0 - gamma_i0, var = 2 gamma_r0 -
+ * b^T M^-1 b) and factorised by Cholesky without pivoting.  An unknown pixel without a sample takes z[idx[p]] and var =
+ * (float)(2 gamma(cellsize * sqrt(d2[p]))) when d2 and idx (tg_edt_nearest's; both or neither) are given and idx[p] >= 0; else
+ * out and var are NaN.  Known pixels: out = z bit for bit, var = 0.  counts [3] int64 (zeroed here): unknown pixels filled from
+ * ray samples, from the nearest pixel, left NaN.  out, var and z are distinct.  Sides in [1, TG_EDT_MAX_SIDE]. */
+int tg_krige(const float* z, const uint8_t* known, const uint16_t* hits, int H, int W, double cellsize, int model, double nugget,
+             double scale, double shape, const int32_t* d2, const int32_t* idx, float* out, float* var, int64_t* counts,
+             tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

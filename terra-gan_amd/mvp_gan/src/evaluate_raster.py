@@ -68,13 +68,20 @@ section 8ad): the second differences of the fill and of the truth over the same 
 their ratio and their correlation; report["baseline"] and every report["compare"][name] gain the same key.  Without it the report
 has no "texture" key and nothing more runs.
 
+With kriging=True (or a kriging.Variogram) the same keep mask is also filled by ordinary kriging (krige_voids; mvp_gan/src/kriging.py,
+DESIGN.md section 8ae; True fits the power variogram to the kept pixels) and report["kriging"] holds that fill's terrain_errors report
+on the same holes and depth classes, "method", the fill info under "fill", the model under "variogram", every optional row above by
+the same calls, and "calibration" = {"cells", "mean_z2", "within_1sigma", "within_2sigma"}: over the scored pixels with a finite
+variance > 0, z^2 = error^2 / variance, its mean and the shares with |error| <= sigma and <= 2 sigma.  Without it the report has no
+"kriging" key and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
          [--flood [--flood-stages s ...]] [--wetness [--exponent e] [--min-slope s]]
-         [--texture [--octaves n]]
+         [--texture [--octaves n]] [--kriging]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -515,6 +522,82 @@ def compare_report(dem, holes, keep, names, *, cellsize, mask=None, nodata=None,
                             wet if wetness else None, tex if texture else None)
 
 
+def _check_kriging(kriging, who="evaluate_raster"):
+    """False or None -> None (no kriging row); True -> True (fit the power model); a kriging.Variogram -> itself."""
+    if kriging is None or kriging is False:
+        return None
+    if kriging is True:
+        return True
+    from .kriging import Variogram
+    if isinstance(kriging, Variogram):
+        return kriging
+    raise ValueError(f"{who}: kriging {kriging!r} must be False, True or a kriging.Variogram")
+
+
+def assemble_calibration(cells, sum_z2, within1, within2):
+    """The calibration dict from the counts over the scored pixels with a finite variance > 0, z^2 = err^2 / var (pure: no GPU):
+    a calibrated variance has mean_z2 near 1, within_1sigma near 0.68 and within_2sigma near 0.95; None without cells."""
+    cells = int(cells)
+    if not cells:
+        return {"cells": 0, "mean_z2": None, "within_1sigma": None, "within_2sigma": None}
+    return {"cells": cells, "mean_z2": float(sum_z2) / cells, "within_1sigma": int(within1) / cells,
+            "within_2sigma": int(within2) / cells}
+
+
+def calibration(dem, pred, variance, holes):
+    """Is |error| <= sigma about 68 % of the time: over the pixels of holes (nonzero = hole) with a finite pred and a finite
+    variance > 0, z^2 = (pred - dem)^2 / variance in float64 (torch reductions on the device: not a hot path)."""
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO).double()
+    p = R.to_f32(pred, device, "pred", WHO).double()
+    v = R.to_f32(variance, device, "variance", WHO).double()
+    sel = (R.to_u8(holes, device, "holes", WHO, nonzero=True, reuse=True) != 0) & torch.isfinite(p) & torch.isfinite(v) & (v > 0)
+    z2 = ((p - z) ** 2 / v)[sel]
+    return assemble_calibration(z2.numel(), z2.sum().item(), (z2 <= 1.0).sum().item(), (z2 <= 4.0).sum().item())
+
+
+@torch.no_grad()
+def kriging_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, variogram=None, area_edges_m2=AREA_EDGES_M2,
+                   quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
+                   stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
+                   wetness_min_slope=1e-3, texture=False, texture_octaves=5):
+    """The krige_voids fill of the keep mask (mvp_gan/src/kriging.py; variogram None: the power model fitted to the kept pixels)
+    scored on the holes like a compare_report fill: terrain_errors' report plus "method", the fill info under "fill", the model
+    under "variogram", the optional rows by the same calls, and "calibration" (calibration's dict) of the kriging variance."""
+    from .kriging import krige_voids
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO)
+    k = R.to_f32(keep, device, "keep", WHO, binary=True)
+    pred, var, finfo = krige_voids(z, k, nodata=R.nodata_value(nodata), cellsize=cellsize, variogram=variogram)
+    rep = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
+                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
+    rep["method"] = "kriging"
+    rep["fill"] = finfo
+    rep["variogram"] = finfo["variogram"]
+    if sinks:
+        rep["sinks"] = sink_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata)
+    if drainage:
+        rep["drainage"] = drainage_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                          stream_tol_m=stream_tol_m)
+    if flood:
+        rep["flood"] = flood_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                    stages_m=flood_stages_m)
+    if wetness:
+        rep["wetness"] = wetness_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=wetness_exponent,
+                                        min_slope=wetness_min_slope)
+    if texture:
+        rep["texture"] = texture_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, octaves=texture_octaves)
+    rep["calibration"] = calibration(z, pred, var, holes)
+    return rep
+
+
+def calibration_summary(c):
+    """One line for a calibration dict."""
+    f = lambda v, spec: "n/a" if v is None else format(v, spec)
+    return (f"calibration: mean z2 {f(c['mean_z2'], '.3f')}, {f(c['within_1sigma'], '.3f')} within 1 sigma, "
+            f"{f(c['within_2sigma'], '.3f')} within 2 sigma over {c['cells']} px")
+
+
 # ---- a fill against the truth: what sink_errors, drainage_raw, flood_raw, wetness_raw and texture_raw open with -----------
 def _fill_shapes(dem, pred, holes, mask, cellsize, who):
     """Host-side rejection before any launch; -> (cellsize, (H, W))."""
@@ -904,7 +987,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
                     solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
                     flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3,
-                    texture=False, texture_octaves=5):
+                    texture=False, texture_octaves=5, kriging=False):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -918,7 +1001,9 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     flood_stages_m) under "flood" to the same three places; wetness=True adds wetness_errors' dict (the TWI from the
     multiple-flow-direction accumulation at wetness_exponent, slopes not below wetness_min_slope) under "wetness" to the same
     three places; texture=True adds texture_errors' dict (second differences at texture_octaves octaves of lags) under "texture" to
-    the same three places."""
+    the same three places.  kriging=True (or a kriging.Variogram; True fits the power model to the kept pixels) adds
+    report["kriging"], kriging_report's dict: the krige_voids fill of the same keep mask scored on the same holes and classes, with
+    the same optional rows and the calibration of its variance."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
@@ -926,7 +1011,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                              depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
                              stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m,
                              wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope,
-                             texture=texture, texture_octaves=texture_octaves)
+                             texture=texture, texture_octaves=texture_octaves, kriging=kriging)
     return rep, pred
 
 
@@ -934,12 +1019,13 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
               stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-              wetness_min_slope=1e-3, texture=False, texture_octaves=5):
+              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
     _check_fill_options(baseline, fallback)
     compare = _check_compare(compare)
+    kriging = _check_kriging(kriging)
     check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
     c = R.cellsize(cellsize, "evaluate_raster")
@@ -947,6 +1033,8 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     H, W = R.raster_shape(dem, mask, "evaluate_raster")
     if compare and max(H, W) > 32767:
         raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
+    if kriging is not None and max(H, W) > 32767:
+        raise ValueError(f"evaluate_raster: kriging needs sides of at most 32767 px, got {H}x{W}")
     if drainage:
         if max(H, W) > 32767:
             raise ValueError(f"evaluate_raster: drainage needs sides of at most 32767 px, got {H}x{W}")
@@ -1001,6 +1089,10 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
                                           depth_edges_m=depth_edges_m, sinks=bool(sinks), **drn)
     if compare:
         rep["compare"] = compare_report(z, hm, keep, compare, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
+                                        quantiles=quantiles, top=top, depth_edges_m=depth_edges_m, sinks=bool(sinks), **drn)
+    if kriging is not None:
+        rep["kriging"] = kriging_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata,
+                                        variogram=None if kriging is True else kriging, area_edges_m2=area_edges_m2,
                                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m, sinks=bool(sinks), **drn)
     return rep, pred, hm
 
@@ -1066,6 +1158,9 @@ def build_parser():
     ap.add_argument("--compare", nargs="+", choices=COMPARES, metavar="NAME",
                     help="also score these interpolate_voids fills of the same holes (" + ", ".join(COMPARES) + "): one more "
                          "summary line each")
+    ap.add_argument("--kriging", action="store_true",
+                    help="also score the ordinary-kriging fill of the same holes (krige_voids, the power variogram fitted to "
+                         "the kept cells) and the calibration of its variance: two more summary lines")
     ap.add_argument("--sinks", action="store_true",
                     help="also fill the depressions of the truth and of every scored fill and report the closed pits each fill "
                          "put into the holes (cells, volume, count): one more summary line per fill")
@@ -1141,7 +1236,7 @@ def main(argv=None):
                                   compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
                                   stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages),
                                   wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope,
-                                  texture=a.texture, texture_octaves=a.octaves)
+                                  texture=a.texture, texture_octaves=a.octaves, kriging=a.kriging)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -1174,6 +1269,9 @@ def main(argv=None):
         if a.compare:
             rep["compare"] = compare_report(dem, hm, keep, a.compare, cellsize=c, mask=mask, nodata=nodata,
                                             depth_edges_m=depth_edges, sinks=a.sinks, **drn)
+        if a.kriging:
+            rep["kriging"] = kriging_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, depth_edges_m=depth_edges,
+                                            sinks=a.sinks, **drn)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -1223,6 +1321,14 @@ def main(argv=None):
             print(f"compare {name} {wetness_summary(r['wetness'])}")
         if "texture" in r:
             print(f"compare {name} {texture_summary(r['texture'])}")
+    if "kriging" in rep:
+        r = rep["kriging"]
+        print(f"kriging: {summary(r)}")
+        print(f"kriging {calibration_summary(r['calibration'])}")
+        for key, line in (("sinks", sinks_summary), ("drainage", drainage_summary), ("flood", flood_summary),
+                          ("wetness", wetness_summary), ("texture", texture_summary)):
+            if key in r:
+                print(f"kriging {line(r[key])}")
     return rep
 
 

@@ -1894,6 +1894,79 @@ def texture_compare(z, p, sel, known, octaves=TEX_OCTAVES, ws=None):
     return counts, sums
 
 
+VGM_OCTAVES, VGM_SCALES = L.TG_VGM_OCTAVES, L.TG_VGM_SCALES
+VGM_MODELS = ("power", "exponential", "spherical")          # TG_VGM_POWER, TG_VGM_EXPONENTIAL, TG_VGM_SPHERICAL
+
+
+def variogram_ws(H, W, device=None):
+    """The workspace of one variogram: uint8 [tg_variogram_ws_bytes], one row of partial sums per workgroup; its contents do
+    not matter.  device: the current HIP device if None."""
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return _ws_make(_lib().tg_variogram_ws_bytes, "variogram", H, W, device, err=ValueError)
+
+
+def variogram(z, known, octaves=VGM_OCTAVES, ws=None):
+    """-> (counts int64 [2 * octaves]: the pairs per scale 2 * octave + class; sums float64 [2 * octaves]: of d * d in a fixed
+    order) of the first differences d of z (float32 [H][W]) at the lags 1, 2, .. 2^(octaves - 1) px along the axes (class 0) and
+    the diagonals (class 1), over the unordered pairs whose two pixels are known (uint8 [H][W]) (tg_variogram).  The
+    semivariance of a scale is sums / (2 counts).  ws: a variogram_ws, made here if None."""
+    import numbers
+    who = "variogram"
+    H, W = _mfd_hw(z, "z", who)
+    _mfd_plane(known, torch.uint8, (H, W), "known", who)
+    if isinstance(octaves, bool) or not isinstance(octaves, numbers.Integral) or not 1 <= octaves <= VGM_OCTAVES:
+        raise ValueError(f"{who}: octaves {octaves!r} must be an integer in [1, {VGM_OCTAVES}]")
+    if known.device != z.device:
+        raise ValueError(f"{who}: known is on {known.device}, z on {z.device}")
+    if ws is None:
+        ws = variogram_ws(H, W, z.device)
+    _ws_chk(ws, H, W, _lib().tg_variogram_ws_bytes, "variogram", who=who, align=8, err=ValueError)
+    counts = torch.empty(VGM_SCALES, dtype=torch.int64, device=z.device)
+    sums = torch.empty(VGM_SCALES, dtype=torch.float64, device=z.device)
+    L.check(_lib().tg_variogram(_p(z), _p(known), H, W, int(octaves), _p(counts), _p(sums), _p(ws), ws.numel(), _stream()),
+            "tg_variogram")
+    return counts[:2 * int(octaves)], sums[:2 * int(octaves)]
+
+
+def krige(z, known, hits, cellsize, model, nugget, scale, shape, d2=None, idx=None):
+    """-> (out float32 [H][W], var float32 [H][W] in m^2, counts int64 [3]: by ray samples, by nearest, left NaN): ordinary
+    kriging of the pixels with known == 0 from the samples of hits (uint16 [8][H][W], rayfill's with want_hits) under the
+    variogram `model` (a name out of VGM_MODELS or its index) with nugget, scale and shape (tg_krige).  d2, idx: edt_nearest's,
+    for the pixels without a sample; both or neither."""
+    import math
+    H, W = _edt_hw(z, "z")
+    _hip(z, torch.float32, (H, W), "z")
+    _hip(known, torch.uint8, (H, W), "known")
+    _hip(hits, torch.uint16, (8, H, W), "hits")
+    if isinstance(model, str):
+        if model not in VGM_MODELS:
+            raise L.TgError(f"krige: model {model!r} must be one of {VGM_MODELS}")
+        model = VGM_MODELS.index(model)
+    if isinstance(model, bool) or not isinstance(model, int) or not 0 <= model < len(VGM_MODELS):
+        raise L.TgError(f"krige: model {model!r} must be one of {VGM_MODELS} or its index")
+    c, nugget, scale, shape = float(cellsize), float(nugget), float(scale), float(shape)
+    if not (math.isfinite(c) and c > 0):
+        raise L.TgError(f"krige: cellsize {cellsize!r} must be finite and > 0")
+    if not (math.isfinite(nugget) and nugget >= 0):
+        raise L.TgError(f"krige: nugget {nugget!r} must be finite and >= 0")
+    if not (math.isfinite(scale) and scale > 0):
+        raise L.TgError(f"krige: scale {scale!r} must be finite and > 0")
+    if not (math.isfinite(shape) and shape > 0 and (model != 0 or shape < 2)):
+        raise L.TgError(f"krige: shape {shape!r} must lie in (0, 2) for the power model, else be finite and > 0")
+    if (d2 is None) != (idx is None):
+        raise L.TgError("krige: d2 and idx go together")
+    if d2 is not None:
+        _hip(d2, torch.int32, (H, W), "d2")
+        _hip(idx, torch.int32, (H, W), "idx")
+    out = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    var = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    counts = torch.empty(3, dtype=torch.int64, device=z.device)
+    L.check(_lib().tg_krige(_p(z), _p(known), _p(hits), H, W, c, model, nugget, scale, shape, _p(d2), _p(idx), _p(out),
+                            _p(var), _p(counts), _stream()), "tg_krige")
+    return out, var, counts
+
+
 VFILL_NSTATS = 4                                # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
