@@ -22,7 +22,14 @@
 // Determinism: every value is computed by one thread in a fixed order; tiles are independent (the down and up passes read one
 // buffer and write the other); the change is a maximum on the bits of a non-negative float (integer atomic).  Results are
 // bitwise reproducible.  No kernel uses scratch.
+//
+// Rounding: this file is compiled with the default contraction, and __fmul_rn / __fadd_rn are a plain product and sum to the
+// compiler, so a product that feeds a sum is one fused multiply-add: the prolongation's 9 a + 3 b (fma(3, b, 9 a)), the SOR
+// update u + omega q, and every x + alpha p, e + alpha p and z + beta p below.  The lines marked "fused" are these sites;
+// tests/vfill_pcg_mirror.py (fma=True) rounds the same way and tests/test_hip_vfill_stages.py compares with it, so a change of
+// the contraction (a pragma, a flag, a compiler) must be made in both places.
 #include <math.h>
+#include <stddef.h>
 
 #include "common.h"
 
@@ -47,6 +54,10 @@ struct VfHdr {
     int32_t ntiles[TG_VFILL_MAX_LEVELS];           // active tiles per level
 };
 static_assert(sizeof(VfHdr) <= VF_ALIGN, "header fits its slot");
+// the layout VFILL_HDR of mvp_gan/src/fill_voids.py reads
+static_assert(offsetof(VfHdr, lo_key) == 0 && offsetof(VfHdr, hi_key) == 4 && offsetof(VfHdr, known) == 8, "VFILL_HDR");
+static_assert(offsetof(VfHdr, c) == 16 && offsetof(VfHdr, ntiles) == 24 && TG_VFILL_MAX_LEVELS == 32, "VFILL_HDR");
+static_assert(sizeof(VfHdr) == 24 + 4 * 32, "VFILL_HDR");
 
 // ---- host-side plan (mirrored by vfill_levels / vfill_layout in mvp_gan/src/fill_voids.py) ---------------------------
 struct VfLevel {
@@ -282,6 +293,7 @@ __global__ __launch_bounds__(256) void vf_pass_kernel(VfPass P) {
                     const int Y = y >> 1, X = x >> 1;
                     const int ly = Y - cy0, lx = X - cx0;
                     const int ny = ly + ((y & 1) ? 1 : -1), nx = lx + ((x & 1) ? 1 : -1);
+                    // fused: 9 a + 3 b is fma(3, b, 9 a)
                     const float e = (9.f * s.ec[ly][lx] + 3.f * s.ec[ny][lx] + 3.f * s.ec[ly][nx] + s.ec[ny][nx]) * 0.0625f;
                     u += e;
                 }
@@ -403,7 +415,7 @@ __global__ __launch_bounds__(256) void vf_coarsest_kernel(VfCoarse P) {
             if (fl[ly + 1][lx] & VF_IN) { acc += u[ly + 1][lx] - up; ++n; }
             if (fl[ly][lx - 1] & VF_IN) { acc += u[ly][lx - 1] - up; ++n; }
             if (fl[ly][lx + 1] & VF_IN) { acc += u[ly][lx + 1] - up; ++n; }
-            if (n) u[ly][lx] = up + om * (acc / (float)n);
+            if (n) u[ly][lx] = up + om * (acc / (float)n);             // fused
         }
         __syncthreads();
     }
@@ -449,6 +461,13 @@ struct VfPcgScal {
     uint32_t _pad;
 };
 static_assert(sizeof(VfPcgScal) <= VF_ALIGN, "scalars fit their slot");
+// the layout VFILL_PCG_SCAL of mvp_gan/src/fill_voids.py reads (the biharmonic fill keeps two such blocks, sc_out and sc_in)
+static_assert(offsetof(VfPcgScal, rho) == 0 && offsetof(VfPcgScal, pap) == 8, "VFILL_PCG_SCAL");
+static_assert(offsetof(VfPcgScal, rz_old) == 16 && offsetof(VfPcgScal, rz_new) == 24, "VFILL_PCG_SCAL");
+static_assert(offsetof(VfPcgScal, alpha) == 32 && offsetof(VfPcgScal, beta) == 36, "VFILL_PCG_SCAL");
+static_assert(offsetof(VfPcgScal, restarts) == 40 && offsetof(VfPcgScal, restart) == 44, "VFILL_PCG_SCAL");
+static_assert(offsetof(VfPcgScal, parity) == 48 && offsetof(VfPcgScal, _pad) == 52, "VFILL_PCG_SCAL");
+static_assert(sizeof(VfPcgScal) == 56, "VFILL_PCG_SCAL");
 
 struct VfPcg {
     const uint8_t* flags;
@@ -503,7 +522,7 @@ __global__ __launch_bounds__(256) void vf_pcg_step_kernel(VfPcg P) {
                 const bool inner = r >= 1 && r <= VF_TY && c >= 1 && c <= VF_TX;
                 if (!(fl & VF_FIX) && alpha != 0.f) {
                     const float d = __fmul_rn(alpha, pin[i]);
-                    v = __fadd_rn(v, d);
+                    v = __fadd_rn(v, d);                           // fused: fma(alpha, p, v); d itself is the rounded product
                     if (inner) {
                         const uint32_t b = __float_as_uint(fabsf(d));
                         mx = b > mx ? b : mx;
@@ -597,7 +616,7 @@ __global__ __launch_bounds__(256) void vf_pcg_dir_kernel(VfPcg P) {
                 fl = VF_IN | P.flags[i];
                 if (!(fl & VF_FIX)) {
                     v = P.z[i];
-                    if (beta != 0.f) v = __fadd_rn(v, __fmul_rn(beta, pin[i]));
+                    if (beta != 0.f) v = __fadd_rn(v, __fmul_rn(beta, pin[i]));    // fused
                 }
                 if (r >= 1 && r <= VF_TY && c >= 1 && c <= VF_TX) pout[i] = v;
             }
@@ -1182,7 +1201,7 @@ __global__ __launch_bounds__(256) void vf_bih_dir_kernel(VfBih P) {
                 fl = VF_IN | P.flags[i];
                 if (!(fl & VF_FIX)) {
                     v = P.z[i];
-                    if (beta != 0.f) v = __fadd_rn(v, __fmul_rn(beta, pin[i]));
+                    if (beta != 0.f) v = __fadd_rn(v, __fmul_rn(beta, pin[i]));    // fused
                 }
                 if (r >= 2 && r < VF_TY + 2 && c >= 2 && c < VF_TX + 2) pout[i] = v;
             }
@@ -1246,7 +1265,7 @@ __global__ __launch_bounds__(256) void vf_rhs_step_kernel(VfRhs P) {
                 fl = VF_IN | P.flags[i];
                 if (!(fl & VF_FIX)) {
                     if (P.e_in) v = P.e_in[i];
-                    if (alpha != 0.f) v = __fadd_rn(v, __fmul_rn(alpha, pin[i]));
+                    if (alpha != 0.f) v = __fadd_rn(v, __fmul_rn(alpha, pin[i]));    // fused
                 }
                 if (r >= 1 && r <= VF_TY && c >= 1 && c <= VF_TX) P.e_out[i] = v;
             }
@@ -1296,7 +1315,7 @@ __global__ __launch_bounds__(256) void vf_rhs_final_kernel(VfRhs P) {
             float v = 0.f;
             if (!(P.flags[i] & VF_FIX)) {
                 if (P.e_in) v = P.e_in[i];
-                if (alpha != 0.f) v = __fadd_rn(v, __fmul_rn(alpha, pin[i]));
+                if (alpha != 0.f) v = __fadd_rn(v, __fmul_rn(alpha, pin[i]));    // fused
             }
             P.e_out[i] = v;
         }

@@ -102,6 +102,16 @@ def vfill_pcg_layout(H, W):
     return out, off
 
 
+# the header of the workspace (VfHdr of csrc/voidfill.hip, pinned there by static_asserts): its first bytes
+VFILL_HDR = np.dtype([("lo_key", "<u4"), ("hi_key", "<u4"), ("known", "<u8"), ("c", "<f4"), ("_pad", "<i4"),
+                      ("ntiles", "<i4", (MAX_LEVELS,))])
+
+# the scalar block of the conjugate gradients (VfPcgScal of csrc/voidfill.hip, pinned there by static_asserts): the first bytes
+# of the pcg workspace, and the blocks at sc_out (outer loop) and sc_in (inner solve) of the biharmonic workspace
+VFILL_PCG_SCAL = np.dtype([("rho", "<f8"), ("pap", "<f8"), ("rz_old", "<f8"), ("rz_new", "<f8"), ("alpha", "<f4"), ("beta", "<f4"),
+                           ("restarts", "<u4"), ("restart", "<u4"), ("parity", "<u4"), ("_pad", "<u4")])
+
+
 def vfill_bih_layout(H, W):
     """-> (dict: sc_out, sc_in (scalars), xa, xb, r (fp64), rf, t, z, p0, p1 (fp32, outer loop), e0, e1, ri, zi, q0, q1, d (fp32,
     inner solve), part (6 offsets: the outer p.Ap, r'.z, r'.z' by tile id, then the inner solve's) byte offsets, total bytes)

@@ -47,7 +47,7 @@ def inner_solve(plan, f, known, inner, counter=None):
                 alpha = a
             else:
                 counter[1] += 1
-        e = e + alpha * p
+        e = M._fma(alpha, p, e) if plan.fma else e + alpha * p
         if k == inner:
             break
         r = M.diff_sum(e, f)
@@ -63,16 +63,22 @@ def inner_solve(plan, f, known, inner, counter=None):
                 beta = b
             else:
                 counter[1] += 1
-        p = z + beta * p
+        p = M._fma(beta, p, z) if plan.fma else z + beta * p
         rho = rho_new
     return e
 
 
-def solve(z, known, tol=None, max_cycles=200, inner=3, dt_in=np.float32):
+def solve(z, known, tol=None, max_cycles=200, inner=3, dt_in=np.float32, trace=None, fma=False):
     """The outer loop.  -> (raster in dt_in, info: cycles (outer iterations), vcycles, change, tol, converged, restarts,
-    history)."""
+    history).
+    trace: a dict whose "states" list receives the outer loop's state as tg_vfill_bih_start (entry 0) and the k-th
+    tg_vfill_bih_iter (entry k) leave it in the block at sc_out and in xa, r, z and the current p: the launches and so the timing
+    of the scalars are those of the pcg loop (the docstring of tests/vfill_pcg_mirror.py; z' = G(G(r')) takes the cycle's
+    place), x and r are fp64, and an entry is recorded once the next pass has formed pap and alpha: run max_cycles = k + 1 to
+    see the state after k iterations (trace["stop"] = n ends the loop once n entries are there).  With trace=None the result is
+    bit for bit what it was.  fma: the compiled kernels' rounding of the fp32 updates (vfill_pcg_mirror.Plan)."""
     known = np.asarray(known, bool)
-    plan = M.Plan(known, dt_in)
+    plan = M.Plan(known, dt_in, fma)
     v, c, rng = M._start(z, known, np.float32)                 # the set-up is fp32 whatever the solve's type
     t = 1e-6 * rng if tol is None else tol
     x = v.astype(np.float64)
@@ -88,9 +94,14 @@ def solve(z, known, tol=None, max_cycles=200, inner=3, dt_in=np.float32):
         zz = pre(r)
         p = zz.copy()
         rho = _dot(r, zz)
+        rz_old, beta = 0.0, np.float32(0)
         while cycles < max_cycles:
             pap = _dot(p, apply_A(p, known))
             cycles += 1
+            if trace is not None:
+                M._record(trace, np.float32, x=x, r=r, z=zz, p=p, rho=rho, pap=pap, rz_old=rz_old, beta=beta)
+                if len(trace["states"]) == trace.get("stop"):   # the caller wants no more entries: skip the rest of the pass
+                    break
             if rho == 0.0:
                 change = 0.0
                 conv = True
@@ -116,7 +127,7 @@ def solve(z, known, tol=None, max_cycles=200, inner=3, dt_in=np.float32):
             if not np.isfinite(beta):
                 restarts += 1
                 beta = np.float32(0)
-            p = (zz + dt_in(beta) * p).astype(dt_in)
+            p = M._fma(beta, p, zz) if plan.fma else (zz + dt_in(beta) * p).astype(dt_in)
             rho = rho_new
     out = M._finish(z, known, x.astype(dt_in), dt_in(c))
     return out, {"cycles": cycles, "vcycles": cnt[0], "change": change, "tol": t, "converged": conv,
