@@ -488,6 +488,28 @@ int tg_raster_gather(const float* dem, const float* mask, const TgRasterPlan* pl
 int tg_raster_blend(const float* dem, const float* mask, const TgRasterPlan* plan, int use_nodata, float nodata,
                     const float* lo, const float* hi, const int32_t* run_of_window, const float* wout, int n_run, float* out,
                     int32_t* unfilled, tg_stream_t stream);
+/* Test-time augmentation (inpaint_raster(tta=...)).  A transform op in [0, 7] is tg_raster_sample's: member
+ * pixel (i, j) reads window pixel (a, b) = op & 4 ? (j, i) : (i, j), then a = wh-1-a if op & 2, b = ww-1-b if op & 1.  Ops 4..7
+ * transpose and are refused unless wh == ww, so a member frame is always [wh][ww].
+ * tg_raster_gather with a transform per list item: item k (1 <= n <= 65535) is window win_idx[k] (device int32) under op_idx[k]
+ * (HOST int32 [n], read and checked before any launch), written in the member's frame; x, m: [n][wh][ww].  Every value is the
+ * one tg_raster_gather computes for the source pixel; with op 0 the result is bitwise tg_raster_gather's. */
+int tg_raster_gather_ops(const float* dem, const float* mask, const TgRasterPlan* plan, int use_nodata, float nodata,
+                         const float* lo, const float* hi, const int32_t* win_idx, const int32_t* op_idx, int n, float* x, float* m,
+                         tg_stream_t stream);
+/* gout [n][T][wh][ww]: the generator outputs of n windows under ops[0..T) (HOST int32 [T]; T = 2, 4 or 8), each in its member
+ * frame.  Per window pixel, in the window's frame, with o_t the member values there: mean = (o_0 + ... + o_{T-1}) * (1 / T) and
+ * var = sum_t (o_t - mean)^2 / (T - 1), both added in member order in IEEE fp32 without contraction (a float32 mirror reproduces
+ * them bit for bit).  mean, var: [n][wh][ww]. */
+int tg_raster_tta_reduce(const float* gout, const int32_t* ops, int T, int n, int wh, int ww, float* mean, float* var,
+                         tg_stream_t stream);
+/* tg_raster_blend of the window means (out and *unfilled bitwise those of tg_raster_blend(..., wout = wmean)) plus the spread
+ * in metres: with d_j = hi_j - lo_j and dn_j = fma(mean_j, d_j, lo_j) over the running covering windows j,
+ * spread = sqrt(sum_j w_j (var_j d_j^2 + (dn_j - out)^2) / sum_j w_j): the law of total variance over the mixture of windows.
+ * A known pixel gets 0, a hole no running window covers NaN.  wmean, wvar: [n_run][wh][ww].  Bitwise deterministic. */
+int tg_raster_blend_tta(const float* dem, const float* mask, const TgRasterPlan* plan, int use_nodata, float nodata,
+                        const float* lo, const float* hi, const int32_t* run_of_window, const float* wmean, const float* wvar,
+                        int n_run, float* out, float* spread, int32_t* unfilled, tg_stream_t stream);
 
 /* ---- training windows from a whole raster (mvp_gan/src/utils/raster_dataset.py; no reference counterpart: the reference
  * trains on uint8 PNG tiles min-max scaled over all pixels, utils/data_extraction.py:96-100) ----

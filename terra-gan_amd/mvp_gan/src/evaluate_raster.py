@@ -81,7 +81,7 @@ CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--m
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
          [--flood [--flood-stages s ...]] [--wetness [--exponent e] [--min-slope s]]
-         [--texture [--octaves n]] [--kriging]
+         [--texture [--octaves n]] [--kriging] [--tta 2|4|8]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -987,7 +987,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
                     solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
                     flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3,
-                    texture=False, texture_octaves=5, kriging=False):
+                    texture=False, texture_octaves=5, kriging=False, tta=1):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -1003,7 +1003,10 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     three places; texture=True adds texture_errors' dict (second differences at texture_octaves octaves of lags) under "texture" to
     the same three places.  kriging=True (or a kriging.Variogram; True fits the power model to the kept pixels) adds
     report["kriging"], kriging_report's dict: the krige_voids fill of the same keep mask scored on the same holes and classes, with
-    the same optional rows and the calibration of its variance."""
+    the same optional rows and the calibration of its variance.  tta (1, 2, 4 or 8) is passed to the inpainting; above 1 the
+    prediction is the mean of the members and report["spread"] = {"members", "mean_m", "max_m", "calibration"}: the spread over
+    the filled holes in metres and calibration's dict of spread^2 over the scored holes, the row kriging's variance is judged
+    by."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
@@ -1011,7 +1014,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                              depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
                              stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m,
                              wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope,
-                             texture=texture, texture_octaves=texture_octaves, kriging=kriging)
+                             texture=texture, texture_octaves=texture_octaves, kriging=kriging, tta=tta)
     return rep, pred
 
 
@@ -1019,18 +1022,19 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
               stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False):
+              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False, tta=1):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
-    from .inpaint_raster import check_resample_options, check_seam_options, inpaint_raster
+    from .inpaint_raster import check_resample_options, check_seam_options, check_tta, inpaint_raster, inpaint_raster_tta
     _check_fill_options(baseline, fallback)
     compare = _check_compare(compare)
     kriging = _check_kriging(kriging)
     check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
     c = R.cellsize(cellsize, "evaluate_raster")
-    check_resample_options(c, model_cellsize, min_coverage, who="evaluate_raster")
+    scale = check_resample_options(c, model_cellsize, min_coverage, who="evaluate_raster")
     H, W = R.raster_shape(dem, mask, "evaluate_raster")
+    check_tta(tta, (H, W), window, scale, who="evaluate_raster")
     if compare and max(H, W) > 32767:
         raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
     if kriging is not None and max(H, W) > 32767:
@@ -1056,9 +1060,15 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     z, m, _, _ = R.upload(dem, mask, None, WHO)
     hm, keep, hinfo = eval_holes(z, m, nodata=nodata, split=split, block=block, tile=tile, holes=holes, seed=seed,
                                  objects=objects, cellsize=c)
-    pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
-                                 fallback=fallback, seam=seam, cellsize=c, model_cellsize=model_cellsize,
-                                 min_coverage=min_coverage, solver=solver)
+    spread = None
+    if tta == 1:
+        pred, iinfo = inpaint_raster(generator_or_checkpoint, z, keep, nodata=nodata, window=window, overlap=overlap, batch=batch,
+                                     fallback=fallback, seam=seam, cellsize=c, model_cellsize=model_cellsize,
+                                     min_coverage=min_coverage, solver=solver)
+    else:
+        pred, spread, iinfo = inpaint_raster_tta(generator_or_checkpoint, z, keep, tta=tta, nodata=nodata, window=window,
+                                                 overlap=overlap, batch=batch, fallback=fallback, seam=seam, cellsize=c,
+                                                 model_cellsize=model_cellsize, min_coverage=min_coverage, solver=solver)
     sinfo = iinfo.get("seam")
     rep = terrain_errors(z, pred, hm, keep, cellsize=c, mask=m, nodata=nodata, area_edges_m2=area_edges_m2,
                          quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
@@ -1067,6 +1077,10 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     rep["inpaint"] = iinfo
     if sinfo is not None:
         rep["seam"] = sinfo
+    if spread is not None:
+        tt = iinfo["tta"]
+        rep["spread"] = {"members": tt["members"], "mean_m": tt["mean_spread_m"], "max_m": tt["max_spread_m"],
+                         "calibration": calibration(z, pred, spread * spread, hm)}
     if sinks:
         rep["sinks"] = sink_errors(z, pred, hm, cellsize=c, mask=m, nodata=nodata)
     drn = {"drainage": bool(drainage), "stream_cells": stream_cells, "stream_tol_m": stream_tol_m, "flood": bool(flood),
@@ -1161,6 +1175,9 @@ def build_parser():
     ap.add_argument("--kriging", action="store_true",
                     help="also score the ordinary-kriging fill of the same holes (krige_voids, the power variogram fitted to "
                          "the kept cells) and the calibration of its variance: two more summary lines")
+    ap.add_argument("--tta", type=int, choices=(1, 2, 4, 8), default=1,
+                    help="test-time augmentation of the inpainting (needs --checkpoint): the mean of this many flips / rotations "
+                         "of every window is scored, and the calibration of their spread gets a summary line")
     ap.add_argument("--sinks", action="store_true",
                     help="also fill the depressions of the truth and of every scored fill and report the closed pits each fill "
                          "put into the holes (cells, volume, count): one more summary line per fill")
@@ -1223,6 +1240,8 @@ def main(argv=None):
         ap.error("--seam needs --checkpoint")
     if a.model_cellsize is not None and a.pred:
         ap.error("--model-cellsize needs --checkpoint")
+    if a.tta != 1 and a.pred:
+        ap.error("--tta needs --checkpoint")
     dem, header, mask, nodata, c = read_inputs(a)
     objects = spec_from_args(a) if a.remove_objects else None
     split = None if a.split == "all" else a.split
@@ -1236,7 +1255,7 @@ def main(argv=None):
                                   compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
                                   stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages),
                                   wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope,
-                                  texture=a.texture, texture_octaves=a.octaves, kriging=a.kriging)
+                                  texture=a.texture, texture_octaves=a.octaves, kriging=a.kriging, tta=a.tta)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -1282,6 +1301,9 @@ def main(argv=None):
     if a.holes_out and hm is not None:
         write_mask(a.holes_out, hm.cpu().numpy(), header)
     print(summary(rep))
+    if "spread" in rep:
+        sp = rep["spread"]
+        print(f"tta {sp['members']}: spread mean {sp['mean_m']:.4g} m, max {sp['max_m']:.4g} m; {calibration_summary(sp['calibration'])}")
     if "sinks" in rep:
         print(sinks_summary(rep["sinks"]))
     if "drainage" in rep:

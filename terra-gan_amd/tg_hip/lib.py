@@ -161,6 +161,9 @@ SIGNATURES = {
     "tg_raster_window_stats": (I, [P, P, RP, I, F, P, P, P, P]),
     "tg_raster_gather": (I, [P, P, RP, I, F, P, P, P, I, P, P, P]),
     "tg_raster_blend": (I, [P, P, RP, I, F, P, P, P, P, I, P, P, P]),
+    "tg_raster_gather_ops": (I, [P, P, RP, I, F, P, P, P, P, I, P, P, P]),
+    "tg_raster_tta_reduce": (I, [P, P, I, I, I, I, P, P, P]),
+    "tg_raster_blend_tta": (I, [P, P, RP, I, F, P, P, P, P, P, I, P, P, P, P]),
     "tg_hole_masks": (I, [P, P, I, I, P, P]),
     "tg_raster_sample": (I, [P, I64, I64, P, I, I, P, I, P, P, P, P]),
     "tg_objmask_known": (I, [P, P, I, I, I, F, P, P, P]),

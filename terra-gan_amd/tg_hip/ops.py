@@ -3,6 +3,7 @@
 Torch is used for allocation and the stream handle only; every arithmetic op is a HIP kernel."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -986,7 +987,78 @@ def raster_blend(dem, mask, plan, lo, hi, run_of_window, wout, nodata=None):
     return out, unfilled
 
 
-HOLE_RECT, HOLE_ELLIPSE, HOLE_STROKE = 0, 1, 2     # primitive kinds of tg_hole_masks (terragan_hip.h)
+def _host_ops(ops, n, name):
+    """The transforms of a call as a host int32 array of n entries (the library reads and checks them before any launch)."""
+    a = np.ascontiguousarray(ops.cpu().numpy() if isinstance(ops, torch.Tensor) else ops)
+    if a.ndim != 1 or a.size != n or a.dtype.kind not in "iu":
+        raise L.TgError(f"{name}: expected {n} integer transforms on the host, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def raster_gather_ops(dem, mask, plan, lo, hi, win_idx, op_idx, nodata=None, x=None, m=None):
+    """raster_gather with a transform per list item: item k is window win_idx[k] (int32 HIP tensor) under op_idx[k] (host
+    integers, 0..7 as in raster_sample), written in the member's frame [n][wh][ww] (tg_raster_gather_ops)."""
+    _raster_in(dem, mask, plan)
+    n, nwin = win_idx.numel(), plan.ny * plan.nx
+    _i32(win_idx, n, "win_idx")
+    op_idx = _host_ops(op_idx, n, "raster_gather_ops")
+    _chk(lo, "lo"); _chk(hi, "hi")
+    assert lo.numel() == nwin and hi.numel() == nwin, (lo.shape, hi.shape, nwin)
+    shape = (n, plan.wh, plan.ww)
+    x = empty(*shape, like=dem) if x is None else x
+    m = empty(*shape, like=dem) if m is None else m
+    for t, nm in ((x, "x"), (m, "m")):
+        _chk(t, nm)
+        if tuple(t.shape) != shape:
+            raise L.TgError(f"raster_gather_ops: {nm} {tuple(t.shape)} != {shape}")
+    L.check(_lib().tg_raster_gather_ops(_p(dem), _p(mask), C.byref(plan), int(nodata is not None),
+                                        0.0 if nodata is None else float(nodata), _p(lo), _p(hi), _p(win_idx),
+                                        op_idx.ctypes.data, n, _p(x), _p(m), _stream()), "tg_raster_gather_ops")
+    return x, m
+
+
+def raster_tta_reduce(gout, ops, mean=None, var=None):
+    """gout [n][T][wh][ww]: generator outputs of n windows under the transforms ops (T host integers, T = 2, 4 or 8), each in
+    its member frame -> (mean, var) [n][wh][ww] in the windows' frame, the sample variance over T - 1 (tg_raster_tta_reduce)."""
+    _chk(gout, "gout")
+    if gout.dim() != 4:
+        raise L.TgError(f"raster_tta_reduce: gout {tuple(gout.shape)} is not [n][T][wh][ww]")
+    n, T, wh, ww = gout.shape
+    ops = _host_ops(ops, T, "raster_tta_reduce")
+    mean = empty(n, wh, ww, like=gout) if mean is None else mean
+    var = empty(n, wh, ww, like=gout) if var is None else var
+    for t, nm in ((mean, "mean"), (var, "var")):
+        _chk(t, nm)
+        if tuple(t.shape) != (n, wh, ww):
+            raise L.TgError(f"raster_tta_reduce: {nm} {tuple(t.shape)} != {(n, wh, ww)}")
+    L.check(_lib().tg_raster_tta_reduce(_p(gout), ops.ctypes.data, T, n, wh, ww, _p(mean), _p(var), _stream()),
+            "tg_raster_tta_reduce")
+    return mean, var
+
+
+def raster_blend_tta(dem, mask, plan, lo, hi, run_of_window, wmean, wvar, nodata=None):
+    """raster_blend of the window means wmean plus the spread map -> (raster [H][W], spread [H][W] in metres: 0 at known pixels,
+    NaN where no running window covers a hole, unfilled int32 [1] device counter) (tg_raster_blend_tta).  wmean, wvar:
+    [n_run][wh][ww], raster_tta_reduce's outputs in the rows run_of_window names."""
+    _raster_in(dem, mask, plan)
+    nwin = plan.ny * plan.nx
+    _i32(run_of_window, nwin, "run_of_window")
+    _chk(lo, "lo"); _chk(hi, "hi"); _chk(wmean, "wmean"); _chk(wvar, "wvar")
+    assert lo.numel() == nwin and hi.numel() == nwin, (lo.shape, hi.shape, nwin)
+    if wmean.dim() != 3 or tuple(wmean.shape[1:]) != (plan.wh, plan.ww) or wvar.shape != wmean.shape:
+        raise L.TgError(f"raster_blend_tta: wmean {tuple(wmean.shape)} / wvar {tuple(wvar.shape)} are not "
+                        f"[n_run][{plan.wh}][{plan.ww}]")
+    out, spread = empty(plan.H, plan.W, like=dem), empty(plan.H, plan.W, like=dem)
+    unfilled = torch.empty(1, dtype=torch.int32, device=dem.device)
+    some = wmean.numel() > 0
+    L.check(_lib().tg_raster_blend_tta(_p(dem), _p(mask), C.byref(plan), int(nodata is not None),
+                                       0.0 if nodata is None else float(nodata), _p(lo), _p(hi), _p(run_of_window),
+                                       _p(wmean) if some else None, _p(wvar) if some else None, wmean.shape[0], _p(out),
+                                       _p(spread), _p(unfilled), _stream()), "tg_raster_blend_tta")
+    return out, spread, unfilled
+
+
+HOLE_RECT, HOLE_ELLIPSE, HOLE_STROKE = 0, 1, 2    # primitive kinds of tg_hole_masks (terragan_hip.h)
 
 
 def _i32_rows(t, cols, name):
