@@ -1053,6 +1053,29 @@ int tg_krige(const float* z, const uint8_t* known, const uint16_t* hits, int H, 
              double scale, double shape, const int32_t* d2, const int32_t* idx, float* out, float* var, int64_t* counts,
              tg_stream_t stream);
 
+/* ---- Conditional simulation of voids (csrc/simulate.hip) ---------------------------------------------------------
+ * tg_sim_field: u fp32 [H][W] = sum_k a_k cos(2 pi t_k) + nugget_amp * g, an unconditional random field.  waves: n_waves (1 ..
+ * TG_SIM_MAX_WAVES) records of 16 bytes {int32 fx, int32 fy, uint32 phase, float amp}, 16-byte aligned; fx, fy are the frequency
+ * in turns per pixel as Q32 fixed point.  The phase t_k = fx * X + fy * Y + phase is taken in wrapping uint32 arithmetic (2^32 =
+ * one turn) at the global pixel X = x0 + x, Y = y0 + y (mod 2^32; x0, y0 in [0, 2^32)), so a tile with its origin set gets the
+ * bits of the whole raster.  The cosine is a fixed fp32 polynomial of the top 26 bits of the phase, the sum over k runs in fp64
+ * in index order, g is an Irwin-Hall sum of twelve 16-bit lanes of a counter hash of (seed, realisation, X, Y) with mean 0 and
+ * variance 1 - 2^-32, skipped when nugget_amp == 0; the head of csrc/simulate.hip states every operation.  nugget_amp finite, >= 0.
+ * Sides in [1, TG_EDT_MAX_SIDE]. */
+#define TG_SIM_MAX_WAVES 512
+int tg_sim_field(float* u, int H, int W, int64_t x0, int64_t y0, const void* waves, int n_waves, float nugget_amp, uint32_t seed,
+                 uint32_t realisation, tg_stream_t stream);
+/* Conditioning by kriging, one pixel at a time: out = z bit for bit where known != 0, else the fp32 value zk + (u - uk), taken as
+ * (float)((double)zk + d), d = (double)u - (double)uk: one rounding (zk, uk: tg_krige of z and of u over the same hits; NaN where zk
+ * is NaN).  With s1 and s2 (fp64 [H][W]; both or neither) an unknown pixel also adds d to s1 and d * d to s2: running sums over
+ * realisations, zeroed by the caller.  out aliases no input. */
+int tg_sim_combine(float* out, const float* z, const uint8_t* known, const float* zk, const float* u, const float* uk, double* s1,
+                   double* s2, int H, int W, tg_stream_t stream);
+/* The ensemble of n >= 2 realisations from the running sums: mean = (float)(zk + s1 / n), sd = (float)sqrt(max(0, (s2 - s1 * s1 /
+ * n) / (n - 1))) in fp64; sd = 0 on known pixels (their sums are zero) and NaN where zk is NaN.  mean, sd and zk are distinct. */
+int tg_sim_stats(float* mean, float* sd, const float* zk, const double* s1, const double* s2, int n, int H, int W,
+                 tg_stream_t stream);
+
 /* When enabled, every launch of the MFMA conv kernels is bracketed by hipEvents on its own launch
  * stream and tagged with its algorithmic FLOPs and bytes.  kind: 0 = fwd/dgrad implicit GEMM,
  * 1 = wgrad.  tg_prof_summary synchronises those events (host-blocking: call it outside any timed

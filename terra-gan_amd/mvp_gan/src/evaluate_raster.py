@@ -75,13 +75,18 @@ the same calls, and "calibration" = {"cells", "mean_z2", "within_1sigma", "withi
 variance > 0, z^2 = error^2 / variance, its mean and the shares with |error| <= sigma and <= 2 sigma.  Without it the report has no
 "kriging" key and nothing more runs.
 
+With simulate=n (n >= 2) the same keep mask is also simulated n times (simulate_voids; mvp_gan/src/simulate.py, DESIGN.md section
+8ah) and report["simulation"] holds the terrain_errors report of the mean of the realisations on the same holes and depth classes,
+"calibration" of their sd^2, "texture" of realisation 0 (the row that kriging's smooth fill fails), "variogram" and "realisations".
+Without it the report has no "simulation" key and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
          [--flood [--flood-stages s ...]] [--wetness [--exponent e] [--min-slope s]]
-         [--texture [--octaves n]] [--kriging] [--tta 2|4|8]
+         [--texture [--octaves n]] [--kriging] [--tta 2|4|8] [--simulate n]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -591,6 +596,45 @@ def kriging_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, variog
     return rep
 
 
+def _check_simulate(simulate, who="evaluate_raster"):
+    """0, None or False -> 0 (no simulation row); an integer in [2, 4096] -> itself: the mean and the deviation need two."""
+    if simulate is None or simulate is False or (simulate == 0 and isinstance(simulate, int)):
+        return 0
+    if isinstance(simulate, bool) or not isinstance(simulate, int) or not 2 <= simulate <= 4096:
+        raise ValueError(f"{who}: simulate {simulate!r} must be 0 (off) or a number of realisations in [2, 4096]")
+    return simulate
+
+
+@torch.no_grad()
+def simulation_report(dem, holes, keep, *, cellsize, realisations, mask=None, nodata=None, variogram=None, seed=0,
+                      area_edges_m2=AREA_EDGES_M2, quantiles=QUANTILES, top=10, depth_edges_m=None, texture_octaves=5):
+    """Conditional simulation of the keep mask (simulate_voids; mvp_gan/src/simulate.py; variogram None:
+    the power model fitted to the kept pixels) scored on the holes: terrain_errors' report of the mean of the realisations plus
+    "method", the info under "fill", "variogram", "realisations", "calibration" (calibration's dict) of sd^2 against the mean's
+    errors, and "texture" (texture_errors' dict) of realisation 0: one surface, where the mean is as smooth as kriging."""
+    from .simulate import simulate_voids
+    n = _check_simulate(realisations, "simulation_report")
+    if not n:
+        raise ValueError("simulation_report: realisations must be at least 2")
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO)
+    k = R.to_f32(keep, device, "keep", WHO, binary=True)
+    nd = R.nodata_value(nodata)
+    _, mean, sd, finfo = simulate_voids(z, k, nodata=nd, cellsize=cellsize, variogram=variogram, realisations=n, seed=seed,
+                                        keep=False)
+    from .kriging import Variogram
+    first, _, _, _ = simulate_voids(z, k, nodata=nd, cellsize=cellsize, variogram=Variogram(**finfo["variogram"]), seed=seed)
+    rep = terrain_errors(z, mean, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
+                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
+    rep["method"] = "simulation"
+    rep["fill"] = finfo
+    rep["variogram"] = finfo["variogram"]
+    rep["realisations"] = n
+    rep["calibration"] = calibration(z, mean, sd * sd, holes)
+    rep["texture"] = texture_errors(z, first[0], holes, cellsize=cellsize, mask=mask, nodata=nodata, octaves=texture_octaves)
+    return rep
+
+
 def calibration_summary(c):
     """One line for a calibration dict."""
     f = lambda v, spec: "n/a" if v is None else format(v, spec)
@@ -987,7 +1031,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
                     solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
                     flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3,
-                    texture=False, texture_octaves=5, kriging=False, tta=1):
+                    texture=False, texture_octaves=5, kriging=False, tta=1, simulate=0):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -1006,7 +1050,9 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     the same optional rows and the calibration of its variance.  tta (1, 2, 4 or 8) is passed to the inpainting; above 1 the
     prediction is the mean of the members and report["spread"] = {"members", "mean_m", "max_m", "calibration"}: the spread over
     the filled holes in metres and calibration's dict of spread^2 over the scored holes, the row kriging's variance is judged
-    by."""
+    by.  simulate=n (n >= 2 realisations; 0: off) adds report["simulation"], simulation_report's dict: the mean of n conditional
+    simulations of the same keep mask scored on the same holes and classes, the calibration of their sd^2 and the texture of
+    realisation 0; with a kriging.Variogram given as kriging it simulates under that model, else under the fitted one."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
@@ -1014,7 +1060,8 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                              depth_edges_m=depth_edges_m, compare=compare, sinks=sinks, drainage=drainage,
                              stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m,
                              wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope,
-                             texture=texture, texture_octaves=texture_octaves, kriging=kriging, tta=tta)
+                             texture=texture, texture_octaves=texture_octaves, kriging=kriging, tta=tta,
+                             simulate=simulate)
     return rep, pred
 
 
@@ -1022,13 +1069,14 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
               stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False, tta=1):
+              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False, tta=1, simulate=0):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, check_tta, inpaint_raster, inpaint_raster_tta
     _check_fill_options(baseline, fallback)
     compare = _check_compare(compare)
     kriging = _check_kriging(kriging)
+    simulate = _check_simulate(simulate)
     check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
     c = R.cellsize(cellsize, "evaluate_raster")
@@ -1039,6 +1087,12 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
     if kriging is not None and max(H, W) > 32767:
         raise ValueError(f"evaluate_raster: kriging needs sides of at most 32767 px, got {H}x{W}")
+    if simulate:
+        if max(H, W) > 32767:
+            raise ValueError(f"evaluate_raster: simulate needs sides of at most 32767 px, got {H}x{W}")
+        if kriging not in (None, True) and kriging.model == "spherical":
+            raise ValueError("evaluate_raster: simulate has no spherical model; give the power or the exponential one")
+        check_octaves(texture_octaves, "evaluate_raster")
     if drainage:
         if max(H, W) > 32767:
             raise ValueError(f"evaluate_raster: drainage needs sides of at most 32767 px, got {H}x{W}")
@@ -1108,6 +1162,11 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         rep["kriging"] = kriging_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata,
                                         variogram=None if kriging is True else kriging, area_edges_m2=area_edges_m2,
                                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m, sinks=bool(sinks), **drn)
+    if simulate:
+        rep["simulation"] = simulation_report(z, hm, keep, cellsize=c, realisations=simulate, mask=m, nodata=nodata,
+                                              variogram=None if kriging in (None, True) else kriging, seed=seed,
+                                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top,
+                                              depth_edges_m=depth_edges_m, texture_octaves=texture_octaves)
     return rep, pred, hm
 
 
@@ -1175,6 +1234,9 @@ def build_parser():
     ap.add_argument("--kriging", action="store_true",
                     help="also score the ordinary-kriging fill of the same holes (krige_voids, the power variogram fitted to "
                          "the kept cells) and the calibration of its variance: two more summary lines")
+    ap.add_argument("--simulate", type=int, default=0, metavar="N",
+                    help="also draw N >= 2 conditional simulations of the same holes (simulate_voids) and score their mean, the "
+                         "calibration of their spread and the texture of the first: three more summary lines")
     ap.add_argument("--tta", type=int, choices=(1, 2, 4, 8), default=1,
                     help="test-time augmentation of the inpainting (needs --checkpoint): the mean of this many flips / rotations "
                          "of every window is scored, and the calibration of their spread gets a summary line")
@@ -1230,6 +1292,10 @@ def main(argv=None):
         ap.error("--min-slope must be finite and > 0")
     if not 1 <= a.octaves <= TEX_OCTAVES:
         ap.error(f"--octaves must lie in [1, {TEX_OCTAVES}]")
+    try:
+        _check_simulate(a.simulate, "--simulate")
+    except ValueError as e:
+        ap.error(str(e))
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
@@ -1255,7 +1321,8 @@ def main(argv=None):
                                   compare=a.compare, sinks=a.sinks, drainage=a.drainage, stream_cells=a.stream_cells,
                                   stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages),
                                   wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope,
-                                  texture=a.texture, texture_octaves=a.octaves, kriging=a.kriging, tta=a.tta)
+                                  texture=a.texture, texture_octaves=a.octaves, kriging=a.kriging, tta=a.tta,
+                                  simulate=a.simulate)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -1291,6 +1358,9 @@ def main(argv=None):
         if a.kriging:
             rep["kriging"] = kriging_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, depth_edges_m=depth_edges,
                                             sinks=a.sinks, **drn)
+        if a.simulate:
+            rep["simulation"] = simulation_report(dem, hm, keep, cellsize=c, realisations=a.simulate, mask=mask, nodata=nodata,
+                                                  seed=a.seed, depth_edges_m=depth_edges, texture_octaves=a.octaves)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -1351,6 +1421,11 @@ def main(argv=None):
                           ("wetness", wetness_summary), ("texture", texture_summary)):
             if key in r:
                 print(f"kriging {line(r[key])}")
+    if "simulation" in rep:
+        r = rep["simulation"]
+        print(f"simulation, mean of {r['realisations']}: {summary(r)}")
+        print(f"simulation {calibration_summary(r['calibration'])}")
+        print(f"simulation, realisation 0: {texture_summary(r['texture'])}")
     return rep
 
 

@@ -64,6 +64,7 @@ TG_MFD_MAX_EXPONENT, TG_MFD_COUNTS = 8, 5
 TG_TEX_OCTAVES, TG_TEX_SCALES, TG_TEX_NSUM = 5, 10, 3
 TG_VGM_OCTAVES, TG_VGM_SCALES = 6, 12
 TG_VGM_POWER, TG_VGM_EXPONENTIAL, TG_VGM_SPHERICAL = 0, 1, 2
+TG_SIM_MAX_WAVES = 512
 
 
 class TgFloodStages(C.Structure):
@@ -238,6 +239,9 @@ SIGNATURES = {
     "tg_variogram_ws_bytes": (SZ, [I, I]),
     "tg_variogram": (I, [P, P, I, I, I, P, P, P, SZ, P]),
     "tg_krige": (I, [P, P, P, I, I, D, I, D, D, D, P, P, P, P, P, P]),
+    "tg_sim_field": (I, [P, I, I, I64, I64, P, I, F, C.c_uint32, C.c_uint32, P]),
+    "tg_sim_combine": (I, [P, P, P, P, P, P, P, P, I, I, P]),
+    "tg_sim_stats": (I, [P, P, P, P, P, I, I, I, P]),
     "tg_prof_enable": (I, [I]),
     "tg_prof_summary": (I, [I, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "tg_prof_dump": (I, [C.c_char_p]),

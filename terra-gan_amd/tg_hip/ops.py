@@ -2039,6 +2039,76 @@ def krige(z, known, hits, cellsize, model, nugget, scale, shape, d2=None, idx=No
     return out, var, counts
 
 
+SIM_MAX_WAVES = L.TG_SIM_MAX_WAVES
+
+
+def sim_field(H, W, waves, origin=(0, 0), nugget_amp=0.0, seed=0, realisation=0):
+    """-> u float32 [H][W]: the unconditional random field sum_k amp_k cos(2 pi (fx_k X + fy_k Y + phase_k) / 2^32) + nugget_amp
+    * g at the global pixels (Y, X) = origin + (y, x) (tg_sim_field).  waves: a HIP int32 tensor [n][4], n in 1 .. SIM_MAX_WAVES,
+    of (fx, fy, phase, the bits of the float32 amp); g: the unit-variance hash noise of (seed, realisation, X, Y)."""
+    import math
+    import numbers
+    who = "sim_field"
+    for name, v in (("H", H), ("W", W)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 1 <= v <= EDT_MAX_SIDE:
+            raise ValueError(f"{who}: {name} {v!r} must be an integer in [1, {EDT_MAX_SIDE}]")
+    if not (isinstance(waves, torch.Tensor) and waves.is_cuda and waves.dtype == torch.int32 and waves.is_contiguous()
+            and waves.dim() == 2 and waves.shape[1] == 4 and 1 <= waves.shape[0] <= SIM_MAX_WAVES):
+        got = f"{waves.dtype} {tuple(waves.shape)} on {waves.device}" if isinstance(waves, torch.Tensor) else type(waves).__name__
+        raise ValueError(f"{who}: waves must be a contiguous int32 HIP tensor [n][4], n in [1, {SIM_MAX_WAVES}], got {got}")
+    try:
+        y0, x0 = origin
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: origin {origin!r} must be (row, column)") from None
+    for name, v in (("origin row", y0), ("origin column", x0), ("seed", seed), ("realisation", realisation)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not 0 <= v < 2 ** 32:
+            raise ValueError(f"{who}: {name} {v!r} must be an integer in [0, 2^32)")
+    a = float(nugget_amp)
+    if not (math.isfinite(a) and a >= 0):
+        raise ValueError(f"{who}: nugget_amp {nugget_amp!r} must be finite and >= 0")
+    u = torch.empty(int(H), int(W), dtype=torch.float32, device=waves.device)
+    L.check(_lib().tg_sim_field(_p(u), int(H), int(W), int(x0), int(y0), _p(waves), int(waves.shape[0]), a, int(seed),
+                                int(realisation), _stream()), "tg_sim_field")
+    return u
+
+
+def sim_combine(z, known, zk, u, uk, s1=None, s2=None):
+    """-> out float32 [H][W]: z bit for bit on known pixels, zk + (u - uk) on the others (tg_sim_combine).  s1, s2: float64
+    [H][W] running sums (both or neither), to which an unknown pixel adds u - uk and its square, in place."""
+    who = "sim_combine"
+    H, W = _mfd_hw(z, "z", who)
+    _mfd_plane(known, torch.uint8, (H, W), "known", who)
+    for name, t in (("zk", zk), ("u", u), ("uk", uk)):
+        _mfd_plane(t, torch.float32, (H, W), name, who)
+    if (s1 is None) != (s2 is None):
+        raise ValueError(f"{who}: s1 and s2 go together")
+    if s1 is not None:
+        _mfd_plane(s1, torch.float64, (H, W), "s1", who)
+        _mfd_plane(s2, torch.float64, (H, W), "s2", who)
+        if s1.data_ptr() == s2.data_ptr():
+            raise ValueError(f"{who}: s1 and s2 must be distinct")
+    out = torch.empty(H, W, dtype=torch.float32, device=z.device)
+    L.check(_lib().tg_sim_combine(_p(out), _p(z), _p(known), _p(zk), _p(u), _p(uk), _p(s1), _p(s2), H, W, _stream()),
+            "tg_sim_combine")
+    return out
+
+
+def sim_stats(zk, s1, s2, n):
+    """-> (mean float32 [H][W] = zk + s1 / n, sd float32 [H][W] = sqrt(max(0, (s2 - s1^2 / n) / (n - 1)))) of n >= 2
+    realisations from sim_combine's running sums; sd is 0 on known pixels and NaN where zk is (tg_sim_stats)."""
+    import numbers
+    who = "sim_stats"
+    H, W = _mfd_hw(zk, "zk", who)
+    _mfd_plane(s1, torch.float64, (H, W), "s1", who)
+    _mfd_plane(s2, torch.float64, (H, W), "s2", who)
+    if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 2 <= n < 2 ** 31:
+        raise ValueError(f"{who}: n {n!r} must be an integer >= 2")
+    mean = torch.empty(H, W, dtype=torch.float32, device=zk.device)
+    sd = torch.empty(H, W, dtype=torch.float32, device=zk.device)
+    L.check(_lib().tg_sim_stats(_p(mean), _p(sd), _p(zk), _p(s1), _p(s2), int(n), H, W, _stream()), "tg_sim_stats")
+    return mean, sd
+
+
 VFILL_NSTATS = 4                                # tg_vfill_setup stats: known, unknown, min bits, max bits
 
 
