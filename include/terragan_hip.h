@@ -774,6 +774,27 @@ int tg_gather_fill(const float* z, const uint8_t* known, const int32_t* idx, int
  * rounded to fp32 once; known and NaN pixels are copied.  in and out are distinct. */
 int tg_void_smooth(const float* in, const uint8_t* known, int H, int W, float* out, tg_stream_t stream);
 
+/* ---- Natural-neighbour (discrete Sibson) void fill (csrc/natural.hip) ------------------------------------------
+ * Sites are the known pixels (known[q] != 0, tg_objmask_known's map).  d2 [H][W] int32: the UNCAPPED feature transform of the
+ * known map (tg_edt_nearest with cap2 = 0; its tie rule is part of this definition); nn [H][W] float: the nearest fill
+ * tg_gather_fill writes from it, nn(q) = known(q) ? z(q) : z[idx(q)], NaN where idx(q) < 0.  radius r in [1, 32];
+ * c(q) = min(d2(q), r^2).  For a void pixel p (known[p] == 0) the raster pixel q contributes iff |p - q|^2 < c(q), in integers,
+ * strictly: a known q (c = 0) never does, q = p always does, and every contributor lies within r - 1 pixels of p on each axis.
+ * out[p] = (float)(sum nn(q) / n(p)): the sum over the contributors in row-major order of q (row, then column, ascending) in
+ * fp64 from 0.0, n(p) their number, one fp64 division, one rounding to fp32.  No atomics on the sums, no data-dependent order:
+ * two calls agree bit for bit.  support (may be NULL) [H][W] int32 = n(p), 0 on known pixels: the discrete area of the Voronoi
+ * cell p would claim.  Known pixels: out[p] = nn[p] bit for bit.  A void pixel with d2[p] == TG_EDT_FAR (no known pixel at
+ * all) is NaN; with lim2 > 0 a void pixel with d2[p] > lim2 is NaN too, while q beyond the limit still contribute to the
+ * pixels within it (the limit masks the output only).  counts [2] int64 (zeroed here): void pixels filled, left NaN.  With
+ * r = 1 out is nn on the void pixels; a constant nn comes back constant.
+ * ws >= tg_natural_fill_ws_bytes(H, W): one uint16 per 4 x 64 tile, the tile's largest c (tg_natural_tile_maxima writes the same
+ * words and nothing else; tg_natural_fill does not need it called first).  Rejected on the host: null pointers, sides outside
+ * [1, TG_EDT_MAX_SIDE] (0 from the query), radius outside [1, 32], a short workspace, out aliasing nn. */
+size_t tg_natural_fill_ws_bytes(int H, int W);
+int tg_natural_tile_maxima(const int32_t* d2, int H, int W, int radius, void* ws, size_t ws_bytes, tg_stream_t stream);
+int tg_natural_fill(const float* nn, const int32_t* d2, const uint8_t* known, int H, int W, int radius, int32_t lim2, float* out,
+                    int32_t* support /* may be NULL */, int64_t* counts, void* ws, size_t ws_bytes, tg_stream_t stream);
+
 /* ---- Depression filling (pit removal) (csrc/depfill.hip) ------------------------------------------------------
  * Known pixels: known[p] != 0 (tg_objmask_known's map).  Connectivity conn = 8 or 4.  An outlet is a known pixel on the raster's
  * edge or with an unknown conn-neighbour.  For a known pixel p, W(p) = min over conn-connected paths of known pixels from p to

@@ -9,7 +9,7 @@ SRC = [os.path.join(HERE, "csrc", f) for f in ("igemm.hip", "pointwise.hip", "sm
                                                   "raster_train.hip", "objmask.hip", "terrain_eval.hip",
                                                   "voidfill.hip", "seam.hip", "resample.hip", "edt.hip", "idw.hip", "depfill.hip",
                                                   "flow.hip", "drainage.hip", "mfd.hip", "texture.hip", "kriging.hip",
-                                                  "simulate.hip")]
+                                                  "simulate.hip", "natural.hip")]
 # every header / include file under csrc/ is a dependency of every object (a stale .so on the GPU box is worse than a rebuild)
 HDR = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".h", ".inc"))) + \
     [os.path.join(ROOT, "include", "terragan_hip.h")]

@@ -80,13 +80,18 @@ With simulate=n (n >= 2) the same keep mask is also simulated n times (simulate_
 "calibration" of their sd^2, "texture" of realisation 0 (the row that kriging's smooth fill fails), "variogram" and "realisations".
 Without it the report has no "simulation" key and nothing more runs.
 
+With natural=True the same keep mask is also filled by natural-neighbour interpolation (natural_neighbour_voids; mvp_gan/src/natural.py,
+DESIGN.md section 8ai; natural_radius cells) and report["natural"] holds that fill's terrain_errors report on the same holes and depth
+classes, "method", the fill info under "fill" and every optional row above by the same calls.  Without it the report has no
+"natural" key and nothing more runs.
+
 CLI: python -m mvp_gan.src.evaluate_raster --dem in.asc --checkpoint ck.pth [--mask m] [--nodata v]
          [--split test|val|train|all] [--block 1024 --tile 256 --seed 0] [--window 512 --overlap 64 --batch 16]
          [--remove-objects [spec flags]] [--json report.json] [--pred-out pred.asc] [--holes-out holes.png|holes.asc]
          [--baseline laplace|biharmonic] [--fallback laplace] [--seam harmonic] [--solver mg|pcg] [--model-cellsize 1.0 [--min-coverage 0.5]]
          [--by-depth [E ...]] [--compare idw nearest] [--sinks] [--drainage [--stream-cells n] [--stream-tol m]]
          [--flood [--flood-stages s ...]] [--wetness [--exponent e] [--min-slope s]]
-         [--texture [--octaves n]] [--kriging] [--tta 2|4|8] [--simulate n]
+         [--texture [--octaves n]] [--kriging] [--tta 2|4|8] [--simulate n] [--natural [--natural-radius r]]
      python -m mvp_gan.src.evaluate_raster --dem in.asc --pred filled.asc --holes holes.png [...]   (score another fill)
 """
 import argparse
@@ -596,6 +601,48 @@ def kriging_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, variog
     return rep
 
 
+def _check_natural(natural, who="evaluate_raster"):
+    """False or None -> False (no natural-neighbour row); True -> True."""
+    if natural is None or natural is False:
+        return False
+    if natural is True:
+        return True
+    raise ValueError(f"{who}: natural {natural!r} must be False or True")
+
+
+@torch.no_grad()
+def natural_report(dem, holes, keep, *, cellsize, mask=None, nodata=None, radius=32, area_edges_m2=AREA_EDGES_M2,
+                   quantiles=QUANTILES, top=10, depth_edges_m=None, sinks=False, drainage=False, stream_cells=1000,
+                   stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
+                   wetness_min_slope=1e-3, texture=False, texture_octaves=5):
+    """The natural-neighbour fill of the keep mask (natural_neighbour_voids; mvp_gan/src/natural.py)
+    scored on the holes like a compare_report fill: terrain_errors' report plus "method", the fill info under "fill" and the
+    optional rows by the same calls."""
+    from .natural import natural_neighbour_voids
+    device = R.device(WHO)
+    z = R.to_f32(dem, device, "dem", WHO)
+    k = R.to_f32(keep, device, "keep", WHO, binary=True)
+    pred, finfo = natural_neighbour_voids(z, k, nodata=R.nodata_value(nodata), cellsize=cellsize, radius=radius)
+    rep = terrain_errors(z, pred, holes, k, cellsize=cellsize, mask=mask, nodata=nodata, area_edges_m2=area_edges_m2,
+                         quantiles=quantiles, top=top, depth_edges_m=depth_edges_m)
+    rep["method"] = "natural"
+    rep["fill"] = finfo
+    if sinks:
+        rep["sinks"] = sink_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata)
+    if drainage:
+        rep["drainage"] = drainage_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                          stream_tol_m=stream_tol_m)
+    if flood:
+        rep["flood"] = flood_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, stream_cells=stream_cells,
+                                    stages_m=flood_stages_m)
+    if wetness:
+        rep["wetness"] = wetness_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, exponent=wetness_exponent,
+                                        min_slope=wetness_min_slope)
+    if texture:
+        rep["texture"] = texture_errors(z, pred, holes, cellsize=cellsize, mask=mask, nodata=nodata, octaves=texture_octaves)
+    return rep
+
+
 def _check_simulate(simulate, who="evaluate_raster"):
     """0, None or False -> 0 (no simulation row); an integer in [2, 4096] -> itself: the mean and the deviation need two."""
     if simulate is None or simulate is False or (simulate == 0 and isinstance(simulate, int)):
@@ -1031,7 +1078,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                     quantiles=QUANTILES, top=10, baseline=None, fallback=None, seam=None, model_cellsize=None, min_coverage=0.5,
                     solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000, stream_tol_m=None,
                     flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1, wetness_min_slope=1e-3,
-                    texture=False, texture_octaves=5, kriging=False, tta=1, simulate=0):
+                    texture=False, texture_octaves=5, kriging=False, tta=1, simulate=0, natural=False, natural_radius=32):
     """eval_holes -> inpaint_raster(mask=keep) -> terrain_errors.  Returns (report, pred float32 HIP tensor [H][W]).
     baseline="laplace" adds report["baseline"]; fallback, seam, model_cellsize and min_coverage are passed to inpaint_raster
     (the holes are cut and scored on the native grid, in metres: block and tile are native pixels, see native_cells for a
@@ -1052,7 +1099,9 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
     the filled holes in metres and calibration's dict of spread^2 over the scored holes, the row kriging's variance is judged
     by.  simulate=n (n >= 2 realisations; 0: off) adds report["simulation"], simulation_report's dict: the mean of n conditional
     simulations of the same keep mask scored on the same holes and classes, the calibration of their sd^2 and the texture of
-    realisation 0; with a kriging.Variogram given as kriging it simulates under that model, else under the fitted one."""
+    realisation 0; with a kriging.Variogram given as kriging it simulates under that model, else under the fitted one.
+    natural=True adds report["natural"], natural_report's dict: the natural-neighbour fill (natural_neighbour_voids at
+    natural_radius) of the same keep mask scored on the same holes and classes, with the same optional rows."""
     rep, pred, _ = _evaluate(generator_or_checkpoint, dem, mask, nodata=nodata, cellsize=cellsize, split=split, block=block,
                              tile=tile, holes=holes, seed=seed, window=window, overlap=overlap, batch=batch, objects=objects,
                              area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, baseline=baseline, fallback=fallback,
@@ -1061,7 +1110,7 @@ def evaluate_raster(generator_or_checkpoint, dem, mask=None, *, nodata=None, cel
                              stream_cells=stream_cells, stream_tol_m=stream_tol_m, flood=flood, flood_stages_m=flood_stages_m,
                              wetness=wetness, wetness_exponent=wetness_exponent, wetness_min_slope=wetness_min_slope,
                              texture=texture, texture_octaves=texture_octaves, kriging=kriging, tta=tta,
-                             simulate=simulate)
+                             simulate=simulate, natural=natural, natural_radius=natural_radius)
     return rep, pred
 
 
@@ -1069,7 +1118,8 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
               objects, area_edges_m2, quantiles, top, baseline=None, fallback=None, seam=None, model_cellsize=None,
               min_coverage=0.5, solver="mg", depth_edges_m=None, compare=None, sinks=False, drainage=False, stream_cells=1000,
               stream_tol_m=None, flood=False, flood_stages_m=FLOOD_STAGES_M, wetness=False, wetness_exponent=1,
-              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False, tta=1, simulate=0):
+              wetness_min_slope=1e-3, texture=False, texture_octaves=5, kriging=False, tta=1, simulate=0, natural=False,
+              natural_radius=32):
     """evaluate_raster, plus the hole map."""
     from .fill_voids import check_solver
     from .inpaint_raster import check_resample_options, check_seam_options, check_tta, inpaint_raster, inpaint_raster_tta
@@ -1077,6 +1127,7 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
     compare = _check_compare(compare)
     kriging = _check_kriging(kriging)
     simulate = _check_simulate(simulate)
+    natural = _check_natural(natural)
     check_solver(solver, who="evaluate_raster")
     check_seam_options(seam, 1, who="evaluate_raster")
     c = R.cellsize(cellsize, "evaluate_raster")
@@ -1087,6 +1138,9 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
         raise ValueError(f"evaluate_raster: compare needs sides of at most 32767 px, got {H}x{W}")
     if kriging is not None and max(H, W) > 32767:
         raise ValueError(f"evaluate_raster: kriging needs sides of at most 32767 px, got {H}x{W}")
+    if natural:
+        from .natural import check_args as check_natural_args
+        check_natural_args(dem, mask, natural_radius, None, c, who="evaluate_raster")
     if simulate:
         if max(H, W) > 32767:
             raise ValueError(f"evaluate_raster: simulate needs sides of at most 32767 px, got {H}x{W}")
@@ -1167,6 +1221,10 @@ def _evaluate(generator_or_checkpoint, dem, mask, *, nodata, cellsize, split, bl
                                               variogram=None if kriging in (None, True) else kriging, seed=seed,
                                               area_edges_m2=area_edges_m2, quantiles=quantiles, top=top,
                                               depth_edges_m=depth_edges_m, texture_octaves=texture_octaves)
+    if natural:
+        rep["natural"] = natural_report(z, hm, keep, cellsize=c, mask=m, nodata=nodata, radius=natural_radius,
+                                        area_edges_m2=area_edges_m2, quantiles=quantiles, top=top, depth_edges_m=depth_edges_m,
+                                        sinks=bool(sinks), **drn)
     return rep, pred, hm
 
 
@@ -1234,6 +1292,11 @@ def build_parser():
     ap.add_argument("--kriging", action="store_true",
                     help="also score the ordinary-kriging fill of the same holes (krige_voids, the power variogram fitted to "
                          "the kept cells) and the calibration of its variance: two more summary lines")
+    ap.add_argument("--natural", action="store_true",
+                    help="also score the natural-neighbour fill of the same holes (natural_neighbour_voids): one more summary "
+                         "line, and one per optional row")
+    ap.add_argument("--natural-radius", type=int, default=32, metavar="R",
+                    help="with --natural: the radius of the fill in cells, an integer in 1..32")
     ap.add_argument("--simulate", type=int, default=0, metavar="N",
                     help="also draw N >= 2 conditional simulations of the same holes (simulate_voids) and score their mean, the "
                          "calibration of their spread and the texture of the first: three more summary lines")
@@ -1296,6 +1359,8 @@ def main(argv=None):
         _check_simulate(a.simulate, "--simulate")
     except ValueError as e:
         ap.error(str(e))
+    if not 1 <= a.natural_radius <= 32:
+        ap.error("--natural-radius must lie in [1, 32]")
     if bool(a.checkpoint) == bool(a.pred):
         ap.error("give exactly one of --checkpoint and --pred")
     if bool(a.pred) != bool(a.holes):
@@ -1322,7 +1387,7 @@ def main(argv=None):
                                   stream_tol_m=a.stream_tol, flood=a.flood, flood_stages_m=tuple(a.flood_stages),
                                   wetness=a.wetness, wetness_exponent=a.exponent, wetness_min_slope=a.min_slope,
                                   texture=a.texture, texture_octaves=a.octaves, kriging=a.kriging, tta=a.tta,
-                                  simulate=a.simulate)
+                                  simulate=a.simulate, natural=a.natural, natural_radius=a.natural_radius)
     else:
         p, ph = read_asc(a.pred)
         if p.shape != dem.shape:
@@ -1361,6 +1426,9 @@ def main(argv=None):
         if a.simulate:
             rep["simulation"] = simulation_report(dem, hm, keep, cellsize=c, realisations=a.simulate, mask=mask, nodata=nodata,
                                                   seed=a.seed, depth_edges_m=depth_edges, texture_octaves=a.octaves)
+        if a.natural:
+            rep["natural"] = natural_report(dem, hm, keep, cellsize=c, mask=mask, nodata=nodata, radius=a.natural_radius,
+                                            depth_edges_m=depth_edges, sinks=a.sinks, **drn)
         pred = None
     if a.json:
         with open(a.json, "w") as f:
@@ -1426,6 +1494,13 @@ def main(argv=None):
         print(f"simulation, mean of {r['realisations']}: {summary(r)}")
         print(f"simulation {calibration_summary(r['calibration'])}")
         print(f"simulation, realisation 0: {texture_summary(r['texture'])}")
+    if "natural" in rep:
+        r = rep["natural"]
+        print(f"natural, radius {r['fill']['radius']}: {summary(r)}")
+        for key, line in (("sinks", sinks_summary), ("drainage", drainage_summary), ("flood", flood_summary),
+                          ("wetness", wetness_summary), ("texture", texture_summary)):
+            if key in r:
+                print(f"natural {line(r[key])}")
     return rep
 
 

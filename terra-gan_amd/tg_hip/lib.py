@@ -205,6 +205,9 @@ SIGNATURES = {
     "tg_rayfill": (I, [P, P, I, I, C.c_int32, D, P, P, P, P, P, P, SZ, P]),
     "tg_gather_fill": (I, [P, P, P, I, I, P, P, P]),
     "tg_void_smooth": (I, [P, P, I, I, P, P]),
+    "tg_natural_fill_ws_bytes": (SZ, [I, I]),
+    "tg_natural_tile_maxima": (I, [P, I, I, I, P, SZ, P]),
+    "tg_natural_fill": (I, [P, P, P, I, I, I, C.c_int32, P, P, P, P, SZ, P]),
     "tg_depfill_ws_bytes": (SZ, [I, I]),
     "tg_depfill_init": (I, [P, P, I, I, I, P, P, SZ, P]),
     "tg_depfill_sweep": (I, [P, P, I, I, I, I, P, P, P, P, SZ, P]),

@@ -1420,6 +1420,53 @@ def gather_fill(z, known, idx):
     return out, counts
 
 
+NATURAL_MAX_RADIUS = 32
+NATURAL_TILE = (4, 64)                                    # natural.hip's NAT_TH, NAT_TW
+
+
+def _natural_radius(radius, who):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= NATURAL_MAX_RADIUS:
+        raise L.TgError(f"{who}: radius {radius!r} must be an integer in [1, {NATURAL_MAX_RADIUS}]")
+    return int(radius)
+
+
+def natural_tile_maxima(d2, radius=32):
+    """-> uint16 [ceil(H / 4)][ceil(W / 64)]: the largest c = min(d2, radius^2) of every tile of NATURAL_TILE pixels
+    (tg_natural_tile_maxima): the pre-pass of natural_fill on its own."""
+    H, W = _edt_hw(d2, "d2")
+    _hip(d2, torch.int32, (H, W), "d2")
+    radius = _natural_radius(radius, "natural_tile_maxima")
+    lib = _lib()
+    th, tw = NATURAL_TILE
+    nty, ntx = -(-H // th), -(-W // tw)
+    nbytes = lib.tg_natural_fill_ws_bytes(H, W)
+    ws = torch.empty(nbytes // 2, dtype=torch.uint16, device=d2.device)
+    L.check(lib.tg_natural_tile_maxima(_p(d2), H, W, radius, _p(ws), nbytes, _stream()), "tg_natural_tile_maxima")
+    return ws[:nty * ntx].view(nty, ntx)
+
+
+def natural_fill(nn, d2, known, radius=32, lim2=0, want_support=False):
+    """-> (out float32 [H][W], counts int64 [2]: void pixels filled, left NaN; support int32 [H][W] or None): the discrete
+    Sibson (natural-neighbour) fill of the pixels with known == 0 (tg_natural_fill).  nn: gather_fill's nearest fill; d2:
+    edt_nearest's squared distances WITHOUT a cap; a void pixel farther than lim2 (> 0) from every known pixel is NaN."""
+    H, W = _edt_hw(nn, "nn")
+    _hip(nn, torch.float32, (H, W), "nn")
+    _hip(d2, torch.int32, (H, W), "d2")
+    _hip(known, torch.uint8, (H, W), "known")
+    radius = _natural_radius(radius, "natural_fill")
+    lim2 = int(lim2)
+    if not -2 ** 31 <= lim2 < 2 ** 31:
+        raise L.TgError(f"natural_fill: lim2 {lim2} does not fit an int32")
+    out = torch.empty(H, W, dtype=torch.float32, device=nn.device)
+    support = torch.empty(H, W, dtype=torch.int32, device=nn.device) if want_support else None
+    counts = torch.empty(2, dtype=torch.int64, device=nn.device)
+    lib = _lib()
+    ws = workspace(lib.tg_natural_fill_ws_bytes(H, W))
+    L.check(lib.tg_natural_fill(_p(nn), _p(d2), _p(known), H, W, radius, lim2, _p(out), _p(support), _p(counts), _p(ws),
+                                ws.numel() * 4, _stream()), "tg_natural_fill")
+    return out, counts, support
+
+
 def void_smooth(x, known, steps=1):
     """-> float32 [H][W]: `steps` Jacobi steps of the 3x3 mean over the non-NaN pixels, on the pixels with known == 0 that are
     not NaN (tg_void_smooth); x is left unchanged."""
